@@ -7,10 +7,16 @@ One step = one batch_train! (src/solver.jl:191-236): sum-tree sample -> gather +
 target(sp) forwards -> double-Q Bellman target -> Huber(w*td)/B -> backward -> max-abs grad norm -> Adam -> priority update.
 
     python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 --full
+    python bench.py --gpus 1 --steps 200 --warmup 20 --dump-outputs DIR
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 N > 1: one process per GPU, per-rank envs + replay (weak scaling: B=32 per rank), gradients all-reduced over RCCL
 between backward and Adam.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds the untimed measurements around it: the
+per-launch profile and roofline, the device env loop, the sustained region, the per-call seam, the secondary configurations and the CPU
+baselines.  --dump-outputs DIR writes what the timed call left a caller after its last step as DIR/<name>.npy (dump_outputs below).
 """
 import argparse
 import json
@@ -242,6 +248,24 @@ def timed_steps(eng, steps, warmup):
     return {"steps_per_s": steps / dt, "ms_per_step": dt / steps * 1e3, "steps": steps, "warmup": max(3, warmup), "last_loss": loss, "last_grad_norm": gn}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+RAMP_CALLS, RAMP_STEPS_PER_CALL = 6, 50      # a plain run's untimed clock ramp before its warm-up (main)
+
+
+def dump_outputs(pkg, eng, out_dir, loss, grad_norm):
+    """--dump-outputs: what the timed dqn_train_steps(K) call leaves its caller after the last step, as out_dir/<name>.npy in float32 / float64 --
+    the returned loss and grad norm, the online parameters it trained, the replay priorities it rewrote and the indices of the last batch.
+    An array over its share of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample of its elements (flat, in index order)."""
+    outs = {"loss": np.array([loss], np.float32), "grad_norm": np.array([grad_norm], np.float32), "params_online": eng.get_params(pkg.NET_ONLINE),
+            "replay_priorities": eng.replay_priorities(), "last_indices": eng.last_indices().astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(outs)
+    for name, a in outs.items():
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_profile(eng, n, steady=True):
     acc = {}
     for _ in range(n):
@@ -425,6 +449,9 @@ def main():
     ap.add_argument("--dw-wgs", type=int, default=0, help="experiment: target workgroup count of the conv dW split (plan dw_kc)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` block (BASELINE configs[0], [3], [4] timed like `value`; default run at N = 1 on the headline workload only)")
     ap.add_argument("--distinct", action="store_true", help="hp.sample_distinct = 1 for the headline engine (the reference's replace=false draws, ...replay.jl:85)")
+    ap.add_argument("--full", action="store_true", help="also run the per-launch profile + roofline, env loop, sustained region, per-call seam, secondary configurations and CPU "
+                                                          "baselines (the options above that configure them take effect only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write the timed call's outputs after its last step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--cpu-worker", default="", choices=["", "twin", "torch"], help=argparse.SUPPRESS)      # internal: the CPU-baseline subprocess (cpu_worker below)
     ap.add_argument("--cpu-worker-cpus", default="", help=argparse.SUPPRESS)
     args = ap.parse_args()
@@ -542,11 +569,17 @@ def main():
         group.barrier()
 
 
-    # the HOST-paced per-launch profile first, the GPU-paced device env loop (~35 ms of dense work) last: what runs right before the 3 ms timed region decides the clocks it sees
-    if args.order == "env-first":
-        section_env_loop(); section_profile()
+    if args.full:
+        # the HOST-paced per-launch profile first, the GPU-paced device env loop (~35 ms of dense work) last: what runs right before the 3 ms timed region decides the clocks it sees
+        if args.order == "env-first":
+            section_env_loop(); section_profile()
+        else:
+            section_profile(); section_env_loop()
     else:
-        section_profile(); section_env_loop()
+        # no untimed section runs before the headline here, so untimed steps of the same call bring the GPU to its clocks instead (~35 ms at config 2,
+        # as the env loop does above; without them the 20-step region read 8096-8104 steps/s against 8472-8485 with them, same box).  Calls of fewer than 64 steps: the 16-step grouped graph's first launch stays where it is with --full.
+        for _ in range(RAMP_CALLS):
+            eng.train_steps(RAMP_STEPS_PER_CALL)
 
     # ---- the headline: W untimed warm-up steps, then EXACTLY K timed steps between barrier + synchronize.  It runs AFTER the secondary sections
     # above (real train steps and env steps, all untimed): the GPU needs ~10 ms of activity to reach its clocks, and with --steps 20 --warmup 5
@@ -568,13 +601,15 @@ def main():
     group.barrier()
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.steps / elapsed            # whole-job train steps/s (each rank runs its own B=32 step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(pkg, eng, args.dump_outputs, loss, gnorm)
 
     # ---- the same measurement over a LONG region (the driver's --steps 20 region is ~3 ms, shorter than its SMI sampler's period): `--sustained-seconds` of GPU time
     # (default 10 s) of the identical call, same barriers, same max-over-ranks clock, BEFORE the CPU baseline.  Reported beside `value`, never instead of it.
     sustained = None
     if args.sustained_steps < 0:
         args.sustained_steps = int(max(1000, args.sustained_seconds * value / world)) if args.sustained_seconds > 0 else 0
-    if args.sustained_steps > 0:
+    if args.full and args.sustained_steps > 0:
         barrier()
         t0 = time.perf_counter()
         eng.train_steps(args.sustained_steps)
@@ -591,7 +626,7 @@ def main():
     # between two log_freq prints (src/solver.jl:154-167).  Both include the step's own sample + gather launch (nothing is pre-gathered across calls).
     per_call = None
     kpc = args.steps if args.per_call_steps < 0 else args.per_call_steps
-    if kpc > 0 and world == 1:
+    if args.full and kpc > 0 and world == 1:
         per_call = {}
         for _ in range(3):
             eng.train_step(want_td=False); eng.step_scalars(eng.train_step_async())
@@ -619,19 +654,19 @@ def main():
     out = None
     n_params = eng.P
     if rank == 0:
-        roof = roofline_block(pkg, eng, layers, args.batch, args.u8, world, value, ms_per_step, prof_acc, single_gather)
-        # ---- BASELINE configs[0], [3], [4] on the SAME line: each timed exactly like `value` (warm-up, K steps between two syncs), on engines of
-        # their own, after the headline engine has been released.  Default single-GPU run on the headline workload only.
-        secondary = None
-        if world == 1 and not args.no_secondary and args.batch == 32 and not args.u8 and not args.distinct:
-            eng.close()
-            args_ms_plain[0] = ms_per_step
-            secondary = secondary_block(pkg, args, local_rank)
-        cpu = None
-        if not args.no_cpu_baseline:           # rank 0 only (this block), at any world size
-            if world > 1:
-                args.cpu_seconds = min(args.cpu_seconds, 5.0)      # the other ranks wait at the final barrier meanwhile
-            cpu = cpu_baseline(pkg, layers, hp, params, env, args)
+        roof = secondary = cpu = None
+        if args.full:
+            roof = roofline_block(pkg, eng, layers, args.batch, args.u8, world, value, ms_per_step, prof_acc, single_gather)
+            # ---- BASELINE configs[0], [3], [4] on the SAME line: each timed exactly like `value` (warm-up, K steps between two syncs), on engines of
+            # their own, after the headline engine has been released.  Default single-GPU run on the headline workload only.
+            if world == 1 and not args.no_secondary and args.batch == 32 and not args.u8 and not args.distinct:
+                eng.close()
+                args_ms_plain[0] = ms_per_step
+                secondary = secondary_block(pkg, args, local_rank)
+            if not args.no_cpu_baseline:           # rank 0 only (this block), at any world size
+                if world > 1:
+                    args.cpu_seconds = min(args.cpu_seconds, 5.0)      # the other ranks wait at the final barrier meanwhile
+                cpu = cpu_baseline(pkg, layers, hp, params, env, args)
         out = {
             "metric": f"train steps/sec (batch={args.batch}, 84x84x4 obs)", "value": value, "unit": "steps/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
@@ -646,11 +681,11 @@ def main():
                        "exchange": {0: "none", 1: "all-gather (wide-dense operands + small gradients)", 2: "all-reduce (flat gradient)", -1: "undecided"}[comm_info["exchange"]],
                        "dp_overlap": bool(comm_info["dp_overlap"]),
                        **({"sim_comm": "SELF-TEST: all ranks share GPU 0, the all-gather is replaced by local copies (DQN_SIM_WORLD); not a scaling measurement"} if sim_comm else {})},
-            "samples_per_s": value * args.batch,
-            "roofline": roof, "cpu_baseline": cpu, "env_loop": env_loop, "sustained": sustained, "per_call": per_call, "host_fill": dict(HOST_FILL),
-            "secondary": secondary,
-            "value_distinct": (secondary or {}).get("config2_distinct", {}).get("steps_per_s"),      # the same step with distinct sampling (secondary.config2_distinct)
+            "samples_per_s": value * args.batch, "clock_ramp_steps": 0 if args.full else RAMP_CALLS * RAMP_STEPS_PER_CALL, "host_fill": dict(HOST_FILL),
         }
+        if args.full:
+            out.update({"roofline": roof, "cpu_baseline": cpu, "env_loop": env_loop, "sustained": sustained, "per_call": per_call, "secondary": secondary,
+                        "value_distinct": (secondary or {}).get("config2_distinct", {}).get("steps_per_s")})      # the same step with distinct sampling (secondary.config2_distinct)
         print(json.dumps(out))
     group.barrier()
     eng.close()

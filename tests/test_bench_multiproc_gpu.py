@@ -30,7 +30,7 @@ def test_bench_two_ranks_script_path(launcher):
     env = dict(os.environ, DQN_BENCH_SIM_COMM="1", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    bench_args = ["--gpus", "2", "--steps", "6", "--warmup", "3", "--replay", "512", "--env-steps", "8", "--profile-steps", "1", "--sustained-steps", "40", "--cpu-seconds", "1"]
+    bench_args = ["--gpus", "2", "--steps", "6", "--warmup", "3", "--replay", "512", "--env-steps", "8", "--profile-steps", "1", "--sustained-steps", "40", "--cpu-seconds", "1", "--full"]
     if launcher == "torchrun":
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
                os.path.join(ge.ROOT, "bench.py")] + bench_args
@@ -54,9 +54,9 @@ def test_bench_two_ranks_script_path(launcher):
 
 
 def test_bench_single_gpu_line_fields():
-    """the default single-GPU line carries per_call (sync + async seam), a sustained region sized in seconds and a dominant kernel named from the committed profile"""
+    """the --full single-GPU line carries per_call (sync + async seam), a sustained region sized in seconds and a dominant kernel named from the committed profile"""
     cmd = [sys.executable, os.path.join(ge.ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--replay", "2048", "--env-steps", "0", "--profile-steps", "2",
-           "--sustained-seconds", "0.5", "--no-cpu-baseline"]
+           "--sustained-seconds", "0.5", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ge.ROOT)
     assert p.returncode == 0, p.stderr[-4000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
@@ -66,3 +66,31 @@ def test_bench_single_gpu_line_fields():
     dk = d["roofline"]["dominant_kernel"]
     assert dk["rocprof_file"].startswith("profiles/") and dk["kernel"] in dk["rocprof_symbol"] and dk["bound"] in ("mfma", "hbm") and 0 < dk["frac"] < 1
     assert d["config"]["rccl_nranks"] == 0 and d["config"]["exchange"] == "none"
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) prints the headline alone; --dump-outputs writes the timed call's last-step outputs as float32 / float64 .npy files,
+    the same from run to run with the same arguments"""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        cmd = [sys.executable, os.path.join(ge.ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--replay", "512", "--dump-outputs", str(tmp_path / str(i))]
+        p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ge.ROOT)
+        assert p.returncode == 0, p.stderr[-4000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        runs.append(json.loads(lines[0]))
+    d = runs[0]
+    assert d["steps"] == 7 and d["warmup"] == 3 and d["unit"] == "steps/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["value"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "cpu_baseline", "env_loop", "sustained", "per_call", "secondary"):
+        assert k not in d, k
+    names = sorted(f.name for f in (tmp_path / "0").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "1").iterdir()) and "params_online.npy" in names and "loss.npy" in names
+    assert sum((tmp_path / "0" / n).stat().st_size for n in names) <= 64 << 20
+    for n in names:
+        a, b = np.load(tmp_path / "0" / n), np.load(tmp_path / "1" / n)
+        assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), n
+        np.testing.assert_array_equal(a, b, err_msg=n)
+    assert np.load(tmp_path / "0" / "loss.npy")[0] == np.float32(d["config"]["last_loss"])
+    assert np.load(tmp_path / "0" / "params_online.npy").size == d["config"]["n_params"]

@@ -4,9 +4,10 @@
 #   config-2 bench (steps/s + per-launch table row) and / or the config-5 bench; -t first runs the parity tests selected by the expression against EVERY build
 #   (a variant that is not bit-exact is reported and skipped); -e sets environment switches for the VARIANT runs only ("" as the variant = the in-tree build with -e).
 # Boxes differ by a few per cent: only same-box, alternating comparisons decide.  One script instead of one launcher per experiment (r05 left 28 of them).
+out=${OUT:-out}      # output folder, relative to the repository root
 reps=3; cfg=both; kexpr=""; venv=""
 while getopts "n:c:t:e:" o; do case $o in n) reps=$OPTARG;; c) cfg=$OPTARG;; t) kexpr=$OPTARG;; e) venv=$OPTARG;; esac; done; shift $((OPTIND - 1))
-mkdir -p gpurun_out
+mkdir -p $out
 builds=("in-tree"); for v in "$@"; do builds+=("$v"); done
 libof() { [ "$1" = "in-tree" ] && echo "" || { [ -z "$1" ] && echo "" || echo "$PWD/deepqlearning.jl_amd/build/$1"; }; }
 envof() { [ "$1" = "in-tree" ] && echo "" || echo "$venv"; }
@@ -26,7 +27,7 @@ print("%-28s %8.1f steps/s  %7.2f us/step  " % (sys.argv[2], d["value"], 1e3 * d
 PY
 }
 for i in $(seq $reps); do for b in "${ok[@]}"; do
-  if [ "$cfg" != 5 ]; then env $(envof "$b") DQN_MI355X_LIB=$(libof "$b") timeout 300 python bench.py --no-cpu-baseline --sustained-seconds 2 --per-call-steps 0 --no-secondary --env-steps 0 2>/dev/null > gpurun_out/_ab.json && line gpurun_out/_ab.json "cfg2 ${b:-in-tree+env}"; fi
-  if [ "$cfg" != 2 ]; then env $(envof "$b") DQN_MI355X_LIB=$(libof "$b") timeout 300 python bench.py --batch 512 --u8 --replay 200000 --device-fill --steps 100 --warmup 10 --no-cpu-baseline --env-steps 0 --sustained-seconds 0 --no-secondary 2>/dev/null > gpurun_out/_ab.json && line gpurun_out/_ab.json "cfg5 ${b:-in-tree+env}"; fi
+  if [ "$cfg" != 5 ]; then env $(envof "$b") DQN_MI355X_LIB=$(libof "$b") timeout 300 python bench.py --full --no-cpu-baseline --sustained-seconds 2 --per-call-steps 0 --no-secondary --env-steps 0 2>/dev/null > $out/_ab.json && line $out/_ab.json "cfg2 ${b:-in-tree+env}"; fi
+  if [ "$cfg" != 2 ]; then env $(envof "$b") DQN_MI355X_LIB=$(libof "$b") timeout 300 python bench.py --full --batch 512 --u8 --replay 200000 --device-fill --steps 100 --warmup 10 --no-cpu-baseline --env-steps 0 --sustained-seconds 0 --no-secondary 2>/dev/null > $out/_ab.json && line $out/_ab.json "cfg5 ${b:-in-tree+env}"; fi
 done; done
-rm -f gpurun_out/_ab.json
+rm -f $out/_ab.json
