@@ -759,8 +759,7 @@ int gemm_set_ktrace(unsigned long long* p);   // debug (-DDQN_KTRACE builds): pe
 #define DQN_LOPT_FWD_M32 1      /* DQN_FWD_M32=1: 32x32x2 MFMA blocks for the 64-channel forward tiles in EVERY launch (default: only the large ones, >= 1024 workgroups, where they measure
                                    conv3 forward 58.3 -> 55.7 us at config 5 since the r04 instruction diet; no faster before it) */
 #define DQN_LOPT_NO_FWD_M32 32  /* DQN_FWD_M32=0: never */
-#define DQN_LOPT_NO_DX_WIDE 4   /* DQN_NO_DX_WIDE: large batches take the 32-sample dX tiles instead of the 128-sample ones */
-#define DQN_LOPT_ST_WT 64       /* small-batch engines (<= 64 columns per sequence set; DQN_NO_ST_WT=1 turns it off): the GEMM launches store their outputs write-through, nn_gemm.hip st_out4 */
+#define DQN_LOPT_ST_WT 64       /* small-batch engines (<= 64 columns per sequence set): the GEMM launches store their outputs write-through, nn_gemm.hip st_out4 */
 #define DQN_LOPT_NO_FWD_WRES 8  /* DQN_NO_FWD_WRES: large-batch forwards of a narrow layer take the per-tile kernel instead of the weights-resident persistent one (A/B) */
 void launch_gemm_fwd(hipStream_t st, const LayerDev& L, int nprob, const float* const* W, const float* const* bias, const float* const* X,
                      const int* ldx, const int* col0, const int* ncols, float* const* out /* Y, or split-K partial slabs */,

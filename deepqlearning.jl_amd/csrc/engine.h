@@ -25,23 +25,29 @@ struct ProfEntry { const char* name; hipEvent_t a, b; };
 // first one's switches.  The communicator switches (force_allreduce, dp_*) are re-read by dqn_comm_init, the call that makes them meaningful.
 struct EngineOpts {
     int no_tiny = 0;              // DQN_NO_TINY: networks that fit in LDS take the multi-launch program
-    int fwd_m32 = -1 /* -1: large launches only */, no_dx_wide = 0, no_fwd_wres = 0;      // DQN_FWD_M32 / DQN_NO_DX_WIDE / DQN_NO_FWD_WRES -> LayerDev::opt bits
-    int mid_group = 4, mid_big = 16;                   // DQN_MID_GROUP / DQN_MID_BIG: middle steps of dqn_train_steps per graph (mid_big also needs mid_group > 1)
+    int fwd_m32 = -1 /* -1: large launches only */, no_fwd_wres = 0;      // DQN_FWD_M32 / DQN_NO_FWD_WRES -> LayerDev::opt bits
     int sim_world = 0;            // DQN_SIM_WORLD=k: one process plays k ranks (tests)
-    int no_graph_upload = 0;      // DQN_NO_GRAPH_UPLOAD
-    int no_rollout_cycle = 0;     // DQN_NO_ROLLOUT_CYCLE
     int no_act_head = 0;          // DQN_NO_ACT_HEAD (A/B, both schedules under test): the acting step keeps k_reduce_multi + heads + k_env_step where the fused tail (act_head.hip) would apply
     int no_rh_pm = 0;             // DQN_NO_RH_PM (A/B, r06): the hidden layers' split-K slabs stay [S][N][columns] where k_red_head reads them (default: piece-major, GFwdProb::pm)
     int dw_split = 128;            // DQN_DW_SPLIT=n: the last n units of a large-batch dW section run as two halves along N (nn_gemm.hip dw_section; 0 = off; LayerDev::opt bits 8..15 in units of 16)
-    int no_st_wt = 0;             // DQN_NO_ST_WT: small-batch engines keep plain / non-temporal output stores in the GEMM launches (A/B)
     int no_head_cols4 = 0;        // DQN_NO_HEAD_COLS4=1: keep k_head_td (one workgroup per column) at large batches where k_head_cols4 (red_head.hip) would apply (A/B); =2: k_head_cols4 without the transposed copies (its fallback loader, under test)
     int no_red_head = 0;          // DQN_NO_RED_HEAD: keep k_reduce_multi + k_head_td where the fused reduce + head launch (red_head.hip) would apply (A/B, both schedules under test)
-    int no_u8_arena = 0, head_fuse_maxb = 1024, no_head_fuse = 0, head_dbg = 0, prio_fork = 0, no_pregather = 0, lstm_dw_mfma = 0;
+    int no_pregather = 0;         // DQN_NO_PREGATHER: dqn_train_steps keeps the gather launch in every step (A/B)
     int force_allreduce = 0, dp_allreduce = 0, dp_overlap = -1 /* -1: decided from world size and bytes (engine_program.hip) */, dp_no_one_graph = 0;      // DQN_FORCE_ALLREDUCE / DQN_DP_ALLREDUCE / DQN_DP_OVERLAP / DQN_DP_NO_ONE_GRAPH
     // timing probes (wrong numbers, right schedule) and stamps
-    int probe_no_tg = 0, drqn_probe = 0, drqn_stamps = 0, tiny_stop = 0;
+    int head_dbg = 0, probe_no_tg = 0, drqn_probe = 0, drqn_stamps = 0, tiny_stop = 0;
 };
 void read_opts(EngineOpts& o, bool comm_only = false);
+
+enum { PH_ALL = 0, PH_PRE = 1, PH_POST = 2, PH_PRE1 = 3, PH_PRE2 = 4, PH_DP_ONE = 5 };      // PRE = PRE1 (up to the point where the wide layers' operands are final) + PRE2 (the rest of the backward pass)
+// One variant of the train step: what enqueue_step enqueues and what names its graph in the engine's cache (get_or_capture keeps, per phase, only the fields that phase reads).
+// take_pre / pregather (common.h PreGather, only between the steps of one dqn_train_steps call): this step runs without its gather launch / its Adam launch gathers the
+// next batch.  publish: the step's last launch writes (loss, grad_norm) into the host mailbox.  repeat: steps back to back in one graph.  slot: the first draw slot of the
+// fused recurrent step (a launch parameter, step r of the key reads slot + r).
+struct StepKey {
+    int phase = PH_ALL; bool sampled = true, take_pre = false, pregather = false, publish = false; int repeat = 1, slot = 0;
+    bool operator==(const StepKey& o) const { return phase == o.phase && sampled == o.sampled && take_pre == o.take_pre && pregather == o.pregather && publish == o.publish && repeat == o.repeat && slot == o.slot; }
+};
 
 struct dqn_engine {
     EngineOpts opt;
@@ -70,8 +76,9 @@ struct dqn_engine {
     // policy workspace
     EnvDev env{}; bool has_envs = false; unsigned char* env_images = nullptr;
     int pol_n = 0; float *pol_obs = nullptr, *pol_x = nullptr, *pol_act[DQN_MAX_LAYERS] = {}, *pol_q = nullptr; int* pol_a = nullptr;
-    // graphs: [0] = step with sampling, [1] = step on given indices; with a communicator the step is cut in two
-    hipGraphExec_t g_full[2] = {nullptr, nullptr}, g_pre[2] = {nullptr, nullptr}, g_post = nullptr;
+    // the train-step graphs, one per StepKey in use (linear lookup: a handful of entries); with a communicator the step is cut in two around the exchange
+    struct StepGraph { StepKey key; hipGraphExec_t g; }; std::vector<StepGraph> graphs;
+    StepKey cur;      // the variant enqueue_step is enqueuing, for the program's closures (default outside enqueue_step)
     bool arena_u8 = false;  // the observation arena x0 holds bytes (u8 replay, first layer converts in its tile loads): set by build_program
     unsigned long long* ktrace_buf = nullptr;     // dqn_debug_ktrace (trace builds): owned by the engine, freed with it
     // comm
@@ -90,7 +97,6 @@ struct dqn_engine {
     float *gx_on[DQN_MAX_LAYERS] = {}, *gx_tg[DQN_MAX_LAYERS] = {}, *cst_on[DQN_MAX_LAYERS] = {}, *cst_tg[DQN_MAX_LAYERS] = {}, *gates[DQN_MAX_LAYERS] = {}, *tcb[DQN_MAX_LAYERS] = {},
           *hprev_buf[DQN_MAX_LAYERS] = {}, *cprev_buf[DQN_MAX_LAYERS] = {}, *dG[DQN_MAX_LAYERS] = {}, *dhn[DQN_MAX_LAYERS] = {}, *dcn[DQN_MAX_LAYERS] = {};
     float *pol_h[DQN_MAX_LAYERS][2] = {}, *pol_c[DQN_MAX_LAYERS][2] = {}, *pol_gx[DQN_MAX_LAYERS] = {}; int pol_flip = 0, pol_state_n = 0; uint64_t drqn_draws = 0;
-    hipGraphExec_t g_drqn[2] = {nullptr, nullptr}, g_drqn_k[2] = {nullptr, nullptr};      // the recurrent step as a graph (fused step: two alternating instances, see draw_ev); g_drqn_k: runs of 8 fused steps
     // static launch program
     struct Step { const char* name; std::function<void(dqn_engine*)> fn; };
     // acting programs (forward on n columns + env kernels), one for the training envs and one for the evaluation envs
@@ -101,35 +107,25 @@ struct dqn_engine {
                      hipGraphExec_t envc = nullptr; int envc_due = 0; };      // envc: one vector step of the reference's cadence (the acting step + its `envc_due` pipelined train steps) as ONE graph
     ActProg act, evalp; std::vector<Step>* sink = nullptr; std::vector<void*>* alloc_sink = nullptr; RolloutDev *roll = nullptr, *eval_roll = nullptr;
     EnvDev eval_env{}; int eval_n = 0;
-    std::vector<Step> prog; size_t prog_post_begin = 0, prog_pre1_end = 0; bool prog_built = false, step_sampled = true, prio_forked = false, prio_in_bwd = false;
-    // pre-gather (common.h PreGather), only between the steps of one dqn_train_steps(n) call: step_pregather = this step's Adam launch gathers
-    // the next batch; step_take_pre = this step runs without its gather launch
+    std::vector<Step> prog; size_t prog_post_begin = 0, prog_pre1_end = 0; bool prog_built = false, prio_forked = false, prio_in_bwd = false;
     int gmax_used = 0;                    // live slots of gmax_part (per-block max |g| of the step's Adam jobs): what the on-demand fold reads
     StepState* state_host = nullptr;      // pinned landing buffer of fetch_scalars
     // scalar mailbox (StepMail, common.h): mapped pinned host ring the step's last launch writes (loss, grad_norm) into; pub_issued = publishes enqueued by the host,
     // pub_ctr = publishes executed by the device (the record of ticket t sits in slot t % DQN_MAIL_SLOTS once its seq == t)
-    StepMail *mail_host = nullptr, *mail_dev = nullptr; unsigned long long* pub_ctr = nullptr; unsigned long long pub_issued = 0; bool step_publish = false;
+    StepMail *mail_host = nullptr, *mail_dev = nullptr; unsigned long long* pub_ctr = nullptr; unsigned long long pub_issued = 0;
     unsigned long long mail_swept = 0; bool mail_plain = false;      // mail_swept: records [1, mail_swept] have been checked for device-side errors (mail_sweep); mail_plain: the ring is ordinary host memory (mapped allocation refused)
-    hipGraphExec_t g_full_pub[2] = {nullptr, nullptr};      // g_full + the publish launch
-    hipGraphExec_t g_pgv_pub = nullptr;                      // the LAST step of dqn_train_steps (takes the pre-gathered batch, gathers nothing) + the publish launch
-    bool pg_ok = false, step_pregather = false, step_take_pre = false; PreGather pg; long adam_step = -1;
-    bool no_tiny = false;   // DQN_NO_TINY at dqn_engine_create: always the multi-launch program
+    bool pg_ok = false; PreGather pg; long adam_step = -1;      // pg_ok: the program supports the pre-gather (StepKey::take_pre / pregather)
     bool tiny = false;      // the whole step is ONE single-workgroup launch that samples and gathers itself (tiny_step.hip)
     // fused recurrent step: episode draws travel through a mapped pinned host buffer of DQN_DRAW_SLOTS slots the kernel reads directly.  A slot is a LAUNCH PARAMETER, fixed per graph
     // node: two 8-step graphs (slots 0-7 / 8-15) and two single-step graphs (16 / 17) alternate, and before the host rewrites the slots of one it waits for the event recorded
     // behind that graph's previous launch
     long long *draw_idx_h = nullptr, *draw_idx_d = nullptr; int *draw_start_h = nullptr, *draw_start_d = nullptr;
-    hipEvent_t draw_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool draw_ev_used[4] = {false, false, false, false}; int drqn_grp_par = 0, drqn_one_par = 0, drqn_slot_next = 0;
+    hipEvent_t draw_ev[4] = {nullptr, nullptr, nullptr, nullptr}; bool draw_ev_used[4] = {false, false, false, false}; int drqn_grp_par = 0, drqn_one_par = 0;
     unsigned long long* drqn_stamps = nullptr;      // timing probe of the fused recurrent step (DQN_DRQN_STAMPS)
     bool launch_failed = false;      // a launcher refused (an LDS attribute the device would not grant): reported by the entry point that enqueued the step
     bool drqn_fused = false;      // recurrent step = the column-parallel launch (which gathers its own episode rows) + the Adam launch (drqn_cols.hip)
-    hipGraphExec_t g_pgv[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // [take_pre][pregather] variants of the sampled single-device step
-    hipGraphExec_t g_mid = nullptr; int mid_group = 4;                          // mid_group consecutive middle steps of dqn_train_steps as one graph
-    bool mid_big_warm = false;                                                  // g_mid_big has been launched at least once (its first launch is the expensive one)
-    hipGraphExec_t g_mid_big = nullptr; int mid_big = 16;                       // ... and runs of mid_big of them (DQN_MID_BIG; 0 = off): 20 steps = first + 16 + 2 single + last
-    hipGraphExec_t g_pre1[3] = {nullptr, nullptr, nullptr}, g_pre2 = nullptr;
-    hipGraphExec_t g_dp_one[4] = {nullptr, nullptr, nullptr, nullptr}; int dp_one_state = 0;      // replicas: the WHOLE step incl. its collective(s) as ONE graph ([take_pre][pregather]); state 0 untried, 1 works, -1 RCCL refused the capture      // dp_overlap: first half cut in two ([0] sampled, [1] given indices, [2] without the gather launch)
-    hipGraphExec_t g_pre_tp = nullptr, g_post_pg = nullptr;                      // replicas: first half without the gather launch / second half whose Adam launch gathers
+    bool mid_big_warm = false;      // the graph of MID_BIG middle steps (dqn_train_steps) has been launched at least once (its first launch is the expensive one)
+    int dp_one_state = 0;           // replicas: the WHOLE step incl. its collective(s) as ONE graph (PH_DP_ONE); state 0 untried, 1 works, -1 RCCL refused the capture
     AdamSegs adam_segs; long final_reduce_step = -1;   // deferred dW slabs: reduced inside k_adam unless a communicator needs the materialised gradient
     std::vector<void*> prog_allocs; std::vector<std::string> prog_names;
     // profiling
@@ -139,7 +135,6 @@ struct dqn_engine {
 void prof_begin(dqn_engine* e, const char* name);
 void prof_end(dqn_engine* e);
 #define RUN(e, name, call) do { prof_begin(e, name); call; prof_end(e); } while (0)
-enum { PH_ALL = 0, PH_PRE = 1, PH_POST = 2, PH_PRE1 = 3, PH_PRE2 = 4, PH_DP_ONE = 5 };      // PRE = PRE1 (up to the point where the wide layers' operands are final) + PRE2 (the rest of the backward pass)
 template <class T> static int dmalloc(T** p, size_t n) {
     hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
     if (e != hipSuccess) return fail("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
@@ -152,10 +147,11 @@ template <class T> static int dmalloc(T** p, size_t n) {
 void drop_graphs(dqn_engine* e);
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a);
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name);
-void enqueue_step(dqn_engine* e, bool sample, int phase);
-int capture(dqn_engine* e, bool sample, int phase, hipGraphExec_t* out, int repeat = 1);
+void enqueue_step(dqn_engine* e, const StepKey& k);
+int capture_graph(dqn_engine* e, const char* what, const std::function<int()>& body, hipGraphExec_t* out);      // the one stream capture of the library
+int run_phase(dqn_engine* e, const StepKey& k, bool eager = false);      // the cached graph of k (captured on first use), or k enqueued eagerly
 int exchange_grads(dqn_engine* e);      // the one collective of a data-parallel step (all-gather or all-reduce)
-int run_step(dqn_engine* e, bool sample, bool take_pre = false, bool pregather = false);
+int run_step(dqn_engine* e, bool sample, bool take_pre = false, bool pregather = false, bool publish = false, bool* published = nullptr);
 int fetch_scalars(dqn_engine* e, float* loss, float* gn);
 int policy_ws(dqn_engine* e, int n);
 int policy_state(dqn_engine* e, int n, bool force_reset);

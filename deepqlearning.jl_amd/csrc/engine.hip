@@ -219,12 +219,9 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     if (build_layers(layers, n_layers, hp, e->L, &e->last_base, &e->last_val, &e->last_adv, &e->P, &e->Pint)) return -1;
     e->nl = n_layers;
     read_opts(e->opt);      // every experiment / test switch, once; nothing below (or later) looks at the environment
-    e->no_tiny = e->opt.no_tiny != 0;
-    e->mid_group = e->opt.mid_group;      // middle steps of dqn_train_steps per graph launch (1 = one step per graph: no grouped graphs at all)
-    e->mid_big = e->opt.mid_group > 1 ? e->opt.mid_big : 0;
-    { const int lopt = (e->opt.fwd_m32 > 0 ? DQN_LOPT_FWD_M32 : 0) | (e->opt.fwd_m32 == 0 ? DQN_LOPT_NO_FWD_M32 : 0) | (e->opt.no_dx_wide ? DQN_LOPT_NO_DX_WIDE : 0) | (e->opt.no_fwd_wres ? DQN_LOPT_NO_FWD_WRES : 0) |
+    { const int lopt = (e->opt.fwd_m32 > 0 ? DQN_LOPT_FWD_M32 : 0) | (e->opt.fwd_m32 == 0 ? DQN_LOPT_NO_FWD_M32 : 0) | (e->opt.no_fwd_wres ? DQN_LOPT_NO_FWD_WRES : 0) |
                        ((std::min(255, std::max(0, e->opt.dw_split / 16)) & 0xff) << 8) | 
-                       ((!e->opt.no_st_wt && (long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
+                       (((long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
@@ -309,29 +306,16 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     return 0;
 }
 
+static void drop_act_graphs(dqn_engine::ActProg& a) {
+    for (hipGraphExec_t* g : {&a.graph, &a.cycle, &a.envc}) if (*g) { hipGraphExecDestroy(*g); *g = nullptr; }
+}
 void drop_graphs(dqn_engine* e) {
-    for (int i = 0; i < 2; i++) {
-        if (e->g_full[i]) { hipGraphExecDestroy(e->g_full[i]); e->g_full[i] = nullptr; }
-        if (e->g_full_pub[i]) { hipGraphExecDestroy(e->g_full_pub[i]); e->g_full_pub[i] = nullptr; }
-        if (e->g_pre[i]) { hipGraphExecDestroy(e->g_pre[i]); e->g_pre[i] = nullptr; }
-        for (int j = 0; j < 2; j++) if (e->g_pgv[i][j]) { hipGraphExecDestroy(e->g_pgv[i][j]); e->g_pgv[i][j] = nullptr; }
-    }
-    if (e->g_pgv_pub) { hipGraphExecDestroy(e->g_pgv_pub); e->g_pgv_pub = nullptr; }
-    if (e->g_post) { hipGraphExecDestroy(e->g_post); e->g_post = nullptr; }
-    if (e->g_post_pg) { hipGraphExecDestroy(e->g_post_pg); e->g_post_pg = nullptr; }
-    if (e->g_mid) { hipGraphExecDestroy(e->g_mid); e->g_mid = nullptr; }
-    for (int k = 0; k < 2; k++) { if (e->g_drqn_k[k]) { hipGraphExecDestroy(e->g_drqn_k[k]); e->g_drqn_k[k] = nullptr; } if (e->g_drqn[k]) { hipGraphExecDestroy(e->g_drqn[k]); e->g_drqn[k] = nullptr; } }
-    if (e->g_mid_big) { hipGraphExecDestroy(e->g_mid_big); e->g_mid_big = nullptr; } e->mid_big_warm = false;
-    if (e->g_pre_tp) { hipGraphExecDestroy(e->g_pre_tp); e->g_pre_tp = nullptr; }
-    for (int i = 0; i < 3; i++) if (e->g_pre1[i]) { hipGraphExecDestroy(e->g_pre1[i]); e->g_pre1[i] = nullptr; }
-    for (int i = 0; i < 4; i++) if (e->g_dp_one[i]) { hipGraphExecDestroy(e->g_dp_one[i]); e->g_dp_one[i] = nullptr; }
-    if (e->g_pre2) { hipGraphExecDestroy(e->g_pre2); e->g_pre2 = nullptr; }
-    for (dqn_engine::ActProg* a : {&e->act, &e->evalp}) { if (a->graph) { hipGraphExecDestroy(a->graph); a->graph = nullptr; } if (a->cycle) { hipGraphExecDestroy(a->cycle); a->cycle = nullptr; } if (a->envc) { hipGraphExecDestroy(a->envc); a->envc = nullptr; } }
+    for (auto& sg : e->graphs) hipGraphExecDestroy(sg.g);
+    e->graphs.clear(); e->mid_big_warm = false;
+    drop_act_graphs(e->act); drop_act_graphs(e->evalp);
 }
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a) {
-    if (a.graph) { hipGraphExecDestroy(a.graph); a.graph = nullptr; }
-    if (a.cycle) { hipGraphExecDestroy(a.cycle); a.cycle = nullptr; }
-    if (a.envc) { hipGraphExecDestroy(a.envc); a.envc = nullptr; }
+    drop_act_graphs(a);
     if (!a.allocs.empty()) hipStreamSynchronize(e->stream);
     for (void* p : a.allocs) hipFree(p);
     a.allocs.clear(); a.steps.clear(); a.n = 0;
@@ -584,68 +568,109 @@ void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X,
     prof_end(e);
 }
 
-void enqueue_step(dqn_engine* e, bool sample, int phase) {
-    e->step_sampled = sample;
-    if (phase == PH_PRE2) { for (size_t i = e->prog_pre1_end; i < e->prog_post_begin; i++) { if ((long)i == e->final_reduce_step && ((e->adam_segs.n > 0 && !e->comm && !e->sim_world) || (e->dp_gather && e->dp_pack_folds))) continue; RUN(e, e->prog[i].name, e->prog[i].fn(e)); } return; }
-    if (phase != PH_POST) {
-        if (e->hp.recurrence) {
-            EpGatherArgs g; g.ep_s = e->ep_s; g.ep_sp = e->ep_sp; g.ep_a = e->ep_a; g.ep_r = e->ep_r; g.ep_done = e->ep_done; g.ep_len = e->ep_len; g.ep_idx = e->ep_idx; g.ep_start = e->ep_start;
-            g.E = e->E; g.B = e->B; g.T = e->T; g.x0 = e->x0; g.a_out = e->r_a; g.r_out = e->r_r; g.done_out = e->r_done; g.mask_out = e->r_mask;
-            if (!e->drqn_fused) RUN(e, "gather_episodes", launch_gather_episodes(e->stream, g));      // the fused recurrent step gathers its own columns (drqn_cols.hip)
-        } else {
-            // the descent is fused into the gather (every workgroup repeats it) while that is cheaper than a launch of its own:
-            // small batches.  At B = 512 / 1e6 leaves the repeats cost more than the ~5 us launch, so sample once, then gather.
-            // hp.sample_distinct (r05): the fused launch's workgroups dedupe the list themselves (gather_distinct_list) -- except on the u8-rows-to-float-arena kernel,
-            // which keeps its own index code: there one workgroup draws AND dedupes (k_sample), then the gather reads the list
-            const bool dist_fused_ok = !(e->hp.obs_dtype == DQN_OBS_U8 && !e->arena_u8 && (e->E & 3) == 0);
-            const bool fused = sample && e->B <= 64 && (!e->hp.sample_distinct || dist_fused_ok);
-            if (e->step_take_pre || e->tiny) {}      // the previous step's Adam launch gathered this batch (PreGather) / the step's one launch gathers itself (tiny_step.hip)
-            else {
-            if (sample && !fused) RUN(e, "sample", launch_sample(e->stream, e->B, e->cap2, e->tree, e->hp.seed, e->idx, e->state, 0, e->hp.sample_distinct));    // k_td bumps the Philox counter
-            BatchMeta bm; bm.a = e->ra; bm.r = e->rr; bm.done = e->rdone; bm.beta = e->hp.prio_beta; bm.a_out = e->gb_a2; bm.r_out = e->gb_r2; bm.done_out = e->gb_done2; bm.w_out = e->gb_w2; bm.distinct = e->hp.sample_distinct ? 1 : 0;
-            RUN(e, fused ? "sample_gather" : "gather", launch_gather_fb(e->stream, e->s_rows, e->sp_rows, e->hp.obs_dtype == DQN_OBS_U8, e->E, e->B, e->idx, e->x0,
-                                                                        fused ? 1 : 0, e->cap2, e->tree, e->hp.seed, e->state, bm, (e->hp.sample_distinct && !fused) ? nullptr : e->idx_pre, e->arena_u8 ? 1 : 0));
+void enqueue_step(dqn_engine* e, const StepKey& k) {
+    const bool fold_final = (e->adam_segs.n > 0 && !e->comm && !e->sim_world) || (e->dp_gather && e->dp_pack_folds);      // the final slab reduce is folded into k_adam / k_dp_pack
+    auto run_pre = [&](size_t beg, size_t end) { for (size_t i = beg; i < end; i++) if (!(fold_final && (long)i == e->final_reduce_step)) RUN(e, e->prog[i].name, e->prog[i].fn(e)); };
+    for (int r = 0; r < k.repeat; r++) {
+        e->cur = k; e->cur.slot = k.slot + r;
+        if (k.phase == PH_PRE2) { run_pre(e->prog_pre1_end, e->prog_post_begin); continue; }
+        if (k.phase != PH_POST) {
+            if (e->hp.recurrence) {
+                EpGatherArgs g; g.ep_s = e->ep_s; g.ep_sp = e->ep_sp; g.ep_a = e->ep_a; g.ep_r = e->ep_r; g.ep_done = e->ep_done; g.ep_len = e->ep_len; g.ep_idx = e->ep_idx; g.ep_start = e->ep_start;
+                g.E = e->E; g.B = e->B; g.T = e->T; g.x0 = e->x0; g.a_out = e->r_a; g.r_out = e->r_r; g.done_out = e->r_done; g.mask_out = e->r_mask;
+                if (!e->drqn_fused) RUN(e, "gather_episodes", launch_gather_episodes(e->stream, g));      // the fused recurrent step gathers its own columns (drqn_cols.hip)
+            } else if (!k.take_pre && !e->tiny) {      // (take_pre: the previous step's Adam launch gathered this batch (PreGather); tiny: the step's one launch gathers itself, tiny_step.hip)
+                // the descent is fused into the gather (every workgroup repeats it) while that is cheaper than a launch of its own:
+                // small batches.  At B = 512 / 1e6 leaves the repeats cost more than the ~5 us launch, so sample once, then gather.
+                // hp.sample_distinct (r05): the fused launch's workgroups dedupe the list themselves (gather_distinct_list) -- except on the u8-rows-to-float-arena kernel,
+                // which keeps its own index code: there one workgroup draws AND dedupes (k_sample), then the gather reads the list
+                const bool dist_fused_ok = !(e->hp.obs_dtype == DQN_OBS_U8 && !e->arena_u8 && (e->E & 3) == 0);
+                const bool fused = k.sampled && e->B <= 64 && (!e->hp.sample_distinct || dist_fused_ok);
+                if (k.sampled && !fused) RUN(e, "sample", launch_sample(e->stream, e->B, e->cap2, e->tree, e->hp.seed, e->idx, e->state, 0, e->hp.sample_distinct));    // k_td bumps the Philox counter
+                BatchMeta bm; bm.a = e->ra; bm.r = e->rr; bm.done = e->rdone; bm.beta = e->hp.prio_beta; bm.a_out = e->gb_a2; bm.r_out = e->gb_r2; bm.done_out = e->gb_done2; bm.w_out = e->gb_w2; bm.distinct = e->hp.sample_distinct ? 1 : 0;
+                RUN(e, fused ? "sample_gather" : "gather", launch_gather_fb(e->stream, e->s_rows, e->sp_rows, e->hp.obs_dtype == DQN_OBS_U8, e->E, e->B, e->idx, e->x0,
+                                                                            fused ? 1 : 0, e->cap2, e->tree, e->hp.seed, e->state, bm, (e->hp.sample_distinct && !fused) ? nullptr : e->idx_pre, e->arena_u8 ? 1 : 0));
             }
+            run_pre(0, k.phase == PH_PRE1 ? e->prog_pre1_end : e->prog_post_begin);
         }
-        for (size_t i = 0; i < (phase == PH_PRE1 ? e->prog_pre1_end : e->prog_post_begin); i++) {
-            if ((long)i == e->final_reduce_step && ((e->adam_segs.n > 0 && !e->comm && !e->sim_world) || (e->dp_gather && e->dp_pack_folds))) continue;   // folded into k_adam / k_dp_pack   // folded into k_adam
-            RUN(e, e->prog[i].name, e->prog[i].fn(e));
-        }
+        if (k.phase != PH_PRE && k.phase != PH_PRE1) for (size_t i = e->prog_post_begin; i < e->prog.size(); i++) RUN(e, (k.pregather && (long)i == e->adam_step) ? "adam+gather" : e->prog[i].name, e->prog[i].fn(e));
+        if (k.publish && k.phase == PH_ALL)
+            RUN(e, "publish", launch_publish_scalars(e->stream, e->state, e->gmax_part, (e->gmax_used > 0 && e->gmax_used <= gmax_slots(e->Pint)) ? e->gmax_used : gmax_slots(e->Pint), e->pub_ctr, e->mail_dev));
     }
-    if (phase != PH_PRE && phase != PH_PRE1) for (size_t i = e->prog_post_begin; i < e->prog.size(); i++) RUN(e, (e->step_pregather && (long)i == e->adam_step) ? "adam+gather" : e->prog[i].name, e->prog[i].fn(e));
-    if (e->step_publish && phase == PH_ALL)
-        RUN(e, "publish", launch_publish_scalars(e->stream, e->state, e->gmax_part, (e->gmax_used > 0 && e->gmax_used <= gmax_slots(e->Pint)) ? e->gmax_used : gmax_slots(e->Pint), e->pub_ctr, e->mail_dev));
+    e->cur = StepKey();
 }
-int exchange_grads(dqn_engine* e);
-int exchange_segment(dqn_engine* e, int seg);
-int capture(dqn_engine* e, bool sample, int phase, hipGraphExec_t* out, int repeat) {
-    hipGraph_t g;
+// the one stream capture of the library.  body() enqueues on e->stream and returns nonzero if it could not (a collective refused); a launch refused during capture never
+// becomes a graph node, so a HIP error or a refusing launcher (launch_failed: dynamic LDS the device would not grant) fails the capture too.  The FIRST launch of an
+// executable graph prepares its packets on the device side; the upload does that here instead, so that a short timed call (the driver's 20 steps launch the 4-step middle
+// graph for the first time inside the timed region: its warm-up of 5 steps is too short to reach it) does not pay it
+int capture_graph(dqn_engine* e, const char* what, const std::function<int()>& body, hipGraphExec_t* out) {
+    hipGraph_t g = nullptr;
     (void)hipGetLastError();
     HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    int xrc = 0;
-    if (phase == PH_DP_ONE) {
-        // the replica step with its collective(s) INSIDE the graph (RCCL supports stream capture): one graph launch and no host-side collective enqueue
-        // per step.  dp_overlap: the exchange stream is forked from / joined to the captured stream with events, so all-gather A runs beside PRE2.
+    const int brc = body();
+    hipError_t lerr = hipGetLastError();
+    if (e->launch_failed) { e->launch_failed = false; if (lerr == hipSuccess) lerr = hipErrorInvalidValue; }
+    const hipError_t ce = hipStreamEndCapture(e->stream, &g);
+    if (ce != hipSuccess || lerr != hipSuccess || brc) {
+        (void)hipGetLastError(); if (ce == hipSuccess) hipGraphDestroy(g);
+        return fail("capturing %s failed (%s%s)", what, hipGetErrorString(ce != hipSuccess ? ce : lerr), brc ? "; collective refused" : "");
+    }
+    const hipError_t ie = hipGraphInstantiate(out, g, nullptr, nullptr, 0);
+    if (ie == hipSuccess) (void)hipGraphUpload(*out, e->stream);
+    (void)hipGetLastError(); hipGraphDestroy(g);
+    if (ie != hipSuccess) { *out = nullptr; return fail("instantiating the graph of %s failed (%s)", what, hipGetErrorString(ie)); }
+    return 0;
+}
+// what the graph of a phase depends on: PRE2 reads no variant field, POST only the Adam launch's pregather, PRE / PRE1 sampled and take_pre
+static StepKey graph_key(const StepKey& k) {
+    StepKey n; n.phase = k.phase;
+    if (k.phase == PH_POST) n.pregather = k.pregather;
+    else if (k.phase != PH_PRE2) {
+        n.sampled = k.sampled; n.take_pre = k.take_pre;
+        if (k.phase == PH_ALL || k.phase == PH_DP_ONE) n.pregather = k.pregather;
+        if (k.phase == PH_ALL) { n.publish = k.publish; n.repeat = k.repeat; n.slot = k.slot; }
+    }
+    return n;
+}
+int exchange_segment(dqn_engine* e, int seg);
+// PH_DP_ONE: the replica step with its collective(s) INSIDE the graph (RCCL supports stream capture): one graph launch and no host-side collective enqueue per step.
+// dp_overlap: the exchange stream is forked from / joined to the captured stream with events, so all-gather A runs beside PRE2.
+static int capture_step(dqn_engine* e, const StepKey& k, hipGraphExec_t* out) {
+    return capture_graph(e, "the train step", [&]() {
+        if (k.phase != PH_DP_ONE) { enqueue_step(e, k); return 0; }
+        StepKey p = k; int xrc = 0;
+        auto phase = [&](int ph) { p.phase = ph; enqueue_step(e, p); };
         if (e->dp_gather && e->dp_overlap) {
-            enqueue_step(e, sample, PH_PRE1);
+            phase(PH_PRE1);
             hipEventRecord(e->ev_xa, e->stream); hipStreamWaitEvent(e->stream3, e->ev_xa, 0); xrc |= exchange_segment(e, 0);
-            enqueue_step(e, sample, PH_PRE2);
+            phase(PH_PRE2);
             hipEventRecord(e->ev_xb, e->stream); hipStreamWaitEvent(e->stream3, e->ev_xb, 0); xrc |= exchange_segment(e, 1);
             hipEventRecord(e->ev_xc, e->stream3); hipStreamWaitEvent(e->stream, e->ev_xc, 0);
-            enqueue_step(e, sample, PH_POST);
-        } else { enqueue_step(e, sample, PH_PRE); xrc |= exchange_grads(e); enqueue_step(e, sample, PH_POST); }
-    } else
-    for (int r = 0; r < repeat; r++) enqueue_step(e, sample, phase);
-    hipError_t lerr = hipGetLastError();          // a launch refused during capture never becomes a graph node
-    if (e->launch_failed) { e->launch_failed = false; if (lerr == hipSuccess) lerr = hipErrorInvalidValue; }      // a launcher could not get the dynamic LDS it needs on this device
-    { const hipError_t ce = hipStreamEndCapture(e->stream, &g); if (ce != hipSuccess || xrc) { (void)hipGetLastError(); if (ce == hipSuccess) hipGraphDestroy(g); return fail("capturing the train step failed (%s%s)", hipGetErrorString(ce), xrc ? "; collective refused" : ""); } }
-    if (lerr != hipSuccess) { hipGraphDestroy(g); return fail("HIP error %s while capturing the train step", hipGetErrorString(lerr)); }
-    HIPCHK(hipGraphInstantiate(out, g, nullptr, nullptr, 0));
-    // the FIRST launch of an executable graph prepares its packets on the device side; done here instead, a short timed call (the driver's 20 steps
-    // launch the 4-step middle graph for the first time inside the timed region: its warm-up of 5 steps is too short to reach it) does not pay it
-    if (!e->opt.no_graph_upload) (void)hipGraphUpload(*out, e->stream);
-    (void)hipGetLastError();
-    HIPCHK(hipGraphDestroy(g)); return 0;
+            phase(PH_POST);
+        } else { phase(PH_PRE); xrc |= exchange_grads(e); phase(PH_POST); }
+        return xrc;
+    }, out);
+}
+// the cached graph of k's variant, captured on first use (nullptr: the capture failed, message set)
+static hipGraphExec_t get_or_capture(dqn_engine* e, const StepKey& key) {
+    const StepKey k = graph_key(key);
+    for (const auto& sg : e->graphs) if (sg.key == k) return sg.g;
+    hipGraphExec_t g = nullptr;
+    if (capture_step(e, k, &g)) return nullptr;
+    e->graphs.push_back({k, g}); return g;
+}
+// eager (use_graph == 0, a profiled step, or `eager`): the launches themselves -- a refused launch (bad LDS size, bad grid) is an error, not a silent no-op
+int run_phase(dqn_engine* e, const StepKey& k, bool eager) {
+    if (!eager && e->hp.use_graph && !e->profiling) {
+        const hipGraphExec_t g = get_or_capture(e, k);
+        if (!g) return -1;
+        const hipError_t le = hipGraphLaunch(g, e->stream);
+        return le == hipSuccess ? 0 : fail("HIP error %s launching the train-step graph", hipGetErrorString(le));
+    }
+    enqueue_step(e, k);
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess || e->launch_failed) { e->launch_failed = false; return fail("HIP error %s enqueuing the train step", hipGetErrorString(le)); }
+    return 0;
 }
 // dp_overlap: segment 0 = the wide layers' operands [0, dp_count_a) -> dp_recv, segment 1 = the small gradients [dp_count_a, dp_count) -> dp_recv_b, both on stream3
 int exchange_segment(dqn_engine* e, int seg) {
@@ -670,83 +695,56 @@ int exchange_grads(dqn_engine* e) {
     if (rc) return fail("ncclAllReduce failed: %s", g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "?");
     return 0;
 }
-// take_pre / pregather: only dqn_train_steps sets them (a sampled step follows / preceded this one and nothing touches the replay in between)
-int run_step(dqn_engine* e, bool sample, bool take_pre, bool pregather) {
+// take_pre / pregather: only dqn_train_steps sets them (a sampled step follows / preceded this one and nothing touches the replay in between).  publish: the step also writes
+// (loss, grad_norm) into the host mailbox (dqn_train_step with scalar outputs, dqn_train_step_async, the last step of dqn_train_steps); *published: it did
+int run_step(dqn_engine* e, bool sample, bool take_pre, bool pregather, bool publish, bool* published) {
+    if (published) *published = false;
     if (build_program(e)) return -1;
-    const int gi = sample ? 0 : 1;
-    e->step_take_pre = e->step_pregather = false;
-    if (sample && e->pg_ok && (take_pre || pregather) && e->world <= 1 && !(e->comm && e->force_comm)) {
-        e->step_take_pre = take_pre; e->step_pregather = pregather;
-        const bool pub = e->step_publish && e->mail_dev != nullptr && take_pre && !pregather; e->step_publish = pub;      // the LAST step of a dqn_train_steps call may publish its scalars
-        int rc = 0;
-        if (e->hp.use_graph && !e->profiling) {
-            hipGraphExec_t& g = pub ? e->g_pgv_pub : e->g_pgv[take_pre ? 1 : 0][pregather ? 1 : 0];
-            if (!g && capture(e, true, PH_ALL, &g)) rc = -1; else HIPCHK(hipGraphLaunch(g, e->stream));
-        } else { enqueue_step(e, true, PH_ALL); HIPCHK(hipGetLastError()); }
-        e->step_take_pre = e->step_pregather = false; e->step_publish = false;
-        if (!rc && pub) e->pub_issued++;
-        return rc;
-    }
-    if (e->world > 1 || (e->comm && e->force_comm)) {      // data-parallel replicas (also DQN_SIM_WORLD: world = k without a communicator)
+    StepKey k; k.sampled = sample;
+    int rc = 0; bool pub = false;
+    if (e->world <= 1 && !(e->comm && e->force_comm)) {
+        if (sample && e->pg_ok && (take_pre || pregather)) { k.take_pre = take_pre; k.pregather = pregather; publish = publish && take_pre && !pregather; }      // only the LAST step of a dqn_train_steps call publishes
+        pub = k.publish = publish && e->mail_dev != nullptr;
+        rc = run_phase(e, k);
+    } else {      // data-parallel replicas (also DQN_SIM_WORLD: world = k without a communicator)
         // scalars on replicas (r05): the publish launch is enqueued EAGERLY behind the step (behind the exchange and the Adam launch that takes grad_norm after it), outside the
         // step's graphs -- one kernel boundary, no fold launch / D2H copy / stream synchronize, so the drop-in seam costs a replica what it costs a single device
-        const bool pub_dp = e->step_publish && e->mail_dev != nullptr && !e->profiling; e->step_publish = false;
-        auto publish_dp = [&]() { if (!pub_dp) return; launch_publish_scalars(e->stream, e->state, e->gmax_part, (e->gmax_used > 0 && e->gmax_used <= gmax_slots(e->Pint)) ? e->gmax_used : gmax_slots(e->Pint), e->pub_ctr, e->mail_dev); e->pub_issued++; };
+        pub = publish && e->mail_dev != nullptr && !e->profiling;
         // the pre-gather is rank-local (own replay, own arena), so it works on replicas too: first half without the gather launch, the Adam
         // launch of the second half gathers the next batch.  Every rank takes the same variant (same configuration, same call).
-        const bool tp = sample && e->pg_ok && take_pre, pgth = sample && e->pg_ok && pregather;
-        e->step_take_pre = tp; e->step_pregather = pgth;
-        int rc = 0;
-        if (!e->opt.dp_no_one_graph && e->hp.use_graph && !e->profiling && !e->sim_world && e->comm && e->dp_one_state >= 0) {
-            hipGraphExec_t& g = e->g_dp_one[(tp ? 2 : 0) + (pgth ? 1 : 0) + 0];
-            if (!g && gi == 0) { if (capture(e, sample, PH_DP_ONE, &g)) { e->dp_one_state = -1; g = nullptr; } else e->dp_one_state = 1; }
-            if (g && gi == 0) { HIPCHK(hipGraphLaunch(g, e->stream)); e->step_take_pre = e->step_pregather = false; publish_dp(); return 0; }
-        }
-        if (e->dp_gather && e->dp_overlap) {
+        k.take_pre = sample && e->pg_ok && take_pre; k.pregather = sample && e->pg_ok && pregather;
+        const bool graph = e->hp.use_graph && !e->profiling;
+        const bool one_graph = graph && sample && !e->opt.dp_no_one_graph && !e->sim_world && e->comm;      // the whole step as one graph, unless RCCL refuses the capture
+        StepKey one = k, k1 = k, k2 = k, k3 = k; one.phase = PH_DP_ONE;
+        if (one_graph && e->dp_one_state >= 0) e->dp_one_state = get_or_capture(e, one) ? 1 : -1;
+        if (one_graph && e->dp_one_state > 0) rc = run_phase(e, one);
+        else if (e->dp_gather && e->dp_overlap) {
             // three segments: [.. head level, pack of the wide operands] | all-gather A on stream3, concurrently: [rest of the backward pass, pack of the small
             // gradients] | all-gather B on stream3 | [wide dW over the gathered samples, sum over ranks, Adam]
-            const bool gr = e->hp.use_graph && !e->profiling;
-            hipGraphExec_t& g1 = e->g_pre1[tp ? 2 : gi]; hipGraphExec_t& gpost = pgth ? e->g_post_pg : e->g_post;
-            if (gr) { if (!g1 && capture(e, sample, PH_PRE1, &g1)) rc = -1; if (!rc && !e->g_pre2 && capture(e, sample, PH_PRE2, &e->g_pre2)) rc = -1; if (!rc && !gpost && capture(e, sample, PH_POST, &gpost)) rc = -1; }
+            k1.phase = PH_PRE1; k2.phase = PH_PRE2; k3.phase = PH_POST;
+            if (graph && (!get_or_capture(e, k1) || !get_or_capture(e, k2) || !get_or_capture(e, k3))) rc = -1;
+            if (!rc) rc = run_phase(e, k1);
+            if (!rc) { HIPCHK(hipEventRecord(e->ev_xa, e->stream)); HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_xa, 0)); rc = exchange_segment(e, 0); }
+            if (!rc) rc = run_phase(e, k2);
             if (!rc) {
-                if (gr) HIPCHK(hipGraphLaunch(g1, e->stream)); else { enqueue_step(e, sample, PH_PRE1); HIPCHK(hipGetLastError()); }
-                HIPCHK(hipEventRecord(e->ev_xa, e->stream)); HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_xa, 0));
-                if (exchange_segment(e, 0)) rc = -1;
-            }
-            if (!rc) {
-                if (gr) HIPCHK(hipGraphLaunch(e->g_pre2, e->stream)); else { enqueue_step(e, sample, PH_PRE2); HIPCHK(hipGetLastError()); }
                 HIPCHK(hipEventRecord(e->ev_xb, e->stream)); HIPCHK(hipStreamWaitEvent(e->stream3, e->ev_xb, 0));
-                if (exchange_segment(e, 1)) rc = -1;
+                rc = exchange_segment(e, 1);
                 HIPCHK(hipEventRecord(e->ev_xc, e->stream3)); HIPCHK(hipStreamWaitEvent(e->stream, e->ev_xc, 0));
             }
-            if (!rc) { if (gr) HIPCHK(hipGraphLaunch(gpost, e->stream)); else { enqueue_step(e, sample, PH_POST); HIPCHK(hipGetLastError()); } }
+            if (!rc) rc = run_phase(e, k3);
+        } else {      // two halves around the collective
+            k1.phase = PH_PRE; k3.phase = PH_POST;
+            if (graph && (!get_or_capture(e, k1) || !get_or_capture(e, k3))) rc = -1;
+            if (!rc) rc = run_phase(e, k1);
+            if (!rc) rc = exchange_grads(e);
+            if (!rc) rc = run_phase(e, k3);
         }
-        else if (e->hp.use_graph && !e->profiling) {
-            hipGraphExec_t& gpre = tp ? e->g_pre_tp : e->g_pre[gi];
-            hipGraphExec_t& gpost = pgth ? e->g_post_pg : e->g_post;
-            if (!gpre && capture(e, sample, PH_PRE, &gpre)) rc = -1;
-            if (!rc && !gpost && capture(e, sample, PH_POST, &gpost)) rc = -1;
-            if (!rc) {
-                HIPCHK(hipGraphLaunch(gpre, e->stream));
-                if (exchange_grads(e)) rc = -1;
-                else HIPCHK(hipGraphLaunch(gpost, e->stream));
-            }
-        } else { enqueue_step(e, sample, PH_PRE); HIPCHK(hipGetLastError()); if (exchange_grads(e)) rc = -1; else { enqueue_step(e, sample, PH_POST); HIPCHK(hipGetLastError()); } }
-        e->step_take_pre = e->step_pregather = false;
-        if (!rc) publish_dp();
-        return rc;
+        if (!rc && pub) launch_publish_scalars(e->stream, e->state, e->gmax_part, (e->gmax_used > 0 && e->gmax_used <= gmax_slots(e->Pint)) ? e->gmax_used : gmax_slots(e->Pint), e->pub_ctr, e->mail_dev);
     }
-    // publish (dqn_train_step with scalar outputs, dqn_train_step_async): the step's last launch also writes (loss, grad_norm) into the host mailbox
-    const bool pub = e->step_publish && e->mail_dev != nullptr; e->step_publish = pub;
-    int rc = 0;
-    if (e->hp.use_graph && !e->profiling) {
-        hipGraphExec_t& g = pub ? e->g_full_pub[gi] : e->g_full[gi];
-        if (!g && capture(e, sample, PH_ALL, &g)) rc = -1;
-        else { const hipError_t le = hipGraphLaunch(g, e->stream); if (le != hipSuccess) rc = fail("HIP error %s launching the train-step graph", hipGetErrorString(le)); }
-    } else { enqueue_step(e, sample, PH_ALL); const hipError_t le = hipGetLastError(); if (le != hipSuccess || e->launch_failed) { e->launch_failed = false; rc = fail("HIP error %s enqueuing the train step", hipGetErrorString(le)); } }      // eager launches: a refused launch (bad LDS size, bad grid) is an error, not a silent no-op
-    e->step_publish = false;
-    if (!rc && pub) e->pub_issued++;
-    return rc;
+    if (rc || !pub) return rc;
+    e->pub_issued++;
+    if (published) *published = true;
+    return 0;
 }
 // ---- the scalar mailbox, host side
 static inline void cpu_relax() {
@@ -850,8 +848,7 @@ extern "C" int dqn_train_step(dqn_engine_t* e, const int64_t* idx, float* loss, 
     // no stream synchronize; the host spins on the record
     const bool mail = (loss || grad_norm) && !td_out && mailbox_ok(e);
     if (mail && mail_reserve(e)) return -1;
-    e->step_publish = mail;
-    if (run_step(e, idx == nullptr)) return -1;
+    if (run_step(e, idx == nullptr, false, false, mail)) return -1;
     if (mail) return wait_mail(e, e->pub_issued, true, loss, grad_norm, nullptr);
     if (td_out) HIPCHK(hipMemcpyAsync(td_out, e->td, (size_t)e->B * 4, hipMemcpyDeviceToHost, e->stream));
     if (loss || grad_norm || td_out) return fetch_scalars(e, loss, grad_norm);
@@ -881,8 +878,7 @@ extern "C" int dqn_train_step_async(dqn_engine_t* e, const int64_t* idx, uint64_
         return 0;
     }
     if (mail_reserve(e)) return -1;
-    e->step_publish = true;
-    if (run_step(e, idx == nullptr)) return -1;
+    if (run_step(e, idx == nullptr, false, false, true)) return -1;
     if (ticket) *ticket = e->pub_issued;
     return 0;
 }
@@ -910,11 +906,11 @@ extern "C" int dqn_sim_ranks_step(dqn_engine_t* e, const int64_t* idx, float* lo
     if (!e->dp_gather) return fail("DQN_SIM_WORLD needs the gather exchange (no wide dense layer in this network, or DQN_DP_ALLREDUCE is set)");
     if (!e->sim_idx) { DM(e->sim_idx, (size_t)k * B); DM(e->sim_td, (size_t)k * B); }      // per-rank index / TD copies: owned by the engine, allocated once (sim_world and B are fixed at create)
     long long* s_idx = e->sim_idx; float* s_td = e->sim_td;
+    StepKey pre, post; pre.phase = PH_PRE; post.phase = PH_POST; pre.sampled = post.sampled = false;      // the given-indices PRE graph and the POST graph of run_step
     int rc = 0;
     for (int r = 0; r < k && !rc; r++) {
         HIPCHK(hipMemcpyAsync(e->idx, idx + (size_t)r * B, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
-        if (e->hp.use_graph) { if (!e->g_pre[1] && capture(e, false, PH_PRE, &e->g_pre[1])) { rc = -1; break; } HIPCHK(hipGraphLaunch(e->g_pre[1], e->stream)); }
-        else enqueue_step(e, false, PH_PRE);
+        if (run_phase(e, pre)) { rc = -1; break; }
         if (e->dp_overlap) {
             const size_t ca = e->dp_count_a, cb = e->dp_count - ca;
             HIPCHK(hipMemcpyAsync(e->dp_recv + (size_t)r * ca, e->dp_send, ca * 4, hipMemcpyDeviceToDevice, e->stream));
@@ -928,10 +924,7 @@ extern "C" int dqn_sim_ranks_step(dqn_engine_t* e, const int64_t* idx, float* lo
         if (loss) loss[r] = st.loss;
         if (r + 1 < k) { st.step -= 1; HIPCHK(hipMemcpy(e->state, &st, sizeof st, hipMemcpyHostToDevice)); }   // k_td counts train steps: the k halves are ONE step
     }
-    if (!rc) {
-        if (e->hp.use_graph) { if (!e->g_post && capture(e, false, PH_POST, &e->g_post)) rc = -1; else HIPCHK(hipGraphLaunch(e->g_post, e->stream)); }
-        else enqueue_step(e, false, PH_POST);
-    }
+    if (!rc) rc = run_phase(e, post);
     if (!rc && e->hp.prioritized_replay)
         for (int r = 0; r + 1 < k; r++) launch_update_priorities(e->stream, B, e->cap2, s_idx + (size_t)r * B, s_td + (size_t)r * B, e->hp.prio_eps, e->hp.prio_alpha, e->tree, e->state, 0, 1.0, 1.0, nullptr, 0);
     if (!rc && td_out) HIPCHK(hipMemcpyAsync(td_out, s_td, (size_t)k * B * 4, hipMemcpyDeviceToHost, e->stream));
@@ -946,42 +939,35 @@ extern "C" int dqn_train_steps(dqn_engine_t* e, int n, float* loss, float* grad_
     if (build_program(e)) return -1;
     // between the steps of this call nothing else touches the replay: step i's Adam launch gathers step i+1's batch (PreGather)
     // Middle steps (no gather launch, the Adam launch gathering) also exist as ONE graph of MID_GROUP consecutive steps: a graph launch costs ~2 us
-    // of stream time on top of its kernels (eager launches of the same step: 148.8 vs 150.9 us/step), which the group amortises.
-    const int MID_GROUP = e->mid_group; const bool pg = e->pg_ok;
+    // of stream time on top of its kernels (eager launches of the same step: 148.8 vs 150.9 us/step), which the group amortises; long calls take runs of MID_BIG
+    enum { MID_GROUP = 4, MID_BIG = 16 };      // 20 steps = first + 16 + 2 single + last once the big group is warm
+    const bool pg = e->pg_ok;
     const bool single = e->world <= 1 && !(e->comm && e->force_comm) && e->hp.use_graph && !e->profiling;
+    StepKey mid[2]; mid[0].take_pre = mid[0].pregather = pg; mid[0].repeat = MID_GROUP; mid[1] = mid[0]; mid[1].repeat = MID_BIG;
     if (single) {
         // every graph this call can need is captured up front (capturing executes nothing): a short timed call -- the driver's 20 steps -- must
         // not pay an instantiate in the middle
-        auto cap1 = [&](bool tp, bool pgth, hipGraphExec_t* g, int rep) { if (*g) return 0; e->step_take_pre = tp; e->step_pregather = pgth; const int rc = capture(e, true, PH_ALL, g, rep);
-                                                                         e->step_take_pre = e->step_pregather = false; return rc; };
-        if (pg) { if (cap1(false, true, &e->g_pgv[0][1], 1) || cap1(true, true, &e->g_pgv[1][1], 1) || cap1(true, false, &e->g_pgv[1][0], 1)) return -1; }
-        if (pg && mailbox_ok(e) && !e->g_pgv_pub) { e->step_publish = true; const int rc = cap1(true, false, &e->g_pgv_pub, 1); e->step_publish = false; if (rc) return -1; }      // last step + publish
-        if (MID_GROUP > 1 && cap1(pg, pg, &e->g_mid, MID_GROUP)) return -1;
+        StepKey first, middle, last, last_pub; first.pregather = true; middle.take_pre = middle.pregather = true; last.take_pre = true; last_pub = last; last_pub.publish = true;
+        if (pg && (!get_or_capture(e, first) || !get_or_capture(e, middle) || !get_or_capture(e, last))) return -1;
+        if (pg && mailbox_ok(e) && !get_or_capture(e, last_pub)) return -1;      // last step + publish
         // (ADVICE r03 suggested capturing the grouped graphs only in calls long enough to use them.  Measured, r04: the driver's `--steps 20 --warmup 5` then pays the capture
         // + instantiate of both grouped graphs INSIDE its 3 ms timed region -- 7100 -> 5984 steps/s.  They are captured by the first call, whatever its length: ~0.6 ms, once.)
-        if (e->mid_big > MID_GROUP && cap1(pg, pg, &e->g_mid_big, e->mid_big)) return -1;
+        if (!get_or_capture(e, mid[0]) || !get_or_capture(e, mid[1])) return -1;
     }
     for (int i = 0; i < n;) {
         // a run of identical steps: middle steps (pipelined gather) or, where that does not apply, any steps
-        const int BIG = e->mid_big;
+        auto fits = [&](int g) { return pg ? (i >= 1 && i + g <= n - 1) : (i + g <= n); };
         // (the FIRST launch of a graph exec costs more than the later ones, uploaded or not, and the more the bigger the graph -- tools/r05_run_y2.sh: a 20-step call that is the
         //  first to use the 16-step group reads 129.5 us/step, with the 4-step group only 128.1.  So a short call stays with the small group until some long call -- which
         //  amortises the ~28 us -- has launched the big one)
-        if (single && BIG > MID_GROUP && e->g_mid_big && (e->mid_big_warm || n >= 4 * BIG) && (pg ? (i >= 1 && i + BIG <= n - 1) : (i + BIG <= n))) {
-            HIPCHK(hipGraphLaunch(e->g_mid_big, e->stream)); e->mid_big_warm = true;
-            i += BIG; continue;
-        }
-        if (single && MID_GROUP > 1 && e->g_mid && (pg ? (i >= 1 && i + MID_GROUP <= n - 1) : (i + MID_GROUP <= n))) {
-            HIPCHK(hipGraphLaunch(e->g_mid, e->stream));
-            i += MID_GROUP; continue;
-        }
+        if (single && (e->mid_big_warm || n >= 4 * MID_BIG) && fits(MID_BIG)) { if (run_phase(e, mid[1])) return -1; e->mid_big_warm = true; i += MID_BIG; continue; }
+        if (single && fits(MID_GROUP)) { if (run_phase(e, mid[0])) return -1; i += MID_GROUP; continue; }
         // the last step of a call that returns scalars publishes them from its own last launch into the host mailbox (no fold launch / D2H copy / stream synchronize)
-        const unsigned long long pub0 = e->pub_issued;
-        e->step_publish = (loss || grad_norm) && i + 1 == n && mailbox_ok(e);
-        if (e->step_publish && mail_reserve(e)) return -1;
-        if (run_step(e, true, pg && i > 0, pg && i + 1 < n)) return -1;
+        const bool pub = (loss || grad_norm) && i + 1 == n && mailbox_ok(e); bool published = false;
+        if (pub && mail_reserve(e)) return -1;
+        if (run_step(e, true, pg && i > 0, pg && i + 1 < n, pub, &published)) return -1;
         i++;
-        if (i == n && e->pub_issued != pub0) return wait_mail(e, e->pub_issued, true, loss, grad_norm, nullptr);
+        if (i == n && published) return wait_mail(e, e->pub_issued, true, loss, grad_norm, nullptr);
     }
     if (loss || grad_norm) return fetch_scalars(e, loss, grad_norm);
     return 0;

@@ -135,13 +135,11 @@ extern "C" int dqn_train_step_drqn(dqn_engine_t* e, const int64_t* ep_idx, const
     if (e->drqn_fused) {
         if (e->draw_ev_used[evi]) HIPCHK(hipEventSynchronize(e->draw_ev[evi]));      // the previous launch of THIS instance has read its slot
         drqn_ring_put(e, 16 + par, ep_idx, ep_start); __atomic_thread_fence(__ATOMIC_RELEASE);
-        e->drqn_slot_next = 16 + par;
     } else if (drqn_upload_draws(e, ep_idx, ep_start)) return -1;
     const bool xch = e->world > 1 || (e->comm && e->force_comm);      // replicas (or DQN_FORCE_ALLREDUCE at world 1, tests): all-reduce of the materialised gradient between backward and Adam
-    if (e->hp.use_graph && !e->profiling && !xch) {
-        if (!e->g_drqn[par] && capture(e, false, PH_ALL, &e->g_drqn[par])) return -1;
-        HIPCHK(hipGraphLaunch(e->g_drqn[par], e->stream));
-    } else { enqueue_step(e, false, PH_PRE); if (xch && exchange_grads(e)) return -1; enqueue_step(e, false, PH_POST); if (e->launch_failed) { e->launch_failed = false; return fail("the recurrent step could not be enqueued (dynamic LDS refused)"); } }
+    StepKey k; k.sampled = false; k.slot = 16 + par;      // the single-step instance `par` reads slot 16 + par
+    if (!xch) { if (run_phase(e, k)) return -1; }
+    else { StepKey post = k; k.phase = PH_PRE; post.phase = PH_POST; if (run_phase(e, k, true) || exchange_grads(e) || run_phase(e, post, true)) return -1; }      // eager: the collective sits between the halves
     if (e->drqn_fused) { HIPCHK(hipEventRecord(e->draw_ev[evi], e->stream)); e->draw_ev_used[evi] = true; e->drqn_one_par ^= 1; }
     if (loss || grad_norm) return fetch_scalars(e, loss, grad_norm);
     return 0;
@@ -159,8 +157,8 @@ int drqn_train_steps(dqn_engine* e, int n, float* loss, float* grad_norm) {
             if (e->draw_ev_used[par]) HIPCHK(hipEventSynchronize(e->draw_ev[par]));
             for (int k = 0; k < DRQN_GROUP; k++) { if (drqn_host_draws(e, di, ds) || drqn_check(e, di.data(), ds.data())) return -1; drqn_ring_put(e, par * DRQN_GROUP + k, di.data(), ds.data()); }
             __atomic_thread_fence(__ATOMIC_RELEASE);
-            if (!e->g_drqn_k[par]) { e->drqn_slot_next = par * DRQN_GROUP; if (capture(e, false, PH_ALL, &e->g_drqn_k[par], DRQN_GROUP)) return -1; }
-            HIPCHK(hipGraphLaunch(e->g_drqn_k[par], e->stream));
+            StepKey k; k.sampled = false; k.repeat = DRQN_GROUP; k.slot = par * DRQN_GROUP;
+            if (run_phase(e, k)) return -1;
             HIPCHK(hipEventRecord(e->draw_ev[par], e->stream)); e->draw_ev_used[par] = true; e->drqn_grp_par ^= 1;
             i += DRQN_GROUP; continue;
         }

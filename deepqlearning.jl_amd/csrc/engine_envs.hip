@@ -163,26 +163,13 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
 }
 static int act_graph(dqn_engine* e, dqn_engine::ActProg& ap) {
     if (ap.graph) return 0;
-    hipGraph_t g;
-    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    for (auto& s : ap.steps) s.fn(e);
-    HIPCHK(hipStreamEndCapture(e->stream, &g));
-    HIPCHK(hipGraphInstantiate(&ap.graph, g, nullptr, nullptr, 0)); HIPCHK(hipGraphDestroy(g)); return 0;
+    return capture_graph(e, "the acting step", [&]() { for (auto& s : ap.steps) s.fn(e); return 0; }, &ap.graph);
 }
 // F acting steps (+ one plain sampled train step) as one graph
 static int cycle_graph(dqn_engine* e, dqn_engine::ActProg& ap, int F, bool with_train) {
     if (ap.cycle && ap.cycle_F == F && ap.cycle_train == with_train) return 0;
     if (ap.cycle) { hipGraphExecDestroy(ap.cycle); ap.cycle = nullptr; }
-    hipGraph_t g;
-    (void)hipGetLastError();
-    e->step_take_pre = e->step_pregather = false;
-    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    for (int f = 0; f < F; f++) for (auto& s : ap.steps) s.fn(e);
-    if (with_train) enqueue_step(e, true, PH_ALL);
-    const hipError_t lerr = hipGetLastError();
-    HIPCHK(hipStreamEndCapture(e->stream, &g));
-    if (lerr != hipSuccess) { hipGraphDestroy(g); return fail("HIP error %s while capturing the rollout cycle", hipGetErrorString(lerr)); }
-    HIPCHK(hipGraphInstantiate(&ap.cycle, g, nullptr, nullptr, 0)); HIPCHK(hipGraphDestroy(g));
+    if (capture_graph(e, "the rollout cycle", [&]() { for (int f = 0; f < F; f++) for (auto& s : ap.steps) s.fn(e); if (with_train) enqueue_step(e, StepKey()); return 0; }, &ap.cycle)) return -1;
     ap.cycle_F = F; ap.cycle_train = with_train; return 0;
 }
 // one vector step of the reference's cadence (src/solver.jl:136-140: a train step every train_freq ENV steps) as ONE graph: the acting step, then its `due` train steps
@@ -191,20 +178,11 @@ static int cycle_graph(dqn_engine* e, dqn_engine::ActProg& ap, int F, bool with_
 static int envc_graph(dqn_engine* e, dqn_engine::ActProg& ap, int due) {
     if (ap.envc && ap.envc_due == due) return 0;
     if (ap.envc) { hipGraphExecDestroy(ap.envc); ap.envc = nullptr; }
-    hipGraph_t g;
-    (void)hipGetLastError();
     const bool pg = e->pg_ok;
-    HIPCHK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    for (auto& s : ap.steps) s.fn(e);
-    for (int i = 0; i < due; i++) { e->step_take_pre = pg && i > 0; e->step_pregather = pg && i + 1 < due; enqueue_step(e, true, PH_ALL); }
-    e->step_take_pre = e->step_pregather = false;
-    hipError_t lerr = hipGetLastError();
-    if (e->launch_failed) { e->launch_failed = false; if (lerr == hipSuccess) lerr = hipErrorInvalidValue; }
-    HIPCHK(hipStreamEndCapture(e->stream, &g));
-    if (lerr != hipSuccess) { hipGraphDestroy(g); return fail("HIP error %s while capturing the env-cadence cycle", hipGetErrorString(lerr)); }
-    HIPCHK(hipGraphInstantiate(&ap.envc, g, nullptr, nullptr, 0)); HIPCHK(hipGraphDestroy(g));
-    if (!e->opt.no_graph_upload) (void)hipGraphUpload(ap.envc, e->stream);
-    (void)hipGetLastError();
+    if (capture_graph(e, "the env-cadence cycle", [&]() {
+            for (auto& s : ap.steps) s.fn(e);
+            for (int i = 0; i < due; i++) { StepKey k; k.take_pre = pg && i > 0; k.pregather = pg && i + 1 < due; enqueue_step(e, k); }
+            return 0; }, &ap.envc)) return -1;
     ap.envc_due = due; return 0;
 }
 extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) { if (!e) return fail("null engine handle");
@@ -227,14 +205,13 @@ extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* 
     const bool single = e->world <= 1 && !(e->comm && e->force_comm);
     const int F = cfg->train_freq > 0 ? cfg->train_freq : 4;
     const bool envc = cfg->cadence_env_steps != 0;      // train_freq / target_update_freq count ENV steps (src/solver.jl:136-145): n / train_freq train steps per vector step
-    const bool cyc = graph && single && F >= 2 && F <= 16 && !e->opt.no_rollout_cycle && !envc;
+    const bool cyc = graph && single && F >= 2 && F <= 16 && !envc;
     for (int k = 0; k < n_steps; k++) {
         const long long t = cfg->t0 + k;
         if (envc) {
             // the whole vector step as one graph where every vector step owes the same number of train steps and the replay holds a batch once this step's experiences are in
-            if (graph && single && !e->opt.no_rollout_cycle && !e->tiny && cfg->train_freq > 0 && n % cfg->train_freq == 0 && n / cfg->train_freq <= 64 && std::min(e->cap, e->size + n) >= e->B) {
+            if (graph && single && !e->tiny && cfg->train_freq > 0 && n % cfg->train_freq == 0 && n / cfg->train_freq <= 64 && std::min(e->cap, e->size + n) >= e->B) {
                 const int due_c = n / cfg->train_freq;
-                e->step_publish = false;
                 if (envc_graph(e, e->act, due_c)) return -1;
                 HIPCHK(hipGraphLaunch(e->act.envc, e->stream));
                 e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); trained += due_c;

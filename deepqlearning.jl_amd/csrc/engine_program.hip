@@ -91,7 +91,7 @@ int build_program(dqn_engine* e) {
             a.slabs = palloc(e, (size_t)G * e->Pint); a.hl = palloc(e, (size_t)B); a.td = e->td; a.st = e->state;
             a.probe = e->opt.drqn_probe | (mf ? 0 : 2);      // hp.use_mfma = 0: the VALU form of the input projection (the same chains, the same bits)
             if (e->opt.drqn_stamps) { a.stamps = (unsigned long long*)palloc(e, 64); e->drqn_stamps = a.stamps; }
-            e->prog.push_back({"drqn_cols", [=](dqn_engine* en) { if (launch_drqn_cols(en->stream, a, en->drqn_slot_next++)) en->launch_failed = true; }});      // the slot is baked into the captured node
+            e->prog.push_back({"drqn_cols", [=](dqn_engine* en) { if (launch_drqn_cols(en->stream, a, en->cur.slot)) en->launch_failed = true; }});      // the slot is baked into the captured node
             e->prog_post_begin = e->prog.size();
             AdamJob J; memset(&J, 0, sizeof J);
             J.p = e->p_on; J.m = e->m; J.v = e->v; J.g = e->grad; J.g_out = e->grad; J.state = e->state; J.gmax_part = e->gmax_part;
@@ -111,7 +111,7 @@ int build_program(dqn_engine* e) {
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
     if (!rec && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
-        (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->no_tiny) {
+        (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
         bool ok = true; size_t fl = 0;
         TinyArgs a; memset(&a, 0, sizeof a);
         for (int i = 0; i < e->nl; i++) { const LayerDev& L = e->L[i]; ok = ok && L.kind == DQN_LAYER_DENSE && dqn_nchunks(L.N, L.dx_kc) == 1 && L.src < i; a.L[i] = L; }
@@ -131,7 +131,7 @@ int build_program(dqn_engine* e) {
             a.x0 = e->x0; a.w_is = e->w_is; a.td = e->td; a.q_on_s = e->q_on_s; a.q_on_sp = e->q_on_sp; a.q_tg_sp = e->q_tg_sp; a.ytarget = e->ytarget; a.best = e->best;
             a.f64mode = e->hp.adam_f64_scalars; a.lr = e->hp.learning_rate; a.b1 = e->hp.adam_beta1; a.b2 = e->hp.adam_beta2; a.adam_eps = e->hp.adam_eps;
             const TinyArgs* a_dev = upload(e, std::vector<TinyArgs>(1, a)); const unsigned lds = a.lds_bytes;
-            e->prog.push_back({"tiny_step", [=](dqn_engine* en) { if (launch_tiny_step(en->stream, a_dev, lds, en->step_sampled ? 1 : 0, en->opt.tiny_stop)) en->launch_failed = true; }});
+            e->prog.push_back({"tiny_step", [=](dqn_engine* en) { if (launch_tiny_step(en->stream, a_dev, lds, en->cur.sampled ? 1 : 0, en->opt.tiny_stop)) en->launch_failed = true; }});
             e->tiny = true; e->arena_u8 = false; e->prio_forked = false; e->prio_in_bwd = false; e->dp_gather = false; e->dp_overlap = false; e->prog_pre1_end = 0;
             e->prog_post_begin = e->prog.size(); e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs); e->gmax_used = 1;
             for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0;
@@ -144,7 +144,7 @@ int build_program(dqn_engine* e) {
     // a quarter of the bytes.  Everything else (VALU / direct-MFMA fallbacks, heads fed by the observation, the operand all-gather) needs floats.
     e->arena_u8 = false;
     for (int i = 0; i < e->nl; i++) { e->L[i].xu8 = 0; LV[i].xu8 = 0; }
-    if (e->hp.obs_dtype == DQN_OBS_U8 && !rec && mf && B % 4 == 0 && e->E % 4 == 0 && levels.size() > 1 && !e->opt.no_u8_arena) {
+    if (e->hp.obs_dtype == DQN_OBS_U8 && !rec && mf && B % 4 == 0 && e->E % 4 == 0 && levels.size() > 1) {
         int n_src = 0; for (int i = 0; i < e->nl; i++) if (e->L[i].src < 0) n_src++;
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
@@ -155,7 +155,7 @@ int build_program(dqn_engine* e) {
     // workgroup per batch column (k_head_td); the heads' dW/db and the loss fold ride as tail tasks of the next backward launch
     int hv_l = -1, ha_l = -1; bool fuse_heads = false;
     // (r03: at ANY batch -- at B = 512 the four launches it replaces, head forwards / slab reduce / single-workgroup k_td / head dX, took 40 us)
-    if (!rec && e->B <= e->opt.head_fuse_maxb && !e->opt.no_head_fuse) {
+    if (!rec) {
         const auto& lv = levels.back();
         if (e->hp.dueling && lv.size() == 2 && lv[0] == e->last_val && lv[1] == e->last_adv) { hv_l = lv[0]; ha_l = lv[1]; }
         else if (!e->hp.dueling && lv.size() == 1 && lv[0] == e->last_base) ha_l = lv[0];
@@ -337,7 +337,7 @@ int build_program(dqn_engine* e) {
             HIPCHK(hipMemset(h.tickets, 0, (size_t)Gc * 4));      // armed once; every launch's last arrivers re-arm their groups
             if (e->opt.drqn_stamps) { h.stamps = (unsigned long long*)palloc(e, 64); HIPCHK(hipMemset(h.stamps, 0, 256)); e->drqn_stamps = h.stamps; }
             const RedHeadArgs* h_dev = upload(e, std::vector<RedHeadArgs>(1, h));
-            e->prog.push_back({h.S == 1 ? "head_cols4" : "red_head", [=](dqn_engine* en) { launch_red_head(en->stream, h, h_dev, en->step_sampled ? 1 : 0, en->step_take_pre ? 1 : 0); }});
+            e->prog.push_back({h.S == 1 ? "head_cols4" : "red_head", [=](dqn_engine* en) { launch_red_head(en->stream, h, h_dev, en->cur.sampled ? 1 : 0, en->cur.take_pre ? 1 : 0); }});
         }
         else if (fuse_heads) {
             HeadTdArgs h; memset(&h, 0, sizeof h);
@@ -365,9 +365,9 @@ int build_program(dqn_engine* e) {
             }
             h.dbg = e->opt.head_dbg;
             const HeadTdArgs* h_dev = upload(e, std::vector<HeadTdArgs>(1, h));
-            e->prog.push_back({"head_td", [=](dqn_engine* en) { launch_head_td(en->stream, h, h_dev, en->step_sampled ? 1 : 0, en->step_take_pre ? 1 : 0); }});
+            e->prog.push_back({"head_td", [=](dqn_engine* en) { launch_head_td(en->stream, h, h_dev, en->cur.sampled ? 1 : 0, en->cur.take_pre ? 1 : 0); }});
         }
-        else if (!rec) e->prog.push_back({"td_huber", [=](dqn_engine* en) { TdArgs a = t; a.bump_sample_ctr = en->step_sampled ? 1 : 0; a.take_pre = en->step_take_pre ? 1 : 0; launch_td(en->stream, a); }});
+        else if (!rec) e->prog.push_back({"td_huber", [=](dqn_engine* en) { TdArgs a = t; a.bump_sample_ctr = en->cur.sampled ? 1 : 0; a.take_pre = en->cur.take_pre ? 1 : 0; launch_td(en->stream, a); }});
         else {
             TdDrqnArgs d; memset(&d, 0, sizeof d); d.B = Bb; d.T = T; d.nA = e->nA; d.ncon = ncon; d.dueling = e->hp.dueling; d.double_q = e->hp.double_q; d.gamma = e->hp.gamma;
             d.on_val = t.on_val; d.on_adv = t.on_adv; d.tg_val = t.tg_val; d.tg_adv = t.tg_adv; d.d_val = t.d_val; d.d_adv = t.d_adv;
@@ -382,7 +382,7 @@ int build_program(dqn_engine* e) {
         // ... unless a backward launch can carry it as a workgroup of its own (r03: the fork + join nodes themselves cost 12 + 10 us of the main
         // stream at config 5, and the block -- split in two, update then draws -- is shorter than the 57-87 us launches it rides in)
         bool big_in_bwd = false;
-        if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world && !e->opt.prio_fork) {
+        if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
             for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (L2.kind != DQN_LAYER_LSTM && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
@@ -510,7 +510,7 @@ int build_program(dqn_engine* e) {
                     float* part = S > 1 ? palloc(e, (size_t)S * (V.K + 1) * V.N) : nullptr; float* dst = S > 1 ? part : grad + V.w_off;
                     // small recurrent layers (config 4: (25+1) x 128 and (32+1) x 128 weights, 256 columns): the two dW contractions as VALU tasks of ONE launch
                     // (15 us) beat two LDS-tiled MFMA launches of 13 us each (r03: 113.4 -> 102.7 us/step); the MFMA tiles win once the sample chains get long
-                    const bool small_dw = B <= 256 && (size_t)(V.K + 1) * V.N <= 16384 && !e->opt.lstm_dw_mfma;
+                    const bool small_dw = B <= 256 && (size_t)(V.K + 1) * V.N <= 16384;
                     if (mf && !small_dw && gemm_dw_eligible(V, B, ldv)) { struct A { const float* X[1]; const float* d[1]; float* o[1]; } a; a.X[0] = Xv; a.d[0] = dG; a.o[0] = dst;
                         e->prog.push_back({nm, [=](dqn_engine* en) { launch_gemm_dw(en->stream, V, 1, a.X, ldv, a.d, B, a.o); }}); }
                     else if (mf && !small_dw && mfma_dw_ok(V, B)) e->prog.push_back({nm, [=](dqn_engine* en) { launch_mfma_dw(en->stream, V, Xv, ldv, dG, B, grad, part, false); }});
@@ -730,7 +730,7 @@ int build_program(dqn_engine* e) {
         J.gscale = e->world > 1 ? 1.0f / (float)e->world : 1.0f;
         const bool fold = e->adam_segs.n > 0 && !e->comm && !e->sim_world;     // with a communicator the gradient must be materialised before the all-reduce
         if (e->dp_gather && e->dp_adam_folds) J.segs = e->dp_adam_segs; else if (fold) J.segs = e->adam_segs;
-        e->prog.push_back({"adam", [=](dqn_engine* en) { launch_adam(en->stream, J, en->step_pregather ? &en->pg : nullptr); }});
+        e->prog.push_back({"adam", [=](dqn_engine* en) { launch_adam(en->stream, J, en->cur.pregather ? &en->pg : nullptr); }});
         e->gmax_used = (int)(J.segs.blocks + J.sblocks);
     }
     e->prog_built = true;

@@ -1347,13 +1347,12 @@ static int conv_max_chunks(const LayerDev& L) {
 // dX body of a launch: 2 = 32 features x 128 samples per workgroup (large batches; dense plan chunks go through slabs, conv taps unchunked),
 // 3 = 32 x 32 tiles with one wave per (source, chunk) unit (dx_units_body; chunks combined in the workgroup), -1 = not covered by the LDS kernels
 static int dx_mode(const LayerDev& L, int nsrc, int B, int ldy) {
-    const bool no_wide = (L.opt & DQN_LOPT_NO_DX_WIDE) != 0;
     const bool dense = L.kind == DQN_LAYER_DENSE;
     const int S = dense ? dqn_nchunks(L.N, L.dx_kc) : 1, kc = dqn_chunk_len(L.N, L.dx_kc);
     if (B % 32 || ldy % 4 || L.N % 32 || (S > 1 && kc % 32) || L.w_off % 4) return -1;
     if (!dense && (L.cin % (16 * U_FT) || L.kh * L.kw > 64 || L.npos > 65535)) return -1;
     const int nch = dense ? S : conv_max_chunks(L);
-    if (B % 128 == 0 && !no_wide && (dense || (nch <= 1 && L.cin % 32 == 0)) && (nsrc == 1 || S == 1)) return 2;
+    if (B % 128 == 0 && (dense || (nch <= 1 && L.cin % 32 == 0)) && (nsrc == 1 || S == 1)) return 2;
     if (nsrc * nch <= U_MAX) return 3;
     return -1;
 }
