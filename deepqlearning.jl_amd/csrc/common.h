@@ -26,10 +26,14 @@ struct LayerDev {
     unsigned long long ew_off, eb_off; // offsets into the EXTERNAL (Flux.params order, unpadded) vector
     // LSTM (Flux Recur(LSTMCell)): K = n_in, N = 4H.  internal block [Wi K x 4H][b 4H][Wh H x 4H][junk 4H][h0 H][c0 H][zeros 4H]:
     // Wi|b and Wh|junk are (K+1) x N blocks for the dW kernels; `zeros` is the bias of the bias-free input projection.
+    // GRU (Flux Recur(GRUCell)): K = n_in, N = 3H.  internal block [Wi K x 3H][b 3H][Wh H x 3H][junk 3H][h0 H][zeros 3H] (no c0: c0_off, ec0_off unused).
     int H; unsigned long long wh_off, h0_off, c0_off, z_off, ewh_off, eh0_off, ec0_off;
     int opt;                           // per-ENGINE experiment switches the kernel launchers look at (DQN_LOPT_*, set at dqn_engine_create from EngineOpts): no process-wide state
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
 };
+
+// a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
+static inline __host__ __device__ bool is_recurrent(int kind) { return kind == DQN_LAYER_LSTM || kind == DQN_LAYER_GRU; }
 
 // device-resident mutable state of one engine (one instance in HBM)
 struct StepState {
@@ -790,6 +794,32 @@ struct LstmSeqArgs { LstmSeqF s[3]; int nseq, H, B, T; };
 bool lstm_seq_fits(int H, int B, int T);
 void launch_lstm_seq(hipStream_t st, const LstmSeqArgs& a);
 void launch_lstm_bwd_seq(hipStream_t st, const LstmBwdArgs& a);   // a.t ignored
+// GRU (gru.hip): the same decomposition as the LSTM's -- Gx = Wi*x by the dense kernels, the recurrence by these, dW / dX by the dense kernels
+struct GruSeq {           // one sequence set advancing one time step: B columns starting at column c0 (+ t*B) of [*][ld] arrays
+    const float* Gx; float* Hout; int ld, c0;
+    const float *Wh, *bias;
+    const float* hprev; int hp_ld, hp_bs;     // h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]   (h0 broadcast: ld 1, bs 0)
+    float *gates, *ghn, *hprev_out; int keep_ld, keep_c0;      // BPTT stash (online s-sequence) or null: r, z, n [3H], Wh_n*h [H], h_{t-1} [H]
+};
+struct GruStepArgs { GruSeq s[3]; int nseq, H, B; };
+void launch_gru_step_t(hipStream_t st, const GruStepArgs& a, int t);
+struct GruSeqF {
+    const float* Gx; float* Hout; int ld, c0;
+    const float *Wh, *bias, *h0;
+    float *gates, *ghn, *hprev_out; int keep_ld, keep_c0;
+};
+struct GruSeqArgs { GruSeqF s[3]; int nseq, H, B, T; };
+struct GruBwdArgs {
+    int t, T, H, B, TB; const float *gates, *ghn, *hprev, *Wh; const float* dH;
+    float *dGx, *dGh;        // [3H][TB] each: [dr; dz; dn] (Wi | b, input dX) and [dr; dz; dn .* r] (Wh)
+    float *dhn, *dhz;        // [H][B]: dh_{t-1}; dh .* z of the current step (per-step form only)
+    float* g_h0;
+};
+bool gru_seq_fits(int H, int B, int T);
+void launch_gru_seq(hipStream_t st, const GruSeqArgs& a);
+void launch_gru_bwd_step(hipStream_t st, const GruBwdArgs& a);
+void launch_gru_bwd_seq(hipStream_t st, const GruBwdArgs& a);   // a.t ignored; folds the state0 gradient too
+void launch_clear_rows(hipStream_t st, float* p, int nrows, size_t stride, int n);   // p[r*stride + i] = 0, r < nrows, i < n
 struct EpGatherArgs {
     const float *ep_s, *ep_sp; const int* ep_a; const float* ep_r; const unsigned char* ep_done; const int* ep_len;
     const long long* ep_idx; const int* ep_start; int E, B, T; float* x0; int* a_out; float *r_out, *done_out, *mask_out;

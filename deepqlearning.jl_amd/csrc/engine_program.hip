@@ -50,7 +50,7 @@ int build_program(dqn_engine* e) {
     LayerDev LV[DQN_MAX_LAYERS]; float *fwd_on[DQN_MAX_LAYERS], *fwd_tg[DQN_MAX_LAYERS];
     for (int i = 0; i < e->nl; i++) {
         LV[i] = e->L[i]; fwd_on[i] = e->act_on[i]; fwd_tg[i] = e->act_tg[i];
-        if (e->L[i].kind == DQN_LAYER_LSTM) { LV[i].kind = DQN_LAYER_DENSE; LV[i].out_feat = LV[i].N; LV[i].b_off = LV[i].z_off; LV[i].act = DQN_ACT_IDENTITY; fwd_on[i] = e->gx_on[i]; fwd_tg[i] = e->gx_tg[i]; }
+        if (is_recurrent(e->L[i].kind)) { LV[i].kind = DQN_LAYER_DENSE; LV[i].out_feat = LV[i].N; LV[i].b_off = LV[i].z_off; LV[i].act = DQN_ACT_IDENTITY; fwd_on[i] = e->gx_on[i]; fwd_tg[i] = e->gx_tg[i]; }
     }
     std::vector<std::vector<int>> levels; std::vector<int> val, adv;
     for (int i = 0; i < e->nl; i++) { if (e->L[i].stream == DQN_STREAM_BASE) levels.push_back({i}); else if (e->L[i].stream == DQN_STREAM_VAL) val.push_back(i); else adv.push_back(i); }
@@ -163,7 +163,7 @@ int build_program(dqn_engine* e) {
             fuse_heads = true; size_t lds = (size_t)(1 + e->nA) * 4;
             for (int l : lv) {
                 const LayerDev& L = e->L[l];
-                fuse_heads = fuse_heads && L.kind == DQN_LAYER_DENSE && dqn_nchunks(L.N, L.dx_kc) == 1 && (L.src < 0 || e->L[L.src].kind != DQN_LAYER_LSTM);
+                fuse_heads = fuse_heads && L.kind == DQN_LAYER_DENSE && dqn_nchunks(L.N, L.dx_kc) == 1 && (L.src < 0 || !is_recurrent(e->L[L.src].kind));
                 lds += ((size_t)3 * L.K + (size_t)3 * L.N * dqn_nchunks(L.K, L.fwd_kc) + (size_t)3 * L.N) * 4;
             }
             fuse_heads = fuse_heads && lds <= 60 * 1024;
@@ -303,6 +303,35 @@ int build_program(dqn_engine* e) {
                 e->prog.push_back({pname(e, "lstm_step", L.kind, l), [=](dqn_engine* en) { launch_lstm_step_t(en->stream, a, t); }});
             }
         }
+        if (e->L[lv[0]].kind == DQN_LAYER_GRU) {      // the GRU's recurrence, where the LSTM's is emitted (gru.hip)
+            const int l = lv[0]; const LayerDev L = e->L[l]; const int H = L.H;
+            if (gru_seq_fits(H, Bb, T) && !e->opt.gru_stepwise) {
+                GruSeqArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; int ns = 0;
+                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
+                    GruSeqF& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off; q.h0 = P + L.h0_off;
+                    if (keep) { q.gates = e->gates[l]; q.ghn = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
+                };
+                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
+                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
+                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
+                a.nseq = ns;
+                e->prog.push_back({pname(e, "gru_seq", L.kind, l), [=](dqn_engine* en) { launch_gru_seq(en->stream, a); }});
+            } else
+            for (int t = 0; t < T; t++) {
+                GruStepArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; int ns = 0;
+                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
+                    GruSeq& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
+                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; }
+                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; }
+                    if (keep) { q.gates = e->gates[l]; q.ghn = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
+                };
+                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
+                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
+                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
+                a.nseq = ns;
+                e->prog.push_back({pname(e, "gru_step", L.kind, l), [=](dqn_engine* en) { launch_gru_step_t(en->stream, a, t); }});
+            }
+        }
     }
     // ---------------- dueling reduce + argmax + Bellman target + TD + Huber + dL/dQ + priority update
     {
@@ -384,7 +413,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (L2.kind != DQN_LAYER_LSTM && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -414,7 +443,7 @@ int build_program(dqn_engine* e) {
     // bandwidth-bound work overlaps the latency-bound conv backward launches; update_priorities! (needs only idx, td) rides on the first of them.
     // The final k_adam is left with the first level's layers and the beta-power tick.
     bool segs_ok = true;
-    for (int i = 0; i < e->nl; i++) { const LayerDev& L = e->L[i]; if (L.kind != DQN_LAYER_LSTM && dqn_nchunks(L.npos * B, L.dw_kc) > 1) segs_ok = segs_ok && L.w_off % 4 == 0 && ((size_t)(L.K + 1) * L.N) % 4 == 0; }
+    for (int i = 0; i < e->nl; i++) { const LayerDev& L = e->L[i]; if (!is_recurrent(L.kind) && dqn_nchunks(L.npos * B, L.dw_kc) > 1) segs_ok = segs_ok && L.w_off % 4 == 0 && ((size_t)(L.K + 1) * L.N) % 4 == 0; }
     // (removed in r06: DQN_ADAM_MODE=1, the Adam update of layers whose gradient is already final carried as tail workgroups of the backward launches -- measured slower in
     //  rounds 2, 3, 4 and, as "the stream in the free CU slots", 5: 159.3 vs 156.9 us/step in r02, +3.4 us per carrying launch for -2.75 us of Adam in r05; docs/history/r02.md, r05.md)
     bool prio_placed = false, prio_draw_pending = false;
@@ -480,6 +509,7 @@ int build_program(dqn_engine* e) {
             continue;
         }
         bool dw_done_sibling = false;   // the level's two sibling layers got their dW from one fused launch
+        std::vector<dqn_engine::Step> post_level;      // launches that run after every launch of this level
         struct DwL { bool on = false; LayerDev L; int nprob = 0; const float* X[2]; int ldx = 0; const float* d[2]; float* o[2]; const char* name = ""; } dwl;
         struct DxL { bool on = false; LayerDev L; int nsrc = 0; const float* W[2]; const float* d[2]; float* out = nullptr; const float* ys = nullptr; int act_src = 0; const char* name = ""; } dxl;
         auto flush_dw = [&]() { if (!dwl.on) return; const DwL a = dwl; e->prog.push_back({a.name, [=](dqn_engine* en) { launch_gemm_dw(en->stream, a.L, a.nprob, a.X, a.ldx, a.d, B, a.o); }}); dwl.on = false; };
@@ -488,10 +518,18 @@ int build_program(dqn_engine* e) {
             const int l = lv[k]; const LayerDev L = e->L[l];
             const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon;
             float* dpre = e->dact[l];
-            if (L.kind == DQN_LAYER_LSTM) {
+            if (is_recurrent(L.kind)) {
                 // BPTT over the s-sequence: T single-workgroup steps produce dG (gate pre-activation gradients) for all columns,
                 // then Wi|b, Wh and the input gradient are ordinary dense contractions over the T*B columns.
+                // GRU: BPTT writes TWO gate gradients, dGx = [dr; dz; dn] for Wi|b and the input dX, dGh = [dr; dz; dn .* r] for Wh (gru.hip)
                 float* grad = e->grad;
+                const bool gru = L.kind == DQN_LAYER_GRU;
+                if (gru) {
+                    GruBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.ghn = e->tcb[l]; a.hprev = e->hprev_buf[l]; a.Wh = e->p_on + L.wh_off;
+                    a.dH = dpre; a.dGx = e->dG[l]; a.dGh = e->dG[l] + (size_t)L.N * B; a.dhn = e->dhn[l]; a.dhz = e->dcn[l]; a.g_h0 = grad + L.h0_off;
+                    if (gru_seq_fits(L.H, Bb, T) && !e->opt.gru_stepwise) e->prog.push_back({pname(e, "gru_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_seq(en->stream, a); }});
+                    else for (int t = T - 1; t >= 0; t--) { GruBwdArgs at = a; at.t = t; e->prog.push_back({pname(e, "gru_bwd", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_step(en->stream, at); }}); }
+                } else
                 if (lstm_seq_fits(L.H, Bb, T)) {
                     LstmBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.tc = e->tcb[l]; a.cprev = e->cprev_buf[l]; a.Wh = e->p_on + L.wh_off;
                     a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.dcn = e->dcn[l]; a.g_h0 = grad + L.h0_off; a.g_c0 = grad + L.c0_off;
@@ -502,10 +540,11 @@ int build_program(dqn_engine* e) {
                     a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.dcn = e->dcn[l]; a.g_h0 = grad + L.h0_off; a.g_c0 = grad + L.c0_off;
                     e->prog.push_back({pname(e, "lstm_bwd", L.kind, l), [=](dqn_engine* en) { launch_lstm_bwd_step(en->stream, a); }});
                 }
-                LayerDev Vi = L; Vi.kind = DQN_LAYER_DENSE; Vi.out_feat = L.N; Vi.act = DQN_ACT_IDENTITY;                    // Wi | b  : (K+1) x 4H
+                LayerDev Vi = L; Vi.kind = DQN_LAYER_DENSE; Vi.out_feat = L.N; Vi.act = DQN_ACT_IDENTITY;                    // Wi | b  : (K+1) x N
                 LayerDev Vh = Vi; Vh.K = L.H; Vh.in_feat = L.H; Vh.w_off = L.wh_off; Vh.b_off = L.wh_off + (size_t)L.H * L.N;  // Wh | junk
-                const float* dG = e->dG[l];
-                auto emit_dw1 = [&](const LayerDev V, const float* Xv, int ldv, const char* nm) {
+                const float* dGi = e->dG[l]; const float* dGw = gru ? e->dG[l] + (size_t)L.N * B : e->dG[l];      // the Wi | b and dX operand, the Wh operand
+                float* wh_dst = nullptr; int wh_S = 1;      // where the Wh | junk block (or its slabs) lands
+                auto emit_dw1 = [&](const LayerDev V, const float* Xv, int ldv, const float* dG, const char* nm) {
                     const int S = dqn_nchunks(B, V.dw_kc);
                     float* part = S > 1 ? palloc(e, (size_t)S * (V.K + 1) * V.N) : nullptr; float* dst = S > 1 ? part : grad + V.w_off;
                     // small recurrent layers (config 4: (25+1) x 128 and (32+1) x 128 weights, 256 columns): the two dW contractions as VALU tasks of ONE launch
@@ -516,17 +555,22 @@ int build_program(dqn_engine* e) {
                     else if (mf && !small_dw && mfma_dw_ok(V, B)) e->prog.push_back({nm, [=](dqn_engine* en) { launch_mfma_dw(en->stream, V, Xv, ldv, dG, B, grad, part, false); }});
                     else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = V; t.X = Xv; t.ldx = ldv; t.dpre = dG; t.B = B; t.S = S; t.kc = dqn_chunk_len(B, V.dw_kc); t.out = dst; add_valu(e, pend, t); }
                     if (S > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(V.K + 1) * V.N; r.mode = 2; r.out = grad + V.w_off; final_segs.push_back(r); }
+                    if (V.w_off == L.wh_off) { wh_dst = dst; wh_S = S; }
                 };
-                emit_dw1(Vh, e->hprev_buf[l], B, pname(e, "dw_wh", L.kind, l));      // first: its junk bias row is then overwritten by nothing that matters
-                emit_dw1(Vi, X, ldx, pname(e, "dw_wi", L.kind, l));
+                emit_dw1(Vh, e->hprev_buf[l], B, dGw, pname(e, "dw_wh", L.kind, l));      // first: its junk bias row is then overwritten by nothing that matters
+                emit_dw1(Vi, X, ldx, dGi, pname(e, "dw_wi", L.kind, l));
+                if (gru) {      // the GRU's junk row (sum of dn .* r) is cleared once the level's launches have written it: Adam folds max |g| over it (gru.hip)
+                    float* jr = wh_dst + (size_t)L.H * L.N; const int nr = wh_S; const size_t stride = (size_t)(L.H + 1) * L.N; const int n = L.N;
+                    post_level.push_back({pname(e, "gru_junk_clear", L.kind, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
+                }
                 if (L.src >= 0) {
                     const int src = L.src; const int act_src = e->L[src].act; float* out = e->dact[src]; const float* ysrc = e->act_on[src]; const float* P = e->p_on;
                     const int S = (mf && gemm_dx_internal_chunks(Vi, B, ncon)) ? 1 : dqn_nchunks(Vi.N, Vi.dx_kc);      // internal: the launch combines its plan chunks itself
                     float* part = S > 1 ? palloc(e, (size_t)S * Vi.in_feat * B) : nullptr;
-                    if (mf && gemm_dx_eligible(Vi, B, ncon)) { struct A1 { const float* W[1]; const float* d[1]; } a; a.W[0] = P + Vi.w_off; a.d[0] = dG; float* dst = S > 1 ? part : out; const float* ys = S > 1 ? nullptr : ysrc;
+                    if (mf && gemm_dx_eligible(Vi, B, ncon)) { struct A1 { const float* W[1]; const float* d[1]; } a; a.W[0] = P + Vi.w_off; a.d[0] = dGi; float* dst = S > 1 ? part : out; const float* ys = S > 1 ? nullptr : ysrc;
                         e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_gemm_dx(en->stream, Vi, 1, a.W, a.d, B, dst, ys, ncon, act_src); }}); }
-                    else if (mf && mfma_dx_ok(Vi, B, ncon)) e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, Vi, P, dG, B, out, part, nullptr, ysrc, ncon, act_src, false); }});
-                    else { VTask t; memset(&t, 0, sizeof t); t.kind = 2; t.L = Vi; t.P = P; t.dpre = dG; t.B = B; t.S = S; t.kc = dqn_chunk_len(Vi.N, Vi.dx_kc); t.out = S > 1 ? part : out; t.ysrc = ysrc; t.ldy = ncon; t.act_src = act_src; add_valu(e, pend, t); }
+                    else if (mf && mfma_dx_ok(Vi, B, ncon)) e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, Vi, P, dGi, B, out, part, nullptr, ysrc, ncon, act_src, false); }});
+                    else { VTask t; memset(&t, 0, sizeof t); t.kind = 2; t.L = Vi; t.P = P; t.dpre = dGi; t.B = B; t.S = S; t.kc = dqn_chunk_len(Vi.N, Vi.dx_kc); t.out = S > 1 ? part : out; t.ysrc = ysrc; t.ldy = ncon; t.act_src = act_src; add_valu(e, pend, t); }
                     if (S > 1) { flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l)); std::vector<RSeg> one; RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)Vi.in_feat * B; r.mode = 1; r.act = act_src; r.ysrc = ysrc; r.B = B; r.ldy = ncon; r.out = out; one.push_back(r); emit_reduce(e, one, pname(e, "dx_reduce", L.kind, l)); }
                 }
                 continue;
@@ -602,7 +646,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && L2.kind != DQN_LAYER_LSTM && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;
@@ -619,6 +663,7 @@ int build_program(dqn_engine* e) {
         else if (dwl.on) { const DwL a = dwl; dwl.on = false; e->prog.push_back({tailed(a.name), [=](dqn_engine* en) { launch_gemm_dw(en->stream, a.L, a.nprob, a.X, a.ldx, a.d, B, a.o, 0, 0, 0, tail); }}); }
         else if (dxl.on) { const DxL a = dxl; dxl.on = false; e->prog.push_back({tailed(a.name), [=](dqn_engine* en) { launch_gemm_dx(en->stream, a.L, a.nsrc, a.W, a.d, B, a.out, a.ys, ncon, a.act_src, tail); }}); }
         flush_dw(); flush_dx();
+        for (auto& st : post_level) e->prog.push_back(st);
     }
     if (!tail_pend.empty()) { std::vector<VTask> own(tail_pend); tail_pend.clear(); flush_valu(e, own, "head_dw"); }      // single-level network: nothing to ride on
     if (e->prio_forked) e->prog.push_back({"prio_join", [](dqn_engine* en) { hipStreamWaitEvent(en->stream, en->ev_join, 0); }});

@@ -59,6 +59,22 @@ class LSTM:
         return [(self.n_in, 4 * h), (h, 4 * h), (4 * h,), (h,), (h,)]
 
 
+class GRU:
+    """Flux GRU(in, out) = Recur(GRUCell), gates r, z, n: params Wi (3out,in), Wh (3out,out), b (3out, zero), state0 h0 (out,1, zero)."""
+    kind = "gru"
+
+    def __init__(self, n_in, n_out):
+        self.n_in, self.n_out, self.act = int(n_in), int(n_out), identity
+
+    def shapes(self):   # Julia memory order: Wi (3out,in) == C (in,3out), Wh (3out,out) == C (out,3out), b, h0
+        h = self.n_out
+        return [(self.n_in, 3 * h), (h, 3 * h), (3 * h,), (h,)]
+
+    def fans(self):     # glorot fans of Wi and Wh
+        h = self.n_out
+        return [(self.n_in, 3 * h), (h, 3 * h)]
+
+
 class Chain:
     def __init__(self, *layers):
         self.layers = [l for l in layers if getattr(l, "kind", None) != "flatten" and l is not flattenbatch]
@@ -107,13 +123,15 @@ def lower(net):
     def add(chain, stream):
         for l in chain:
             d = _abi.LayerDesc()
-            if getattr(l, "kind", None) not in ("dense", "lstm", "conv"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / Dense / LSTM / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "conv"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / Dense / LSTM / GRU / flattenbatch only)")
             d.act, d.stream = l.act, stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
             elif l.kind == "lstm":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_LSTM, l.n_in, l.n_out
+            elif l.kind == "gru":
+                d.kind, d.n_in, d.n_out = _abi.LAYER_GRU, l.n_in, l.n_out
             else:
                 d.kind = _abi.LAYER_CONV
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
@@ -130,7 +148,7 @@ def lower(net):
 
 def isrecurrent(m):
     """src/helpers.jl:25-32."""
-    return any(getattr(l, "kind", None) == "lstm" for l in all_layers(m))
+    return any(getattr(l, "kind", None) in ("lstm", "gru") for l in all_layers(m))
 
 
 def all_layers(net):
@@ -150,6 +168,11 @@ def glorot_params(net, seed=1):
             b = np.zeros(4 * h, np.float32)
             b[h:2 * h] = 1.0        # Flux LSTMCell: forget-gate bias initialised to 1
             parts += [b, np.zeros(h, np.float32), np.zeros(h, np.float32)]
+            continue
+        if l.kind == "gru":      # Flux GRUCell: glorot Wi, Wh; zero b (no forget-gate bias); zero state0
+            for shp, (fi, fo) in zip(l.shapes()[:2], l.fans()):
+                parts.append(((rng.random(shp, dtype=np.float32) - np.float32(0.5)) * np.sqrt(np.float32(24.0) / np.float32(fi + fo))).astype(np.float32).reshape(-1))
+            parts += [np.zeros(3 * l.n_out, np.float32), np.zeros(l.n_out, np.float32)]
             continue
         wshape, bshape = l.shapes()
         fi, fo = l.fans()

@@ -1,5 +1,7 @@
 """Config 4: TestMDP((5,5),1,6) observations (25), Chain(flattenbatch, LSTM(25,32), Dense(32,4)) (benchmark/flux_dqn.jl:35-36),
-trace_length 8, B = 32, double-Q, no dueling.  Prints DRQN train steps/s (hipGraph replay, sampler on the device) and the per-launch table."""
+trace_length 8, B = 32, double-Q, no dueling.  Prints DRQN train steps/s (hipGraph replay, sampler on the device) and the per-launch table.
+--cell gru: the same shape with GRU(25,32) (the multi-launch recurrent program); --contiguous-dw: the LSTM on a dw_kc >= 0 plan (its
+multi-launch program instead of the fused column-parallel step), the like-for-like comparison for the GRU."""
 import argparse
 import importlib
 import os
@@ -17,16 +19,19 @@ ap.add_argument("--hidden", type=int, default=32)
 ap.add_argument("--trace", type=int, default=8)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--no-mfma", action="store_true")
+ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm")
+ap.add_argument("--contiguous-dw", action="store_true")
 args = ap.parse_args()
 pkg = ge.load_package()
 nn = importlib.import_module(pkg.__name__ + ".nn")
 envs = importlib.import_module(pkg.__name__ + ".envs")
 S = importlib.import_module(pkg.__name__ + ".solver")
-model = nn.Chain(nn.flattenbatch, nn.LSTM(25, args.hidden), nn.Dense(args.hidden, 4))
+model = nn.Chain(nn.flattenbatch, (nn.GRU if args.cell == "gru" else nn.LSTM)(25, args.hidden), nn.Dense(args.hidden, 4))
 layers, _ = nn.lower(model)
 hp = pkg.default_hparams(batch_size=32, n_actions=4, obs_c=1, obs_h=5, obs_w=5, gamma=0.99, double_q=1, dueling=0, prioritized_replay=0,
                          buffer_size=1000, recurrence=1, trace_length=args.trace, learning_rate=1e-3, use_mfma=0 if args.no_mfma else 1)
-eng = pkg.Engine(layers, hp)
+plan = [(p[0], p[1], max(p[2], 0)) for p in pkg.default_plan(layers, hp)] if args.contiguous_dw else None
+eng = pkg.Engine(layers, hp, plan=plan)
 eng.set_params(nn.glorot_params(model, seed=1), pkg.NET_ONLINE)
 eng.sync_target()
 env = envs.TestMDP((5, 5), 1, 6, n=1, seed=7)
@@ -38,7 +43,8 @@ t0 = time.perf_counter()
 loss, gn = eng.train_steps(args.steps)
 eng.sync()
 dt = time.perf_counter() - t0
-print(f"config 4 DRQN: {args.steps / dt:.0f} train steps/s ({dt / args.steps * 1e6:.1f} us/step), loss {loss:.4g}")
+tag = "" if args.cell == "lstm" and not args.contiguous_dw else f" ({args.cell}{', dw_kc >= 0' if args.contiguous_dw else ''})"
+print(f"config 4 DRQN{tag}: {args.steps / dt:.0f} train steps/s ({dt / args.steps * 1e6:.1f} us/step), loss {loss:.4g}")
 if args.profile:
     acc = {}
     for _ in range(5):
