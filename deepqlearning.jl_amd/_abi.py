@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-LAYER_DENSE, LAYER_CONV, LAYER_LSTM, LAYER_GRU = 0, 1, 2, 3
+LAYER_DENSE, LAYER_CONV, LAYER_LSTM, LAYER_GRU, LAYER_RNN = 0, 1, 2, 3, 4
 ACT_IDENTITY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 STREAM_BASE, STREAM_VAL, STREAM_ADV = 0, 1, 2
 OBS_F32, OBS_U8 = 0, 1
@@ -429,11 +429,11 @@ class Handle:
         self._check(self.f["reset_state"](self._h))
 
     def hidden_size(self, streams=1):
-        """floats in the flat Recur state: per recurrent layer in chain order, an LSTM's h then c, a GRU's h, each [out][streams] (src/helpers.jl:61-63)"""
-        return sum({LAYER_LSTM: 2, LAYER_GRU: 1}.get(l.kind, 0) * int(l.n_out) * streams for l in self.layers[:self.n_layers])
+        """floats in the flat Recur state: per recurrent layer in chain order, an LSTM's h then c, a GRU's or an RNN's h, each [out][streams] (src/helpers.jl:61-63)"""
+        return sum({LAYER_LSTM: 2, LAYER_GRU: 1, LAYER_RNN: 1}.get(l.kind, 0) * int(l.n_out) * streams for l in self.layers[:self.n_layers])
 
     def get_hidden(self, streams=1):
-        """hiddenstates(m) (src/helpers.jl:61-63): per recurrent layer, (h, c) for an LSTM, h for a GRU, each [out, streams]"""
+        """hiddenstates(m) (src/helpers.jl:61-63): per recurrent layer, (h, c) for an LSTM, h for a GRU or an RNN, each [out, streams]"""
         buf = np.empty(self.hidden_size(streams), np.float32)
         self._check(self.f["get_hidden"](self._h, _ptr(buf, _f32p), buf.size))
         out, off = [], 0
@@ -442,13 +442,13 @@ class Handle:
             if l.kind == LAYER_LSTM:
                 out.append((buf[off:off + m].reshape(int(l.n_out), streams).copy(), buf[off + m:off + 2 * m].reshape(int(l.n_out), streams).copy()))
                 off += 2 * m
-            elif l.kind == LAYER_GRU:
+            elif l.kind in (LAYER_GRU, LAYER_RNN):
                 out.append(buf[off:off + m].reshape(int(l.n_out), streams).copy())
                 off += m
         return out
 
     def set_hidden(self, hs):
-        """sethiddenstates!(m, hs) (src/helpers.jl:71-79): what get_hidden returned -- (h, c) per LSTM layer, h per GRU layer"""
+        """sethiddenstates!(m, hs) (src/helpers.jl:71-79): what get_hidden returned -- (h, c) per LSTM layer, h per GRU or RNN layer"""
         parts = [_as(x, np.float32).ravel() for st in hs for x in (st if isinstance(st, tuple) else (st,))]
         buf = np.concatenate(parts) if parts else np.empty(0, np.float32)
         buf = np.ascontiguousarray(buf, np.float32)

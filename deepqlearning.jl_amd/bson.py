@@ -17,7 +17,7 @@ dependency beyond NumPy.  The container format is BSON 1.1 (bsonspec.org); the a
 UNVERIFIED AGAINST BSON.jl: no Julia exists in the build image or on the GPU box, so the lowering above cannot be
 exercised against the real reader; tests/test_bson_cpu.py round-trips it through the independent reader below and
 checks the byte-level structure against the BSON spec.  Arrays are stored in JULIA memory order and with Julia's
-`size`: Dense weight (out, in), Conv weight (kw, kh, cin, cout), LSTM Wi (4h, in), Wh (4h, h), GRU Wi (3h, in), Wh (3h, h) -- exactly the bytes the
+`size`: Dense weight (out, in), Conv weight (kw, kh, cin, cout), LSTM Wi (4h, in), Wh (4h, h), GRU Wi (3h, in), Wh (3h, h), RNN Wi (h, in), Wh (h, h) -- exactly the bytes the
 C ABI's flat vector already holds.
 """
 from __future__ import annotations
@@ -45,6 +45,9 @@ def julia_param_shapes(net):
         elif l.kind == "gru":    # Flux 0.14 Recur(GRUCell): Wi, Wh, b, state0 = h0 as an (out, 1) matrix
             h = l.n_out
             out += [((3 * h, l.n_in), 3 * h * l.n_in), ((3 * h, h), 3 * h * h), ((3 * h,), 3 * h), ((h, 1), h)]
+        elif l.kind == "rnn":    # Flux 0.14 Recur(RNNCell): Wi, Wh, b, state0 = h0 as an (out, 1) matrix
+            h = l.n_out
+            out += [((h, l.n_in), h * l.n_in), ((h, h), h * h), ((h,), h), ((h, 1), h)]
         else:
             raise ValueError(f"unsupported layer kind {l.kind}")
     return out

@@ -27,13 +27,15 @@ struct LayerDev {
     // LSTM (Flux Recur(LSTMCell)): K = n_in, N = 4H.  internal block [Wi K x 4H][b 4H][Wh H x 4H][junk 4H][h0 H][c0 H][zeros 4H]:
     // Wi|b and Wh|junk are (K+1) x N blocks for the dW kernels; `zeros` is the bias of the bias-free input projection.
     // GRU (Flux Recur(GRUCell)): K = n_in, N = 3H.  internal block [Wi K x 3H][b 3H][Wh H x 3H][junk 3H][h0 H][zeros 3H] (no c0: c0_off, ec0_off unused).
+    // RNN (Flux Recur(RNNCell)): K = n_in, N = H.  internal block [Wi K x H][b H][Wh H x H][junk H][h0 H][zeros H] (the GRU's with N = H).
     int H; unsigned long long wh_off, h0_off, c0_off, z_off, ewh_off, eh0_off, ec0_off;
+    int cell_act;                      // RNN: the cell's activation (DQN_ACT_*).  `act` stays IDENTITY for every recurrent layer: the generic forward / dX epilogues read `act`
     int opt;                           // per-ENGINE experiment switches the kernel launchers look at (DQN_LOPT_*, set at dqn_engine_create from EngineOpts): no process-wide state
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
-static inline __host__ __device__ bool is_recurrent(int kind) { return kind == DQN_LAYER_LSTM || kind == DQN_LAYER_GRU; }
+static inline __host__ __device__ bool is_recurrent(int kind) { return kind == DQN_LAYER_LSTM || kind == DQN_LAYER_GRU || kind == DQN_LAYER_RNN; }
 
 // device-resident mutable state of one engine (one instance in HBM)
 struct StepState {
@@ -820,6 +822,33 @@ void launch_gru_seq(hipStream_t st, const GruSeqArgs& a);
 void launch_gru_bwd_step(hipStream_t st, const GruBwdArgs& a);
 void launch_gru_bwd_seq(hipStream_t st, const GruBwdArgs& a);   // a.t ignored; folds the state0 gradient too
 void launch_clear_rows(hipStream_t st, float* p, int nrows, size_t stride, int n);   // p[r*stride + i] = 0, r < nrows, i < n
+// RNN (rnn.hip): Gx = Wi*x by the dense kernels, h' = act((Gx + Wh*h) + b) by these, dW / dX by the dense kernels (one gate gradient dG for all three)
+struct RnnSeq {           // one sequence set advancing one time step: B columns starting at column c0 (+ t*B) of [*][ld] arrays
+    const float* Gx; float* Hout; int ld, c0;
+    const float *Wh, *bias;
+    const float* hprev; int hp_ld, hp_bs;     // h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]   (h0 broadcast: ld 1, bs 0)
+    float* hprev_out; int keep_ld, keep_c0;   // BPTT stash (online s-sequence) or null: h_{t-1} [H]
+};
+struct RnnStepArgs { RnnSeq s[3]; int nseq, H, B, act; };
+void launch_rnn_step_t(hipStream_t st, const RnnStepArgs& a, int t);
+struct RnnSeqF {
+    const float* Gx; float* Hout; int ld, c0;
+    const float *Wh, *bias, *h0;
+    float* hprev_out; int keep_ld, keep_c0;
+};
+struct RnnSeqArgs { RnnSeqF s[3]; int nseq, H, B, T, act; };
+struct RnnBwdArgs {
+    int t, T, H, B, TB, act;
+    const float* hout; int ld_h;            // h_t of the online s-sequence: hout[u*ld_h + t*B + b] (the forward's output, read back for act')
+    const float *Wh, *dH;
+    float* dG;                              // [H][TB]: dact(dh) -> Wi | b, Wh (X = h_{t-1}) and the input dX
+    float* dhn;                             // [H][B]: dh_{t-1}
+    float* g_h0;
+};
+bool rnn_seq_fits(int H, int B, int T);
+void launch_rnn_seq(hipStream_t st, const RnnSeqArgs& a);
+void launch_rnn_bwd_step(hipStream_t st, const RnnBwdArgs& a);
+void launch_rnn_bwd_seq(hipStream_t st, const RnnBwdArgs& a);   // a.t ignored; folds the state0 gradient too
 struct EpGatherArgs {
     const float *ep_s, *ep_sp; const int* ep_a; const float* ep_r; const unsigned char* ep_done; const int* ep_len;
     const long long* ep_idx; const int* ep_start; int E, B, T; float* x0; int* a_out; float *r_out, *done_out, *mask_out;

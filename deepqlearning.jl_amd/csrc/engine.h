@@ -34,6 +34,7 @@ struct EngineOpts {
     int no_red_head = 0;          // DQN_NO_RED_HEAD: keep k_reduce_multi + k_head_td where the fused reduce + head launch (red_head.hip) would apply (A/B, both schedules under test)
     int no_pregather = 0;         // DQN_NO_PREGATHER: dqn_train_steps keeps the gather launch in every step (A/B)
     int gru_stepwise = 0;         // DQN_GRU_STEPWISE: GRU layers take the per-step recurrence / BPTT launches where the whole-sequence kernels would apply (both schedules under test)
+    int rnn_stepwise = 0;         // DQN_RNN_STEPWISE: RNN layers take the per-step recurrence / BPTT launches where the whole-sequence kernels would apply (both schedules under test)
     int force_allreduce = 0, dp_allreduce = 0, dp_overlap = -1 /* -1: decided from world size and bytes (engine_program.hip) */, dp_no_one_graph = 0;      // DQN_FORCE_ALLREDUCE / DQN_DP_ALLREDUCE / DQN_DP_OVERLAP / DQN_DP_NO_ONE_GRAPH
     // timing probes (wrong numbers, right schedule) and stamps
     int head_dbg = 0, probe_no_tg = 0, drqn_probe = 0, drqn_stamps = 0, tiny_stop = 0;

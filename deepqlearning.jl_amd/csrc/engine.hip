@@ -95,13 +95,19 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (l.stream != DQN_STREAM_BASE) return fail("GRU layers are supported in the base chain only");
             if (d[i].n_in != l.in_feat) return fail("layer %d: GRU n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.H = d[i].n_out; l.K = d[i].n_in; l.N = 3 * l.H; l.npos = 1; l.out_feat = l.H; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (l.kind == DQN_LAYER_RNN) {      // the LSTM's restrictions, with the same messages; the cell's activation goes to cell_act, never to act (rnn.hip applies it)
+            if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
+            if (l.stream != DQN_STREAM_BASE) return fail("RNN layers are supported in the base chain only");
+            if (d[i].n_in != l.in_feat) return fail("layer %d: RNN n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID) return fail("layer %d: RNN activation %d is not one of DQN_ACT_*", i, d[i].act);
+            l.H = d[i].n_out; l.K = d[i].n_in; l.N = l.H; l.npos = 1; l.out_feat = l.H; l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
         } else return fail("layer %d: unknown kind %d", i, l.kind);
         if (l.kind == DQN_LAYER_LSTM) {
             const size_t kn = (size_t)l.K * l.N, hn = (size_t)l.H * l.N;
             l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H; l.ec0_off = eoff; eoff += l.H;
             off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
             l.h0_off = off; off += l.H; l.c0_off = off; off += l.H; off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
-        } else if (l.kind == DQN_LAYER_GRU) {      // Flux.params Wi, Wh, b, h0 -> internal [Wi][b][Wh][junk][h0][zeros]
+        } else if (l.kind == DQN_LAYER_GRU || l.kind == DQN_LAYER_RNN) {      // Flux.params Wi, Wh, b, h0 -> internal [Wi][b][Wh][junk][h0][zeros]
             const size_t kn = (size_t)l.K * l.N, hn = (size_t)l.H * l.N;
             l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H;
             off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
@@ -131,7 +137,7 @@ void read_opts(EngineOpts& o, bool comm_only) {
     // switches that keep a SECOND SCHEDULE of the same arithmetic under parity tests (tests/ name each of them) or that a tool under tools/ drives
     o.no_tiny = F("DQN_NO_TINY"); o.fwd_m32 = I("DQN_FWD_M32", -1); o.no_fwd_wres = F("DQN_NO_FWD_WRES"); o.sim_world = I("DQN_SIM_WORLD", 0); o.no_pregather = F("DQN_NO_PREGATHER");
     o.no_red_head = F("DQN_NO_RED_HEAD"); o.no_head_cols4 = I("DQN_NO_HEAD_COLS4", 0); o.dw_split = I("DQN_DW_SPLIT", 128); o.no_rh_pm = F("DQN_NO_RH_PM"); o.no_act_head = F("DQN_NO_ACT_HEAD"); o.drqn_stamps = F("DQN_DRQN_STAMPS");
-    o.gru_stepwise = F("DQN_GRU_STEPWISE");
+    o.gru_stepwise = F("DQN_GRU_STEPWISE"); o.rnn_stepwise = F("DQN_RNN_STEPWISE");
     // r06 removed (the constants they set are now the only behaviour): DQN_ADAM_MODE, DQN_PRIO_LEVEL, DQN_PRIO_NOSPLIT, DQN_PRIO_FORK, DQN_HEAD_FUSE_MAXB,
     // DQN_NO_HEAD_FUSE, DQN_NO_U8_ARENA, DQN_LSTM_DW_MFMA, DQN_NO_GRAPH_UPLOAD, DQN_NO_ST_WT, DQN_NO_DX_WIDE, DQN_NO_ROLLOUT_CYCLE, DQN_MID_GROUP, DQN_MID_BIG
     // (docs/history/r06.md lists each with the number that decided it)
@@ -302,6 +308,9 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
             DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc);
             DM(e->gates[i], (size_t)l.N * Bc); DM(e->tcb[i], (size_t)l.H * Bc); DM(e->hprev_buf[i], (size_t)l.H * Bc);
             DM(e->dG[i], 2 * (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B); DM(e->dcn[i], (size_t)l.H * B);
+        } else if (l.kind == DQN_LAYER_RNN) {      // no gate stash: BPTT reads h_t back from act_on; dG: the one gate gradient
+            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc);
+            DM(e->hprev_buf[i], (size_t)l.H * Bc); DM(e->dG[i], (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B);
         }
     }
     if (hp->recurrence) {   // EpisodeReplayBuffer (src/episode_replay.jl:3-40): buffer_size EPISODES, first trace_length transitions of each
@@ -1018,7 +1027,7 @@ int policy_state(dqn_engine* e, int n, bool force_reset) {
     if (!e->hp.recurrence) return 0;
     if (n != e->pol_state_n) {
         for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-            const bool lstm = e->L[i].kind == DQN_LAYER_LSTM;      // a GRU carries h only
+            const bool lstm = e->L[i].kind == DQN_LAYER_LSTM;      // a GRU or an RNN carries h only
             for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(e->pol_h[i][k], (size_t)e->L[i].H * n); if (lstm) DM(e->pol_c[i][k], (size_t)e->L[i].H * n); }
             hipFree(e->pol_gx[i]); e->pol_gx[i] = nullptr; DM(e->pol_gx[i], (size_t)e->L[i].N * n);
         }
@@ -1061,6 +1070,14 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
             GruSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
             q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1;
             launch_gru_step_t(e->stream, a, 0);
+            HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
+        } else if (l.kind == DQN_LAYER_RNN) {      // one Recur step of the RNN: Gx = Wi*x (bias-free view), then the cell with the carried h
+            LayerDev V = l; V.kind = DQN_LAYER_DENSE; V.out_feat = l.N; V.b_off = l.z_off; V.act = DQN_ACT_IDENTITY;
+            fwd_layer(e, V, P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
+            RnnStepArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.nseq = 1; a.act = l.cell_act;
+            RnnSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
+            q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1;
+            launch_rnn_step_t(e->stream, a, 0);
             HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
         } else fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");
     }

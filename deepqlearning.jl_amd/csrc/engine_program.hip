@@ -332,6 +332,35 @@ int build_program(dqn_engine* e) {
                 e->prog.push_back({pname(e, "gru_step", L.kind, l), [=](dqn_engine* en) { launch_gru_step_t(en->stream, a, t); }});
             }
         }
+        if (e->L[lv[0]].kind == DQN_LAYER_RNN) {      // the RNN's recurrence, where the LSTM's and the GRU's are emitted (rnn.hip)
+            const int l = lv[0]; const LayerDev L = e->L[l]; const int H = L.H;
+            if (rnn_seq_fits(H, Bb, T) && !e->opt.rnn_stepwise) {
+                RnnSeqArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; a.act = L.cell_act; int ns = 0;
+                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
+                    RnnSeqF& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off; q.h0 = P + L.h0_off;
+                    if (keep) { q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
+                };
+                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
+                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
+                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
+                a.nseq = ns;
+                e->prog.push_back({pname(e, "rnn_seq", L.kind, l), [=](dqn_engine* en) { launch_rnn_seq(en->stream, a); }});
+            } else
+            for (int t = 0; t < T; t++) {
+                RnnStepArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.act = L.cell_act; int ns = 0;
+                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
+                    RnnSeq& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
+                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; }
+                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; }
+                    if (keep) { q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
+                };
+                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
+                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
+                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
+                a.nseq = ns;
+                e->prog.push_back({pname(e, "rnn_step", L.kind, l), [=](dqn_engine* en) { launch_rnn_step_t(en->stream, a, t); }});
+            }
+        }
     }
     // ---------------- dueling reduce + argmax + Bellman target + TD + Huber + dL/dQ + priority update
     {
@@ -529,6 +558,12 @@ int build_program(dqn_engine* e) {
                     a.dH = dpre; a.dGx = e->dG[l]; a.dGh = e->dG[l] + (size_t)L.N * B; a.dhn = e->dhn[l]; a.dhz = e->dcn[l]; a.g_h0 = grad + L.h0_off;
                     if (gru_seq_fits(L.H, Bb, T) && !e->opt.gru_stepwise) e->prog.push_back({pname(e, "gru_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_seq(en->stream, a); }});
                     else for (int t = T - 1; t >= 0; t--) { GruBwdArgs at = a; at.t = t; e->prog.push_back({pname(e, "gru_bwd", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_step(en->stream, at); }}); }
+                } else
+                if (L.kind == DQN_LAYER_RNN) {      // RNN: ONE gate gradient dG = act'(dh) feeds Wi | b, Wh and the input dX, as the LSTM's dG does (rnn.hip)
+                    RnnBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.act = L.cell_act; a.hout = e->act_on[l]; a.ld_h = ncon; a.Wh = e->p_on + L.wh_off;
+                    a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.g_h0 = grad + L.h0_off;
+                    if (rnn_seq_fits(L.H, Bb, T) && !e->opt.rnn_stepwise) e->prog.push_back({pname(e, "rnn_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_rnn_bwd_seq(en->stream, a); }});
+                    else for (int t = T - 1; t >= 0; t--) { RnnBwdArgs at = a; at.t = t; e->prog.push_back({pname(e, "rnn_bwd", L.kind, l), [=](dqn_engine* en) { launch_rnn_bwd_step(en->stream, at); }}); }
                 } else
                 if (lstm_seq_fits(L.H, Bb, T)) {
                     LstmBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.tc = e->tcb[l]; a.cprev = e->cprev_buf[l]; a.Wh = e->p_on + L.wh_off;

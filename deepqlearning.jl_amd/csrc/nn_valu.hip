@@ -565,7 +565,7 @@ __global__ void k_convert_params(const LayerDev* __restrict__ layers, int nl, co
             j = L.w_off + e; break;
         }
         if (i >= L.eb_off && i < L.eb_off + (size_t)L.N) { j = L.b_off + (i - L.eb_off); break; }
-        if (is_recurrent(L.kind)) {              // Flux.params order Wi, Wh, b, h0(, c0) -> internal [Wi][b][Wh][junk][h0]([c0])[zeros]
+        if (is_recurrent(L.kind)) {              // Flux.params order Wi, Wh, b, h0(, c0) -> internal [Wi][b][Wh][junk][h0]([c0])[zeros] (LSTM; GRU, RNN without c0)
             if (i >= L.ewh_off && i < L.ewh_off + (size_t)L.H * L.N) { j = L.wh_off + (i - L.ewh_off); break; }
             if (i >= L.eh0_off && i < L.eh0_off + (size_t)L.H) { j = L.h0_off + (i - L.eh0_off); break; }
             if (L.kind == DQN_LAYER_LSTM && i >= L.ec0_off && i < L.ec0_off + (size_t)L.H) { j = L.c0_off + (i - L.ec0_off); break; }

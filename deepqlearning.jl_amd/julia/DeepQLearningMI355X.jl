@@ -62,10 +62,12 @@ function lower_layer(l, stream)::LayerDesc
         return LayerDesc(1, ACT[l.σ], stream, 0, 0, cin, cout, kh, kw, l.stride[2], l.stride[1])
     elseif l isa Flux.Recur && l.cell isa Flux.LSTMCell     # Flux.params order Wi, Wh, b, state0 (h0, c0) == the ABI's LSTM block
         return LayerDesc(2, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
-    elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (GRUv3Cell / RNNCell: unsupported)
+    elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (Flux's GRUv3 has another block: unsupported)
         return LayerDesc(3, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
+    elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ
+        return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / Dense / LSTM / GRU / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / Dense / LSTM / GRU / RNN / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 function lower(q)
@@ -251,10 +253,10 @@ function getnetwork(p::HIPNNPolicy)                    # Flux.params(active_q) <
 end
 resetstate!(p::HIPNNPolicy) = check(ccall((:dqn_reset_state, LIB), Cint, (Ptr{Cvoid},), p.e.h))   # Flux.reset!: Recur state <- state0
 # hiddenstates(m) / sethiddenstates!(m, hs) (src/helpers.jl:61-79) for the policy's Recur state, which lives in the engine: flat Float32 vector, per
-# recurrent layer in chain order: an LSTM layer's h then c, a GRU layer's h.  The engine keeps it apart from the train step's sequences, so the save / restore the reference does around batch_train! (:137-139) is a no-op
+# recurrent layer in chain order: an LSTM layer's h then c, a GRU or RNN layer's h.  The engine keeps it apart from the train step's sequences, so the save / restore the reference does around batch_train! (:137-139) is a no-op
 # here; these exist for callers that checkpoint or transplant the state themselves.
 function hiddenstates(p::HIPNNPolicy)
-    n = sum(Int[(l.cell isa Flux.LSTMCell ? 2 : 1) * size(l.cell.Wh, 2) for l in filter(l -> l isa Flux.Recur, collect(p.qnetwork))])      # Wh: (4h, h) / (3h, h)
+    n = sum(Int[(l.cell isa Flux.LSTMCell ? 2 : 1) * size(l.cell.Wh, 2) for l in filter(l -> l isa Flux.Recur, collect(p.qnetwork))])      # Wh: (4h, h) / (3h, h) / (h, h)
     hc = zeros(Float32, n)
     check(ccall((:dqn_get_hidden, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Csize_t), p.e.h, hc, n))
     hc

@@ -75,6 +75,22 @@ class GRU:
         return [(self.n_in, 3 * h), (h, 3 * h)]
 
 
+class RNN:
+    """Flux RNN(in, out, σ = tanh) = Recur(RNNCell): h' = σ.(Wi*x .+ Wh*h .+ b); params Wi (out,in), Wh (out,out), b (out, zero), state0 h0 (out,1, zero)."""
+    kind = "rnn"
+
+    def __init__(self, n_in, n_out, act=tanh):
+        self.n_in, self.n_out, self.act = int(n_in), int(n_out), act     # act: the CELL's σ (lowered into dqn_layer_desc.act)
+
+    def shapes(self):   # Julia memory order: Wi (out,in) == C (in,out), Wh (out,out) == C (out,out), b, h0
+        h = self.n_out
+        return [(self.n_in, h), (h, h), (h,), (h,)]
+
+    def fans(self):     # glorot fans of Wi and Wh
+        h = self.n_out
+        return [(self.n_in, h), (h, h)]
+
+
 class Chain:
     def __init__(self, *layers):
         self.layers = [l for l in layers if getattr(l, "kind", None) != "flatten" and l is not flattenbatch]
@@ -123,8 +139,8 @@ def lower(net):
     def add(chain, stream):
         for l in chain:
             d = _abi.LayerDesc()
-            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "conv"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / Dense / LSTM / GRU / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / Dense / LSTM / GRU / RNN / flattenbatch only)")
             d.act, d.stream = l.act, stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -132,6 +148,8 @@ def lower(net):
                 d.kind, d.n_in, d.n_out = _abi.LAYER_LSTM, l.n_in, l.n_out
             elif l.kind == "gru":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_GRU, l.n_in, l.n_out
+            elif l.kind == "rnn":       # act carries the cell's σ
+                d.kind, d.n_in, d.n_out = _abi.LAYER_RNN, l.n_in, l.n_out
             else:
                 d.kind = _abi.LAYER_CONV
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
@@ -148,7 +166,7 @@ def lower(net):
 
 def isrecurrent(m):
     """src/helpers.jl:25-32."""
-    return any(getattr(l, "kind", None) in ("lstm", "gru") for l in all_layers(m))
+    return any(getattr(l, "kind", None) in ("lstm", "gru", "rnn") for l in all_layers(m))
 
 
 def all_layers(net):
@@ -169,10 +187,10 @@ def glorot_params(net, seed=1):
             b[h:2 * h] = 1.0        # Flux LSTMCell: forget-gate bias initialised to 1
             parts += [b, np.zeros(h, np.float32), np.zeros(h, np.float32)]
             continue
-        if l.kind == "gru":      # Flux GRUCell: glorot Wi, Wh; zero b (no forget-gate bias); zero state0
+        if l.kind in ("gru", "rnn"):      # Flux GRUCell / RNNCell: glorot Wi, Wh; zero b (no forget-gate bias); zero state0
             for shp, (fi, fo) in zip(l.shapes()[:2], l.fans()):
                 parts.append(((rng.random(shp, dtype=np.float32) - np.float32(0.5)) * np.sqrt(np.float32(24.0) / np.float32(fi + fo))).astype(np.float32).reshape(-1))
-            parts += [np.zeros(3 * l.n_out, np.float32), np.zeros(l.n_out, np.float32)]
+            parts += [np.zeros(l.shapes()[2], np.float32), np.zeros(l.n_out, np.float32)]
             continue
         wshape, bshape = l.shapes()
         fi, fo = l.fans()

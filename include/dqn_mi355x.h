@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4 };
 enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3 };
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
@@ -53,10 +53,12 @@ enum { DQN_NET_ONLINE = 0, DQN_NET_TARGET = 1 };
  * flattenbatch (src/helpers.jl:6-8) is implicit between a Conv and a Dense. */
 typedef struct {
     int32_t kind;   /* DQN_LAYER_* */
-    int32_t act;    /* DQN_ACT_* */
+    int32_t act;    /* DQN_ACT_*; for an RNN layer the cell's activation */
     int32_t stream; /* DQN_STREAM_*; all BASE when dueling == 0 */
     int32_t n_in, n_out;               /* Dense(in,out); LSTM(in,out) = Flux Recur(LSTMCell): params Wi (4out,in), Wh (4out,out), b (4out), state0 h0, c0;
-                                          GRU(in,out) = Flux Recur(GRUCell): params Wi (3out,in), Wh (3out,out), b (3out), state0 h0 */
+                                          GRU(in,out) = Flux Recur(GRUCell): params Wi (3out,in), Wh (3out,out), b (3out), state0 h0;
+                                          RNN(in,out,act) = Flux Recur(RNNCell): params Wi (out,in), Wh (out,out), b (out), state0 h0 (out,1),
+                                          in C order Wi[in][out], Wh[out][out], b, h0; act carries the cell's activation (default tanh) */
     int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw)), pad 0 */
 } dqn_layer_desc;
 
@@ -204,8 +206,8 @@ int dqn_train_step_drqn(dqn_engine_t* e, const int64_t* ep_idx, const int32_t* e
  * dqn_forward / dqn_greedy_action advance it for recurrent networks (n streams, one per observation row). */
 int dqn_reset_state(dqn_engine_t* e);
 /* Flat layout, per recurrent layer in chain order: an LSTM layer writes h then c, a GRU layer writes h; each is [out][streams]
- * (streams = observations per dqn_forward call, 1 before the first).  n = sum over LSTM layers of 2 x out x streams + sum over
- * GRU layers of out x streams floats. */
+ * (streams = observations per dqn_forward call, 1 before the first).  An RNN layer writes h only, [out][streams], as a GRU layer does.
+ * n = sum over LSTM layers of 2 x out x streams + sum over GRU and RNN layers of out x streams floats. */
 int dqn_get_hidden(dqn_engine_t* e, float* hc, size_t n);
 int dqn_set_hidden(dqn_engine_t* e, const float* hc, size_t n);
 

@@ -1,7 +1,7 @@
 """Config 4: TestMDP((5,5),1,6) observations (25), Chain(flattenbatch, LSTM(25,32), Dense(32,4)) (benchmark/flux_dqn.jl:35-36),
 trace_length 8, B = 32, double-Q, no dueling.  Prints DRQN train steps/s (hipGraph replay, sampler on the device) and the per-launch table.
---cell gru: the same shape with GRU(25,32) (the multi-launch recurrent program); --contiguous-dw: the LSTM on a dw_kc >= 0 plan (its
-multi-launch program instead of the fused column-parallel step), the like-for-like comparison for the GRU."""
+--cell gru / --cell rnn: the same shape with GRU(25,32) / RNN(25,32) (tanh) (the multi-launch recurrent program); --contiguous-dw: the LSTM on a dw_kc >= 0 plan (its
+multi-launch program instead of the fused column-parallel step), the like-for-like comparison for the GRU and the RNN."""
 import argparse
 import importlib
 import os
@@ -19,14 +19,14 @@ ap.add_argument("--hidden", type=int, default=32)
 ap.add_argument("--trace", type=int, default=8)
 ap.add_argument("--profile", action="store_true")
 ap.add_argument("--no-mfma", action="store_true")
-ap.add_argument("--cell", choices=["lstm", "gru"], default="lstm")
+ap.add_argument("--cell", choices=["lstm", "gru", "rnn"], default="lstm")
 ap.add_argument("--contiguous-dw", action="store_true")
 args = ap.parse_args()
 pkg = ge.load_package()
 nn = importlib.import_module(pkg.__name__ + ".nn")
 envs = importlib.import_module(pkg.__name__ + ".envs")
 S = importlib.import_module(pkg.__name__ + ".solver")
-model = nn.Chain(nn.flattenbatch, (nn.GRU if args.cell == "gru" else nn.LSTM)(25, args.hidden), nn.Dense(args.hidden, 4))
+model = nn.Chain(nn.flattenbatch, {"lstm": nn.LSTM, "gru": nn.GRU, "rnn": nn.RNN}[args.cell](25, args.hidden), nn.Dense(args.hidden, 4))
 layers, _ = nn.lower(model)
 hp = pkg.default_hparams(batch_size=32, n_actions=4, obs_c=1, obs_h=5, obs_w=5, gamma=0.99, double_q=1, dueling=0, prioritized_replay=0,
                          buffer_size=1000, recurrence=1, trace_length=args.trace, learning_rate=1e-3, use_mfma=0 if args.no_mfma else 1)
