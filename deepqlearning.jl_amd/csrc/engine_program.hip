@@ -651,7 +651,7 @@ int build_program(dqn_engine* e) {
             }
             float* out = e->dact[src]; const float *addend = nullptr, *ysrc = e->act_on[src];
             if (is_join && !joined) { out = e->join_tmp; ysrc = nullptr; joined = true; }
-            else if (is_join) { addend = e->join_tmp; flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l)); }   // depends on the first stream's dX
+            else if (is_join) { addend = e->join_tmp; flush_dx(); flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l)); }   // depends on the first stream's dX: an LDS-tiled one still waits in dxl
             const int S = (mf && !addend && gemm_dx_internal_chunks(L, B, ncon)) ? 1 : S_plan;      // internal: the launch combines its plan chunks itself (no slabs)
             float* part = S > 1 ? palloc(e, (size_t)S * L.in_feat * B) : nullptr;
             if (mf && !addend && gemm_dx_eligible(L, B, ncon)) {

@@ -156,18 +156,19 @@ LIVE_BLOCK = 1e-4      # a checked block's fp64 gradient must reach this fractio
 WORST = {}             # largest error / scale seen per block name while checking (for choosing GRAD_C)
 
 
-def dead_blocks(net, nn, g):
-    """the blocks whose fp64 gradient is negligible (see LIVE_BLOCK); a test config must have none"""
+def dead_blocks(net, nn, g, blks=None):
+    """the blocks whose fp64 gradient is negligible (see LIVE_BLOCK); a test config must have none.  blks: the [(name, slice)] list of a network
+    that blocks() does not describe (feedforward_reference.blocks: Conv and Dense layers of an oracle Network)"""
     gmax = np.abs(g).max()
-    return [nm for nm, sl in blocks(net, nn) if not np.abs(g[sl]).max() > LIVE_BLOCK * gmax]
+    return [nm for nm, sl in (blocks(net, nn) if blks is None else blks) if not np.abs(g[sl]).max() > LIVE_BLOCK * gmax]
 
 
-def check_grads(net, nn, got, want, c=GRAD_C, rtol=GRAD_RTOL, live=True):
+def check_grads(net, nn, got, want, c=GRAD_C, rtol=GRAD_RTOL, live=True, blks=None):
     """got (engine) against want (fp64) block by block.  live: also assert that no block's fp64 gradient is negligible (a config's first
-    step; training may kill a block later -- a dead relu stream -- and the block is then still held to c * 1e-2 * max |g|)"""
+    step; training may kill a block later -- a dead relu stream -- and the block is then still held to c * 1e-2 * max |g|).  blks: as in dead_blocks"""
     gmax = np.abs(want).max()
     assert gmax > 0
-    for nm, sl in blocks(net, nn):
+    for nm, sl in (blocks(net, nn) if blks is None else blks):
         w = want[sl]; bmax = np.abs(w).max()
         assert not live or bmax > LIVE_BLOCK * gmax, f"{nm}: fp64 gradient {bmax:.3g} is negligible against max |g| = {gmax:.3g}"
         scale = max(bmax, 1e-2 * gmax)
