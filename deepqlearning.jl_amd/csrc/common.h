@@ -756,6 +756,7 @@ int adam_blocks(size_t P);
 static inline int gmax_slots(size_t) { return 65536; }   // per-block max |g| of every Adam job of a step (each job owns a slot range)
 void launch_adam(hipStream_t st, const AdamJob& job, const PreGather* pg = nullptr /* see PreGather */);
 void launch_q_columns(hipStream_t st, int n, int nA, int dueling, const float* val, const float* adv, float* q_out /*[n][nA]*/, int* argmax_out);
+void launch_clear_rows(hipStream_t st, float* p, int nrows, size_t stride, int n);   // p[r*stride + i] = 0, r < nrows, i < n
 void launch_convert_params(hipStream_t st, const LayerDev* layers_dev, int nl, const float* src, float* dst, int to_internal, size_t P_ext);
 
 // LDS-tiled MFMA path (nn_gemm.hip): up to two problems (online / target net) of one layer per launch
@@ -772,83 +773,70 @@ void launch_gemm_fwd(hipStream_t st, const LayerDev& L, int nprob, const float* 
                      float* const* outT = nullptr /* optional, dense unsplit layers: a TRANSPOSED copy [column][feature] of Y per problem (k_head_td's input columns) */,
                      int piece_major = 0 /* dense split-K layers whose slabs only k_red_head reads: slabs laid out [S][column quad][N][4] (GFwdProb::pm, nn_gemm.hip) */);
 
-// ---- DRQN (drqn.hip): EpisodeReplayBuffer gather, LSTM recurrence / BPTT steps, recurrent TD
-struct LstmSeq {          // one sequence set advancing one time step: B columns starting at column c0 (+ t*B) of [*][ld] arrays
-    const float* Gx; float* Hout; float* Cst; int ld, c0;
-    const float *Wh, *bias;
-    const float* hprev; int hp_ld, hp_bs;     // h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]   (h0 broadcast: ld 1, bs 0)
-    const float* cprev; int cp_ld, cp_bs;
-    float *gates, *tc, *hprev_out, *cprev_out; int keep_ld, keep_c0;   // BPTT stash (online s-sequence) or null
+// ---- DRQN: EpisodeReplayBuffer gather and recurrent TD (drqn.hip); the recurrent cells -- LSTM (drqn.hip), GRU (gru.hip), RNN (rnn.hip).
+// Every cell is decomposed the same way: Gx = Wi*x over all T*B columns by the dense kernels, the recurrence and BPTT by the cell's own kernels
+// (one launch per time step, or one whole-sequence launch where <cell>_seq_fits), dW / dX by the dense kernels.  The three cells share the
+// argument structs below and the engine reaches them through the cell table (cell_ops).
+struct CellSeq {          // one sequence set: B columns starting at column c0 (+ t*B) of [*][ld] arrays
+    const float* Gx; float* Hout;             // all cells: the input projection [N][ld], the output h [H][ld]
+    float* Cst; int ld, c0;                   // Cst: LSTM, the cell state c [H][ld]
+    const float *Wh, *bias;                   // all cells
+    const float* hprev; int hp_ld, hp_bs;     // all cells: h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]; state0 broadcast over the batch (Flux.reset!): ld 1, bs 0.
+                                              // Step kernels: the state before step t; whole-sequence kernels: the state before step 0
+    const float* cprev; int cp_ld, cp_bs;     // LSTM: c_{t-1}, likewise
+    // BPTT stash (online s-sequence) or null, [*][keep_ld] from column keep_c0: gates -- LSTM i, f, g, o [4H], GRU r, z, n [3H]; aux [H] -- LSTM tanh(c),
+    // GRU Wh_n*h; hprev_out [H] -- all cells, h_{t-1}; cprev_out [H] -- LSTM, c_{t-1}.  (The RNN stashes h_{t-1} alone: BPTT reads h_t back from Hout)
+    float *gates, *aux, *hprev_out, *cprev_out; int keep_ld, keep_c0;
 };
-struct LstmStepArgs { LstmSeq s[3]; int nseq, H, B; };
-void launch_lstm_step_t(hipStream_t st, const LstmStepArgs& a, int t);
-struct LstmBwdArgs {
-    int t, T, H, B, TB; const float *gates, *tc, *cprev, *Wh; const float* dH; float* dG; float *dhn, *dcn; float *g_h0, *g_c0;
-};
-void launch_lstm_bwd_step(hipStream_t st, const LstmBwdArgs& a);
-// whole-sequence variants (small LSTMs: Wh and one step's state in LDS)
-struct LstmSeqF {
-    const float* Gx; float* Hout; float* Cst; int ld, c0;
-    const float *Wh, *bias, *h0, *c0v;
-    float *gates, *tc, *hprev_out, *cprev_out; int keep_ld, keep_c0;
-};
-struct LstmSeqArgs { LstmSeqF s[3]; int nseq, H, B, T; };
-bool lstm_seq_fits(int H, int B, int T);
-void launch_lstm_seq(hipStream_t st, const LstmSeqArgs& a);
-void launch_lstm_bwd_seq(hipStream_t st, const LstmBwdArgs& a);   // a.t ignored
-// GRU (gru.hip): the same decomposition as the LSTM's -- Gx = Wi*x by the dense kernels, the recurrence by these, dW / dX by the dense kernels
-struct GruSeq {           // one sequence set advancing one time step: B columns starting at column c0 (+ t*B) of [*][ld] arrays
-    const float* Gx; float* Hout; int ld, c0;
-    const float *Wh, *bias;
-    const float* hprev; int hp_ld, hp_bs;     // h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]   (h0 broadcast: ld 1, bs 0)
-    float *gates, *ghn, *hprev_out; int keep_ld, keep_c0;      // BPTT stash (online s-sequence) or null: r, z, n [3H], Wh_n*h [H], h_{t-1} [H]
-};
-struct GruStepArgs { GruSeq s[3]; int nseq, H, B; };
-void launch_gru_step_t(hipStream_t st, const GruStepArgs& a, int t);
-struct GruSeqF {
-    const float* Gx; float* Hout; int ld, c0;
-    const float *Wh, *bias, *h0;
-    float *gates, *ghn, *hprev_out; int keep_ld, keep_c0;
-};
-struct GruSeqArgs { GruSeqF s[3]; int nseq, H, B, T; };
-struct GruBwdArgs {
-    int t, T, H, B, TB; const float *gates, *ghn, *hprev, *Wh; const float* dH;
-    float *dGx, *dGh;        // [3H][TB] each: [dr; dz; dn] (Wi | b, input dX) and [dr; dz; dn .* r] (Wh)
-    float *dhn, *dhz;        // [H][B]: dh_{t-1}; dh .* z of the current step (per-step form only)
-    float* g_h0;
-};
-bool gru_seq_fits(int H, int B, int T);
-void launch_gru_seq(hipStream_t st, const GruSeqArgs& a);
-void launch_gru_bwd_step(hipStream_t st, const GruBwdArgs& a);
-void launch_gru_bwd_seq(hipStream_t st, const GruBwdArgs& a);   // a.t ignored; folds the state0 gradient too
-void launch_clear_rows(hipStream_t st, float* p, int nrows, size_t stride, int n);   // p[r*stride + i] = 0, r < nrows, i < n
-// RNN (rnn.hip): Gx = Wi*x by the dense kernels, h' = act((Gx + Wh*h) + b) by these, dW / dX by the dense kernels (one gate gradient dG for all three)
-struct RnnSeq {           // one sequence set advancing one time step: B columns starting at column c0 (+ t*B) of [*][ld] arrays
-    const float* Gx; float* Hout; int ld, c0;
-    const float *Wh, *bias;
-    const float* hprev; int hp_ld, hp_bs;     // h_{t-1}(j,b) = hprev[j*hp_ld + b*hp_bs]   (h0 broadcast: ld 1, bs 0)
-    float* hprev_out; int keep_ld, keep_c0;   // BPTT stash (online s-sequence) or null: h_{t-1} [H]
-};
-struct RnnStepArgs { RnnSeq s[3]; int nseq, H, B, act; };
-void launch_rnn_step_t(hipStream_t st, const RnnStepArgs& a, int t);
-struct RnnSeqF {
-    const float* Gx; float* Hout; int ld, c0;
-    const float *Wh, *bias, *h0;
-    float* hprev_out; int keep_ld, keep_c0;
-};
-struct RnnSeqArgs { RnnSeqF s[3]; int nseq, H, B, T, act; };
-struct RnnBwdArgs {
-    int t, T, H, B, TB, act;
-    const float* hout; int ld_h;            // h_t of the online s-sequence: hout[u*ld_h + t*B + b] (the forward's output, read back for act')
+struct CellFwdArgs { CellSeq s[3]; int nseq, H, B, T, act; };      // T: whole-sequence launches; act: RNN, the cell's activation
+struct CellBwdArgs {      // BPTT over the online s-sequence, all [*][TB] arrays in the stash's column order
+    int t, T, H, B, TB, act;                  // t: per-step launches; act: RNN
+    const float *gates, *aux, *hprev, *cprev; // the forward's stash: gates, aux -- LSTM, GRU; hprev -- GRU; cprev -- LSTM
+    const float* hout; int ld_h;              // RNN: h_t = hout[u*ld_h + t*B + b] (the forward's output, read back for act')
     const float *Wh, *dH;
-    float* dG;                              // [H][TB]: dact(dh) -> Wi | b, Wh (X = h_{t-1}) and the input dX
-    float* dhn;                             // [H][B]: dh_{t-1}
-    float* g_h0;
+    float *dG, *dGh;         // gate gradients [N][TB]: dG -> Wi | b dW and the input dX, dGh -> Wh dW (X = h_{t-1}).  LSTM, RNN: dGh == dG; GRU: [dr; dz; dn] and [dr; dz; dn .* r]
+    float *dhn, *dh2;        // [H][B]: dh_{t-1}; LSTM dc_{t-1}, GRU dh .* z of the current step (per-step launches only)
+    float *g_h0, *g_c0;      // state0 gradients; g_c0: LSTM, else null
 };
+void launch_lstm_step_t(hipStream_t st, const CellFwdArgs& a, int t);
+void launch_lstm_bwd_step(hipStream_t st, const CellBwdArgs& a);
+// whole-sequence variants (small cells: Wh and one step's state in LDS); the backward ones fold the state0 gradient too
+bool lstm_seq_fits(int H, int B, int T);
+void launch_lstm_seq(hipStream_t st, const CellFwdArgs& a);
+void launch_lstm_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
+void launch_gru_step_t(hipStream_t st, const CellFwdArgs& a, int t);
+void launch_gru_bwd_step(hipStream_t st, const CellBwdArgs& a);
+bool gru_seq_fits(int H, int B, int T);
+void launch_gru_seq(hipStream_t st, const CellFwdArgs& a);
+void launch_gru_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
+void launch_rnn_step_t(hipStream_t st, const CellFwdArgs& a, int t);
+void launch_rnn_bwd_step(hipStream_t st, const CellBwdArgs& a);
 bool rnn_seq_fits(int H, int B, int T);
-void launch_rnn_seq(hipStream_t st, const RnnSeqArgs& a);
-void launch_rnn_bwd_step(hipStream_t st, const RnnBwdArgs& a);
-void launch_rnn_bwd_seq(hipStream_t st, const RnnBwdArgs& a);   // a.t ignored; folds the state0 gradient too
+void launch_rnn_seq(hipStream_t st, const CellFwdArgs& a);
+void launch_rnn_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
+// the cell table: all that the engine's host code knows about a recurrent layer kind
+struct CellOps {
+    const char *name, *display;      // program step names ("<name>_seq", "<name>_bwd", ...); error messages
+    int ngates;                      // N = ngates * H.  Cells with more than one gate stash them (and aux) for BPTT and use dh2
+    bool has_act;                    // the layer descriptor's activation is the cell's (LayerDev::cell_act, CellFwdArgs / CellBwdArgs::act)
+    bool has_c;                      // carries a cell state c beside h: c0 in the parameter block, Cst / cprev / cprev_out / g_c0, the policy's second state
+    bool two_dG;                     // BPTT writes dGh apart from dG (dG buffer [2N][TB])
+    bool clear_junk;                 // the junk bias row of the Wh | junk dW pass is not a copy of db and may raise max |g|: cleared after the level's dW
+    bool (*seq_fits)(int H, int B, int T);
+    void (*launch_step)(hipStream_t, const CellFwdArgs&, int t);
+    void (*launch_seq)(hipStream_t, const CellFwdArgs&);
+    void (*launch_bwd_step)(hipStream_t, const CellBwdArgs&);
+    void (*launch_bwd_seq)(hipStream_t, const CellBwdArgs&);
+};
+static inline const CellOps* cell_ops(int kind) {      // kind: is_recurrent
+    static const CellOps tab[] = {
+        {"lstm", "LSTM", 4, false, true, false, false, lstm_seq_fits, launch_lstm_step_t, launch_lstm_seq, launch_lstm_bwd_step, launch_lstm_bwd_seq},
+        {"gru", "GRU", 3, false, false, true, true, gru_seq_fits, launch_gru_step_t, launch_gru_seq, launch_gru_bwd_step, launch_gru_bwd_seq},
+        {"rnn", "RNN", 1, true, false, false, false, rnn_seq_fits, launch_rnn_step_t, launch_rnn_seq, launch_rnn_bwd_step, launch_rnn_bwd_seq},
+    };
+    static_assert(DQN_LAYER_GRU == DQN_LAYER_LSTM + 1 && DQN_LAYER_RNN == DQN_LAYER_LSTM + 2, "cell table order");
+    return &tab[kind - DQN_LAYER_LSTM];
+}
 struct EpGatherArgs {
     const float *ep_s, *ep_sp; const int* ep_a; const float* ep_r; const unsigned char* ep_done; const int* ep_len;
     const long long* ep_idx; const int* ep_start; int E, B, T; float* x0; int* a_out; float *r_out, *done_out, *mask_out;

@@ -7,10 +7,7 @@
 // ordinary kernels (the LSTM's input projection Wi*x included); only the h/c recurrence is sequential: one small launch
 // per time step, all three sequence sets (online s, online sp, target sp) batched in it.  Canonical order as in the CPU
 // twin: gate pre-activation = ((chain_k Wi x) + (chain_j Wh h)) + b, sigm/tanh through double, rounded once.
-#include "common.h"
-
-__device__ __forceinline__ float sigm_f(float x) { return (float)(1.0 / (1.0 + exp(-(double)x))); }
-__device__ __forceinline__ float tanh_f(float x) { return (float)tanh((double)x); }
+#include "cell.h"
 
 // ------------------------------------------------------------------ sample(r::EpisodeReplayBuffer) for given draws
 __global__ void k_gather_episodes(EpGatherArgs A) {
@@ -40,11 +37,11 @@ void launch_gather_episodes(hipStream_t st, const EpGatherArgs& a) {
 }
 
 // ------------------------------------------------------------------ one LSTM time step for up to 3 sequence sets
-__global__ void k_lstm_step(LstmStepArgs A, int t) {
+__global__ void k_lstm_step(CellFwdArgs A, int t) {
     const int per = A.H * A.B;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= per * A.nseq) return;
-    const LstmSeq& S = A.s[i / per];
+    const CellSeq& S = A.s[i / per];
     const int e = i % per, u = e / A.B, b = e % A.B, H = A.H, N = 4 * H;
     const int col = S.c0 + t * A.B + b;
     float g[4];
@@ -61,25 +58,25 @@ __global__ void k_lstm_step(LstmStepArgs A, int t) {
     if (S.gates) {
         const size_t k = (size_t)S.keep_c0 + t * A.B + b; const size_t kl = S.keep_ld;
         S.gates[(size_t)(0 * H + u) * kl + k] = ig; S.gates[(size_t)(1 * H + u) * kl + k] = fg; S.gates[(size_t)(2 * H + u) * kl + k] = gg; S.gates[(size_t)(3 * H + u) * kl + k] = og;
-        S.tc[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = S.hprev[(size_t)u * S.hp_ld + (size_t)b * S.hp_bs]; S.cprev_out[(size_t)u * kl + k] = cp;
+        S.aux[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = S.hprev[(size_t)u * S.hp_ld + (size_t)b * S.hp_bs]; S.cprev_out[(size_t)u * kl + k] = cp;
     }
 }
-void launch_lstm_step_t(hipStream_t st, const LstmStepArgs& a, int t) {
+void launch_lstm_step_t(hipStream_t st, const CellFwdArgs& a, int t) {
     const int n = a.H * a.B * a.nseq;
     hipLaunchKernelGGL(k_lstm_step, dim3((n + 255) / 256), dim3(256), 0, st, a, t);
 }
 
 // ------------------------------------------------------------------ one BPTT step (single workgroup: dh_{t-1} needs all 4H gate gradients of step t)
-__global__ __launch_bounds__(1024) void k_lstm_bwd_step(LstmBwdArgs A) {
+__global__ __launch_bounds__(1024) void k_lstm_bwd_step(CellBwdArgs A) {
     const int H = A.H, B = A.B, TB = A.TB, N = 4 * H, t = A.t, per = H * B;
     for (int e = threadIdx.x; e < per; e += blockDim.x) {
         const int u = e / B, b = e % B; const size_t k = (size_t)t * B + b;
         const float ig = A.gates[(size_t)u * TB + k], fg = A.gates[(size_t)(H + u) * TB + k], gg = A.gates[(size_t)(2 * H + u) * TB + k], og = A.gates[(size_t)(3 * H + u) * TB + k];
-        const float tc = A.tc[(size_t)u * TB + k], cprev = A.cprev[(size_t)u * TB + k];
-        const float dhn = t == A.T - 1 ? 0.0f : A.dhn[e], dcn = t == A.T - 1 ? 0.0f : A.dcn[e];
+        const float tc = A.aux[(size_t)u * TB + k], cprev = A.cprev[(size_t)u * TB + k];
+        const float dhn = t == A.T - 1 ? 0.0f : A.dhn[e], dcn = t == A.T - 1 ? 0.0f : A.dh2[e];
         const float dh = A.dH[(size_t)u * TB + k] + dhn;
         const float dov = dh * tc; const float t1 = dh * og; const float t2 = tc * tc; const float t3 = 1.0f - t2; const float t4 = t1 * t3; const float dc = dcn + t4;
-        const float di = dc * gg, df = dc * cprev, dgc = dc * ig; A.dcn[e] = dc * fg;
+        const float di = dc * gg, df = dc * cprev, dgc = dc * ig; A.dh2[e] = dc * fg;
         const float a1 = di * ig, a2 = 1.0f - ig; A.dG[(size_t)u * TB + k] = a1 * a2;
         const float b1 = df * fg, b2 = 1.0f - fg; A.dG[(size_t)(H + u) * TB + k] = b1 * b2;
         const float c1 = gg * gg, c2 = 1.0f - c1; A.dG[(size_t)(2 * H + u) * TB + k] = dgc * c2;
@@ -94,14 +91,10 @@ __global__ __launch_bounds__(1024) void k_lstm_bwd_step(LstmBwdArgs A) {
     }
     if (t == 0) {                                              // trainable state0: gradient summed over the batch, ascending b
         __syncthreads();
-        for (int u = threadIdx.x; u < H; u += blockDim.x) {
-            float sh = 0.0f, sc = 0.0f;
-            for (int b = 0; b < B; b++) { sh = sh + A.dhn[u * B + b]; sc = sc + A.dcn[u * B + b]; }
-            A.g_h0[u] = sh; A.g_c0[u] = sc;
-        }
+        for (int u = threadIdx.x; u < H; u += blockDim.x) state0_fold<true>(u, B, A.dhn, A.dh2, A.g_h0, A.g_c0);
     }
 }
-void launch_lstm_bwd_step(hipStream_t st, const LstmBwdArgs& a) {
+void launch_lstm_bwd_step(hipStream_t st, const CellBwdArgs& a) {
     int bs = ((a.H * a.B + 63) / 64) * 64; if (bs > 1024) bs = 1024;
     hipLaunchKernelGGL(k_lstm_bwd_step, dim3(1), dim3(bs), 0, st, a);
 }
@@ -110,12 +103,11 @@ void launch_lstm_bwd_step(hipStream_t st, const LstmBwdArgs& a) {
 // The per-step launches above cost a dispatch and a cold walk over Wh per time step.  When Wh (H x 4H) and one step's state fit in
 // LDS, ONE launch runs the whole recurrence: workgroup s owns sequence set s (online s, online sp, target sp), keeps Wh, the bias
 // and the (h, c) state in LDS and walks t = 0..T-1; the arithmetic per output -- and therefore every bit -- is that of k_lstm_step.
-// Batch columns are independent in the recurrence, so a sequence set is further split into groups of CB columns (one workgroup
+// Batch columns are independent in the recurrence, so a sequence set is further split into groups of CB columns (cell_cb; one workgroup
 // each, its own LDS copy of Wh): H*CB ~ 256 outputs per step keeps one wave per SIMD busy and the double-precision sigm/tanh
 // (most of a step's instructions) spread over 4x more CUs.
-static int lstm_cb(int H, int B) { int cb = 256 / H; if (cb < 1) cb = 1; if (cb > B) cb = B; while (B % cb) cb--; return cb; }
 bool lstm_seq_fits(int H, int B, int T) {     // both kernels within 64 KB of dynamic LDS; the gate-parallel forward wants whole waves per gate
-    const int cb = lstm_cb(H, B);
+    const int cb = cell_cb(H, B);
     const size_t fwd = (size_t)H * 4 * H + 4 * H + 7 * (size_t)H * cb, bwd = (size_t)H * (4 * H + 1) + 6 * (size_t)H * cb;
     return fwd <= 16384 && bwd <= 16384 && (H * cb) % 64 == 0 && H * cb <= 256 && T <= 64;
 }
@@ -125,7 +117,7 @@ bool lstm_seq_fits(int H, int B, int T) {     // both kernels within 64 KB of dy
 // (2) the input projections Gx of ALL time steps are requested before the recurrence starts (they do not depend on it) -- one round trip instead of one
 // per time step.  Per-element arithmetic unchanged (same chains, same association), so every bit is k_lstm_step's.  TT: compile-time bound on T.
 template <int TT>
-__global__ __launch_bounds__(1024) void k_lstm_seq(LstmSeqArgs A, int CB) {
+__global__ __launch_bounds__(1024) void k_lstm_seq(CellFwdArgs A, int CB) {
     extern __shared__ float lds[];
     const int H = A.H, B = A.B, N = 4 * H, per = H * CB, T = A.T, nsplit = B / CB;
     float* Wh_s = lds;                 // [H][4H]
@@ -133,11 +125,11 @@ __global__ __launch_bounds__(1024) void k_lstm_seq(LstmSeqArgs A, int CB) {
     float* h_s = bias_s + N;           // [2][H*CB]
     float* c_s = h_s + 2 * per;        // [H*CB]
     float* g_s = c_s + per;            // [4][H*CB] activated gates of the current step
-    const LstmSeqF& S = A.s[blockIdx.x / nsplit];
+    const CellSeq& S = A.s[blockIdx.x / nsplit];
     const int b0 = (blockIdx.x % nsplit) * CB;
     for (int i = threadIdx.x; i < H * N; i += blockDim.x) Wh_s[i] = S.Wh[i];
     for (int i = threadIdx.x; i < N; i += blockDim.x) bias_s[i] = S.bias[i];
-    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB; h_s[e] = S.h0[u]; c_s[e] = S.c0v[u]; }      // Flux.reset!: state0 broadcast over the batch
+    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB; h_s[e] = S.hprev[u]; c_s[e] = S.cprev[u]; }      // Flux.reset!: state0 broadcast over the batch
     const int q = threadIdx.x / per, e = threadIdx.x - q * per;      // gate, (unit, column) element; per is a multiple of 64, so a wave has one gate
     const bool on = q < 4;
     const int u = e / CB, bl = e - u * CB, b = b0 + bl;
@@ -167,15 +159,15 @@ __global__ __launch_bounds__(1024) void k_lstm_seq(LstmSeqArgs A, int CB) {
             const float cp = c_s[e];
             const float t1 = fg * cp; const float t2 = ig * gg; const float c = t1 + t2; const float tc = tanh_f(c); const float h = og * tc;
             S.Hout[(size_t)u * S.ld + col] = h; S.Cst[(size_t)u * S.ld + col] = c;
-            if (S.gates) { const size_t k = (size_t)S.keep_c0 + t * B + b; const size_t kl = S.keep_ld; S.tc[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = hp[e]; S.cprev_out[(size_t)u * kl + k] = cp; }
+            if (S.gates) { const size_t k = (size_t)S.keep_c0 + t * B + b; const size_t kl = S.keep_ld; S.aux[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = hp[e]; S.cprev_out[(size_t)u * kl + k] = cp; }
             hn[e] = h; c_s[e] = c;
         }
         __syncthreads();
         cur ^= 1;
     }
 }
-void launch_lstm_seq(hipStream_t st, const LstmSeqArgs& a) {
-    const int cb = lstm_cb(a.H, a.B);
+void launch_lstm_seq(hipStream_t st, const CellFwdArgs& a) {
+    const int cb = cell_cb(a.H, a.B);
     const size_t lds = ((size_t)a.H * 4 * a.H + 4 * a.H + 7 * (size_t)a.H * cb) * sizeof(float);
     const int bs = 4 * a.H * cb;                      // 4 gates x (unit, column) elements; lstm_seq_fits: H * cb is a multiple of 64 and <= 256
     if (a.T <= 8) hipLaunchKernelGGL((k_lstm_seq<8>), dim3(a.nseq * (a.B / cb)), dim3(bs), lds, st, a, cb);
@@ -184,11 +176,11 @@ void launch_lstm_seq(hipStream_t st, const LstmSeqArgs& a) {
 }
 
 // BPTT over the whole s-sequence, one workgroup per group of CB columns (same arithmetic as T calls of k_lstm_bwd_step); the
-// trainable state0's gradient (a sum over ALL columns, ascending b) is folded by k_state0_grad afterwards.
+// trainable state0's gradient (a sum over ALL columns, ascending b) is folded by k_state0_grad (cell.h) afterwards.
 // PF: the seven stashed values of EVERY time step are requested before the loop (T <= 8: 56 registers) instead of one step ahead -- their round trip
 // was longer than a step's arithmetic (r03: 4.6 us per time step)
 template <bool PF>
-__global__ __launch_bounds__(1024) void k_lstm_bwd_seq(LstmBwdArgs A, int CB) {
+__global__ __launch_bounds__(1024) void k_lstm_bwd_seq(CellBwdArgs A, int CB) {
     extern __shared__ float lds[];
     const int H = A.H, B = A.B, TB = A.TB, N = 4 * H, per = H * CB, b0 = blockIdx.x * CB;
     const int NP = N + 1;              // padded row stride: lanes of one wave hold different rows j of Wh at the same n -- stride 4H put all of them on ONE bank (8-way conflict on every read of the 128-deep chain)
@@ -206,7 +198,7 @@ __global__ __launch_bounds__(1024) void k_lstm_bwd_seq(LstmBwdArgs A, int CB) {
     struct St { float ig, fg, gg, og, tc, cprev, dH; };
     auto fetch = [&](int t) { St s; const size_t k = (size_t)t * B + b0 + bl;
         s.ig = A.gates[(size_t)u * TB + k]; s.fg = A.gates[(size_t)(H + u) * TB + k]; s.gg = A.gates[(size_t)(2 * H + u) * TB + k]; s.og = A.gates[(size_t)(3 * H + u) * TB + k];
-        s.tc = A.tc[(size_t)u * TB + k]; s.cprev = A.cprev[(size_t)u * TB + k]; s.dH = A.dH[(size_t)u * TB + k]; return s; };
+        s.tc = A.aux[(size_t)u * TB + k]; s.cprev = A.cprev[(size_t)u * TB + k]; s.dH = A.dH[(size_t)u * TB + k]; return s; };
     St all[PF ? 8 : 1];
     if constexpr (PF) {
 #pragma unroll
@@ -243,22 +235,15 @@ __global__ __launch_bounds__(1024) void k_lstm_bwd_seq(LstmBwdArgs A, int CB) {
         }
         __syncthreads();
     }
-    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB, bl = e - u * CB; A.dhn[u * B + b0 + bl] = dhn_s[e]; A.dcn[u * B + b0 + bl] = dcn_s[e]; }
+    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB, bl = e - u * CB; A.dhn[u * B + b0 + bl] = dhn_s[e]; A.dh2[u * B + b0 + bl] = dcn_s[e]; }
 }
-__global__ void k_state0_grad(int H, int B, const float* __restrict__ dhn, const float* __restrict__ dcn, float* __restrict__ g_h0, float* __restrict__ g_c0) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= H) return;
-    float sh = 0.0f, sc = 0.0f;
-    for (int b = 0; b < B; b++) { sh = sh + dhn[u * B + b]; sc = sc + dcn[u * B + b]; }      // ascending b
-    g_h0[u] = sh; g_c0[u] = sc;
-}
-void launch_lstm_bwd_seq(hipStream_t st, const LstmBwdArgs& a) {
-    const int cb = lstm_cb(a.H, a.B);
+void launch_lstm_bwd_seq(hipStream_t st, const CellBwdArgs& a) {
+    const int cb = cell_cb(a.H, a.B);
     const size_t lds = ((size_t)a.H * (4 * a.H + 1) + 6 * (size_t)a.H * cb) * sizeof(float);
     int bs = ((a.H * cb + 63) / 64) * 64; if (bs > 1024) bs = 1024;
     if (a.T <= 8) hipLaunchKernelGGL((k_lstm_bwd_seq<true>), dim3(a.B / cb), dim3(bs), lds, st, a, cb);
     else hipLaunchKernelGGL((k_lstm_bwd_seq<false>), dim3(a.B / cb), dim3(bs), lds, st, a, cb);
-    hipLaunchKernelGGL(k_state0_grad, dim3((a.H + 63) / 64), dim3(64), 0, st, a.H, a.B, a.dhn, a.dcn, a.g_h0, a.g_c0);
+    launch_state0_grad(st, a);
 }
 
 // ------------------------------------------------------------------ recurrent TD: targets, masked Huber / B / T, dL/dQ  (src/solver.jl:259-282)

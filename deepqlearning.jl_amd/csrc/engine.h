@@ -40,6 +40,8 @@ struct EngineOpts {
     int head_dbg = 0, probe_no_tg = 0, drqn_probe = 0, drqn_stamps = 0, tiny_stop = 0;
 };
 void read_opts(EngineOpts& o, bool comm_only = false);
+// the per-step recurrence / BPTT launches are forced where the cell's whole-sequence kernels would apply (the LSTM has no such switch)
+static inline bool stepwise(const EngineOpts& o, int kind) { return kind == DQN_LAYER_GRU ? o.gru_stepwise != 0 : kind == DQN_LAYER_RNN ? o.rnn_stepwise != 0 : false; }
 
 enum { PH_ALL = 0, PH_PRE = 1, PH_POST = 2, PH_PRE1 = 3, PH_PRE2 = 4, PH_DP_ONE = 5 };      // PRE = PRE1 (up to the point where the wide layers' operands are final) + PRE2 (the rest of the backward pass)
 // One variant of the train step: what enqueue_step enqueues and what names its graph in the engine's cache (get_or_capture keeps, per phase, only the fields that phase reads).

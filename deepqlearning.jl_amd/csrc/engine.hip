@@ -85,33 +85,20 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (l.kind == DQN_LAYER_LSTM) {
+        } else if (is_recurrent(l.kind)) {      // the cell's activation (CellOps::has_act) goes to cell_act, never to act (the cell's kernels apply it)
+            const CellOps* C = cell_ops(l.kind);
             if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
-            if (l.stream != DQN_STREAM_BASE) return fail("LSTM layers are supported in the base chain only");
-            if (d[i].n_in != l.in_feat) return fail("layer %d: LSTM n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            l.H = d[i].n_out; l.K = d[i].n_in; l.N = 4 * l.H; l.npos = 1; l.out_feat = l.H; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (l.kind == DQN_LAYER_GRU) {      // the LSTM's restrictions, with the same messages
-            if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
-            if (l.stream != DQN_STREAM_BASE) return fail("GRU layers are supported in the base chain only");
-            if (d[i].n_in != l.in_feat) return fail("layer %d: GRU n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            l.H = d[i].n_out; l.K = d[i].n_in; l.N = 3 * l.H; l.npos = 1; l.out_feat = l.H; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (l.kind == DQN_LAYER_RNN) {      // the LSTM's restrictions, with the same messages; the cell's activation goes to cell_act, never to act (rnn.hip applies it)
-            if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
-            if (l.stream != DQN_STREAM_BASE) return fail("RNN layers are supported in the base chain only");
-            if (d[i].n_in != l.in_feat) return fail("layer %d: RNN n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID) return fail("layer %d: RNN activation %d is not one of DQN_ACT_*", i, d[i].act);
-            l.H = d[i].n_out; l.K = d[i].n_in; l.N = l.H; l.npos = 1; l.out_feat = l.H; l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
+            if (l.stream != DQN_STREAM_BASE) return fail("%s layers are supported in the base chain only", C->display);
+            if (d[i].n_in != l.in_feat) return fail("layer %d: %s n_in %d != incoming features %d", i, C->display, d[i].n_in, l.in_feat);
+            if (C->has_act && (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID)) return fail("layer %d: %s activation %d is not one of DQN_ACT_*", i, C->display, d[i].act);
+            l.H = d[i].n_out; l.K = d[i].n_in; l.N = C->ngates * l.H; l.npos = 1; l.out_feat = l.H; if (C->has_act) l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
         } else return fail("layer %d: unknown kind %d", i, l.kind);
-        if (l.kind == DQN_LAYER_LSTM) {
+        if (is_recurrent(l.kind)) {      // Flux.params Wi, Wh, b, h0(, c0) -> internal [Wi][b][Wh][junk][h0]([c0])[zeros]
+            const bool has_c = cell_ops(l.kind)->has_c;
             const size_t kn = (size_t)l.K * l.N, hn = (size_t)l.H * l.N;
-            l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H; l.ec0_off = eoff; eoff += l.H;
+            l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H; if (has_c) { l.ec0_off = eoff; eoff += l.H; }
             off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
-            l.h0_off = off; off += l.H; l.c0_off = off; off += l.H; off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
-        } else if (l.kind == DQN_LAYER_GRU || l.kind == DQN_LAYER_RNN) {      // Flux.params Wi, Wh, b, h0 -> internal [Wi][b][Wh][junk][h0][zeros]
-            const size_t kn = (size_t)l.K * l.N, hn = (size_t)l.H * l.N;
-            l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H;
-            off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
-            l.h0_off = off; off += l.H; off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
+            l.h0_off = off; off += l.H; if (has_c) { l.c0_off = off; off += l.H; } off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
         } else {
             l.ew_off = eoff; eoff += (size_t)l.K * l.N; l.eb_off = eoff; eoff += l.N;
             off = (off + 3) / 4 * 4; l.w_off = off; off += (size_t)l.K * l.N; l.b_off = off; off += l.N;
@@ -300,17 +287,13 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
         const size_t sw = dqn_nchunks(l.npos * Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
         const size_t sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
         jmax = std::max(jmax, (size_t)l.in_feat * Bc);
-        if (l.kind == DQN_LAYER_LSTM) {
-            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc); DM(e->cst_on[i], (size_t)l.H * e->ncon); DM(e->cst_tg[i], (size_t)l.H * Bc);
-            DM(e->gates[i], (size_t)l.N * Bc); DM(e->tcb[i], (size_t)l.H * Bc); DM(e->hprev_buf[i], (size_t)l.H * Bc); DM(e->cprev_buf[i], (size_t)l.H * Bc);
-            DM(e->dG[i], (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B); DM(e->dcn[i], (size_t)l.H * B);
-        } else if (l.kind == DQN_LAYER_GRU) {      // gates: r, z, n; tcb: Wh_n*h; dG: dGx then dGh; dcn: dh .* z of the per-step BPTT
-            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc);
-            DM(e->gates[i], (size_t)l.N * Bc); DM(e->tcb[i], (size_t)l.H * Bc); DM(e->hprev_buf[i], (size_t)l.H * Bc);
-            DM(e->dG[i], 2 * (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B); DM(e->dcn[i], (size_t)l.H * B);
-        } else if (l.kind == DQN_LAYER_RNN) {      // no gate stash: BPTT reads h_t back from act_on; dG: the one gate gradient
-            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc);
-            DM(e->hprev_buf[i], (size_t)l.H * Bc); DM(e->dG[i], (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B);
+        if (is_recurrent(l.kind)) {
+            // gates, tcb (CellSeq::aux) and dcn (CellBwdArgs::dh2) belong to the cells with a gate stash: the RNN's BPTT reads h_t back from act_on and has one gate gradient
+            const CellOps* C = cell_ops(l.kind);
+            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc); DM(e->hprev_buf[i], (size_t)l.H * Bc);
+            if (C->has_c) { DM(e->cst_on[i], (size_t)l.H * e->ncon); DM(e->cst_tg[i], (size_t)l.H * Bc); DM(e->cprev_buf[i], (size_t)l.H * Bc); }
+            if (C->ngates > 1) { DM(e->gates[i], (size_t)l.N * Bc); DM(e->tcb[i], (size_t)l.H * Bc); DM(e->dcn[i], (size_t)l.H * B); }
+            DM(e->dG[i], (C->two_dG ? 2 : 1) * (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B);
         }
     }
     if (hp->recurrence) {   // EpisodeReplayBuffer (src/episode_replay.jl:3-40): buffer_size EPISODES, first trace_length transitions of each
@@ -1027,8 +1010,8 @@ int policy_state(dqn_engine* e, int n, bool force_reset) {
     if (!e->hp.recurrence) return 0;
     if (n != e->pol_state_n) {
         for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-            const bool lstm = e->L[i].kind == DQN_LAYER_LSTM;      // a GRU or an RNN carries h only
-            for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(e->pol_h[i][k], (size_t)e->L[i].H * n); if (lstm) DM(e->pol_c[i][k], (size_t)e->L[i].H * n); }
+            const bool has_c = cell_ops(e->L[i].kind)->has_c;      // else the cell carries h only
+            for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(e->pol_h[i][k], (size_t)e->L[i].H * n); if (has_c) DM(e->pol_c[i][k], (size_t)e->L[i].H * n); }
             hipFree(e->pol_gx[i]); e->pol_gx[i] = nullptr; DM(e->pol_gx[i], (size_t)e->L[i].N * n);
         }
         e->pol_state_n = n; force_reset = true;
@@ -1036,7 +1019,7 @@ int policy_state(dqn_engine* e, int n, bool force_reset) {
     if (force_reset) {
         for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
             launch_bcast_state(e->stream, e->p_on + e->L[i].h0_off, e->L[i].H, n, e->pol_h[i][e->pol_flip]);
-            if (e->L[i].kind == DQN_LAYER_LSTM) launch_bcast_state(e->stream, e->p_on + e->L[i].c0_off, e->L[i].H, n, e->pol_c[i][e->pol_flip]);
+            if (cell_ops(e->L[i].kind)->has_c) launch_bcast_state(e->stream, e->p_on + e->L[i].c0_off, e->L[i].H, n, e->pol_c[i][e->pol_flip]);
         }
     }
     return 0;
@@ -1055,29 +1038,15 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
     const int fl = e->pol_flip;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev& l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src];
-        if (l.kind == DQN_LAYER_LSTM) {      // one Recur step: Gx = Wi*x (bias-free view), then the cell with the carried (h, c)
+        if (is_recurrent(l.kind)) {      // one Recur step: Gx = Wi*x (bias-free view), then the cell with the carried h (and c)
+            const CellOps* C = cell_ops(l.kind);
             LayerDev V = l; V.kind = DQN_LAYER_DENSE; V.out_feat = l.N; V.b_off = l.z_off; V.act = DQN_ACT_IDENTITY;
             fwd_layer(e, V, P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
-            LstmStepArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.nseq = 1;
-            LstmSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.Cst = e->pol_c[i][fl ^ 1]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
-            q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1; q.cprev = e->pol_c[i][fl]; q.cp_ld = n; q.cp_bs = 1;
-            launch_lstm_step_t(e->stream, a, 0);
-            HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
-        } else if (l.kind == DQN_LAYER_GRU) {      // one Recur step of the GRU: Gx = Wi*x (bias-free view), then the cell with the carried h
-            LayerDev V = l; V.kind = DQN_LAYER_DENSE; V.out_feat = l.N; V.b_off = l.z_off; V.act = DQN_ACT_IDENTITY;
-            fwd_layer(e, V, P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
-            GruStepArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.nseq = 1;
-            GruSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
+            CellFwdArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.T = 1; a.nseq = 1; a.act = l.cell_act;
+            CellSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
             q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1;
-            launch_gru_step_t(e->stream, a, 0);
-            HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
-        } else if (l.kind == DQN_LAYER_RNN) {      // one Recur step of the RNN: Gx = Wi*x (bias-free view), then the cell with the carried h
-            LayerDev V = l; V.kind = DQN_LAYER_DENSE; V.out_feat = l.N; V.b_off = l.z_off; V.act = DQN_ACT_IDENTITY;
-            fwd_layer(e, V, P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
-            RnnStepArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.nseq = 1; a.act = l.cell_act;
-            RnnSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
-            q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1;
-            launch_rnn_step_t(e->stream, a, 0);
+            if (C->has_c) { q.Cst = e->pol_c[i][fl ^ 1]; q.cprev = e->pol_c[i][fl]; q.cp_ld = n; q.cp_bs = 1; }
+            C->launch_step(e->stream, a, 0);
             HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
         } else fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");
     }

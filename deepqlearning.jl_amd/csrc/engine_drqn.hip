@@ -173,14 +173,14 @@ extern "C" int dqn_reset_state(dqn_engine_t* e) { if (!e) return fail("null engi
     if (!e->hp.recurrence) return 0;
     return policy_state(e, e->pol_state_n > 0 ? e->pol_state_n : 1, true);
 }
-extern "C" int dqn_get_hidden(dqn_engine_t* e, float* hc, size_t n) { if (!e) return fail("null engine handle");   // hiddenstates(m) (src/helpers.jl:61-63): per recurrent layer h (then c for an LSTM), [out][streams]
+extern "C" int dqn_get_hidden(dqn_engine_t* e, float* hc, size_t n) { if (!e) return fail("null engine handle");   // hiddenstates(m) (src/helpers.jl:61-63): per recurrent layer h (then c where the cell has one), [out][streams]
     HIPCHK(hipSetDevice(e->device)); size_t off = 0;
     if (e->hp.recurrence && e->pol_state_n == 0 && policy_state(e, 1, true)) return -1;      // no forward yet: one stream at state0
     for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-        const bool lstm = e->L[i].kind == DQN_LAYER_LSTM;
-        const size_t m = (size_t)e->L[i].H * e->pol_state_n; if (off + (lstm ? 2 : 1) * m > n) return fail("get_hidden: buffer too small");
+        const bool has_c = cell_ops(e->L[i].kind)->has_c;
+        const size_t m = (size_t)e->L[i].H * e->pol_state_n; if (off + (has_c ? 2 : 1) * m > n) return fail("get_hidden: buffer too small");
         HIPCHK(hipMemcpyAsync(hc + off, e->pol_h[i][e->pol_flip], m * 4, hipMemcpyDeviceToHost, e->stream)); off += m;
-        if (lstm) { HIPCHK(hipMemcpyAsync(hc + off, e->pol_c[i][e->pol_flip], m * 4, hipMemcpyDeviceToHost, e->stream)); off += m; }
+        if (has_c) { HIPCHK(hipMemcpyAsync(hc + off, e->pol_c[i][e->pol_flip], m * 4, hipMemcpyDeviceToHost, e->stream)); off += m; }
     }
     HIPCHK(hipStreamSynchronize(e->stream)); return 0;
 }
@@ -188,10 +188,10 @@ extern "C" int dqn_set_hidden(dqn_engine_t* e, const float* hc, size_t n) { if (
     HIPCHK(hipSetDevice(e->device)); size_t off = 0;
     if (e->hp.recurrence && e->pol_state_n == 0 && policy_state(e, 1, true)) return -1;
     for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-        const bool lstm = e->L[i].kind == DQN_LAYER_LSTM;
-        const size_t m = (size_t)e->L[i].H * e->pol_state_n; if (off + (lstm ? 2 : 1) * m > n) return fail("set_hidden: buffer too small");
+        const bool has_c = cell_ops(e->L[i].kind)->has_c;
+        const size_t m = (size_t)e->L[i].H * e->pol_state_n; if (off + (has_c ? 2 : 1) * m > n) return fail("set_hidden: buffer too small");
         HIPCHK(hipMemcpyAsync(e->pol_h[i][e->pol_flip], hc + off, m * 4, hipMemcpyHostToDevice, e->stream)); off += m;
-        if (lstm) { HIPCHK(hipMemcpyAsync(e->pol_c[i][e->pol_flip], hc + off, m * 4, hipMemcpyHostToDevice, e->stream)); off += m; }
+        if (has_c) { HIPCHK(hipMemcpyAsync(e->pol_c[i][e->pol_flip], hc + off, m * 4, hipMemcpyHostToDevice, e->stream)); off += m; }
     }
     HIPCHK(hipStreamSynchronize(e->stream)); return 0;
 }

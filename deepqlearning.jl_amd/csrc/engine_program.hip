@@ -272,93 +272,31 @@ int build_program(dqn_engine* e) {
             head[q.l][q.net] = h;
         }
         emit_reduce(e, segs, pname(e, "fwd_reduce", e->L[lv[0]].kind, lv[0]));
-        if (e->L[lv[0]].kind == DQN_LAYER_LSTM) {
-            // the recurrence: T launches, each advancing the online s-sequence, the online sp-sequence (double-Q) and the target
-            // sp-sequence by one step from the reset state (Flux.reset!, src/solver.jl:249-250,271)
-            const int l = lv[0]; const LayerDev L = e->L[l]; const int H = L.H;
-            if (lstm_seq_fits(H, Bb, T)) {        // small LSTM: the whole recurrence of the three sequence sets in ONE launch
-                LstmSeqArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; int ns = 0;
+        if (is_recurrent(e->L[lv[0]].kind)) {
+            // the recurrence: each launch advances the online s-sequence, the online sp-sequence (double-Q) and the target sp-sequence from the reset
+            // state (Flux.reset!, src/solver.jl:249-250,271) -- ONE launch for the whole recurrence where the cell's whole-sequence kernels fit, else T
+            const int l = lv[0]; const LayerDev L = e->L[l]; const CellOps* C = cell_ops(L.kind); const int H = L.H;
+            auto args = [&](int t) {      // the sequence sets before step t
+                CellFwdArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; a.act = L.cell_act;
                 auto seq = [&](const float* P, const float* gx, float* hout, float* cst, int ld, int c0, bool keep) {
-                    LstmSeqF& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.Cst = cst; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off; q.h0 = P + L.h0_off; q.c0v = P + L.c0_off;
-                    if (keep) { q.gates = e->gates[l]; q.tc = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.cprev_out = e->cprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
+                    CellSeq& q = a.s[a.nseq++]; q.Gx = gx; q.Hout = hout; q.Cst = cst; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
+                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; if (C->has_c) { q.cprev = P + L.c0_off; q.cp_ld = 1; q.cp_bs = 0; } }
+                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; if (C->has_c) { q.cprev = cst + c0 + (t - 1) * Bb; q.cp_ld = ld; q.cp_bs = 1; } }
+                    if (keep) { q.gates = e->gates[l]; q.aux = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.cprev_out = e->cprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }      // null where the cell has none
                 };
                 seq(e->p_on, e->gx_on[l], e->act_on[l], e->cst_on[l], ncon, 0, true);
                 if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], e->cst_on[l], ncon, B, false);
                 seq(e->p_tg, e->gx_tg[l], e->act_tg[l], e->cst_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "lstm_seq", L.kind, l), [=](dqn_engine* en) { launch_lstm_seq(en->stream, a); }});
+                return a;
+            };
+            char op[24];
+            if (C->seq_fits(H, Bb, T) && !stepwise(e->opt, L.kind)) {
+                const CellFwdArgs a = args(0); snprintf(op, sizeof op, "%s_seq", C->name);
+                e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_seq(en->stream, a); }});
             } else
             for (int t = 0; t < T; t++) {
-                LstmStepArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; int ns = 0;
-                auto seq = [&](const float* P, const float* gx, float* hout, float* cst, int ld, int c0, bool keep) {
-                    LstmSeq& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.Cst = cst; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
-                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; q.cprev = P + L.c0_off; q.cp_ld = 1; q.cp_bs = 0; }
-                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; q.cprev = cst + c0 + (t - 1) * Bb; q.cp_ld = ld; q.cp_bs = 1; }
-                    if (keep) { q.gates = e->gates[l]; q.tc = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.cprev_out = e->cprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
-                };
-                seq(e->p_on, e->gx_on[l], e->act_on[l], e->cst_on[l], ncon, 0, true);
-                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], e->cst_on[l], ncon, B, false);
-                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], e->cst_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "lstm_step", L.kind, l), [=](dqn_engine* en) { launch_lstm_step_t(en->stream, a, t); }});
-            }
-        }
-        if (e->L[lv[0]].kind == DQN_LAYER_GRU) {      // the GRU's recurrence, where the LSTM's is emitted (gru.hip)
-            const int l = lv[0]; const LayerDev L = e->L[l]; const int H = L.H;
-            if (gru_seq_fits(H, Bb, T) && !e->opt.gru_stepwise) {
-                GruSeqArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; int ns = 0;
-                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
-                    GruSeqF& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off; q.h0 = P + L.h0_off;
-                    if (keep) { q.gates = e->gates[l]; q.ghn = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
-                };
-                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
-                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
-                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "gru_seq", L.kind, l), [=](dqn_engine* en) { launch_gru_seq(en->stream, a); }});
-            } else
-            for (int t = 0; t < T; t++) {
-                GruStepArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; int ns = 0;
-                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
-                    GruSeq& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
-                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; }
-                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; }
-                    if (keep) { q.gates = e->gates[l]; q.ghn = e->tcb[l]; q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
-                };
-                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
-                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
-                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "gru_step", L.kind, l), [=](dqn_engine* en) { launch_gru_step_t(en->stream, a, t); }});
-            }
-        }
-        if (e->L[lv[0]].kind == DQN_LAYER_RNN) {      // the RNN's recurrence, where the LSTM's and the GRU's are emitted (rnn.hip)
-            const int l = lv[0]; const LayerDev L = e->L[l]; const int H = L.H;
-            if (rnn_seq_fits(H, Bb, T) && !e->opt.rnn_stepwise) {
-                RnnSeqArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.T = T; a.act = L.cell_act; int ns = 0;
-                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
-                    RnnSeqF& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off; q.h0 = P + L.h0_off;
-                    if (keep) { q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
-                };
-                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
-                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
-                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "rnn_seq", L.kind, l), [=](dqn_engine* en) { launch_rnn_seq(en->stream, a); }});
-            } else
-            for (int t = 0; t < T; t++) {
-                RnnStepArgs a; memset(&a, 0, sizeof a); a.H = H; a.B = Bb; a.act = L.cell_act; int ns = 0;
-                auto seq = [&](const float* P, const float* gx, float* hout, int ld, int c0, bool keep) {
-                    RnnSeq& q = a.s[ns++]; q.Gx = gx; q.Hout = hout; q.ld = ld; q.c0 = c0; q.Wh = P + L.wh_off; q.bias = P + L.b_off;
-                    if (t == 0) { q.hprev = P + L.h0_off; q.hp_ld = 1; q.hp_bs = 0; }
-                    else { q.hprev = hout + c0 + (t - 1) * Bb; q.hp_ld = ld; q.hp_bs = 1; }
-                    if (keep) { q.hprev_out = e->hprev_buf[l]; q.keep_ld = B; q.keep_c0 = 0; }
-                };
-                seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, 0, true);
-                if (e->hp.double_q) seq(e->p_on, e->gx_on[l], e->act_on[l], ncon, B, false);
-                seq(e->p_tg, e->gx_tg[l], e->act_tg[l], B, 0, false);
-                a.nseq = ns;
-                e->prog.push_back({pname(e, "rnn_step", L.kind, l), [=](dqn_engine* en) { launch_rnn_step_t(en->stream, a, t); }});
+                const CellFwdArgs a = args(t); snprintf(op, sizeof op, "%s_step", C->name);
+                e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_step(en->stream, a, t); }});
             }
         }
     }
@@ -550,34 +488,21 @@ int build_program(dqn_engine* e) {
             if (is_recurrent(L.kind)) {
                 // BPTT over the s-sequence: T single-workgroup steps produce dG (gate pre-activation gradients) for all columns,
                 // then Wi|b, Wh and the input gradient are ordinary dense contractions over the T*B columns.
-                // GRU: BPTT writes TWO gate gradients, dGx = [dr; dz; dn] for Wi|b and the input dX, dGh = [dr; dz; dn .* r] for Wh (gru.hip)
+                // Cells whose Wh dW pass reads a gate gradient of its own (CellOps::two_dG; the GRU: gru.hip) get it in the second half of dG
                 float* grad = e->grad;
-                const bool gru = L.kind == DQN_LAYER_GRU;
-                if (gru) {
-                    GruBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.ghn = e->tcb[l]; a.hprev = e->hprev_buf[l]; a.Wh = e->p_on + L.wh_off;
-                    a.dH = dpre; a.dGx = e->dG[l]; a.dGh = e->dG[l] + (size_t)L.N * B; a.dhn = e->dhn[l]; a.dhz = e->dcn[l]; a.g_h0 = grad + L.h0_off;
-                    if (gru_seq_fits(L.H, Bb, T) && !e->opt.gru_stepwise) e->prog.push_back({pname(e, "gru_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_seq(en->stream, a); }});
-                    else for (int t = T - 1; t >= 0; t--) { GruBwdArgs at = a; at.t = t; e->prog.push_back({pname(e, "gru_bwd", L.kind, l), [=](dqn_engine* en) { launch_gru_bwd_step(en->stream, at); }}); }
-                } else
-                if (L.kind == DQN_LAYER_RNN) {      // RNN: ONE gate gradient dG = act'(dh) feeds Wi | b, Wh and the input dX, as the LSTM's dG does (rnn.hip)
-                    RnnBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.act = L.cell_act; a.hout = e->act_on[l]; a.ld_h = ncon; a.Wh = e->p_on + L.wh_off;
-                    a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.g_h0 = grad + L.h0_off;
-                    if (rnn_seq_fits(L.H, Bb, T) && !e->opt.rnn_stepwise) e->prog.push_back({pname(e, "rnn_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_rnn_bwd_seq(en->stream, a); }});
-                    else for (int t = T - 1; t >= 0; t--) { RnnBwdArgs at = a; at.t = t; e->prog.push_back({pname(e, "rnn_bwd", L.kind, l), [=](dqn_engine* en) { launch_rnn_bwd_step(en->stream, at); }}); }
-                } else
-                if (lstm_seq_fits(L.H, Bb, T)) {
-                    LstmBwdArgs a; a.t = 0; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.tc = e->tcb[l]; a.cprev = e->cprev_buf[l]; a.Wh = e->p_on + L.wh_off;
-                    a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.dcn = e->dcn[l]; a.g_h0 = grad + L.h0_off; a.g_c0 = grad + L.c0_off;
-                    e->prog.push_back({pname(e, "lstm_bwd_seq", L.kind, l), [=](dqn_engine* en) { launch_lstm_bwd_seq(en->stream, a); }});
-                } else
-                for (int t = T - 1; t >= 0; t--) {
-                    LstmBwdArgs a; a.t = t; a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.gates = e->gates[l]; a.tc = e->tcb[l]; a.cprev = e->cprev_buf[l]; a.Wh = e->p_on + L.wh_off;
-                    a.dH = dpre; a.dG = e->dG[l]; a.dhn = e->dhn[l]; a.dcn = e->dcn[l]; a.g_h0 = grad + L.h0_off; a.g_c0 = grad + L.c0_off;
-                    e->prog.push_back({pname(e, "lstm_bwd", L.kind, l), [=](dqn_engine* en) { launch_lstm_bwd_step(en->stream, a); }});
+                const CellOps* C = cell_ops(L.kind);
+                float* const dGh = C->two_dG ? e->dG[l] + (size_t)L.N * B : e->dG[l];
+                {
+                    CellBwdArgs a; memset(&a, 0, sizeof a); a.T = T; a.H = L.H; a.B = Bb; a.TB = B; a.act = L.cell_act;
+                    a.gates = e->gates[l]; a.aux = e->tcb[l]; a.hprev = e->hprev_buf[l]; a.cprev = e->cprev_buf[l]; a.hout = e->act_on[l]; a.ld_h = ncon; a.Wh = e->p_on + L.wh_off;
+                    a.dH = dpre; a.dG = e->dG[l]; a.dGh = dGh; a.dhn = e->dhn[l]; a.dh2 = e->dcn[l]; a.g_h0 = grad + L.h0_off; if (C->has_c) a.g_c0 = grad + L.c0_off;
+                    char op[24];
+                    if (C->seq_fits(L.H, Bb, T) && !stepwise(e->opt, L.kind)) { snprintf(op, sizeof op, "%s_bwd_seq", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_seq(en->stream, a); }}); }
+                    else for (int t = T - 1; t >= 0; t--) { CellBwdArgs at = a; at.t = t; snprintf(op, sizeof op, "%s_bwd", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_step(en->stream, at); }}); }
                 }
                 LayerDev Vi = L; Vi.kind = DQN_LAYER_DENSE; Vi.out_feat = L.N; Vi.act = DQN_ACT_IDENTITY;                    // Wi | b  : (K+1) x N
                 LayerDev Vh = Vi; Vh.K = L.H; Vh.in_feat = L.H; Vh.w_off = L.wh_off; Vh.b_off = L.wh_off + (size_t)L.H * L.N;  // Wh | junk
-                const float* dGi = e->dG[l]; const float* dGw = gru ? e->dG[l] + (size_t)L.N * B : e->dG[l];      // the Wi | b and dX operand, the Wh operand
+                const float* dGi = e->dG[l]; const float* dGw = dGh;      // the Wi | b and dX operand, the Wh operand
                 float* wh_dst = nullptr; int wh_S = 1;      // where the Wh | junk block (or its slabs) lands
                 auto emit_dw1 = [&](const LayerDev V, const float* Xv, int ldv, const float* dG, const char* nm) {
                     const int S = dqn_nchunks(B, V.dw_kc);
@@ -594,7 +519,7 @@ int build_program(dqn_engine* e) {
                 };
                 emit_dw1(Vh, e->hprev_buf[l], B, dGw, pname(e, "dw_wh", L.kind, l));      // first: its junk bias row is then overwritten by nothing that matters
                 emit_dw1(Vi, X, ldx, dGi, pname(e, "dw_wi", L.kind, l));
-                if (gru) {      // the GRU's junk row (sum of dn .* r) is cleared once the level's launches have written it: Adam folds max |g| over it (gru.hip)
+                if (C->clear_junk) {      // the GRU's junk row (sum of dn .* r) is cleared once the level's launches have written it: Adam folds max |g| over it (gru.hip)
                     float* jr = wh_dst + (size_t)L.H * L.N; const int nr = wh_S; const size_t stride = (size_t)(L.H + 1) * L.N; const int n = L.N;
                     post_level.push_back({pname(e, "gru_junk_clear", L.kind, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
                 }

@@ -499,6 +499,16 @@ void launch_q_columns(hipStream_t st, int n, int nA, int dueling, const float* v
     hipLaunchKernelGGL(k_q_columns, dim3((n + 63) / 64), dim3(64), 0, st, n, nA, dueling, val, adv, q_out, argmax_out);
 }
 
+// p[r*stride + i] = 0 for r < nrows, i < n: the junk bias row of a recurrent layer's Wh | junk dW pass (or of each of its slabs), for the cells whose
+// junk row is not a copy of db (CellOps::clear_junk; the GRU's holds sum(dn .* r)): Adam folds max |g| over the whole internal vector
+__global__ void k_clear_rows(float* __restrict__ p, int nrows, size_t stride, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < nrows * n) p[(size_t)(i / n) * stride + i % n] = 0.0f;
+}
+void launch_clear_rows(hipStream_t st, float* p, int nrows, size_t stride, int n) {
+    hipLaunchKernelGGL(k_clear_rows, dim3((nrows * n + 255) / 256), dim3(256), 0, st, p, nrows, stride, n);
+}
+
 // ------------------------------------------------------------------ globalnorm (helpers.jl:38-46) + Flux Adam (solver.jl:66,228), fused, HBM-bound:
 // per element 16 B read (p,m,v,g) + 12 B written; the job body lives in adam_body.h (shared with the backward launches' tails)
 __global__ __launch_bounds__(256) void k_adam(AdamJob J) {

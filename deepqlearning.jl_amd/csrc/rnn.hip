@@ -10,14 +10,14 @@
 //   dG -> Wi | b dW, Wh dW (X = h_{t-1}) and the input dX (dense contractions over T*B columns).  The Wh | junk pass reads the same dG as
 //         Wi | b, so its junk row equals db (as the LSTM's) and never raises max |g|: nothing to clear.
 //   dh_{t-1}[j] = chain_n (+0; n ascending over H) fma(dG[n], Wh[j][n], .) ;  dstate0[u] = sum_b (ascending) dh_{-1}[u][b]
-#include "common.h"
+#include "cell.h"
 
 // ------------------------------------------------------------------ one time step for up to 3 sequence sets (online s, online sp, target sp)
-__global__ void k_rnn_step(RnnStepArgs A, int t) {
+__global__ void k_rnn_step(CellFwdArgs A, int t) {
     const int per = A.H * A.B;
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= per * A.nseq) return;
-    const RnnSeq& S = A.s[i / per];
+    const CellSeq& S = A.s[i / per];
     const int e = i % per, u = e / A.B, b = e % A.B, H = A.H;
     const int col = S.c0 + t * A.B + b;
     const float* hpb = S.hprev + (size_t)b * S.hp_bs;
@@ -27,13 +27,13 @@ __global__ void k_rnn_step(RnnStepArgs A, int t) {
     S.Hout[(size_t)u * S.ld + col] = h;
     if (S.hprev_out) S.hprev_out[(size_t)u * S.keep_ld + S.keep_c0 + (size_t)t * A.B + b] = hpb[(size_t)u * S.hp_ld];
 }
-void launch_rnn_step_t(hipStream_t st, const RnnStepArgs& a, int t) {
+void launch_rnn_step_t(hipStream_t st, const CellFwdArgs& a, int t) {
     const int n = a.H * a.B * a.nseq;
     hipLaunchKernelGGL(k_rnn_step, dim3((n + 255) / 256), dim3(256), 0, st, a, t);
 }
 
 // ------------------------------------------------------------------ one BPTT step (single workgroup: dh_{t-1} needs all H gate gradients of step t)
-__global__ __launch_bounds__(1024) void k_rnn_bwd_step(RnnBwdArgs A) {
+__global__ __launch_bounds__(1024) void k_rnn_bwd_step(CellBwdArgs A) {
     const int H = A.H, B = A.B, TB = A.TB, t = A.t, per = H * B;
     for (int e = threadIdx.x; e < per; e += blockDim.x) {
         const int u = e / B, b = e % B; const size_t k = (size_t)t * B + b;
@@ -50,14 +50,10 @@ __global__ __launch_bounds__(1024) void k_rnn_bwd_step(RnnBwdArgs A) {
     }
     if (t == 0) {                                              // trainable state0: gradient summed over the batch, ascending b
         __syncthreads();
-        for (int u = threadIdx.x; u < H; u += blockDim.x) {
-            float sh = 0.0f;
-            for (int b = 0; b < B; b++) sh = sh + A.dhn[u * B + b];
-            A.g_h0[u] = sh;
-        }
+        for (int u = threadIdx.x; u < H; u += blockDim.x) state0_fold<false>(u, B, A.dhn, nullptr, A.g_h0, nullptr);
     }
 }
-void launch_rnn_bwd_step(hipStream_t st, const RnnBwdArgs& a) {
+void launch_rnn_bwd_step(hipStream_t st, const CellBwdArgs& a) {
     int bs = ((a.H * a.B + 63) / 64) * 64; if (bs > 1024) bs = 1024;
     hipLaunchKernelGGL(k_rnn_bwd_step, dim3(1), dim3(bs), 0, st, a);
 }
@@ -69,12 +65,11 @@ void launch_rnn_bwd_step(hipStream_t st, const RnnBwdArgs& a) {
 // that two of its workgroups can share a gfx950 CU's 160 KB (the grids are nseq * B / CB and B / CB small workgroups, at most a few per CU on
 // 256 CUs); that admits H <= 141 (H > 128: one column per workgroup, H*H + 3H floats), above ~H = 124 through a raised LDS limit.  T <= 64
 // as for the LSTM and the GRU.
-static int rnn_cb(int H, int B) { int cb = 256 / H; if (cb < 1) cb = 1; if (cb > B) cb = B; while (B % cb) cb--; return cb; }
 static size_t rnn_fwd_lds(int H, int cb) { return (size_t)H * H + (size_t)H + 2 * (size_t)H * cb; }       // Wh, bias, h [2][H*cb]
 static size_t rnn_bwd_lds(int H, int cb) { return (size_t)H * (H + 1) + 2 * (size_t)H * cb; }            // Wh (padded rows), dG [H][cb], dh [H*cb]
 static const size_t RNN_SEQ_LDS = 80 * 1024;
 bool rnn_seq_fits(int H, int B, int T) {
-    const int cb = rnn_cb(H, B);
+    const int cb = cell_cb(H, B);
     return rnn_fwd_lds(H, cb) * sizeof(float) <= RNN_SEQ_LDS && rnn_bwd_lds(H, cb) * sizeof(float) <= RNN_SEQ_LDS && H * cb <= 1024 && T <= 64;
 }
 static void rnn_raise_lds(const void* f, size_t lds) {      // beyond the default 64 KB of dynamic LDS (gfx950: up to 160 KB per workgroup)
@@ -83,17 +78,17 @@ static void rnn_raise_lds(const void* f, size_t lds) {      // beyond the defaul
 
 // PF (T <= 8): the input projections Gx of ALL time steps are requested before the recurrence starts; otherwise one step ahead.
 template <bool PF>
-__global__ __launch_bounds__(1024) void k_rnn_seq(RnnSeqArgs A, int CB) {
+__global__ __launch_bounds__(1024) void k_rnn_seq(CellFwdArgs A, int CB) {
     extern __shared__ float lds[];
     const int H = A.H, B = A.B, per = H * CB, T = A.T, nsplit = B / CB;
     float* Wh_s = lds;                 // [H][H]
     float* bias_s = Wh_s + H * H;      // [H]
     float* h_s = bias_s + H;           // [2][H*CB]
-    const RnnSeqF& S = A.s[blockIdx.x / nsplit];
+    const CellSeq& S = A.s[blockIdx.x / nsplit];
     const int b0 = (blockIdx.x % nsplit) * CB;
     for (int i = threadIdx.x; i < H * H; i += blockDim.x) Wh_s[i] = S.Wh[i];
     for (int i = threadIdx.x; i < H; i += blockDim.x) bias_s[i] = S.bias[i];
-    for (int e = threadIdx.x; e < per; e += blockDim.x) h_s[e] = S.h0[e / CB];      // Flux.reset!: state0 broadcast over the batch
+    for (int e = threadIdx.x; e < per; e += blockDim.x) h_s[e] = S.hprev[e / CB];      // Flux.reset!: state0 broadcast over the batch
     const int e = threadIdx.x; const bool on = e < per;
     const int u = on ? e / CB : 0, bl = on ? e - u * CB : 0, b = b0 + bl;
     const float* gx = S.Gx + (size_t)u * S.ld + S.c0 + b;      // + t * B
@@ -126,8 +121,8 @@ __global__ __launch_bounds__(1024) void k_rnn_seq(RnnSeqArgs A, int CB) {
         for (int t = 0; t < T; t++) { const float g = nx; if (t + 1 < T) nx = gx[(size_t)(t + 1) * B]; step(t, g); }
     }
 }
-void launch_rnn_seq(hipStream_t st, const RnnSeqArgs& a) {
-    const int cb = rnn_cb(a.H, a.B);
+void launch_rnn_seq(hipStream_t st, const CellFwdArgs& a) {
+    const int cb = cell_cb(a.H, a.B);
     const size_t lds = rnn_fwd_lds(a.H, cb) * sizeof(float);
     const int bs = ((a.H * cb + 63) / 64) * 64;      // rnn_seq_fits: H * cb <= 1024
     const dim3 grid(a.nseq * (a.B / cb));
@@ -136,10 +131,10 @@ void launch_rnn_seq(hipStream_t st, const RnnSeqArgs& a) {
 }
 
 // BPTT over the whole s-sequence, one workgroup per group of CB columns (the arithmetic of T calls of k_rnn_bwd_step); the state0 gradient
-// (a sum over ALL columns, ascending b) is folded by k_rnn_state0_grad afterwards.  PF (T <= 8): dH and h of every step are requested before
+// (a sum over ALL columns, ascending b) is folded by k_state0_grad (cell.h) afterwards.  PF (T <= 8): dH and h of every step are requested before
 // the loop; otherwise one step ahead.
 template <bool PF>
-__global__ __launch_bounds__(1024) void k_rnn_bwd_seq(RnnBwdArgs A, int CB) {
+__global__ __launch_bounds__(1024) void k_rnn_bwd_seq(CellBwdArgs A, int CB) {
     extern __shared__ float lds[];
     const int H = A.H, B = A.B, TB = A.TB, per = H * CB, b0 = blockIdx.x * CB;
     const int NP = H + 1;              // padded row stride (the lanes of a wave read different rows u at the same n)
@@ -185,18 +180,11 @@ __global__ __launch_bounds__(1024) void k_rnn_bwd_seq(RnnBwdArgs A, int CB) {
     }
     for (int e2 = threadIdx.x; e2 < per; e2 += blockDim.x) { const int u2 = e2 / CB, bl2 = e2 - u2 * CB; A.dhn[u2 * B + b0 + bl2] = dhn_s[e2]; }
 }
-__global__ void k_rnn_state0_grad(int H, int B, const float* __restrict__ dhn, float* __restrict__ g_h0) {
-    const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= H) return;
-    float sh = 0.0f;
-    for (int b = 0; b < B; b++) sh = sh + dhn[u * B + b];      // ascending b
-    g_h0[u] = sh;
-}
-void launch_rnn_bwd_seq(hipStream_t st, const RnnBwdArgs& a) {
-    const int cb = rnn_cb(a.H, a.B);
+void launch_rnn_bwd_seq(hipStream_t st, const CellBwdArgs& a) {
+    const int cb = cell_cb(a.H, a.B);
     const size_t lds = rnn_bwd_lds(a.H, cb) * sizeof(float);
     const int bs = ((a.H * cb + 63) / 64) * 64;      // rnn_seq_fits: H * cb <= 1024
     if (a.T <= 8) { rnn_raise_lds((const void*)k_rnn_bwd_seq<true>, lds); hipLaunchKernelGGL((k_rnn_bwd_seq<true>), dim3(a.B / cb), dim3(bs), lds, st, a, cb); }
     else { rnn_raise_lds((const void*)k_rnn_bwd_seq<false>, lds); hipLaunchKernelGGL((k_rnn_bwd_seq<false>), dim3(a.B / cb), dim3(bs), lds, st, a, cb); }
-    hipLaunchKernelGGL(k_rnn_state0_grad, dim3((a.H + 63) / 64), dim3(64), 0, st, a.H, a.B, a.dhn, a.g_h0);
+    launch_state0_grad(st, a);
 }
