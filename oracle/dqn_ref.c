@@ -62,7 +62,7 @@ typedef struct ref_engine {
     float *p_on, *p_tg, *grad, *m, *v;
     double bp1, bp2;
     /* replay */
-    int64_t cap, cap2, size, widx; uint64_t sample_ctr;
+    int64_t cap, cap2, size, widx; uint64_t sample_ctr, train_steps;
     float *s_f32, *sp_f32; uint8_t *s_u8, *sp_u8;
     int32_t* a; float* r; uint8_t* done; float* tree; /* tree[1]=root, leaves at cap2+i */
     /* step workspace */
@@ -81,6 +81,12 @@ typedef struct ref_engine {
     struct ref_envs* envs;
 } ref_engine;
 
+#ifndef REF_SRC_HASH
+#define REF_SRC_HASH "unknown"
+#endif
+/* the hash of the sources this library was built from (oracle/Makefile); oracle/ref.py looks for the marker in the file before it loads it */
+static const char g_src_hash[] = "DQNREF_SRC_HASH=" REF_SRC_HASH;
+const char* ref_source_hash(void) { return g_src_hash + 16; }
 static char g_err[512];
 const char* ref_last_error(void) { return g_err; }
 #define FAIL(...) do { snprintf(g_err, sizeof g_err, __VA_ARGS__); return -1; } while (0)
@@ -462,6 +468,47 @@ int ref_update_priorities(ref_engine* e, const int64_t* idx, const float* td, in
     return 0;
 }
 
+/* checkpoint / resume of the replay (dqn_replay_export / dqn_replay_import / dqn_get_counters / dqn_set_counters, include/dqn_mi355x.h): rows first .. first + n - 1
+ * out; n rows into slots 0 .. n - 1 with their priorities, every other leaf 0, every internal node rebuilt as left + right, the ring cursor behind them */
+int ref_replay_export(ref_engine* e, int64_t first, int64_t n, void* s, void* sp, int32_t* a, float* r, uint8_t* done, float* prio) {
+    if (first < 0 || n < 0 || first + n > e->size) FAIL("BoundsError: rows %lld..%lld outside 0..%lld", (long long)first, (long long)(first + n - 1), (long long)e->size - 1);
+    const size_t row = (size_t)e->obs_elems * (e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 4);
+    const uint8_t* s0 = e->hp.obs_dtype == DQN_OBS_U8 ? e->s_u8 : (const uint8_t*)e->s_f32; const uint8_t* sp0 = e->hp.obs_dtype == DQN_OBS_U8 ? e->sp_u8 : (const uint8_t*)e->sp_f32;
+    if (s) memcpy(s, s0 + (size_t)first * row, (size_t)n * row);
+    if (sp) memcpy(sp, sp0 + (size_t)first * row, (size_t)n * row);
+    if (a) memcpy(a, e->a + first, (size_t)n * 4);
+    if (r) memcpy(r, e->r + first, (size_t)n * 4);
+    if (done) memcpy(done, e->done + first, (size_t)n);
+    if (prio) memcpy(prio, e->tree + e->cap2 + first, (size_t)n * 4);
+    return 0;
+}
+int ref_replay_import(ref_engine* e, int64_t n, const void* s, const void* sp, const int32_t* a, const float* r, const uint8_t* done, const float* prio) {
+    if (n < 0 || n > e->cap) FAIL("import of %lld transitions into a replay of capacity %lld", (long long)n, (long long)e->cap);
+    for (int64_t i = 0; i < n; i++) {
+        if (a[i] < 0 || a[i] >= e->nA) FAIL("action index %d out of range 0..%d", a[i], e->nA - 1);
+        if (!(prio[i] > 0.0f)) FAIL("AssertionError: all(new_priorities .> 0f0)");
+    }
+    const size_t row = (size_t)e->obs_elems * (e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 4);
+    uint8_t* s0 = e->hp.obs_dtype == DQN_OBS_U8 ? e->s_u8 : (uint8_t*)e->s_f32; uint8_t* sp0 = e->hp.obs_dtype == DQN_OBS_U8 ? e->sp_u8 : (uint8_t*)e->sp_f32;
+    memcpy(s0, s, (size_t)n * row); memcpy(sp0, sp, (size_t)n * row);
+    memcpy(e->a, a, (size_t)n * 4); memcpy(e->r, r, (size_t)n * 4); memcpy(e->done, done, (size_t)n);
+    memset(e->tree, 0, 2 * (size_t)e->cap2 * 4);
+    memcpy(e->tree + e->cap2, prio, (size_t)n * 4);
+    for (int64_t node = e->cap2 - 1; node >= 1; node--) e->tree[node] = e->tree[2 * node] + e->tree[2 * node + 1];
+    e->size = n; e->widx = n % e->cap;
+    return 0;
+}
+int ref_get_counters(ref_engine* e, dqn_counters* out) {
+    if (e->hp.recurrence) FAIL("the twin keeps counters of the transition replay only");
+    out->size = e->size; out->widx = e->widx; out->sample_ctr = e->sample_ctr; out->train_steps = e->train_steps; return 0;
+}
+int ref_set_counters(ref_engine* e, const dqn_counters* in) {
+    if (e->hp.recurrence) FAIL("the twin keeps counters of the transition replay only");
+    if (in->size != e->size) FAIL("counters.size (%lld) differs from the replay's (%lld): import the replay first", (long long)in->size, (long long)e->size);
+    if (in->widx < 0 || in->widx >= e->cap) FAIL("counters.widx out of range");
+    e->widx = in->widx; e->sample_ctr = in->sample_ctr; e->train_steps = in->train_steps; return 0;
+}
+
 /* ---------------------------------------------------------------- layers */
 /* input X[in_feat][ldx] at column col0, ncols columns -> Y[out_feat][ncols] */
 static void layer_forward(const RLayer* L, const float* P, const float* X, int ldx, int col0, int ncols, float* Y) {
@@ -717,7 +764,7 @@ int ref_train_step(ref_engine* e, const int64_t* idx_or_null, float* loss_out, f
             e->m[i] = mn; e->v[i] = vn; e->p_on[i] = e->p_on[i] - dl;
         }
     }
-    e->bp1 *= e->hp.adam_beta1; e->bp2 *= e->hp.adam_beta2;
+    e->bp1 *= e->hp.adam_beta1; e->bp2 *= e->hp.adam_beta2; e->train_steps++;
     if (e->hp.prioritized_replay) if (ref_update_priorities(e, e->idx, e->td, B)) return -1;   /* :231-233, unweighted td */
     if (loss_out) *loss_out = e->loss; if (gnorm_out) *gnorm_out = e->gnorm; if (td_out) memcpy(td_out, e->td, (size_t)B * 4);
     return 0;

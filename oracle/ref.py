@@ -7,6 +7,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg import this
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 import os
 import subprocess
 import sys
@@ -32,19 +33,43 @@ ALIASES = {"engine_create": "create", "engine_destroy": "destroy", "engine_get_p
 ARGTYPES = {"engine_create": [C.POINTER(abi.LayerDesc), C.c_int, C.POINTER(abi.HParams), C.POINTER(abi.LayerPlan), C.POINTER(C.c_void_p)]}
 
 
+def source_hash():
+    """oracle/Makefile's HASH: sha256 of dqn_ref.c and the ABI header, 32 hex digits"""
+    h = hashlib.sha256()
+    for f in (os.path.join(HERE, "dqn_ref.c"), os.path.join(ROOT, "include", "dqn_mi355x.h")):
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()[:32]
+
+
+def is_current():
+    """the library exists and carries the hash of THIS tree's sources (read from the file, not through dlopen: a loaded library cannot be replaced)"""
+    if not os.path.exists(LIB_PATH):
+        return False
+    with open(LIB_PATH, "rb") as fh:
+        return b"DQNREF_SRC_HASH=" + source_hash().encode() in fh.read()
+
+
 def build(force=False):
-    if force or not os.path.exists(LIB_PATH) or os.path.getmtime(LIB_PATH) < os.path.getmtime(os.path.join(HERE, "dqn_ref.c")):
-        subprocess.run(["make", "-C", HERE, "-B" if force else "-s"], check=True, capture_output=True)
+    """a library left behind by another commit's build is rebuilt even when its file time is the newest"""
+    if force or not is_current():
+        subprocess.run(["make", "-s", "-B", "-C", HERE], check=True, capture_output=True)
     return LIB_PATH
+
+
+# what tests call on a Twin beyond the step itself: a library without one of these was built from older sources
+REQUIRED = ("replay_export", "replay_import", "get_counters", "set_counters", "replay_sample", "update_priorities", "train_steps")
 
 
 def fns():
     global _fns
     if _fns is None:
-        if not os.path.exists(LIB_PATH):
-            build()
+        build()                                               # nothing to do when the library is current
         lib = C.CDLL(LIB_PATH)
         _fns = abi.bind(lib, PREFIX, aliases=ALIASES, argtypes=ARGTYPES)
+        missing = [n for n in REQUIRED if n not in _fns]
+        if missing:
+            raise RuntimeError(f"{LIB_PATH} does not export {[PREFIX + n for n in missing]}: it was not built from this tree's oracle/dqn_ref.c")
         lib.ref_set_threads.argtypes = [C.c_void_p, C.c_int]
         _fns["set_threads"] = lib.ref_set_threads
     return _fns
