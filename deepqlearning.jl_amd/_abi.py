@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 LAYER_DENSE, LAYER_CONV, LAYER_LSTM, LAYER_GRU, LAYER_RNN = 0, 1, 2, 3, 4
+LAYER_MAXPOOL, LAYER_MEANPOOL = 5, 6      # parameter-free: Flux.params skips them
 ACT_IDENTITY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 STREAM_BASE, STREAM_VAL, STREAM_ADV = 0, 1, 2
 OBS_F32, OBS_U8 = 0, 1

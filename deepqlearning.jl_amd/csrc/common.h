@@ -37,6 +37,10 @@ struct LayerDev {
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
 static inline __host__ __device__ bool is_recurrent(int kind) { return kind == DQN_LAYER_LSTM || kind == DQN_LAYER_GRU || kind == DQN_LAYER_RNN; }
 
+// Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
+static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
+static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind); }      // the layer's output is a (cout, oh, ow) map
+
 // device-resident mutable state of one engine (one instance in HBM)
 struct StepState {
     unsigned long long sample_ctr;     // Philox counter: number of sample() calls so far
@@ -956,6 +960,10 @@ void launch_gemm_dwdx(hipStream_t st, const LayerDev& Lw, int nprob, const float
                       GemmTail tail = gemm_no_tail());
 
 // (reduce == false leaves split-K partial slabs in `partials` for the caller's batched k_reduce_multi)
+// pool.hip: MaxPool / MeanPool over Y[feature][column]; the backward gathers dY per input element and applies the producing layer's activation derivative
+void launch_pool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/);
+void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
+                     float* dX /*[in_feat][B]*/, int act_src);
 bool mfma_fwd_ok(const LayerDev& L, int ncols);
 bool mfma_dw_ok(const LayerDev& L, int B);
 bool mfma_dx_ok(const LayerDev& L, int B, int ldy);

@@ -73,7 +73,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         l.src = prev;
         int c, h, w;
         if (prev < 0) { c = hp->obs_c; h = hp->obs_h; w = hp->obs_w; }
-        else if (L[prev].kind == DQN_LAYER_CONV) { c = L[prev].cout; h = L[prev].oh; w = L[prev].ow; }
+        else if (has_map(L[prev].kind)) { c = L[prev].cout; h = L[prev].oh; w = L[prev].ow; }
         else { c = L[prev].out_feat; h = 1; w = 1; }
         l.in_feat = c * h * w;
         if (l.kind == DQN_LAYER_CONV) {
@@ -82,6 +82,17 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (l.kh > h || l.kw > w || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
             l.ih = h; l.iw = w; l.oh = (h - l.kh) / l.sh + 1; l.ow = (w - l.kw) / l.sw + 1;
             l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
+        } else if (is_pool(l.kind)) {      // Flux MaxPool / MeanPool, pad 0 (pool.hip): per channel on the incoming (c, h, w) map; no parameters (K = N = 0), no activation
+            const char* nm = l.kind == DQN_LAYER_MAXPOOL ? "MaxPool" : "MeanPool";
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream)", i, nm);
+            if (prev >= 0 && !has_map(L[prev].kind)) return fail("layer %d: %s must be the first layer or follow a Conv / MaxPool / MeanPool layer (it follows a Dense or recurrent layer, whose output is no (c, h, w) map)", i, nm);
+            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
+            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
+            if (d[i].sh < 1 || d[i].sw < 1) return fail("layer %d: %s stride (%d, %d) must be positive", i, nm, d[i].sh, d[i].sw);
+            if (d[i].kh < 1 || d[i].kw < 1 || d[i].kh > h || d[i].kw > w) return fail("layer %d: %s window (%d, %d) does not fit the %dx%d input map", i, nm, d[i].kh, d[i].kw, h, w);
+            l.cin = l.cout = c; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
+            l.ih = h; l.iw = w; l.oh = (h - l.kh) / l.sh + 1; l.ow = (w - l.kw) / l.sw + 1;      // trailing rows / columns no window covers are dropped
+            l.K = 0; l.N = 0; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
@@ -110,6 +121,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         if (*lv < 0 || *la < 0 || L[*lv].out_feat != 1 || L[*la].out_feat != hp->n_actions)
             return fail("DeepQLearningError: the qnetwork provided is incompatible with dueling");   // src/dueling.jl:47
     } else if (*lb < 0 || L[*lb].out_feat != hp->n_actions) return fail("network output size != n_actions");
+    if (!hp->dueling && is_pool(L[*lb].kind)) return fail("layer %d: a MaxPool / MeanPool layer cannot be the network's output layer", *lb);
     if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
     return 0;
 }
@@ -226,12 +238,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     { const int lopt = (e->opt.fwd_m32 > 0 ? DQN_LOPT_FWD_M32 : 0) | (e->opt.fwd_m32 == 0 ? DQN_LOPT_NO_FWD_M32 : 0) | (e->opt.no_fwd_wres ? DQN_LOPT_NO_FWD_WRES : 0) |
                        ((std::min(255, std::max(0, e->opt.dw_split / 16)) & 0xff) << 8) | 
                        (((long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
+    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
     if (!plan) { default_plan(e->L, e->nl, e->B, defp, hp); plan = defp; }
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
+        if (is_pool(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool layer's plan entry is ignored
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
@@ -570,7 +584,8 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 // ---------------------------------------------------------------- the train step
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name) {
     prof_begin(e, name);
-    if (!(e->hp.use_mfma && launch_mfma_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials)))
+    if (is_pool(l.kind)) launch_pool_fwd(e->stream, l, X, ldx, col0, ncols, Y);
+    else if (!(e->hp.use_mfma && launch_mfma_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials)))
         launch_valu_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials);
     prof_end(e);
 }
@@ -1069,6 +1084,8 @@ extern "C" int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32
 // ---------------------------------------------------------------- data-parallel replicas
 extern "C" int dqn_comm_unique_id(void* id128) { if (rccl_load()) return -1; const int rc = g_rccl.GetUniqueId(id128); return rc ? fail("ncclGetUniqueId failed (%d)", rc) : 0; }
 extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int world) { if (!e) return fail("null engine handle");
+    // MaxPool / MeanPool networks: the exchange paths (operand all-gather, all-reduce) have never run with a pool level in the program -- refused instead of claimed
+    for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (rccl_load()) return -1;
     HIPCHK(hipSetDevice(e->device));
     // Recurrent engines on the fused column-parallel step (plan dw_kc = -cg, drqn_cols.hip): that step has no point at which a gradient could be exchanged.  A DEFAULTED

@@ -92,6 +92,11 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
         const auto& lv = levels[li]; const bool last = li + 1 == levels.size();
         if (use_ah && last) break;                          // the head level runs inside k_act_head
         const bool ah_prod = use_ah && li + 2 == levels.size();      // this level = the heads' producers: their slabs stay unreduced
+        if (is_pool(e->L[lv[0]].kind)) {      // a pool layer: one launch on the n columns (pool.hip), never grouped with a GEMM layer
+            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
+            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, n, 0, n, Y); }});
+            continue;
+        }
         struct Prob { int l; const float* X; float *Y, *part; int S; };
         std::vector<Prob> pr;
         for (int l : lv) { const LayerDev& L = e->L[l]; Prob q; q.l = l; q.X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; q.Y = e->pol_act[l]; q.S = dqn_nchunks(L.K, L.fwd_kc);

@@ -35,7 +35,7 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
     segs.clear();
 }
 const char* pname(dqn_engine* e, const char* op, int kind, int i) {
-    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
+    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
 int build_program(dqn_engine* e) {
     if (e->prog_built) return 0;
@@ -148,7 +148,7 @@ int build_program(dqn_engine* e) {
         int n_src = 0; for (int i = 0; i < e->nl; i++) if (e->L[i].src < 0) n_src++;
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
-        if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
+        if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && !is_pool(e->L[l0].kind) /* pool.hip reads floats: a pool as the first layer keeps the fp32 arena */ && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
             gemm_fwd_eligible(LV[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)) { e->arena_u8 = true; e->L[l0].xu8 = 1; LV[l0].xu8 = 1; }
     }
     // ---------------- small batches: the head level (forwards of both nets), the TD kernel and the head layers' dX run as ONE launch with a
@@ -204,6 +204,16 @@ int build_program(dqn_engine* e) {
         // launch (small batches); at B = 512 the 7680 head values x 16 slabs belong on many workgroups
         const auto& lv = levels[li]; const bool last = li + 1 == levels.size() && !rec && e->B <= 64;
         if (fuse_heads && li + 1 == levels.size()) continue;      // computed inside k_head_td
+        if (is_pool(e->L[lv[0]].kind)) {      // a pool layer (always alone on its level: base chain only) is one launch per pass, never grouped with a GEMM layer
+            const int l = lv[0]; const LayerDev L = e->L[l];
+            for (int net = 0; net < 2; net++) {
+                if (net == 1 && e->opt.probe_no_tg) continue;
+                float** act = net ? e->act_tg : e->act_on;
+                const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
+                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, ldx, col0, ncols, Y); }});
+            }
+            continue;
+        }
         struct Prob { int l, net; const float *P, *X; int ldx, col0, ncols; float *Y, *part; int S; };
         std::vector<Prob> pr;
         const bool probe_no_tg = e->opt.probe_no_tg != 0;      // TIMING PROBE (wrong numbers, right schedule): the forward launches without the target network's problems
@@ -380,7 +390,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -435,6 +445,8 @@ int build_program(dqn_engine* e) {
     const bool pg_want = e->hp.prioritized_replay && !rec && (prio_in_adam ? (fuse_heads || e->prio_in_bwd) : e->prio_forked) && !e->sim_world &&
                          (e->hp.obs_dtype != DQN_OBS_U8 || e->arena_u8) && !e->opt.no_pregather && (!e->hp.sample_distinct || Bb <= 64 || e->prio_in_bwd);      // u8 rows: only onto the byte arena; distinct mode at B > 64 without a carrying backward launch: sample launch + gather launch every step
     bool joined = false;
+    // a layer's input gradient has a reader unless the layer reads the observation -- directly, or through pool layers only (a pool has no parameters: its dY would feed nothing)
+    auto wants_dx = [&](int l) { int s = e->L[l].src; while (s >= 0 && is_pool(e->L[s].kind)) s = e->L[s].src; return s >= 0; };
     std::vector<VTask> tail_pend;    // small tasks waiting for a launch to ride on (fused heads: their dW/db and the loss fold)
     auto make_tail = [&](std::vector<VTask>& v) {
         GemmTail t = gemm_no_tail();
@@ -485,6 +497,15 @@ int build_program(dqn_engine* e) {
             const int l = lv[k]; const LayerDev L = e->L[l];
             const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon;
             float* dpre = e->dact[l];
+            if (is_pool(L.kind)) {
+                // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (a pool has no activation); the pool's backward gathers it per
+                // input element and applies the producing layer's activation derivative.  No parameters, so no dW; a pool on the observation has no input gradient to compute
+                if (wants_dx(l)) {
+                    const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act;
+                    e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
+                }
+                continue;
+            }
             if (is_recurrent(L.kind)) {
                 // BPTT over the s-sequence: T single-workgroup steps produce dG (gate pre-activation gradients) for all columns,
                 // then Wi|b, Wh and the input gradient are ordinary dense contractions over the T*B columns.
@@ -523,7 +544,7 @@ int build_program(dqn_engine* e) {
                     float* jr = wh_dst + (size_t)L.H * L.N; const int nr = wh_S; const size_t stride = (size_t)(L.H + 1) * L.N; const int n = L.N;
                     post_level.push_back({pname(e, "gru_junk_clear", L.kind, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
                 }
-                if (L.src >= 0) {
+                if (wants_dx(l)) {
                     const int src = L.src; const int act_src = e->L[src].act; float* out = e->dact[src]; const float* ysrc = e->act_on[src]; const float* P = e->p_on;
                     const int S = (mf && gemm_dx_internal_chunks(Vi, B, ncon)) ? 1 : dqn_nchunks(Vi.N, Vi.dx_kc);      // internal: the launch combines its plan chunks itself
                     float* part = S > 1 ? palloc(e, (size_t)S * Vi.in_feat * B) : nullptr;
@@ -558,7 +579,7 @@ int build_program(dqn_engine* e) {
                 else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = L; t.X = X; t.ldx = ldx; t.dpre = dpre; t.B = B; t.S = S; t.kc = dqn_chunk_len(L.npos * B, L.dw_kc); t.out = dst; add_valu(e, pend, t); }
                 if (S > 1 && !(dw_done_sibling && k == 0 && lv.size() == 2)) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = grad + L.w_off; final_segs.push_back(r); }
             }
-            if (L.src < 0) continue;
+            if (!wants_dx(l)) continue;
             // dX, then act' of the producing layer; the two streams of a dueling net meet at the base output (dX_val + dX_adv)
             const int src = L.src; const bool is_join = e->hp.dueling && src == e->last_base && L.stream != DQN_STREAM_BASE;
             const bool dense = L.kind == DQN_LAYER_DENSE; const int S_plan = dense ? dqn_nchunks(L.N, L.dx_kc) : 1;
@@ -606,7 +627,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;

@@ -60,6 +60,12 @@ function lower_layer(l, stream)::LayerDesc
         kw, kh, cin, cout = size(l.weight)
         all(==(0), l.pad) || throw("DeepQLearningError: the MI355X engine supports Conv with pad=0 only")
         return LayerDesc(1, ACT[l.σ], stream, 0, 0, cin, cout, kh, kw, l.stride[2], l.stride[1])
+    elseif l isa Flux.MaxPool      # fields k, pad, stride; no parameters; cin = cout = 0: the engine takes the channels of the incoming map
+        any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MaxPool with pad=0 only")
+        return LayerDesc(5, 0, stream, 0, 0, 0, 0, l.k[2], l.k[1], l.stride[2], l.stride[1])
+    elseif l isa Flux.MeanPool
+        any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MeanPool with pad=0 only")
+        return LayerDesc(6, 0, stream, 0, 0, 0, 0, l.k[2], l.k[1], l.stride[2], l.stride[1])
     elseif l isa Flux.Recur && l.cell isa Flux.LSTMCell     # Flux.params order Wi, Wh, b, state0 (h0, c0) == the ABI's LSTM block
         return LayerDesc(2, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (Flux's GRUv3 has another block: unsupported)
@@ -67,7 +73,7 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / Dense / LSTM / GRU / RNN / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 function lower(q)

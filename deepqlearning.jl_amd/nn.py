@@ -47,6 +47,33 @@ class Conv:
         return self.kh * self.kw * self.cin, self.kh * self.kw * self.cout
 
 
+class _Pool:
+    """Flux MaxPool / MeanPool((kh, kw); pad = 0, stride = (kh, kw)): per channel on a (C, H, W) map, output (C, (H-kh)÷sh+1, (W-kw)÷sw+1); trailing rows / columns that
+    no window covers are dropped.  No parameters, no activation."""
+
+    def __init__(self, k, stride=None, pad=0):
+        self.kh, self.kw = (int(k), int(k)) if np.isscalar(k) else (int(k[0]), int(k[1]))
+        stride = (self.kh, self.kw) if stride is None else stride      # Flux: stride defaults to the window
+        self.sh, self.sw = (int(stride), int(stride)) if np.isscalar(stride) else (int(stride[0]), int(stride[1]))
+        if np.any(np.asarray(pad) != 0):
+            raise _abi.DQNError(f"DeepQLearningError: the MI355X engine supports {type(self).__name__} with pad=0 only (got pad={pad!r})")
+        self.act = identity
+
+    def shapes(self):   # Flux.params holds nothing for a pool layer
+        return []
+
+    def __repr__(self):
+        return f"{type(self).__name__}(({self.kh}, {self.kw}), stride=({self.sh}, {self.sw}))"
+
+
+class MaxPool(_Pool):
+    kind = "maxpool"
+
+
+class MeanPool(_Pool):
+    kind = "meanpool"
+
+
 class LSTM:
     """Flux LSTM(in, out) = Recur(LSTMCell): params Wi (4out,in), Wh (4out,out), b (4out, forget gate bias 1), state0 (h0, c0)."""
     kind = "lstm"
@@ -135,12 +162,13 @@ def create_dueling_network(m: Chain) -> DuelingNetwork:
 def lower(net):
     """Chain | DuelingNetwork -> (list[LayerDesc], dueling flag)."""
     out = []
+    chan = [0]      # channels of the map the next layer reads (0 in front of the first Conv: the engine takes the observation's)
 
     def add(chain, stream):
         for l in chain:
             d = _abi.LayerDesc()
-            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / Dense / LSTM / GRU / RNN / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / flattenbatch only)")
             d.act, d.stream = l.act, stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -150,9 +178,14 @@ def lower(net):
                 d.kind, d.n_in, d.n_out = _abi.LAYER_GRU, l.n_in, l.n_out
             elif l.kind == "rnn":       # act carries the cell's σ
                 d.kind, d.n_in, d.n_out = _abi.LAYER_RNN, l.n_in, l.n_out
+            elif l.kind in ("maxpool", "meanpool"):      # cin == cout == channels of the incoming map
+                d.kind = _abi.LAYER_MAXPOOL if l.kind == "maxpool" else _abi.LAYER_MEANPOOL
+                d.cin = d.cout = chan[0]
+                d.kh, d.kw, d.sh, d.sw = l.kh, l.kw, l.sh, l.sw
             else:
                 d.kind = _abi.LAYER_CONV
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
+                chan[0] = l.cout
             out.append(d)
 
     if isinstance(net, DuelingNetwork):
@@ -179,6 +212,8 @@ def glorot_params(net, seed=1):
     rng = np.random.default_rng(seed)
     parts = []
     for l in all_layers(net):
+        if l.kind in ("maxpool", "meanpool"):      # no parameters
+            continue
         if l.kind == "lstm":
             h = l.n_out
             for shp, fi, fo in (((l.n_in, 4 * h), l.n_in, 4 * h), ((h, 4 * h), h, 4 * h)):

@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6 };
 enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3 };
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
@@ -59,7 +59,9 @@ typedef struct {
                                           GRU(in,out) = Flux Recur(GRUCell): params Wi (3out,in), Wh (3out,out), b (3out), state0 h0;
                                           RNN(in,out,act) = Flux Recur(RNNCell): params Wi (out,in), Wh (out,out), b (out), state0 h0 (out,1),
                                           in C order Wi[in][out], Wh[out][out], b, h0; act carries the cell's activation (default tanh) */
-    int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw)), pad 0 */
+    int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw)), pad 0;
+                                          MaxPool((kh,kw); stride=(sh,sw)) / MeanPool(...), pad 0: cin == cout == channels of the incoming map (or both 0: the engine fills them in), act = IDENTITY,
+                                          no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored */
 } dqn_layer_desc;
 
 /* Summation-order plan of one layer: the K dimension of each contraction is cut
