@@ -32,6 +32,7 @@ struct LayerDev {
     int cell_act;                      // RNN: the cell's activation (DQN_ACT_*).  `act` stays IDENTITY for every recurrent layer: the generic forward / dX epilogues read `act`
     int opt;                           // per-ENGINE experiment switches the kernel launchers look at (DQN_LOPT_*, set at dqn_engine_create from EngineOpts): no process-wide state
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
+    int ph, pw;                        // Conv: symmetric zero padding per axis (dqn_layer_desc n_in / n_out slots); ih, iw stay the UNPADDED map, oh = (ih + 2 ph - kh) / sh + 1
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
@@ -40,6 +41,8 @@ static inline __host__ __device__ bool is_recurrent(int kind) { return kind == D
 // Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
 static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
 static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind); }      // the layer's output is a (cout, oh, ow) map
+// a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
+static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 
 // device-resident mutable state of one engine (one instance in HBM)
 struct StepState {
@@ -964,6 +967,11 @@ void launch_gemm_dwdx(hipStream_t st, const LayerDev& Lw, int nprob, const float
 void launch_pool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/);
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
                      float* dX /*[in_feat][B]*/, int act_src);
+// conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');
+// mf = hp.use_mfma (MFMA tiles where the shape allows, the same bits either way); xu8: X is the byte arena of a u8 replay
+void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8);
+void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
+void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf);
 bool mfma_fwd_ok(const LayerDev& L, int ncols);
 bool mfma_dw_ok(const LayerDev& L, int B);
 bool mfma_dx_ok(const LayerDev& L, int B, int ldy);

@@ -79,8 +79,14 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         if (l.kind == DQN_LAYER_CONV) {
             l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
             if (l.cin != c) return fail("layer %d: conv cin %d != incoming channels %d", i, l.cin, c);
-            if (l.kh > h || l.kw > w || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
-            l.ih = h; l.iw = w; l.oh = (h - l.kh) / l.sh + 1; l.ow = (w - l.kw) / l.sw + 1;
+            // pad = (ph, pw) rides in the n_in / n_out slots (zero in every pad-0 descriptor): symmetric zero padding, at most kernel - 1 per axis (conv_pad.hip)
+            l.ph = d[i].n_in; l.pw = d[i].n_out;
+            if (l.ph < 0 || l.pw < 0) return fail("layer %d: Conv pad (%d, %d) must not be negative", i, l.ph, l.pw);
+            if ((l.ph || l.pw) && (l.kh < 1 || l.kw < 1 || l.ph > l.kh - 1 || l.pw > l.kw - 1)) return fail("layer %d: Conv pad (%d, %d) is larger than kernel - 1 = (%d, %d): a window would lie in the padding alone", i, l.ph, l.pw, l.kh - 1, l.kw - 1);
+            if ((l.ph || l.pw) && l.stream != DQN_STREAM_BASE) return fail("layer %d: Conv with pad (%d, %d) is supported in the base chain only (not in a value / advantage stream)", i, l.ph, l.pw);
+            if ((l.ph || l.pw) && (l.sh < 1 || l.sw < 1 || l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw)) return fail("layer %d: Conv kernel (%d, %d) / stride (%d, %d) does not fit the %dx%d input map extended by pad (%d, %d)", i, l.kh, l.kw, l.sh, l.sw, h, w, l.ph, l.pw);
+            if (l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
+            l.ih = h; l.iw = w; l.oh = (h + 2 * l.ph - l.kh) / l.sh + 1; l.ow = (w + 2 * l.pw - l.kw) / l.sw + 1;      // trailing rows / columns of the extended map no window covers are dropped
             l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
         } else if (is_pool(l.kind)) {      // Flux MaxPool / MeanPool, pad 0 (pool.hip): per channel on the incoming (c, h, w) map; no parameters (K = N = 0), no activation
             const char* nm = l.kind == DQN_LAYER_MAXPOOL ? "MaxPool" : "MeanPool";
@@ -238,6 +244,7 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     { const int lopt = (e->opt.fwd_m32 > 0 ? DQN_LOPT_FWD_M32 : 0) | (e->opt.fwd_m32 == 0 ? DQN_LOPT_NO_FWD_M32 : 0) | (e->opt.no_fwd_wres ? DQN_LOPT_NO_FWD_WRES : 0) |
                        ((std::min(255, std::max(0, e->opt.dw_split / 16)) & 0xff) << 8) | 
                        (((long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
+    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("DQN_SIM_WORLD: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
@@ -585,6 +592,7 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name) {
     prof_begin(e, name);
     if (is_pool(l.kind)) launch_pool_fwd(e->stream, l, X, ldx, col0, ncols, Y);
+    else if (is_padded(l)) launch_cpad_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma, 0);      // the policy workspace holds floats
     else if (!(e->hp.use_mfma && launch_mfma_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials)))
         launch_valu_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials);
     prof_end(e);
@@ -1085,6 +1093,8 @@ extern "C" int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32
 extern "C" int dqn_comm_unique_id(void* id128) { if (rccl_load()) return -1; const int rc = g_rccl.GetUniqueId(id128); return rc ? fail("ncclGetUniqueId failed (%d)", rc) : 0; }
 extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int world) { if (!e) return fail("null engine handle");
     // MaxPool / MeanPool networks: the exchange paths (operand all-gather, all-reduce) have never run with a pool level in the program -- refused instead of claimed
+    // ... and none with a padded convolution either (conv_pad.hip)
+    for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (rccl_load()) return -1;
     HIPCHK(hipSetDevice(e->device));

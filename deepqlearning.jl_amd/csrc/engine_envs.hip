@@ -72,7 +72,8 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     // the fused tail (act_head.hip): reduce of the heads' producers + heads + Q / argmax + eps-greedy + act! + add_exp!'s per-experience part in ONE launch, where the shapes allow
     // (the conditions of the train step's fused reduce + head launch, engine_program.hip); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
-    bool use_ah = !e->opt.no_act_head && levels.size() >= 2; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
+    bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
+    bool use_ah = !e->opt.no_act_head && levels.size() >= 2 && !any_padded; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
     if (use_ah) {
         const LayerDev& La = e->L[lq]; ah_pa = La.src; ah_pv = lvh >= 0 ? e->L[lvh].src : -1;
         bool ok = La.kind == DQN_LAYER_DENSE && ah_pa >= 0 && (lvh < 0 || (e->L[lvh].kind == DQN_LAYER_DENSE && ah_pv >= 0 && ah_pv != ah_pa));
@@ -95,6 +96,12 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
         if (is_pool(e->L[lv[0]].kind)) {      // a pool layer: one launch on the n columns (pool.hip), never grouped with a GEMM layer
             const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
             ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, n, 0, n, Y); }});
+            continue;
+        }
+        if (is_padded(e->L[lv[0]])) {      // a padded conv: one launch on the n columns (conv_pad.hip), never grouped
+            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
+            HeadSrc h; h.p = Y; h.ld = n; h.S = 1; h.per_s = 0; h.bias = P + L.b_off; h.act = L.act; head[l] = h;
+            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, P, X, n, 0, n, Y, mf ? 1 : 0, 0); }});
             continue;
         }
         struct Prob { int l; const float* X; float *Y, *part; int S; };

@@ -9,7 +9,7 @@
 float* palloc(dqn_engine* e, size_t n) { float* d = nullptr; hipMalloc((void**)&d, n * 4); (e->alloc_sink ? *e->alloc_sink : e->prog_allocs).push_back(d); return d; }
 bool same_geo(const LayerDev& a, const LayerDev& b) {
     return a.kind == b.kind && a.act == b.act && a.K == b.K && a.N == b.N && a.npos == b.npos && a.cin == b.cin && a.kh == b.kh && a.kw == b.kw &&
-           a.sh == b.sh && a.sw == b.sw && a.ih == b.ih && a.iw == b.iw && a.fwd_kc == b.fwd_kc && a.src == b.src;
+           a.sh == b.sh && a.sw == b.sw && a.ph == b.ph && a.pw == b.pw && a.ih == b.ih && a.iw == b.iw && a.fwd_kc == b.fwd_kc && a.src == b.src;
 }
 void add_valu(dqn_engine* e, std::vector<VTask>& pend, const VTask& t) { pend.push_back(t); }
 // prio: the step's priority block (update_priorities! + the next step's index draw) rides as workgroup 0 of this launch
@@ -149,7 +149,7 @@ int build_program(dqn_engine* e) {
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
         if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && !is_pool(e->L[l0].kind) /* pool.hip reads floats: a pool as the first layer keeps the fp32 arena */ && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
-            gemm_fwd_eligible(LV[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)) { e->arena_u8 = true; e->L[l0].xu8 = 1; LV[l0].xu8 = 1; }
+            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || (gemm_fwd_eligible(LV[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; LV[l0].xu8 = 1; }
     }
     // ---------------- small batches: the head level (forwards of both nets), the TD kernel and the head layers' dX run as ONE launch with a
     // workgroup per batch column (k_head_td); the heads' dW/db and the loss fold ride as tail tasks of the next backward launch
@@ -211,6 +211,17 @@ int build_program(dqn_engine* e) {
                 float** act = net ? e->act_tg : e->act_on;
                 const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
                 e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, ldx, col0, ncols, Y); }});
+            }
+            continue;
+        }
+        if (is_padded(e->L[lv[0]])) {      // a padded conv (base chain only, so alone on its level): one launch per pass (conv_pad.hip walks the plan chunks itself), never grouped
+            const int l = lv[0]; const LayerDev L = LV[l]; const int xu8 = L.xu8;
+            for (int net = 0; net < 2; net++) {
+                float** act = net ? e->act_tg : e->act_on; const float* P = net ? e->p_tg : e->p_on;
+                const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
+                HeadSrc h; h.p = Y; h.ld = ncols; h.S = 1; h.per_s = 0; h.bias = P + L.b_off; h.act = L.act; head[l][net] = h;
+                if (net == 1 && e->opt.probe_no_tg) continue;
+                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, P, X, ldx, col0, ncols, Y, mf ? 1 : 0, xu8); }});
             }
             continue;
         }
@@ -390,7 +401,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -503,6 +514,19 @@ int build_program(dqn_engine* e) {
                 if (wants_dx(l)) {
                     const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act;
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
+                }
+                continue;
+            }
+            if (is_padded(L)) {
+                // a padded conv's backward (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then
+                // -- unless the layer reads the observation -- dX with the producing layer's activation derivative.  Two launches of the layer's own, never grouped
+                const int S = dqn_nchunks(L.npos * B, L.dw_kc); float* grad = e->grad;
+                float* part = S > 1 ? palloc(e, (size_t)S * (L.K + 1) * L.N) : nullptr; float* dst = S > 1 ? part : grad + L.w_off; const int xu8 = L.xu8;
+                e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
+                if (S > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = grad + L.w_off; final_segs.push_back(r); }
+                if (wants_dx(l)) {
+                    const float* P = e->p_on; float* out = e->dact[L.src]; const float* ysrc = e->act_on[L.src]; const int act_src = e->L[L.src].act;
+                    e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, ysrc, ncon, act_src, mf ? 1 : 0); }});
                 }
                 continue;
             }
@@ -627,7 +651,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;

@@ -58,8 +58,11 @@ function lower_layer(l, stream)::LayerDesc
         return LayerDesc(0, ACT[l.σ], stream, size(l.weight, 2), size(l.weight, 1), 0, 0, 0, 0, 0, 0)
     elseif l isa Conv
         kw, kh, cin, cout = size(l.weight)
-        all(==(0), l.pad) || throw("DeepQLearningError: the MI355X engine supports Conv with pad=0 only")
-        return LayerDesc(1, ACT[l.σ], stream, 0, 0, cin, cout, kh, kw, l.stride[2], l.stride[1])
+        # l.pad is NTuple{4}: (lo, hi) of the W axis, then of the H axis -- the first pair belongs to the W axis, as l.stride[1] does.  Symmetric zero padding only
+        # (SamePad() on an even kernel yields lo != hi); the engine checks 0 <= pad <= kernel - 1.  (pad_h, pad_w) ride in the n_in, n_out slots a Conv leaves unused
+        p = length(l.pad) == 4 ? l.pad : (l.pad[1], l.pad[1], l.pad[2], l.pad[2])
+        (p[1] == p[2] && p[3] == p[4]) || throw("DeepQLearningError: the MI355X engine supports Conv with symmetric pad only (lo == hi on each axis), got asymmetric pad=$(l.pad)")
+        return LayerDesc(1, ACT[l.σ], stream, p[3], p[1], cin, cout, kh, kw, l.stride[2], l.stride[1])
     elseif l isa Flux.MaxPool      # fields k, pad, stride; no parameters; cin = cout = 0: the engine takes the channels of the incoming map
         any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MaxPool with pad=0 only")
         return LayerDesc(5, 0, stream, 0, 0, 0, 0, l.k[2], l.k[1], l.stride[2], l.stride[1])

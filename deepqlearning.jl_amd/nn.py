@@ -31,14 +31,53 @@ class Dense:
         return self.n_in, self.n_out
 
 
+class SamePad:
+    """Flux SamePad(): output size = input size ÷ stride.  For an odd kernel that is the symmetric pad (k - 1) ÷ 2 per axis; for an even kernel Flux pads one more element
+    on the high side than on the low side, an asymmetric pad the engine does not run."""
+
+    def __repr__(self):
+        return "SamePad()"
+
+
+def _resolve_pad(pad, kh, kw):
+    """Flux's pad argument -> symmetric (ph, pw): an int, a 2-tuple (per axis), a 4-tuple (lo, hi per axis: W axis first, as Flux stores it) or SamePad()."""
+    name = f"Conv(({kh}, {kw}), ...; pad={pad!r})"
+    if isinstance(pad, SamePad) or pad is SamePad:
+        if kh % 2 == 0 or kw % 2 == 0:
+            raise _abi.DQNError(f"DeepQLearningError: {name}: SamePad() on an even kernel is an asymmetric pad (lo != hi); the MI355X engine supports symmetric zero padding only")
+        return (kh - 1) // 2, (kw - 1) // 2
+    if np.isscalar(pad):
+        ph = pw = int(pad)
+    else:
+        t = tuple(int(v) for v in pad)
+        if len(t) == 2:
+            ph, pw = t
+        elif len(t) == 4:      # Flux: (w_lo, w_hi, h_lo, h_hi) -- the first pair belongs to the W axis, as stride[1] does
+            if t[0] != t[1] or t[2] != t[3]:
+                raise _abi.DQNError(f"DeepQLearningError: {name}: asymmetric pad (lo != hi on an axis); the MI355X engine supports symmetric zero padding only")
+            pw, ph = t[0], t[2]
+        else:
+            raise _abi.DQNError(f"DeepQLearningError: {name}: pad must be an int, a 2-tuple, a symmetric 4-tuple or SamePad()")
+    if ph < 0 or pw < 0:
+        raise _abi.DQNError(f"DeepQLearningError: {name}: pad ({ph}, {pw}) must not be negative")
+    if ph > kh - 1 or pw > kw - 1:
+        raise _abi.DQNError(f"DeepQLearningError: {name}: pad ({ph}, {pw}) is larger than kernel - 1 = ({kh - 1}, {kw - 1})")
+    return ph, pw
+
+
 class Conv:
-    """Flux Conv((k,k), cin=>cout, act; stride) -- true convolution, no padding."""
+    """Flux Conv((kh,kw), cin=>cout, act; stride, pad) -- true convolution; pad = symmetric zero padding per axis (an int, (ph, pw), a symmetric Flux 4-tuple or
+    SamePad() on an odd kernel), 0 <= pad <= kernel - 1.  Output map (H + 2 ph - kh) ÷ sh + 1 by (W + 2 pw - kw) ÷ sw + 1."""
     kind = "conv"
 
-    def __init__(self, k, cin, cout, act=identity, stride=1):
+    def __init__(self, k, cin, cout, act=identity, stride=1, pad=0):
         self.kh, self.kw = (k, k) if np.isscalar(k) else (int(k[0]), int(k[1]))
         self.sh, self.sw = (stride, stride) if np.isscalar(stride) else (int(stride[0]), int(stride[1]))
         self.cin, self.cout, self.act = int(cin), int(cout), act
+        self.ph, self.pw = _resolve_pad(pad, self.kh, self.kw)
+
+    def __repr__(self):
+        return f"Conv(({self.kh}, {self.kw}), {self.cin} => {self.cout}, act={self.act}, stride=({self.sh}, {self.sw}), pad=({self.ph}, {self.pw}))"
 
     def shapes(self):  # weight (kw,kh,cin,cout) == C (cout,cin,kh,kw)
         return [(self.cout, self.cin, self.kh, self.kw), (self.cout,)]
@@ -185,6 +224,7 @@ def lower(net):
             else:
                 d.kind = _abi.LAYER_CONV
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
+                d.n_in, d.n_out = l.ph, l.pw      # the pad rides in the slots a Conv leaves unused (0, 0 for every unpadded layer)
                 chan[0] = l.cout
             out.append(d)
 

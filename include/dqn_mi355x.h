@@ -59,7 +59,9 @@ typedef struct {
                                           GRU(in,out) = Flux Recur(GRUCell): params Wi (3out,in), Wh (3out,out), b (3out), state0 h0;
                                           RNN(in,out,act) = Flux Recur(RNNCell): params Wi (out,in), Wh (out,out), b (out), state0 h0 (out,1),
                                           in C order Wi[in][out], Wh[out][out], b, h0; act carries the cell's activation (default tanh) */
-    int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw)), pad 0;
+    int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw), pad=(pad_h,pad_w)): for DQN_LAYER_CONV the slots n_in / n_out carry pad_h / pad_w,
+                                          symmetric zero padding per axis, 0 <= pad_h <= kh - 1, 0 <= pad_w <= kw - 1 (0, 0 = no padding); output map
+                                          (H + 2 pad_h - kh) / sh + 1 by (W + 2 pad_w - kw) / sw + 1; a padded Conv is base chain only and single GPU only;
                                           MaxPool((kh,kw); stride=(sh,sw)) / MeanPool(...), pad 0: cin == cout == channels of the incoming map (or both 0: the engine fills them in), act = IDENTITY,
                                           no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored */
 } dqn_layer_desc;
