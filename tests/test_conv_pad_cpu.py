@@ -33,34 +33,26 @@ def mods(pkg):
 def test_reference_legs_agree_and_the_seed_keeps_the_margins(c):
     """NumPy (np.pad + the oracle's pad-0 conv + crop) and torch autograd (F.conv2d's padding) share no padding code: 1e-10 relative on every quantity along the
     fp64 trajectory of the case's three steps.  prepare() asserts the case's fixed seed against the argmax, relu and MaxPool margins."""
-    net, D = CR.prepare(c)
-    p = D["p_on"].astype(np.float64); adam = FR.Adam(p.size, lr=CR.LR)
-    prio = O.priority_from_td(np.abs(D["r"]), np.float32(1e-3), np.float32(0.6)).astype(np.float64)
-    for k in range(3):
-        batch = E._fp64_batch(c, D, D["idx"][k], prio)
-        a = CR.step_numpy(net, p, D["p_tg"], batch, float(np.float32(c.gamma)), c.dq)
-        FR.legs_agree(a, CR.step_torch(net, p, D["p_tg"], batch, float(np.float32(c.gamma)), c.dq))
-        prio[D["idx"][k]] = O.priority_from_td(np.abs(a["td"]), np.float32(1e-3), np.float32(0.6), np.float64)
-        p = adam.step(p, a["grads"])
+    E.check_legs_along_trajectory(c)
 
 
 def test_the_table_holds_the_cases_and_every_first_layer_case_is_padded():
     assert set(CR.FIRST_LAYER) <= set(CR.BY_NAME) and len(CR.CASES) == 13
     for name in CR.FIRST_LAYER:
-        assert any(CR.pad_of(CR.network(CR.BY_NAME[name]).base[0])), name
+        assert any(CR.pad_of(E.network(CR.BY_NAME[name]).base[0])), name
     for c in CR.CASES:
-        assert any(any(CR.pad_of(l)) for l in CR.network(c).base), c.name
+        assert any(any(CR.pad_of(l)) for l in E.network(c).base), c.name
 
 
 def test_recurrent_case_seed_keeps_the_margin(mods):
-    assert CR.rec_trajectory_ok(mods[0])
+    assert FR.rec_trajectory_ok(mods[0], CR.REC)
 
 
 def test_padded_output_of_the_reference_is_the_pad0_conv_on_the_extended_map():
     """the definition itself, on the NumPy leg: stride 2 drops part of the trailing padding"""
     rng = np.random.default_rng(0); l = CR.PConv(3, 2, 4, CR.TANH, stride=2, pad=1)
     x = rng.standard_normal((3, 2, 7, 8)); W = rng.standard_normal((4, 2, 3, 3)); b = rng.standard_normal(4)
-    y = CR._fwd([l], [W, b], x)[0]
+    y = FR._fwd([l], [W, b], x)[0]
     assert y.shape == (3, 4, 4, 4) == (3,) + l.out_shape((2, 7, 8))
     np.testing.assert_array_equal(y, O.layer_forward(O.Conv(3, 2, 4, CR.TANH, 2), np.pad(x, ((0, 0), (0, 0), (1, 1), (1, 1))), W, b)[0])
 

@@ -18,6 +18,7 @@ import dqn_oracle as O
 import ref
 
 IDS = lambda cs: [c.name for c in cs]
+TWIN = dict(threads=8, plan=ref.default_plan)      # the twin has no planner of its own: the default plan, restated in oracle/ref.py
 
 
 @pytest.mark.parametrize("c", C.CASES, ids=IDS(C.CASES))
@@ -43,28 +44,66 @@ def test_table_covers_both_sides_of_every_rule():
 @pytest.mark.parametrize("c", C.CASES + C.RANDOM, ids=IDS(C.CASES + C.RANDOM))
 def test_reference_legs_agree(c):
     """NumPy oracle and torch autograd, both fp64, on the case's first batch: 1e-10 relative on every quantity"""
-    net, D = C._prepared(c.name, 3)
-    prio = O.priority_from_td(np.abs(D["r"]), np.float32(1e-3), np.float32(0.6)).astype(np.float64)
-    batch = C._fp64_batch(c, D, D["idx"][0], prio)
+    net, D, batch = _first_batch(c)
     args = (net, D["p_on"], D["p_tg"], batch, float(np.float32(c.gamma)), c.dq)
     FR.legs_agree(FR.step_numpy(*args), FR.step_torch(*args))
 
 
+def _first_batch(c):
+    net, D = C.prepare(c)
+    prio = O.priority_from_td(np.abs(D["r"]), np.float32(1e-3), np.float32(0.6)).astype(np.float64)
+    return net, D, C._fp64_batch(c, D, D["idx"][0], prio)
+
+
+@pytest.mark.parametrize("c", C.CASES + C.RANDOM, ids=IDS(C.CASES + C.RANDOM))
+def test_reference_numpy_leg_is_the_oracles_whole_step_bit_for_bit(c):
+    """step_numpy is built from the oracle's layer functions, not from its batch_train_step: on a network the oracle can describe the two are the same
+    operations in the same order, so every quantity of KEYS is equal bit for bit"""
+    net, D, batch = _first_batch(c)
+    gamma = float(np.float32(c.gamma))
+    a = FR.step_numpy(net, D["p_on"], D["p_tg"], batch, gamma, c.dq)
+    o = O.batch_train_step(net, net.unflatten(D["p_on"].astype(np.float64)), net.unflatten(D["p_tg"].astype(np.float64)), batch, gamma=gamma, double_q=bool(c.dq), adam=None)
+    want = dict(o, q_on_s=o["q"], grads=O.Network.flatten(o["grads"]))
+    assert set(a) == set(FR.KEYS)
+    for k in FR.KEYS:
+        np.testing.assert_array_equal(a[k], want[k], err_msg=k)
+
+
+@pytest.mark.parametrize("c", C.CASES + C.RANDOM, ids=IDS(C.CASES + C.RANDOM))
+def test_layer_descs_are_the_oracles_field_by_field(c):
+    """feedforward_reference.layer_descs = ref.layers_from_network where there is neither pad nor pool"""
+    net = C.network(c)
+    a, b = FR.layer_descs(net), ref.layers_from_network(net)
+    assert len(a) == len(b)
+    for x, y in zip(a, b):
+        assert [getattr(x, f) for f, _ in x._fields_] == [getattr(y, f) for f, _ in y._fields_]
+
+
+@pytest.mark.parametrize("c", C.CASES + C.RANDOM, ids=IDS(C.CASES + C.RANDOM))
+def test_init_params_are_the_oracles_bit_for_bit(c):
+    net = C.network(c)
+    pa, pb = FR.init_params(net, c.seed), O.init_params(net, c.seed)
+    assert len(pa) == len(pb)
+    for x, y in zip(pa, pb):
+        assert x.dtype == y.dtype and x.shape == y.shape
+        np.testing.assert_array_equal(x, y)
+
+
 @pytest.mark.parametrize("c", C.CASES, ids=IDS(C.CASES))
 def test_twin_case_vs_fp64_reference(c):
-    h, _ = C.run_checked(ref.Twin, c, threads=8)
+    h, _ = C.run_checked(ref.Twin, c, **TWIN)
     h.close()
 
 
 @pytest.mark.parametrize("c", C.RANDOM, ids=IDS(C.RANDOM))
 def test_twin_random_configuration_vs_fp64_reference(c):
-    h, _ = C.run_checked(ref.Twin, c, threads=8)
+    h, _ = C.run_checked(ref.Twin, c, **TWIN)
     h.close()
 
 
 @pytest.mark.parametrize("c", C.LONG, ids=IDS(C.LONG))
 def test_twin_adam_over_200_steps(c):
-    C.long_adam(ref.Twin, c, threads=8).close()
+    C.long_adam(ref.Twin, c, **TWIN).close()
 
 
 def test_zz_report_worst_errors():

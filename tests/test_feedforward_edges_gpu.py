@@ -40,9 +40,9 @@ def check_case(pkg, c):
     f = C.check_want(c)                                   # the case stands on the side of the rule it was written for
     net = C.network(c); hp = C.hparams(c, net); layers = ref.layers_from_network(net)
     assert pkg.default_plan(layers, hp) == ref.default_plan(layers, hp)
-    h, rec = C.run_checked(pkg.Engine, c)                 # against the fp64 reference
-    C.same_bits(rec, C.replay_steps(ref.Twin, c, threads=8), f"{c.name}: engine vs twin")
-    C.same_bits(rec, C.replay_steps(pkg.Engine, c, graph=1 - c.graph), f"{c.name}: use_graph {c.graph} vs {1 - c.graph}")
+    h, rec = C.run_checked(pkg.Engine, c, plan=ref.default_plan)                 # against the fp64 reference
+    C.same_bits(rec, C.replay_steps(ref.Twin, c, threads=8, plan=ref.default_plan), f"{c.name}: engine vs twin")
+    C.same_bits(rec, C.replay_steps(pkg.Engine, c, graph=1 - c.graph, plan=ref.default_plan), f"{c.name}: use_graph {c.graph} vs {1 - c.graph}")
     if not f["tiny"]:
         assert h.batch_arena_elem_bytes() == (1 if f["arena"] else 4), c.name
     C.assert_launches(h, f, c.name)                       # profile_step runs one more (eager) step: last
@@ -61,7 +61,7 @@ def test_random_configuration_vs_fp64_reference_twin_and_schedule(pkg, c):
 
 @pytest.mark.parametrize("c", C.LONG, ids=IDS(C.LONG))
 def test_adam_over_200_steps(pkg, c):
-    C.long_adam(pkg.Engine, c).close()
+    C.long_adam(pkg.Engine, c, plan=ref.default_plan).close()
 
 
 def test_zz_report_worst_errors():

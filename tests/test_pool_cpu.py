@@ -88,24 +88,16 @@ def test_julia_shim_maps_the_two_pools():
 def test_reference_legs_agree_and_the_seed_keeps_the_margins(c):
     """NumPy (hand-written backward) and torch autograd (F.max_pool2d / F.avg_pool2d) share no pooling code: 1e-10 relative on every quantity, along the
     fp64 trajectory of the case's three steps.  prepare() asserts the case's fixed seed against the argmax, relu and MaxPool margins."""
-    net, D = PR.prepare(c)
-    p = D["p_on"].astype(np.float64); adam = FR.Adam(p.size, lr=PR.LR)
-    prio = O.priority_from_td(np.abs(D["r"]), np.float32(1e-3), np.float32(0.6)).astype(np.float64)
-    for k in range(3):
-        batch = E._fp64_batch(c, D, D["idx"][k], prio)
-        a = PR.step_numpy(net, p, D["p_tg"], batch, float(np.float32(c.gamma)), c.dq)
-        FR.legs_agree(a, PR.step_torch(net, p, D["p_tg"], batch, float(np.float32(c.gamma)), c.dq))
-        prio[D["idx"][k]] = O.priority_from_td(np.abs(a["td"]), np.float32(1e-3), np.float32(0.6), np.float64)
-        p = adam.step(p, a["grads"])
+    E.check_legs_along_trajectory(c)
 
 
 def test_tie_case_ties_everywhere_and_both_legs_take_the_first_tap():
     """case `ties`: every MaxPool window of the online net holds four equal taps (fp64 and, by construction, fp32), and the NumPy leg's argmax is tap 0"""
-    c = PR.BY_NAME["ties"]; net, D = PR.prepare(c)
+    c = PR.BY_NAME["ties"]; net, D = E.prepare(c)
     x = D["s"][D["idx"][0]].astype(np.float64); ps = net.unflatten(D["p_on"].astype(np.float64))
     y, _ = O.layer_forward(net.base[0], x, ps[0], ps[1])
-    t = PR._taps(net.base[1], y)[0]
-    assert (t == t[0]).all() and (PR.pool_forward(net.base[1], y)[1] == 0).all()
+    t = FR._taps(net.base[1], y)[0]
+    assert (t == t[0]).all() and (FR.pool_forward(net.base[1], y)[1] == 0).all()
 
 
 def test_margin_rule_sees_a_near_tie():
@@ -113,12 +105,12 @@ def test_margin_rule_sees_a_near_tie():
     net = O.Network((1, 2, 2), [PR.MaxPool(2), O.Dense(1, 2)])
     p = np.array([1.0, 1.0, 0.0, 0.0])
     s = np.array([[[[0.5, 0.5 + 1e-6], [0.1, 0.2]]]])
-    assert PR.margins(net, p, s)[1] < E.RELU_MARGIN
+    assert FR.margins(net, p, s)[1] < E.RELU_MARGIN
     net2 = O.Network((1, 3, 3), [O.Conv(2, 1, 1, O.ACT_RELU), PR.MaxPool(2), O.Dense(1, 2)])
     p2 = np.array([1.0, 1.0, 1.0, 1.0, -100.0, 1.0, 1.0, 0.0, 0.0])      # every pre-activation far below 0: the map is all relu zeros
-    assert PR.margins(net2, p2, np.ones((1, 1, 3, 3)))[1] == np.inf
+    assert FR.margins(net2, p2, np.ones((1, 1, 3, 3)))[1] == np.inf
 
 
 def test_recurrent_case_seed_keeps_the_margins(mods):
     nn, _, _ = mods
-    assert PR.rec_trajectory_ok(nn)
+    assert FR.rec_trajectory_ok(nn, PR.REC)
