@@ -41,6 +41,8 @@ def fns():
 class Engine(_abi.Handle):
     """One engine per GPU: replay + sum-tree + networks + Adam state + a HIP stream."""
 
+    recurrent_device_envs = True      # dqn_envs_create / dqn_rollout / dqn_evaluate drive recurrent networks too (solver.dqn_train reads this; the CPU twin lacks it)
+
     def __init__(self, layers, hp, plan=None, device=0):
         super().__init__(fns(), layers, hp, plan=plan, device=device)
 

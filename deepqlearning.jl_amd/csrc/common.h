@@ -931,6 +931,21 @@ struct ActHeadArgs {
 bool act_head_ok(int n, int K, int S, int nA, int nstream, int N0, int N1);
 void launch_act_head(hipStream_t st, const ActHeadArgs& a);
 void launch_env_reset_pending(hipStream_t st, const EnvDev& V, const RolloutDev* rs, int force_all);
+// ---- recurrent engines: the copies' open episodes (staging [n][T]) and the committed episode ring (envs.hip, engine_envs.hip)
+struct EpStage {
+    int T; long long ep_cap;
+    float *st_s, *st_sp; int* st_a; float* st_r; unsigned char* st_done; int* open_len;      // open episodes: rows [n][T][E], a / r / done [n][T], length so far [n] (counts on past T)
+    float *ep_s, *ep_sp; int* ep_a; float* ep_r; unsigned char* ep_done; int* ep_len;         // the engine's EpisodeReplayBuffer storage
+    int* cur;                                                                                 // [0] ring cursor (ep_widx), [1] committed episodes (ep_size): the two ints behind ep_len[ep_cap - 1]
+};
+struct RecurState {      // the Recur state an acting program carries: per recurrent layer h (and c) [H][n], and where state0 sits in the online parameters
+    int nrec; int H[DQN_MAX_LAYERS]; float *h[DQN_MAX_LAYERS], *c[DQN_MAX_LAYERS]; const float *h0[DQN_MAX_LAYERS], *c0[DQN_MAX_LAYERS];
+};
+void launch_env_step_rec(hipStream_t st, const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const EpStage& ES);
+void launch_env_observe_rec(hipStream_t st, const EnvDev& V, const RolloutDev* rs, const EpStage& ES, float* x);
+void launch_ep_commit(hipStream_t st, const EnvDev& V, const EpStage& ES);
+void launch_recur_reset(hipStream_t st, const unsigned char* pending, int n, const RecurState& RS);
+void launch_state_copy(hipStream_t st, const float* src, float* dst, int m);
 
 // ---- data-parallel exchange (dp.hip)
 #define DP_MAX_REGIONS 48

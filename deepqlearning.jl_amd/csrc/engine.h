@@ -101,12 +101,15 @@ struct dqn_engine {
     float *gx_on[DQN_MAX_LAYERS] = {}, *gx_tg[DQN_MAX_LAYERS] = {}, *cst_on[DQN_MAX_LAYERS] = {}, *cst_tg[DQN_MAX_LAYERS] = {}, *gates[DQN_MAX_LAYERS] = {}, *tcb[DQN_MAX_LAYERS] = {},
           *hprev_buf[DQN_MAX_LAYERS] = {}, *cprev_buf[DQN_MAX_LAYERS] = {}, *dG[DQN_MAX_LAYERS] = {}, *dhn[DQN_MAX_LAYERS] = {}, *dcn[DQN_MAX_LAYERS] = {};
     float *pol_h[DQN_MAX_LAYERS][2] = {}, *pol_c[DQN_MAX_LAYERS][2] = {}, *pol_gx[DQN_MAX_LAYERS] = {}; int pol_flip = 0, pol_state_n = 0; uint64_t drqn_draws = 0;
+    // device environments on a recurrent engine (engine_envs.hip): the training copies' Recur state IS the policy state above (n streams, buffer set pol_flip; pol_state_gen
+    // counts its reallocations, an acting program is rebuilt when (pol_state_gen, pol_flip) moved); the evaluation copies own a private state; ep_stage: the open episodes
+    int pol_state_gen = 0; EpStage ep_stage{}; float *eval_h[DQN_MAX_LAYERS] = {}, *eval_c[DQN_MAX_LAYERS] = {}, *eval_gx[DQN_MAX_LAYERS] = {};
     // static launch program
     struct Step { const char* name; std::function<void(dqn_engine*)> fn; };
     // acting programs (forward on n columns + env kernels), one for the training envs and one for the evaluation envs
     // cycle: ONE graph of `cycle_F` acting steps (+ a plain sampled train step when cycle_train) -- the device loop's unit of work between two
     // train steps; a graph launch costs ~5 us of stream time, a GridWorld vector step 28
-    struct ActProg { std::vector<Step> steps; int n = 0; bool fused_tail = false; hipGraphExec_t graph = nullptr; std::vector<void*> allocs;
+    struct ActProg { std::vector<Step> steps; int n = 0; bool fused_tail = false; hipGraphExec_t graph = nullptr; std::vector<void*> allocs; int state_gen = -1, state_flip = -1;
                      hipGraphExec_t cycle = nullptr; int cycle_F = 0; bool cycle_train = false;
                      hipGraphExec_t envc = nullptr; int envc_due = 0; };      // envc: one vector step of the reference's cadence (the acting step + its `envc_due` pipelined train steps) as ONE graph
     ActProg act, evalp; std::vector<Step>* sink = nullptr; std::vector<void*>* alloc_sink = nullptr; RolloutDev *roll = nullptr, *eval_roll = nullptr;
@@ -175,3 +178,5 @@ const char* pname(dqn_engine* e, const char* op, int kind, int i);
 int build_program(dqn_engine* e);
 // engine_envs.hip
 void free_envs(dqn_engine* e);
+int ep_mirror_push(dqn_engine* e);      // recurrent env sets: host (ep_widx, ep_size) -> the device cursor, before a rollout
+int ep_mirror_pull(dqn_engine* e);      // ... and the device cursor and lengths -> the host mirror (ep_widx, ep_size, ep_len_host): one D2H + one synchronize

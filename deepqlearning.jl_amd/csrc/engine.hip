@@ -321,7 +321,10 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
         e->ep_cap = hp->buffer_size; e->ep_len_host.assign((size_t)e->ep_cap, 0);
         if (hp->obs_dtype != DQN_OBS_F32) return fail("DRQN episode storage is float32 only");
         DM(e->ep_s, (size_t)e->ep_cap * e->T * e->E); DM(e->ep_sp, (size_t)e->ep_cap * e->T * e->E); DM(e->ep_a, (size_t)e->ep_cap * e->T); DM(e->ep_r, (size_t)e->ep_cap * e->T);
-        DM(e->ep_done, (size_t)e->ep_cap * e->T); DM(e->ep_len, e->ep_cap); HIPCHK(hipMemset(e->ep_len, 0, (size_t)e->ep_cap * 4));
+        DM(e->ep_done, (size_t)e->ep_cap * e->T); DM(e->ep_len, e->ep_cap + 2); HIPCHK(hipMemset(e->ep_len, 0, (size_t)(e->ep_cap + 2) * 4));      // + the device-side (cursor, count) of a recurrent env set
+        // positions past an episode's stored prefix are never read by a gather; zeroed so that an export is a function of what was added
+        HIPCHK(hipMemset(e->ep_s, 0, (size_t)e->ep_cap * e->T * e->E * 4)); HIPCHK(hipMemset(e->ep_sp, 0, (size_t)e->ep_cap * e->T * e->E * 4));
+        HIPCHK(hipMemset(e->ep_a, 0, (size_t)e->ep_cap * e->T * 4)); HIPCHK(hipMemset(e->ep_r, 0, (size_t)e->ep_cap * e->T * 4)); HIPCHK(hipMemset(e->ep_done, 0, (size_t)e->ep_cap * e->T));
         DM(e->ep_idx, B); DM(e->ep_start, B); DM(e->r_a, Bc); DM(e->r_r, Bc); DM(e->r_done, Bc); DM(e->r_mask, Bc);
     }
     e->partials_elems = pmax; DM(e->partials, 2 * pmax);   // second half: the target net's split-K partials (fused on+tg launches)
@@ -1037,7 +1040,7 @@ int policy_state(dqn_engine* e, int n, bool force_reset) {
             for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(e->pol_h[i][k], (size_t)e->L[i].H * n); if (has_c) DM(e->pol_c[i][k], (size_t)e->L[i].H * n); }
             hipFree(e->pol_gx[i]); e->pol_gx[i] = nullptr; DM(e->pol_gx[i], (size_t)e->L[i].N * n);
         }
-        e->pol_state_n = n; force_reset = true;
+        e->pol_state_n = n; e->pol_state_gen++; force_reset = true;
     }
     if (force_reset) {
         for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
@@ -1096,6 +1099,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     // ... and none with a padded convolution either (conv_pad.hip)
     for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
+    if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;
     HIPCHK(hipSetDevice(e->device));
     // Recurrent engines on the fused column-parallel step (plan dw_kc = -cg, drqn_cols.hip): that step has no point at which a gradient could be exchanged.  A DEFAULTED

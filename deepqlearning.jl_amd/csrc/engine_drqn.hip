@@ -3,8 +3,11 @@
 #include "engine.h"
 
 // ---------------------------------------------------------------- DRQN: EpisodeReplayBuffer + recurrent batch_train!
+// the device env loop commits its copies' episodes at the device-side cursor; a host-side open episode would sit in the slot the next finisher takes: one collector at a time
+#define NO_ENVS(e, what) do { if ((e)->has_envs) return fail("%s: this engine collects with device environments (dqn_envs_create), which commit episodes on the device; the host-side open episode and the device copies' cannot be mixed", what); } while (0)
 extern "C" int dqn_episode_commit(dqn_engine_t* e) { if (!e) return fail("null engine handle");          // add_episode! (src/episode_replay.jl:54-60)
     NEED_REC(e); HIPCHK(hipSetDevice(e->device));
+    NO_ENVS(e, "dqn_episode_commit");
     const int len = (int)e->ep_cur_len;
     e->ep_len_host[(size_t)e->ep_widx] = len;
     HIPCHK(hipMemcpyAsync(e->ep_len + e->ep_widx, &e->ep_len_host[(size_t)e->ep_widx], 4, hipMemcpyHostToDevice, e->stream));
@@ -14,6 +17,7 @@ extern "C" int dqn_episode_commit(dqn_engine_t* e) { if (!e) return fail("null e
 }
 extern "C" int dqn_episode_add(dqn_engine_t* e, const void* s, const int32_t* a, const float* r, const void* sp, const uint8_t* done, int n) { if (!e) return fail("null engine handle");
     NEED_REC(e); HIPCHK(hipSetDevice(e->device));
+    NO_ENVS(e, "dqn_episode_add");
     const size_t row = (size_t)e->E * 4;
     for (int i = 0; i < n; i++) {                              // add_exp! (:46-52): push; the episode is stored when done
         if (a[i] < 0 || a[i] >= e->nA) return fail("action index %d out of range 0..%d", a[i], e->nA - 1);

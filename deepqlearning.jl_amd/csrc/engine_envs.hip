@@ -8,6 +8,9 @@ static void free_env_arrays(EnvDev& V) {      // the per-copy arrays of an evalu
     hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
     memset(&V, 0, sizeof V);
 }
+static void free_eval_state(dqn_engine* e) {      // the evaluation copies' private Recur state
+    for (int i = 0; i < DQN_MAX_LAYERS; i++) { hipFree(e->eval_h[i]); hipFree(e->eval_c[i]); hipFree(e->eval_gx[i]); e->eval_h[i] = e->eval_c[i] = e->eval_gx[i] = nullptr; }
+}
 void free_envs(dqn_engine* e) {
     EnvDev& V = e->env;
     hipFree(e->env_images); hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(e->roll);
@@ -15,10 +18,21 @@ void free_envs(dqn_engine* e) {
     e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false;
     free_env_arrays(e->eval_env); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
     drop_act(e, e->act); drop_act(e, e->evalp);
+    free_eval_state(e);
+    EpStage& S = e->ep_stage;      // the open episodes go with the env set; the committed ring is the engine's
+    hipFree(S.st_s); hipFree(S.st_sp); hipFree(S.st_a); hipFree(S.st_r); hipFree(S.st_done); hipFree(S.open_len); memset(&S, 0, sizeof S);
 }
 extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
-    if (e->hp.recurrence) return fail("device environments drive the feed-forward path (recurrence = false)");
+    const bool rec = e->hp.recurrence != 0;
+    if (rec) {
+        // the episode commits and the host sampler's mirror of the ring are single-device
+        if (e->comm) return fail("device environments on a recurrent engine are single-device: this engine has a communicator (dqn_comm_init)");
+        if (e->opt.sim_world >= 1) return fail("device environments on a recurrent engine are single-device: this engine was created under DQN_SIM_WORLD");
+        if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before creating device environments");
+        if (e->ep_cap > 0x7ffffff0ll) return fail("episode replay capacity %lld is too large for device environments", e->ep_cap);
+        if (sp->n_envs < 1 || sp->n_envs > 1024) return fail("n_envs must be in 1..1024");      // buffer_size counts episodes: the transition-ring capacity does not apply
+    } else
     if (sp->n_envs < 1 || sp->n_envs > std::min<long long>(1024, e->cap)) return fail("n_envs must be in 1..min(1024, replay capacity)");
     if (sp->max_episode_length < 1) return fail("max_episode_length must be >= 1");
     HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
@@ -45,6 +59,12 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
     HIPCHK(hipMemsetAsync(V.fin_eps, 0, (size_t)n * 8, e->stream)); HIPCHK(hipMemsetAsync(V.fin_reward, 0, (size_t)n * 8, e->stream));
     HIPCHK(hipMemsetAsync(V.actions, 0, (size_t)n * 4, e->stream)); HIPCHK(hipMemsetAsync(V.rewards, 0, (size_t)n * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->roll, 0, sizeof(RolloutDev) * DQN_ROLL_RECORDS, e->stream));
+    if (rec) {      // the copies' open episodes: staging [n][T] (rows of s, rows of sp, a, r, done) and the open length
+        EpStage& S = e->ep_stage; const size_t nt = (size_t)n * e->T;
+        S.T = e->T; S.ep_cap = e->ep_cap;
+        DM(S.st_s, nt * e->E); DM(S.st_sp, nt * e->E); DM(S.st_a, nt); DM(S.st_r, nt); DM(S.st_done, nt); DM(S.open_len, n);
+        S.ep_s = e->ep_s; S.ep_sp = e->ep_sp; S.ep_a = e->ep_a; S.ep_r = e->ep_r; S.ep_done = e->ep_done; S.ep_len = e->ep_len; S.cur = e->ep_len + e->ep_cap;
+    }
     e->has_envs = true;
     return dqn_envs_reset(e);
 }
@@ -52,12 +72,80 @@ extern "C" int dqn_envs_reset(dqn_engine_t* e) { if (!e) return fail("null engin
     HIPCHK(hipSetDevice(e->device));
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
     launch_env_reset_pending(e->stream, e->env, e->roll, 1);
+    if (e->hp.recurrence) {      // reset!(env) of every copy: their open episodes are dropped, resetstate!(policy) on n streams
+        HIPCHK(hipMemsetAsync(e->ep_stage.open_len, 0, (size_t)e->env.n * 4, e->stream));
+        if (policy_state(e, e->env.n, true)) return -1;
+    }
     return 0;
+}
+int ep_mirror_push(dqn_engine* e) {
+    const int cur[2] = {(int)e->ep_widx, (int)e->ep_size};
+    HIPCHK(hipMemcpyAsync(e->ep_stage.cur, cur, sizeof cur, hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));      // cur lives in this scope
+    return 0;
+}
+int ep_mirror_pull(dqn_engine* e) {
+    std::vector<int> b((size_t)e->ep_cap + 2);
+    HIPCHK(hipMemcpyAsync(b.data(), e->ep_len, b.size() * 4, hipMemcpyDeviceToHost, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));
+    for (long long i = 0; i < e->ep_cap; i++) e->ep_len_host[(size_t)i] = b[(size_t)i];
+    e->ep_widx = b[(size_t)e->ep_cap]; e->ep_size = b[(size_t)e->ep_cap + 1];
+    return 0;
+}
+// the Recur state an acting program of a recurrent engine carries: the policy state (training copies) or the evaluation set's private one
+static RecurState recur_state(dqn_engine* e, bool eval) {
+    RecurState R; memset(&R, 0, sizeof R);
+    for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
+        const int k = R.nrec++; const bool has_c = cell_ops(e->L[i].kind)->has_c;
+        R.H[k] = e->L[i].H; R.h[k] = eval ? e->eval_h[i] : e->pol_h[i][e->pol_flip]; R.c[k] = has_c ? (eval ? e->eval_c[i] : e->pol_c[i][e->pol_flip]) : nullptr;
+        R.h0[k] = e->p_on + e->L[i].h0_off; R.c0[k] = has_c ? e->p_on + e->L[i].c0_off : nullptr;
+    }
+    return R;
+}
+// the acting program of a recurrent engine: what policy_forward does on n streams (the same launchers under the same plan: the forward of a copy is, bit for bit,
+// dqn_forward on a stream reset at the same points), with the state in ONE buffer set so that the step replays as a graph -- the cell writes h_t into the layer's
+// activation and c_t over c_{t-1} (element-wise: each thread reads and writes its own element), then h_t is copied over h_{t-1}.
+//   k_recur_reset (copies whose episode ended) | layers | k_env_step_rec (Q, argmax, eps-greedy, act!, staging of a / r / done) | k_env_observe_rec | k_ep_commit, k_ep_advance
+static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs) {
+    const int n = V.n; const bool eval = V.eval_mode != 0;
+    const int gen = eval ? -2 : e->pol_state_gen, flip = eval ? 0 : e->pol_flip;
+    if (ap.n == n && ap.state_gen == gen && ap.state_flip == flip) return 0;
+    if (policy_ws(e, std::max(n, std::max(e->env.n, e->eval_n)))) return -1;
+    drop_act(e, ap);
+    e->prog_names.reserve(512);
+    const bool mf = e->hp.use_mfma != 0; const float* P = e->p_on;
+    const RecurState RS = recur_state(e, eval); const EnvDev Vc = V; const EpStage ES = e->ep_stage;
+    if (!eval) ap.steps.push_back({"recur_reset", [=](dqn_engine* en) { launch_recur_reset(en->stream, Vc.pending, n, RS); }});
+    auto fwd = [](dqn_engine* en, const LayerDev& l, const float* P, const float* X, int n, float* Y, bool mf) {      // fwd_layer without its profiling bracket (the step has its own)
+        if (is_pool(l.kind)) launch_pool_fwd(en->stream, l, X, n, 0, n, Y);
+        else if (is_padded(l)) launch_cpad_fwd(en->stream, l, P, X, n, 0, n, Y, mf ? 1 : 0, 0);
+        else if (!(mf && launch_mfma_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials))) launch_valu_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials);
+    };
+    int k = 0;
+    for (int i = 0; i < e->nl; i++) {
+        const LayerDev l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src]; float* Y = e->pol_act[i];
+        if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l.kind, i), [=](dqn_engine* en) { fwd(en, l, P, X, n, Y, mf); }}); continue; }
+        const CellOps* C = cell_ops(l.kind);
+        LayerDev Vw = l; Vw.kind = DQN_LAYER_DENSE; Vw.out_feat = l.N; Vw.b_off = l.z_off; Vw.act = DQN_ACT_IDENTITY;      // Gx = Wi*x (bias-free view)
+        float* gx = eval ? e->eval_gx[i] : e->pol_gx[i]; float* h = RS.h[k]; float* c = RS.c[k]; k++;
+        ap.steps.push_back({pname(e, "act_gx", l.kind, i), [=](dqn_engine* en) { fwd(en, Vw, P, X, n, gx, mf); }});
+        CellFwdArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.T = 1; a.nseq = 1; a.act = l.cell_act;
+        CellSeq& q = a.s[0]; q.Gx = gx; q.Hout = Y; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off; q.hprev = h; q.hp_ld = n; q.hp_bs = 1;
+        if (C->has_c) { q.Cst = c; q.cprev = c; q.cp_ld = n; q.cp_bs = 1; }
+        ap.steps.push_back({pname(e, "act_cell", l.kind, i), [=](dqn_engine* en) { C->launch_step(en->stream, a, 0); launch_state_copy(en->stream, Y, h, l.H * n); }});
+    }
+    const int lq = e->hp.dueling ? e->last_adv : e->last_base;
+    auto head_of = [&](int l) { HeadSrc h; h.p = e->pol_act[l]; h.ld = n; h.S = 1; h.per_s = 0; h.bias = P + e->L[l].b_off; h.act = e->L[l].act; return h; };
+    ActHeads Hd; memset(&Hd, 0, sizeof Hd); Hd.adv = head_of(lq); if (e->hp.dueling) Hd.val = head_of(e->last_val); Hd.dueling = e->hp.dueling; Hd.q_out = e->pol_q; Hd.amax = e->pol_a;
+    float* px = e->pol_x;
+    ap.steps.push_back({"env_step_stage", [=](dqn_engine* en) { launch_env_step_rec(en->stream, Vc, rs, Hd, ES); }});
+    ap.steps.push_back({"env_observe_stage", [=](dqn_engine* en) { launch_env_observe_rec(en->stream, Vc, rs, ES, px); }});
+    if (!eval) ap.steps.push_back({"episode_commit", [=](dqn_engine* en) { launch_ep_commit(en->stream, Vc, ES); }});
+    ap.n = n; ap.fused_tail = false; ap.state_gen = gen; ap.state_flip = flip; return 0;
 }
 // the acting program: online net forward on the n columns of pol_x (batch-innermost), then Q columns + first-max argmax
 // (action(policy, obs), src/policy.jl:38-64) -- the same tiled kernels and the same plan as the train step, compiled once per n
 static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs) {
     const int n = V.n;
+    if (e->hp.recurrence) return build_act_program_rec(e, ap, V, rs);      // act_head.hip and the GEMM grouping below stay feed-forward only
     if (ap.n == n) return 0;
     if (policy_ws(e, std::max(n, std::max(e->env.n, e->eval_n)))) return -1;      // one workspace serves both env sets (no realloc when they alternate)
     drop_act(e, ap);
@@ -197,10 +285,54 @@ static int envc_graph(dqn_engine* e, dqn_engine::ActProg& ap, int due) {
             return 0; }, &ap.envc)) return -1;
     ap.envc_due = due; return 0;
 }
+// dqn_rollout on a recurrent engine: the acting step (graph or launches), then -- when train steps are due and the ring holds a batch of episodes -- the sampled
+// recurrent step(s) with the host SplitMix sampler, whose mirror of the ring (ep_size, ep_widx, ep_len_host) is refreshed from the device before the draw.  No cycle
+// or whole-step graphs: the draw is a host decision.  The train step works on its own sequence buffers and leaves the policy's Recur state alone (src/solver.jl:137-139).
+static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) {
+    EnvDev& V = e->env; const int n = V.n;
+    if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before dqn_rollout");
+    if (e->comm) return fail("device environments on a recurrent engine are single-device: this engine has a communicator");
+    if (policy_state(e, n, false)) return -1;      // (the host ran another stream count in between: n streams again, at state0)
+    if (build_act_program(e, e->act, V, e->roll)) return -1;
+    if (cfg->train_freq > 0 && build_program(e)) return -1;
+    RolloutDev h; memset(&h, 0, sizeof h); h.t = cfg->t0 - 1; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
+    { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
+      HIPCHK(hipMemcpyAsync(e->roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); if (ep_mirror_push(e)) return -1; }
+    launch_env_observe(e->stream, V, nullptr, 0, e->pol_x);
+    const bool graph = e->hp.use_graph && !e->profiling;
+    if (graph && act_graph(e, e->act)) return -1;
+    const bool envc = cfg->cadence_env_steps != 0; const long long tf = cfg->train_freq, tu = cfg->target_update_freq;
+    long long trained = 0;
+    for (int k = 0; k < n_steps; k++) {
+        const long long t = cfg->t0 + k;
+        if (graph) HIPCHK(hipGraphLaunch(e->act.graph, e->stream));
+        else for (auto& s : e->act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
+        const long long due = tf > 0 ? (envc ? (t * n) / tf - ((t - 1) * n) / tf : (t % tf == 0 ? 1 : 0)) : 0;
+        if (due > 0) {
+            if (ep_mirror_pull(e)) return -1;
+            if (e->ep_size >= e->B) { if (envc ? drqn_train_steps(e, (int)due, nullptr, nullptr) : dqn_train_step_drqn(e, nullptr, nullptr, nullptr, nullptr)) return -1; trained += due; }
+        }
+        if (tu > 0 && (envc ? (t * n) / tu != ((t - 1) * n) / tu : t % tu == 0)) { if (dqn_sync_target(e)) return -1; }
+    }
+    launch_recur_reset(e->stream, V.pending, n, recur_state(e, false));      // resetstate!(policy) of the copies whose episode ended in the last step, then their env reset
+    launch_env_reset_pending(e->stream, V, e->roll, 0);
+    std::vector<long long> fe(n); std::vector<double> fr(n);
+    HIPCHK(hipMemcpyAsync(fe.data(), V.fin_eps, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(fr.data(), V.fin_reward, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+    if (ep_mirror_pull(e)) return -1;      // dqn_episode_export / dqn_get_counters describe the committed ring
+    if (out) {
+        out->last_loss = out->last_grad_norm = 0.0f;
+        if (trained && fetch_scalars(e, &out->last_loss, &out->last_grad_norm)) return -1;
+        out->episodes = 0; out->reward_sum = 0.0; out->train_steps = trained;
+        for (int i = 0; i < n; i++) { out->episodes += fe[i]; out->reward_sum += fr[i]; }
+    }
+    return 0;
+}
 extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
     if (cfg->t0 < 1) return fail("t0 counts from 1 (src/solver.jl:82)");
+    if (e->hp.recurrence) return rollout_rec(e, n_steps, cfg, out);
     EnvDev& V = e->env; const int n = V.n;
     if (build_act_program(e, e->act, V, e->roll)) return -1;
     if (cfg->train_freq > 0 && build_program(e)) return -1;       // may reallocate split-K workspaces: before any capture
@@ -286,7 +418,15 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
         else { DM(W.gw_pos, (size_t)n_eval * 2); DM(W.gw_prev, (size_t)n_eval * 2); }
         DM(W.actions, n_eval); DM(W.rewards, n_eval); DM(W.dones, n_eval); DM(W.pending, n_eval); DM(W.ep_reward, n_eval); DM(W.ep_step, n_eval); DM(W.fin_eps, n_eval); DM(W.fin_reward, n_eval);
         DM(e->eval_roll, DQN_ROLL_RECORDS);
+        free_eval_state(e);      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
+        for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
+            DM(e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(e->eval_gx[i], (size_t)e->L[i].N * n_eval);
+        }
         e->eval_n = n_eval;
+    }
+    for (int i = 0; i < e->nl; i++) if (e->eval_h[i]) {      // resetstate!(policy) of the evaluation: state0 of the online net on every stream
+        launch_bcast_state(e->stream, e->p_on + e->L[i].h0_off, e->L[i].H, n_eval, e->eval_h[i]);
+        if (e->eval_c[i]) launch_bcast_state(e->stream, e->p_on + e->L[i].c0_off, e->L[i].H, n_eval, e->eval_c[i]);
     }
     if (W.seed != seed || W.max_episode_length != max_episode_length) { W.seed = seed; W.max_episode_length = max_episode_length; drop_act(e, e->evalp); }   // baked into the program
     if (build_act_program(e, e->evalp, W, e->eval_roll)) return -1;

@@ -126,10 +126,12 @@ __device__ __forceinline__ void env_tree_rebuild(const ReplayMeta& R, const int 
 //   src/dueling.jl:13-16) and its first-max argmax = action(policy, obs) (src/policy.jl:38-64);
 //   eps-greedy (POMDPTools EpsGreedyPolicy: rand(rng) < eps ? rand(rng, actions) : greedy), act! (:89): transition, reward, terminal;
 //   add_exp!(replay, exp, abs(exp.r)) (:91-94): metadata + leaf priority, then the sum-tree ancestors of the written leaves.
-__global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, ActHeads Hd, ReplayMeta R) {
+// REC (recurrent engines, envs_drqn below): add_exp! goes to the copy's open-episode staging area instead of the prioritized ring -- no ring row, no leaf, no tree
+template <bool REC>
+__device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const ReplayMeta& R, const EpStage* ES) {
     const int n = V.n;
     const unsigned long long t_prev = (unsigned long long)rs->t, t = t_prev + 1;
-    const long long start = (rs->widx + n) % R.cap;
+    const long long start = REC ? 0 : (rs->widx + n) % R.cap;
     float eps = rs->eps_start - (float)t * ((rs->eps_start - rs->eps_stop) / rs->eps_steps);     // LinearDecaySchedule, fp32
     if (!(rs->eps_steps > 0.0f) || eps < rs->eps_stop) eps = rs->eps_stop;
     // head outputs of the acting forward -> LDS in one round of independent loads (split-K slabs included); the per-env
@@ -237,6 +239,12 @@ __global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, Act
             V.fin_reward[i] += (double)r; V.pending[i] = (done || V.ep_step[i] > V.max_episode_length) ? 1 : 0; continue;
         }
         V.pending[i] = (done || V.ep_step[i] >= V.max_episode_length) ? 1 : 0;
+        if (REC) {      // push!(r._episode, exp) (src/episode_replay.jl:46-52): only the first trace_length transitions can ever be sampled (:82-92); the length counts on
+            const int pos = ES->open_len[i];
+            if (pos < ES->T) { const size_t q = (size_t)i * ES->T + pos; ES->st_a[q] = a; ES->st_r[q] = r; ES->st_done[q] = done ? 1 : 0; }
+            ES->open_len[i] = pos + 1;
+            continue;
+        }
         const long long slot = (start + i) % R.cap;
         R.a[slot] = a; R.r[slot] = r; R.done[slot] = done ? 1 : 0;
         const float td = V.prioritized ? fabsf(r) : 0.0f;                     // add_exp!(replay, exp, abs(exp.r)) / 0f0, src/solver.jl:91-94
@@ -244,11 +252,16 @@ __global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, Act
         const float pr = prio_f(td, R.eps, R.alpha);
         R.tree[R.cap2 + slot] = pr; lvl[0][i] = pr;
     }
-    if (V.eval_mode) return;                                    // no add_exp! (uniform branch: eval_mode is a kernel argument)
+    if (V.eval_mode || REC) return;                             // no add_exp! into the ring (uniform branch: eval_mode is a kernel argument)
     env_tree_rebuild(R, n, start, lvl, rim);
 }
+__global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, ActHeads Hd, ReplayMeta R) { env_step_body<false>(V, rs, Hd, R, nullptr); }
+__global__ __launch_bounds__(1024) void k_env_step_rec(EnvDev V, RolloutDev* rs, ActHeads Hd, EpStage ES) { ReplayMeta R; R.cap = 1; R.cap2 = 1; R.a = nullptr; R.r = nullptr; R.done = nullptr; R.tree = nullptr; R.state = nullptr; R.eps = 0.0f; R.alpha = 0.0f; env_step_body<true>(V, rs, Hd, R, &ES); }
 void launch_env_step(hipStream_t st, const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const ReplayMeta& R) {
     hipLaunchKernelGGL(k_env_step, dim3(1), dim3(1024), 0, st, V, rs, Hd, R);
+}
+void launch_env_step_rec(hipStream_t st, const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const EpStage& ES) {
+    hipLaunchKernelGGL(k_env_step_rec, dim3(1), dim3(1024), 0, st, V, rs, Hd, ES);
 }
 
 // after k_env_step: the transition's rows go straight into the ring -- s = observation of the saved pre-step state, sp = observe(env)
@@ -346,4 +359,106 @@ __global__ void k_env_reset_pending(EnvDev V, const RolloutDev* rs, int force_al
 }
 void launch_env_reset_pending(hipStream_t st, const EnvDev& V, const RolloutDev* rs, int force_all) {
     hipLaunchKernelGGL(k_env_reset_pending, dim3((V.n + 255) / 256), dim3(256), 0, st, V, rs, force_all);
+}
+
+// ---------------------------------------------------------------- recurrent engines (DRQN): per-copy resetstate!, add_exp! into the episode replay
+// One vector step of a recurrent engine is: k_recur_reset  [Gx = Wi*x, cell step, k_state_copy per recurrent layer; the other layers' forwards]  k_env_step_rec
+// k_env_observe_rec  k_ep_commit  k_ep_advance -- fixed device pointers throughout, the Recur state lives in ONE buffer set, so the step replays as a hipGraph.
+
+// resetstate!(policy) (src/policy.jl:32-34) for the copies whose episode ended in the previous step (pending: done, or ep_step >= max_episode_length): their state
+// columns become state0 of the ONLINE net as it is now (h0 / c0 are trainable); the other copies' columns are untouched
+__global__ void k_recur_reset(const unsigned char* __restrict__ pending, int n, RecurState RS) {
+    for (int l = 0; l < RS.nrec; l++) {
+        const int H = RS.H[l];
+        for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < H * n; q += gridDim.x * blockDim.x) {
+            const int u = q / n, i = q - u * n;
+            if (!pending[i]) continue;
+            RS.h[l][q] = RS.h0[l][u];
+            if (RS.c[l]) RS.c[l][q] = RS.c0[l][u];
+        }
+    }
+}
+void launch_recur_reset(hipStream_t st, const unsigned char* pending, int n, const RecurState& RS) {
+    int hmax = 1; for (int l = 0; l < RS.nrec; l++) hmax = RS.H[l] > hmax ? RS.H[l] : hmax;
+    unsigned blocks = (unsigned)(((size_t)hmax * n + 255) / 256); if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_recur_reset, dim3(blocks), dim3(256), 0, st, pending, n, RS);
+}
+// h_t of the cell step (the layer's activation, which every thread of the step read h_{t-1} beside) becomes the carried state
+__global__ void k_state_copy(const float* __restrict__ src, float* __restrict__ dst, int m) {
+    for (int q = blockIdx.x * blockDim.x + threadIdx.x; q < m; q += gridDim.x * blockDim.x) dst[q] = src[q];
+}
+void launch_state_copy(hipStream_t st, const float* src, float* dst, int m) {
+    unsigned blocks = (unsigned)((m + 255) / 256); if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(k_state_copy, dim3(blocks), dim3(256), 0, st, src, dst, m);
+}
+
+// after k_env_step_rec: the transition's rows -- s = observation of the saved pre-step state, sp = observe(env) -- go to staging position open_len[i] - 1 of copy i
+// (while it is < trace_length), and the NEXT step's observation (of the reset state if the episode just ended) becomes the policy input x[E][n]
+__global__ __launch_bounds__(256) void k_env_observe_rec(EnvDev V, const RolloutDev* __restrict__ rs, EpStage ES, float* __restrict__ x) {
+    const size_t tot = (size_t)V.n * V.E, rows = V.eval_mode ? 0 : tot;
+    for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < rows + tot; q += (size_t)gridDim.x * blockDim.x) {
+        unsigned char b;
+        if (q < rows) {
+            const int i = (int)(q / V.E), f = (int)(q - (size_t)i * V.E);      // f fastest: coalesced rows
+            const int pos = ES.open_len[i] - 1;
+            if (pos < 0 || pos >= ES.T) continue;
+            uint32_t sw0 = 0x01010101u, sw1; int p0x = 0, p0y = 0, p1x, p1y;
+            load_state(V, i, &sw1, &p1x, &p1y);
+            if (V.kind == DQN_ENV_TESTMDP) sw0 = *(const uint32_t*)(V.tm_prev + i * 4); else { p0x = V.gw_prev[i * 2]; p0y = V.gw_prev[i * 2 + 1]; }
+            const size_t dst = ((size_t)i * ES.T + pos) * V.E + f;
+            ES.st_s[dst] = obs_elem(V, sw0, p0x, p0y, f, &b);
+            ES.st_sp[dst] = obs_elem(V, sw1, p1x, p1y, f, &b);
+        } else {
+            const size_t p = q - rows; const int f = (int)(p / V.n), i = (int)(p - (size_t)f * V.n);      // i fastest
+            uint32_t sw; int px, py, tm = 0; load_state(V, i, &sw, &px, &py);
+            if (V.pending[i] && !V.eval_mode) reset_state(V, i, (unsigned long long)rs->t, &sw, &tm, &px, &py);
+            x[p] = obs_elem(V, sw, px, py, f, &b);
+        }
+    }
+}
+void launch_env_observe_rec(hipStream_t st, const EnvDev& V, const RolloutDev* rs, const EpStage& ES, float* x) {
+    const size_t tot = (size_t)V.n * V.E * (V.eval_mode ? 1 : 2); unsigned blocks = (unsigned)((tot + 255) / 256); if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_env_observe_rec, dim3(blocks), dim3(256), 0, st, V, rs, ES, x);
+}
+
+// add_episode! (src/episode_replay.jl:54-60) for the copies whose transition of this step was terminal.  Workgroup i = copy i; k = the rank of copy i among this step's
+// finishers in ascending copy index, F = their number: the staged prefix goes to ring slot (ep_widx + k) % ep_cap with the episode's TRUE length.  (More finishers than
+// slots: only the last ep_cap of them are written, as if committed one after the other.)  The cursor is read here and advanced by k_ep_advance, the next launch.
+__global__ __launch_bounds__(256) void k_ep_commit(EnvDev V, EpStage ES) {
+    const int i = blockIdx.x, n = V.n;
+    if (!V.dones[i]) return;                                    // uniform per workgroup
+    __shared__ int cnt[2];
+    if (threadIdx.x < 2) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    int before = 0, all = 0;
+    for (int j = threadIdx.x; j < n; j += blockDim.x) if (V.dones[j]) { all++; if (j < i) before++; }
+    if (before) atomicAdd(&cnt[0], before);
+    if (all) atomicAdd(&cnt[1], all);
+    __syncthreads();
+    const int k = cnt[0], F = cnt[1];
+    if ((long long)(F - k) > ES.ep_cap) return;                 // a later finisher of this step takes the slot
+    const long long slot = ((long long)ES.cur[0] + k) % ES.ep_cap;
+    const int len = ES.open_len[i], m = len < ES.T ? len : ES.T;
+    const size_t src = (size_t)i * ES.T, dst = (size_t)slot * ES.T, ne = (size_t)m * V.E;
+    for (size_t q = threadIdx.x; q < ne; q += blockDim.x) { ES.ep_s[dst * V.E + q] = ES.st_s[src * V.E + q]; ES.ep_sp[dst * V.E + q] = ES.st_sp[src * V.E + q]; }
+    for (int q = threadIdx.x; q < m; q += blockDim.x) { ES.ep_a[dst + q] = ES.st_a[src + q]; ES.ep_r[dst + q] = ES.st_r[src + q]; ES.ep_done[dst + q] = ES.st_done[src + q]; }
+    if (threadIdx.x == 0) ES.ep_len[slot] = len;
+}
+// one workgroup: the finishers' open episodes are empty again; cursor and count advance by the number of finishers
+__global__ __launch_bounds__(1024) void k_ep_advance(EnvDev V, EpStage ES) {
+    __shared__ int cnt;
+    if (threadIdx.x == 0) cnt = 0;
+    __syncthreads();
+    int mine = 0;
+    for (int i = threadIdx.x; i < V.n; i += blockDim.x) if (V.dones[i]) { ES.open_len[i] = 0; mine++; }
+    if (mine) atomicAdd(&cnt, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && cnt) {
+        ES.cur[0] = (int)(((long long)ES.cur[0] + cnt) % ES.ep_cap);
+        const long long s = (long long)ES.cur[1] + cnt; ES.cur[1] = (int)(s > ES.ep_cap ? ES.ep_cap : s);
+    }
+}
+void launch_ep_commit(hipStream_t st, const EnvDev& V, const EpStage& ES) {
+    hipLaunchKernelGGL(k_ep_commit, dim3(V.n), dim3(256), 0, st, V, ES);
+    hipLaunchKernelGGL(k_ep_advance, dim3(1), dim3(1024), 0, st, V, ES);
 }

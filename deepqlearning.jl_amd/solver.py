@@ -289,7 +289,8 @@ def initialize_replay_buffer(solver, env, engine):
     """src/solver.jl:180-189: buffer defaults alpha=0.6 beta=0.4 eps=1e-3 are used whatever the solver says."""
     if solver.recurrence:
         replay = HIPEpisodeReplayBuffer(engine)                      # EpisodeReplayBuffer(env, buffer_size, batch_size, trace_length), :183
-        populate_episode_replay(replay, env, max_pop=solver.train_start, rng=solver.rng)
+        if not (solver.device_envs and getattr(engine, "recurrent_device_envs", False)):      # the device loop prefills itself (populate_episode_replay_device)
+            populate_episode_replay(replay, env, max_pop=solver.train_start, rng=solver.rng)
         return replay
     replay = HIPReplayBuffer(engine)
     populate_replay_buffer(replay, env, max_pop=solver.train_start, rng=solver.rng)
@@ -357,6 +358,23 @@ def restore_best_model(solver, policy):
     return policy
 
 
+def populate_episode_replay_device(solver, env, engine):
+    """The device loop's analogue of populate_replay_buffer! for a recurrent engine: random rollouts (eps = 1, no training) of the env.n copies until at least
+    train_start env steps are taken AND batch_size episodes are committed, under a seed derived from the solver's."""
+    n = env.n
+    engine.envs_create(env, n_envs=n, max_episode_length=solver.max_episode_length, seed=(solver.seed * 0x9E3779B97F4A7C15 + 0x5DEECE66D) % 2 ** 64)
+    chunk = max(1, -(-solver.train_start // n))                  # vector steps that make train_start env steps
+    t = 1
+    while True:
+        engine.rollout(chunk, t0=t, train_freq=0, target_update_freq=0, eps=(1.0, 1.0, 1.0), stats=False)
+        t += chunk
+        if (t - 1) * n >= solver.train_start and engine.episode_count()[0] >= solver.batch_size:
+            return
+        if t - 1 >= 100 * chunk:
+            raise DQNError(f"device prefill: {engine.episode_count()[0]} episodes ended in {(t - 1) * n} random env steps, batch_size = {solver.batch_size} are needed "
+                           "(episodes enter the replay when they reach a terminal state: raise train_start, or lower batch_size)")
+
+
 def dqn_train_device(solver, env, policy, replay):
     """dqn_train! (src/solver.jl:59-178) with the env loop on the device: `env` is only the SPEC (images, grid, rewards) of the
     env.n copies that dqn_envs_create builds in HBM; exploration uses the engine's Philox eps-greedy with the solver's
@@ -370,6 +388,8 @@ def dqn_train_device(solver, env, policy, replay):
     else:
         v = float(solver.exploration_policy.eps(1))
         eps = (v, v, 1.0)
+    if solver.recurrence:
+        populate_episode_replay_device(solver, env, e)      # then the env set is created again under the solver's seed; committed episodes stay
     e.envs_create(env, n_envs=env.n, max_episode_length=solver.max_episode_length, seed=solver.seed)
     saved_mean_reward, scores_eval, model_saved = -np.inf, -np.inf, False
     marks = sorted({solver.eval_freq, solver.log_freq, solver.save_freq})
@@ -405,7 +425,7 @@ def dqn_train_device(solver, env, policy, replay):
 def dqn_train(solver, env, policy, replay):
     """src/solver.jl:59-178.  `env` holds env.n lock-stepped copies (the reference: 1); t counts vector steps."""
     if solver.device_envs:
-        if solver.recurrence:
+        if solver.recurrence and not getattr(policy.engine, "recurrent_device_envs", False):      # the engine says whether its env loop drives recurrent networks
             raise DQNError("device_envs drives the feed-forward path (recurrence = false)")
         return dqn_train_device(solver, env, policy, replay)
     e = policy.engine

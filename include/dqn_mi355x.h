@@ -226,7 +226,30 @@ int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32_t* a_out /
  * rand < eps ? random action : greedy), act!, observe, add_exp!(replay, exp, |r|) straight into the replay ring, episode
  * bookkeeping (reset on done or max_episode_length), every train_freq vector steps one batch_train!, every
  * target_update_freq a target sync.  No observation crosses PCIe.  Randomness: Philox4x32-10 keyed by seed, counter =
- * (global vector step, env, purpose), so the CPU twin reproduces every trajectory bit for bit. */
+ * (global vector step, env, purpose), so the CPU twin reproduces every trajectory bit for bit.
+ *
+ * RECURRENT engines (hparams.recurrence = 1; single device: refused on an engine with a communicator or under DQN_SIM_WORLD, and dqn_comm_init is refused once
+ * such an env set exists).  1 <= n_envs <= 1024; buffer_size counts episodes, the transition-ring capacity does not apply.
+ *  - Policy state.  The training copies' Recur state IS the engine's policy state with n_envs streams: dqn_get_hidden (streams = n_envs) reads it, dqn_set_hidden
+ *    writes it, dqn_reset_state resets it -- resetstate!(policy) acts on the one policy.  The evaluation copies own a private state of n_eval streams.
+ *  - State advance.  every vector step advances every copy's state, exploring or not (this project's host loop also computes the greedy action on every step;
+ *    what POMDPTools' EpsGreedyPolicy does to a recurrent policy on the exploring branch is third-party: recalled, not executed here).
+ *  - resetstate! per copy.  A copy whose episode ended (done, or max_episode_length steps) gets, before the first recurrent layer of its next acting step, state0
+ *    of the ONLINE net as it is then (h0 / c0 are trainable); other copies' columns are untouched.  The acting forward of a copy equals, bit for bit,
+ *    dqn_forward on a stream that was reset at the same points and fed the same observations.
+ *  - add_exp!.  Nothing is written to the prioritized ring or the sum-tree.  Each copy has an open episode; a transition is kept only while the open length is below
+ *    trace_length (the prefix is all a sample can read), the length counts on.  Truncation at max_episode_length resets the env and the Recur state but does NOT
+ *    close the open episode (the reference stores an episode only on done, src/episode_replay.jl:46-52; dqn_episode_add behaves the same).  On done the
+ *    staged prefix, with the episode's true length, is committed to ring slot (ep_widx + k) % capacity, where k is the rank of the copy among the copies that
+ *    finished in this vector step in ascending copy index; cursor and count advance by the number of finishers.  (The reference has one copy: the order among
+ *    copies is this project's definition.)  dqn_envs_create on an engine that has an env set discards the open episodes and keeps the committed ones.
+ *  - One collector at a time.  dqn_envs_create and dqn_rollout are refused while the host-side open episode (dqn_episode_add) is non-empty; dqn_episode_add and
+ *    dqn_episode_commit are refused on an engine that has an env set.
+ *  - Training.  Where a train step is due and the ring holds batch_size episodes, dqn_rollout runs the sampled recurrent step (dqn_train_step_drqn with NULL
+ *    draws: the same host sampler, the same draw counter), after refreshing the host's view of the ring from the device.  The train step leaves the policy's
+ *    Recur state as it found it (src/solver.jl:137-139).  dqn_episode_export / dqn_get_counters after a rollout describe the committed ring; open episodes
+ *    are not part of a checkpoint.
+ *  - dqn_evaluate leaves the training copies, the policy state, the ring, the open episodes and the counters exactly as they were. */
 enum { DQN_ENV_TESTMDP = 0, DQN_ENV_GRIDWORLD = 1 };
 typedef struct {
     int32_t kind;               /* DQN_ENV_* */
