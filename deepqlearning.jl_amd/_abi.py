@@ -11,6 +11,8 @@ import ctypes as C
 
 import numpy as np
 
+from . import envs
+
 LAYER_DENSE, LAYER_CONV, LAYER_LSTM, LAYER_GRU, LAYER_RNN = 0, 1, 2, 3, 4
 LAYER_MAXPOOL, LAYER_MEANPOOL = 5, 6      # parameter-free: Flux.params skips them
 ACT_IDENTITY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
@@ -78,6 +80,12 @@ class EnvSpec(C.Structure):
                 ("reward_xy", (C.c_int32 * 2) * 8), ("reward_val", C.c_float * 8)]
 
 
+class TabularEnv(C.Structure):
+    """dqn_tabular_env (include/dqn_mi355x.h): a discrete MDP / POMDP as its matrices."""
+    _fields_ = [("n_envs", C.c_int32), ("max_episode_length", C.c_int32), ("seed", C.c_uint64), ("n_states", C.c_int32), ("n_obs", C.c_int32),
+                ("T", C.c_void_p), ("Z", C.c_void_p), ("Z0", C.c_void_p), ("R", C.c_void_p), ("terminal", C.c_void_p), ("b0", C.c_void_p), ("features", C.c_void_p)]
+
+
 class RolloutCfg(C.Structure):
     _fields_ = [("train_freq", C.c_int32), ("target_update_freq", C.c_int32),
                 ("eps_start", C.c_float), ("eps_stop", C.c_float), ("eps_steps", C.c_float), ("cadence_env_steps", C.c_int32), ("t0", C.c_int64)]
@@ -92,7 +100,7 @@ class Counters(C.Structure):
     _fields_ = [("size", C.c_int64), ("widx", C.c_int64), ("sample_ctr", C.c_uint64), ("train_steps", C.c_uint64)]
 
 
-ENV_TESTMDP, ENV_GRIDWORLD = 0, 1
+ENV_TESTMDP, ENV_GRIDWORLD, ENV_TABULAR = 0, 1, 2
 
 _P = C.POINTER
 _f32p, _i32p, _i64p, _u8p, _f64p = _P(C.c_float), _P(C.c_int32), _P(C.c_int64), _P(C.c_uint8), _P(C.c_double)
@@ -151,6 +159,7 @@ PROTOS = {
     "get_hidden": [_vp, _f32p, _sz],
     "set_hidden": [_vp, _f32p, _sz],
     "envs_create": [_vp, _P(EnvSpec)],
+    "envs_create_tabular": [_vp, _P(TabularEnv)],
     "envs_reset": [_vp],
     "rollout": [_vp, C.c_int, _P(RolloutCfg), _P(RolloutStats)],
     "envs_peek": [_vp, _f32p, _i32p, _f32p, _u8p],
@@ -457,7 +466,10 @@ class Handle:
 
     # ---- vectorised environments on the device
     def envs_create(self, env, n_envs=None, max_episode_length=100, seed=0):
-        """`env` is an envs.TestMDP / envs.SimpleGridWorld instance used as the SPEC (images, sizes, rewards); its own state is not used."""
+        """`env` is an envs.TestMDP / envs.SimpleGridWorld / envs.TabularPOMDP instance used as the SPEC (images, sizes, rewards, tables); its own state is not used."""
+        if envs.is_tabular(env):
+            return self.envs_create_tabular(env.T, env.R, env.terminal, env.b0, env.features, Z=env.Z, Z0=env.Z0,
+                                            n_envs=n_envs if n_envs is not None else env.n, max_episode_length=max_episode_length, seed=seed)
         sp = EnvSpec()
         sp.n_envs = int(n_envs if n_envs is not None else env.n)
         sp.max_episode_length, sp.seed = int(max_episode_length), int(seed)
@@ -471,6 +483,21 @@ class Handle:
             for k, ((x, y), v) in enumerate(env.reward_cells.items()):
                 sp.reward_xy[k][0], sp.reward_xy[k][1], sp.reward_val[k] = x, y, v
         self._check(self.f["envs_create"](self._h, C.byref(sp)))
+        self.n_envs = sp.n_envs
+
+    def envs_create_tabular(self, T, R, terminal, b0, features, Z=None, Z0=None, n_envs=1, max_episode_length=100, seed=0, n_states=None, n_obs=None):
+        """dqn_envs_create_tabular: the tables are copied by the call.  n_states / n_obs default to what the shapes of T and Z say."""
+        if "envs_create_tabular" not in self.f:
+            raise DQNError("this library does not export envs_create_tabular")
+        arrs = dict(T=_as(T, np.float32), Z=_as(Z, np.float32), Z0=_as(Z0, np.float32), R=_as(R, np.float32), terminal=_as(terminal, np.uint8),
+                    b0=_as(b0, np.float32), features=_as(features, np.float32))
+        sp = TabularEnv()
+        sp.n_envs, sp.max_episode_length, sp.seed = int(n_envs), int(max_episode_length), int(seed)
+        sp.n_states = int(n_states if n_states is not None else (arrs["T"].shape[0] if arrs["T"] is not None else 0))
+        sp.n_obs = int(n_obs if n_obs is not None else (arrs["Z"].shape[-1] if arrs["Z"] is not None else 0))
+        for k, a in arrs.items():
+            setattr(sp, k, None if a is None else a.ctypes.data)
+        self._check(self.f["envs_create_tabular"](self._h, C.byref(sp)))
         self.n_envs = sp.n_envs
 
     def envs_reset(self):

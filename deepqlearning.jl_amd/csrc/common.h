@@ -908,6 +908,9 @@ struct EnvDev {
     int *gw_pos, *gw_prev; int size_x, size_y, n_reward; float tprob; int reward_xy[8][2]; float reward_val[8];
     // per-env loop state / outputs
     int* actions; float* rewards; unsigned char* dones; unsigned char* pending; float* ep_reward; int* ep_step; long long* fin_eps; double* fin_reward;
+    // tabular (PO)MDP (DQN_ENV_TABULAR): tb_T / tb_Z / tb_Z0 / tb_b0 hold CUMULATIVE rows (built on the host at creation); tb_O == 0: an MDP, the observation
+    // index is the state index.  Per copy: state, observation index, observation index before the step
+    int tb_S, tb_O; const float *tb_T, *tb_Z, *tb_Z0, *tb_R, *tb_b0, *tb_feat; const unsigned char* tb_term; int *tb_s, *tb_o, *tb_oprev;
 };
 struct RolloutDev { long long t, widx; float eps_start, eps_stop, eps_steps; int pad; };     // t, widx: values of the LAST completed vector step
 struct ReplayMeta { long long cap, cap2; int* a; float* r; unsigned char* done; float* tree; StepState* state; float eps, alpha; };

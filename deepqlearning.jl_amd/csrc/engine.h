@@ -79,6 +79,7 @@ struct dqn_engine {
     float *gb_r2 = nullptr, *gb_done2 = nullptr, *gb_w2 = nullptr; int* gb_a2 = nullptr;
     // policy workspace
     EnvDev env{}; bool has_envs = false; unsigned char* env_images = nullptr;
+    float* env_tab = nullptr; unsigned char* env_term = nullptr;      // a tabular env set's tables (cumulative rows, rewards, feature rows) and terminal flags
     int pol_n = 0; float *pol_obs = nullptr, *pol_x = nullptr, *pol_act[DQN_MAX_LAYERS] = {}, *pol_q = nullptr; int* pol_a = nullptr;
     // the train-step graphs, one per StepKey in use (linear lookup: a handful of entries); with a communicator the step is cut in two around the exchange
     struct StepGraph { StepKey key; hipGraphExec_t g; }; std::vector<StepGraph> graphs;

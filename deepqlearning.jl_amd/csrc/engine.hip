@@ -1099,6 +1099,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     // ... and none with a padded convolution either (conv_pad.hip)
     for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
+    if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;
     HIPCHK(hipSetDevice(e->device));

@@ -1,10 +1,11 @@
 // engine_envs.hip -- C ABI of the device-resident environments: dqn_envs_create / dqn_rollout / dqn_evaluate /
 // dqn_envs_peek; kernels in envs.hip.
+#include <cmath>
 #include "engine.h"
 
 // ---------------------------------------------------------------- vectorised environments on the device
 static void free_env_arrays(EnvDev& V) {      // the per-copy arrays of an evaluation env set (images and spec are shared with the training set)
-    hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev);
+    hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(V.tb_s); hipFree(V.tb_o); hipFree(V.tb_oprev);
     hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
     memset(&V, 0, sizeof V);
 }
@@ -14,6 +15,7 @@ static void free_eval_state(dqn_engine* e) {      // the evaluation copies' priv
 void free_envs(dqn_engine* e) {
     EnvDev& V = e->env;
     hipFree(e->env_images); hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(e->roll);
+    hipFree(e->env_tab); hipFree(e->env_term); hipFree(V.tb_s); hipFree(V.tb_o); hipFree(V.tb_oprev); e->env_tab = nullptr; e->env_term = nullptr;
     hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
     e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false;
     free_env_arrays(e->eval_env); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
@@ -22,8 +24,8 @@ void free_envs(dqn_engine* e) {
     EpStage& S = e->ep_stage;      // the open episodes go with the env set; the committed ring is the engine's
     hipFree(S.st_s); hipFree(S.st_sp); hipFree(S.st_a); hipFree(S.st_r); hipFree(S.st_done); hipFree(S.open_len); memset(&S, 0, sizeof S);
 }
-extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e) return fail("null engine handle");
-    HIPCHK(hipSetDevice(e->device));
+// what every kind of env set checks before it replaces the engine's current one
+static int envs_admit(dqn_engine* e, int n_envs, int max_episode_length) {
     const bool rec = e->hp.recurrence != 0;
     if (rec) {
         // the episode commits and the host sampler's mirror of the ring are single-device
@@ -31,10 +33,16 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
         if (e->opt.sim_world >= 1) return fail("device environments on a recurrent engine are single-device: this engine was created under DQN_SIM_WORLD");
         if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before creating device environments");
         if (e->ep_cap > 0x7ffffff0ll) return fail("episode replay capacity %lld is too large for device environments", e->ep_cap);
-        if (sp->n_envs < 1 || sp->n_envs > 1024) return fail("n_envs must be in 1..1024");      // buffer_size counts episodes: the transition-ring capacity does not apply
+        if (n_envs < 1 || n_envs > 1024) return fail("n_envs must be in 1..1024");      // buffer_size counts episodes: the transition-ring capacity does not apply
     } else
-    if (sp->n_envs < 1 || sp->n_envs > std::min<long long>(1024, e->cap)) return fail("n_envs must be in 1..min(1024, replay capacity)");
-    if (sp->max_episode_length < 1) return fail("max_episode_length must be >= 1");
+    if (n_envs < 1 || n_envs > std::min<long long>(1024, e->cap)) return fail("n_envs must be in 1..min(1024, replay capacity)");
+    if (max_episode_length < 1) return fail("max_episode_length must be >= 1");
+    return 0;
+}
+static int envs_finish(dqn_engine* e);
+extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e) return fail("null engine handle");
+    HIPCHK(hipSetDevice(e->device));
+    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
     HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
     EnvDev& V = e->env; const int n = sp->n_envs;
     V.kind = sp->kind; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
@@ -55,6 +63,11 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
         for (int k = 0; k < V.n_reward; k++) { V.reward_xy[k][0] = sp->reward_xy[k][0]; V.reward_xy[k][1] = sp->reward_xy[k][1]; V.reward_val[k] = sp->reward_val[k]; }
         DM(V.gw_pos, (size_t)n * 2); DM(V.gw_prev, (size_t)n * 2);
     } else return fail("unknown environment kind %d", sp->kind);
+    return envs_finish(e);
+}
+// the per-copy loop state every kind shares, the open episodes of a recurrent engine, and the first reset
+static int envs_finish(dqn_engine* e) {
+    EnvDev& V = e->env; const int n = V.n; const bool rec = e->hp.recurrence != 0;
     DM(V.actions, n); DM(V.rewards, n); DM(V.dones, n); DM(V.pending, n); DM(V.ep_reward, n); DM(V.ep_step, n); DM(V.fin_eps, n); DM(V.fin_reward, n); DM(e->roll, DQN_ROLL_RECORDS);
     HIPCHK(hipMemsetAsync(V.fin_eps, 0, (size_t)n * 8, e->stream)); HIPCHK(hipMemsetAsync(V.fin_reward, 0, (size_t)n * 8, e->stream));
     HIPCHK(hipMemsetAsync(V.actions, 0, (size_t)n * 4, e->stream)); HIPCHK(hipMemsetAsync(V.rewards, 0, (size_t)n * 4, e->stream));
@@ -67,6 +80,66 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
     }
     e->has_envs = true;
     return dqn_envs_reset(e);
+}
+// a tabular (PO)MDP from its matrices (the law: include/dqn_mi355x.h).  Everything is validated before the engine's current env set is touched.
+extern "C" int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* sp) { if (!e) return fail("null engine handle");
+    if (!sp) return fail("null tabular spec");
+    HIPCHK(hipSetDevice(e->device));
+    const long long S = sp->n_states, O = sp->n_obs, A = e->nA, E = e->E, NO = O ? O : S;
+    if (S < 1 || S > 1024) return fail("tabular env: n_states = %d must be in 1..1024", sp->n_states);
+    if (O < 0 || O > 1024) return fail("tabular env: n_obs = %d must be in 0..1024 (0: an MDP)", sp->n_obs);
+    if (e->hp.obs_dtype == DQN_OBS_U8) return fail("tabular env: the feature rows are floats, this engine stores observations as u8: use obs_dtype f32");
+    if (e->comm) return fail("tabular env: device environments from tables are single-device: this engine has a communicator (dqn_comm_init)");
+    if (e->opt.sim_world >= 1) return fail("tabular env: device environments from tables are single-device: this engine was created under DQN_SIM_WORLD");
+    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
+    if (!sp->T) return fail("tabular env: T (transition table [S][A][S]) is NULL");
+    if (!sp->R) return fail("tabular env: R (reward table [S][A][S]) is NULL");
+    if (!sp->terminal) return fail("tabular env: terminal ([S]) is NULL");
+    if (!sp->b0) return fail("tabular env: b0 (initial-state distribution [S]) is NULL");
+    if (!sp->features) return fail("tabular env: features ([%lld][%lld]) is NULL", NO, E);
+    if (O > 0 && !sp->Z) return fail("tabular env: Z (observation table [A][S][O]) is NULL with n_obs = %d", sp->n_obs);
+    if (O > 0 && !sp->Z0) return fail("tabular env: Z0 (initial observation table [S][O]) is NULL with n_obs = %d", sp->n_obs);
+    if (O == 0 && sp->Z) return fail("tabular env: Z is given with n_obs = 0 (an MDP observes its state)");
+    if (O == 0 && sp->Z0) return fail("tabular env: Z0 is given with n_obs = 0 (an MDP observes its state)");
+    // one float block: cumulative T | R | cumulative Z | cumulative Z0 | cumulative b0 | features, each part 16-byte aligned
+    auto up4 = [](size_t x) { return (x + 3) & ~(size_t)3; };
+    const size_t nT = (size_t)(S * A * S), nZ = (size_t)(A * S * O), nZ0 = (size_t)(S * O), nF = (size_t)(NO * E);
+    const size_t oT = 0, oR = up4(oT + nT), oZ = up4(oR + nT), oZ0 = up4(oZ + nZ), oB = up4(oZ0 + nZ0), oF = up4(oB + (size_t)S), tot = up4(oF + nF);
+    std::vector<float> h(tot, 0.0f);
+    // rows of `len` probabilities -> cumulative rows by a plain fp32 loop in ascending index order.  `rank` is the table's own ([S][A][S]: 3, [S][O]: 2, [S]: 1), so a
+    // message names a value by the caller's indices: row r of a rank-3 table is [r / d1][r % d1]
+    auto rows = [&](const char* name, const float* p, int rank, long long nrows, long long d1, long long len, bool exempt_terminal, float* out) -> int {
+        char at[64];
+        for (long long r = 0; r < nrows; r++) {
+            if (rank == 3) snprintf(at, sizeof at, "%s[%lld][%lld]", name, r / d1, r % d1); else if (rank == 2) snprintf(at, sizeof at, "%s[%lld]", name, r); else snprintf(at, sizeof at, "%s", name);
+            double sum = 0.0; float acc = 0.0f;
+            for (long long j = 0; j < len; j++) {
+                const float v = p[r * len + j];
+                if (!(v >= 0.0f) || !std::isfinite(v)) return fail("tabular env: %s[%lld] = %g is negative or not finite", at, j, (double)v);
+                sum += (double)v; acc = acc + v; out[r * len + j] = acc;
+            }
+            if (exempt_terminal && sp->terminal[r / d1]) continue;
+            if (!(sum >= 1.0 - 1e-3 && sum <= 1.0 + 1e-3)) return fail("tabular env: row %s sums to %.6f, further than 1e-3 from 1", at, sum);
+        }
+        return 0;
+    };
+    if (rows("T", sp->T, 3, S * A, A, S, true, h.data() + oT)) return -1;
+    if (O > 0 && rows("Z", sp->Z, 3, A * S, S, O, false, h.data() + oZ)) return -1;
+    if (O > 0 && rows("Z0", sp->Z0, 2, S, 1, O, false, h.data() + oZ0)) return -1;
+    if (rows("b0", sp->b0, 1, 1, 1, S, false, h.data() + oB)) return -1;
+    for (size_t q = 0; q < nT; q++) { const float v = sp->R[q]; if (!std::isfinite(v)) return fail("tabular env: R[%zu][%zu][%zu] = %g is not finite", q / (size_t)(A * S), q / (size_t)S % (size_t)A, q % (size_t)S, (double)v); h[oR + q] = v; }
+    for (size_t q = 0; q < nF; q++) { const float v = sp->features[q]; if (!std::isfinite(v)) return fail("tabular env: features[%zu][%zu] = %g is not finite", q / (size_t)E, q % (size_t)E, (double)v); h[oF + q] = v; }
+    HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
+    EnvDev& V = e->env; const int n = sp->n_envs;
+    V.kind = DQN_ENV_TABULAR; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
+    V.tb_S = (int)S; V.tb_O = (int)O;
+    DM(e->env_tab, tot); HIPCHK(hipMemcpy(e->env_tab, h.data(), tot * sizeof(float), hipMemcpyHostToDevice));
+    DM(e->env_term, (size_t)S); HIPCHK(hipMemcpy(e->env_term, sp->terminal, (size_t)S, hipMemcpyHostToDevice));
+    V.tb_T = e->env_tab + oT; V.tb_R = e->env_tab + oR; V.tb_Z = O ? e->env_tab + oZ : nullptr; V.tb_Z0 = O ? e->env_tab + oZ0 : nullptr; V.tb_b0 = e->env_tab + oB; V.tb_feat = e->env_tab + oF;
+    V.tb_term = e->env_term;
+    DM(V.tb_s, n); DM(V.tb_o, n); DM(V.tb_oprev, n);
+    HIPCHK(hipMemsetAsync(V.tb_oprev, 0, (size_t)n * 4, e->stream));
+    return envs_finish(e);
 }
 extern "C" int dqn_envs_reset(dqn_engine_t* e) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
@@ -161,7 +234,8 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     // (the conditions of the train step's fused reduce + head launch, engine_program.hip); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
     bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
-    bool use_ah = !e->opt.no_act_head && levels.size() >= 2 && !any_padded; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
+    const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
+    bool use_ah = !e->opt.no_act_head && levels.size() >= 2 && !any_padded && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
     if (use_ah) {
         const LayerDev& La = e->L[lq]; ah_pa = La.src; ah_pv = lvh >= 0 ? e->L[lvh].src : -1;
         bool ok = La.kind == DQN_LAYER_DENSE && ah_pa >= 0 && (lvh < 0 || (e->L[lvh].kind == DQN_LAYER_DENSE && ah_pv >= 0 && ah_pv != ah_pa));
@@ -412,9 +486,10 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
     if (e->eval_n != n_eval) {
         HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_env_arrays(W); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
         W = e->env; W.n = n_eval; W.eval_mode = 1;
-        W.tm_s = W.tm_prev = nullptr; W.tm_t = nullptr; W.gw_pos = W.gw_prev = nullptr; W.actions = nullptr; W.rewards = nullptr; W.dones = W.pending = nullptr;
+        W.tm_s = W.tm_prev = nullptr; W.tm_t = nullptr; W.gw_pos = W.gw_prev = nullptr; W.tb_s = W.tb_o = W.tb_oprev = nullptr; W.actions = nullptr; W.rewards = nullptr; W.dones = W.pending = nullptr;
         W.ep_reward = nullptr; W.ep_step = nullptr; W.fin_eps = nullptr; W.fin_reward = nullptr;
         if (W.kind == DQN_ENV_TESTMDP) { DM(W.tm_s, (size_t)n_eval * 4); DM(W.tm_prev, (size_t)n_eval * 4); DM(W.tm_t, n_eval); }
+        else if (W.kind == DQN_ENV_TABULAR) { DM(W.tb_s, n_eval); DM(W.tb_o, n_eval); DM(W.tb_oprev, n_eval); }      // the tables are the training set's
         else { DM(W.gw_pos, (size_t)n_eval * 2); DM(W.gw_prev, (size_t)n_eval * 2); }
         DM(W.actions, n_eval); DM(W.rewards, n_eval); DM(W.dones, n_eval); DM(W.pending, n_eval); DM(W.ep_reward, n_eval); DM(W.ep_step, n_eval); DM(W.fin_eps, n_eval); DM(W.fin_reward, n_eval);
         DM(e->eval_roll, DQN_ROLL_RECORDS);

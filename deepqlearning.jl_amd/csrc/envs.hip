@@ -1,6 +1,6 @@
 // envs.hip -- vectorised environments on the device: the env loop of dqn_train! (src/solver.jl:82-132) for n
 // lock-stepped copies without any host round trip.  TestMDP restates test/test_env.jl:10-87, SimpleGridWorld restates the
-// POMDPModels defaults (third-party; recalled).  All randomness is Philox4x32-10 with counter (vector step, env, purpose) so
+// POMDPModels defaults (third-party; recalled), a tabular (PO)MDP is stepped from its matrices (POMDPTools' MDPCommonRLEnv / POMDPCommonRLEnv; recalled).  All randomness is Philox4x32-10 with counter (vector step, env, purpose) so
 // that the CPU twin (oracle/dqn_ref.c) reproduces trajectories bit for bit.
 //
 // One vector step is: [policy forward on pol_x -> greedy]  k_env_step  k_env_observe2   -- every argument is a fixed device
@@ -16,7 +16,25 @@ __device__ __forceinline__ uint32_t env_rand(unsigned long long seed, unsigned l
 }
 __device__ __forceinline__ float u01(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 
-// element f of the observation of an env in state (sw = the 4 TestMDP state bytes packed little-endian | px, py).  No local
+// tabular (PO)MDP draws (the law: include/dqn_mi355x.h).  cdf = one cumulative row of n non-decreasing fp32 values, u in [0, 1): the first j with u < cdf[j]; if
+// the row's fp32 sum lies at or below u, the last j at which the row still rose (= the first j with cdf[j] >= cdf[n - 1]; an all-zero row gives 0).  Either is the
+// first index at which a monotone predicate holds, and it holds at n - 1: ONE branch-free lower bound of at most 10 dependent loads for n <= 1024, whose trip
+// count depends on n alone (uniform across the lanes); the result always lies in [0, n - 1]
+__device__ __forceinline__ int cdf_pick(const float* __restrict__ cdf, int n, float u) {
+    const float top = cdf[n - 1];
+    const bool fb = !(u < top);
+    int base = 0;
+    for (int len = n; len > 1;) {
+        const int half = len >> 1;
+        const float v = cdf[base + half - 1];
+        const bool ok = fb ? v >= top : u < v;
+        base = ok ? base : base + half; len -= half;
+    }
+    return base;
+}
+enum { TAB_NEXT = DQN_ENV_RAND_TAB_NEXT, TAB_OBS = DQN_ENV_RAND_TAB_OBS, TAB_INIT = DQN_ENV_RAND_TAB_INIT, TAB_INIT_OBS = DQN_ENV_RAND_TAB_INIT_OBS };
+
+// element f of the observation of an env in state (sw = the 4 TestMDP state bytes packed little-endian | px, py; tabular: px = the observation index).  No local
 // arrays: a dynamically indexed one would live in scratch.
 __device__ __forceinline__ float obs_elem(const EnvDev& V, uint32_t sw, int px_, int py_, int f, unsigned char* raw) {
     if (V.kind == DQN_ENV_TESTMDP) {
@@ -25,20 +43,35 @@ __device__ __forceinline__ float obs_elem(const EnvDev& V, uint32_t sw, int px_,
         const unsigned char b = V.images[sel * hw + px];
         *raw = b; return (float)b / 255.0f;
     }
+    if (V.kind == DQN_ENV_TABULAR) { *raw = 0; return V.tb_feat[(size_t)px_ * V.E + f]; }      // convert_o / convert_s row of the index
     *raw = 0; return (float)(f == 0 ? px_ : py_);                          // Float32[x, y]
 }
 __device__ __forceinline__ void reset_state(const EnvDev& V, int i, unsigned long long t, uint32_t* sw, int* tm_t, int* px, int* py) {
     if (V.kind == DQN_ENV_TESTMDP) { *sw = 0x01010101u; *tm_t = 1; }                                                  // initialstate, :46-52
+    else if (V.kind == DQN_ENV_TABULAR) {      // s ~ b0, o ~ Z0[s] (an MDP: o = s); py = state, px = observation index
+        const int s = cdf_pick(V.tb_b0, V.tb_S, u01(env_rand(V.seed, t, i, TAB_INIT)));
+        *py = s; *px = V.tb_O ? cdf_pick(V.tb_Z0 + (size_t)s * V.tb_O, V.tb_O, u01(env_rand(V.seed, t, i, TAB_INIT_OBS))) : s;
+    }
     else { *px = 1 + (int)(env_rand(V.seed, t, i, 5u) % (uint32_t)V.size_x); *py = 1 + (int)(env_rand(V.seed, t, i, 6u) % (uint32_t)V.size_y); }
 }
 __device__ __forceinline__ void load_state(const EnvDev& V, int i, uint32_t* sw, int* px, int* py) {
     *sw = 0x01010101u; *px = *py = 0;
     if (V.kind == DQN_ENV_TESTMDP) *sw = *(const uint32_t*)(V.tm_s + i * 4);
+    else if (V.kind == DQN_ENV_TABULAR) { *px = V.tb_o[i]; *py = V.tb_s[i]; }
     else { *px = V.gw_pos[i * 2]; *py = V.gw_pos[i * 2 + 1]; }
+}
+// the state the last k_env_step saved before it stepped: what the transition's s is the observation of
+__device__ __forceinline__ void load_prev(const EnvDev& V, int i, uint32_t* sw, int* px, int* py) {
+    *sw = 0x01010101u; *px = *py = 0;
+    if (V.kind == DQN_ENV_TESTMDP) *sw = *(const uint32_t*)(V.tm_prev + i * 4);
+    else if (V.kind == DQN_ENV_TABULAR) *px = V.tb_oprev[i];
+    else { *px = V.gw_prev[i * 2]; *py = V.gw_prev[i * 2 + 1]; }
 }
 __device__ __forceinline__ void store_reset(const EnvDev& V, int i, unsigned long long t) {
     uint32_t sw; int tm = 1, px, py; reset_state(V, i, t, &sw, &tm, &px, &py);
-    if (V.kind == DQN_ENV_TESTMDP) { *(uint32_t*)(V.tm_s + i * 4) = sw; V.tm_t[i] = tm; } else { V.gw_pos[i * 2] = px; V.gw_pos[i * 2 + 1] = py; }
+    if (V.kind == DQN_ENV_TESTMDP) { *(uint32_t*)(V.tm_s + i * 4) = sw; V.tm_t[i] = tm; }
+    else if (V.kind == DQN_ENV_TABULAR) { V.tb_s[i] = py; V.tb_o[i] = px; }
+    else { V.gw_pos[i * 2] = px; V.gw_pos[i * 2 + 1] = py; }
 }
 
 // observation of every env into (a) the staged rows[i][E] in the replay storage dtype and (b) batch-innermost x[E][n] (policy input)
@@ -190,6 +223,7 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
             store_reset(V, i, t_prev);
         }
         if (V.kind == DQN_ENV_TESTMDP) *(uint32_t*)(V.tm_prev + i * 4) = *(const uint32_t*)(V.tm_s + i * 4);       // s of this transition = observation of the pre-step state
+        else if (V.kind == DQN_ENV_TABULAR) V.tb_oprev[i] = V.tb_o[i];
         else { V.gw_prev[i * 2] = V.gw_pos[i * 2]; V.gw_prev[i * 2 + 1] = V.gw_pos[i * 2 + 1]; }
         int a = 0;
         {   // Q column without per-lane arrays (they would live in scratch): advantages are re-read for the second pass
@@ -222,6 +256,13 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
             r = (last == 1 ? -0.1f : (last == 2 ? 0.0f : 0.1f));
             if (was_second) r = r * -10.0f;                                   // :77-83
             V.tm_t[i] += 1; done = V.tm_t[i] >= V.max_time;                   // isterminal: t >= max_time, :85-87
+        } else if (V.kind == DQN_ENV_TABULAR) {      // sp ~ T[s][a], o ~ Z[a][sp] (an MDP: o = sp), r = R[s][a][sp], done = terminal[sp]
+            const int s = V.tb_s[i];
+            const size_t row = ((size_t)s * V.nA + a) * V.tb_S;
+            const int sp = cdf_pick(V.tb_T + row, V.tb_S, u01(env_rand(V.seed, t, i, TAB_NEXT)));
+            const int o = V.tb_O ? cdf_pick(V.tb_Z + ((size_t)a * V.tb_S + sp) * V.tb_O, V.tb_O, u01(env_rand(V.seed, t, i, TAB_OBS))) : sp;
+            r = V.tb_R[row + sp]; done = V.tb_term[sp];
+            V.tb_s[i] = sp; V.tb_o[i] = o;
         } else {
             int* p = V.gw_pos + i * 2; float rv = 0.0f;
             for (int k = 0; k < V.n_reward; k++) if (p[0] == V.reward_xy[k][0] && p[1] == V.reward_xy[k][1]) rv = V.reward_val[k];
@@ -279,6 +320,11 @@ __device__ __forceinline__ void obs_vec(const EnvDev& V, uint32_t sw, int px_, i
             ob[u] = b; of[u] = (float)b / 255.0f;
             if (++px == hw) { px = 0; c++; }
         }
+    } else if (V.kind == DQN_ENV_TABULAR) {      // VEC elements of ONE feature row (VEC == 4: E % 4 == 0 and f % 4 == 0, the rows of the table are 16-byte aligned)
+        typedef float FeatV __attribute__((ext_vector_type(VEC)));
+        const FeatV v = *(const FeatV*)(V.tb_feat + (size_t)px_ * V.E + f);
+#pragma unroll
+        for (int u = 0; u < VEC; u++) { ob[u] = 0; of[u] = v[u]; }
     } else {
 #pragma unroll
         for (int u = 0; u < VEC; u++) { ob[u] = 0; of[u] = (float)((f + u) == 0 ? px_ : py_); }
@@ -305,9 +351,9 @@ __global__ __launch_bounds__(256) void k_env_observe2(EnvDev V, const RolloutDev
         const unsigned f = fv * VEC;
         const RolloutDev* rs = rs0 + (grouped ? (i >> 2) : 0u);
         long long slot = rs->widx + i; if (slot >= cap) slot -= cap;
-        uint32_t sw0 = 0x01010101u, sw1; int p0x = 0, p0y = 0, p1x, p1y;
+        uint32_t sw0, sw1; int p0x, p0y, p1x, p1y;
         load_state(V, (int)i, &sw1, &p1x, &p1y);
-        if (V.kind == DQN_ENV_TESTMDP) sw0 = *(const uint32_t*)(V.tm_prev + i * 4); else { p0x = V.gw_prev[i * 2]; p0y = V.gw_prev[i * 2 + 1]; }
+        load_prev(V, (int)i, &sw0, &p0x, &p0y);
         float of[VEC]; unsigned char ob[VEC]; RowT r[VEC];
         const size_t dst = (size_t)slot * E + f;
         obs_vec<VEC>(V, sw0, p0x, p0y, (int)f, of, ob);
@@ -402,9 +448,9 @@ __global__ __launch_bounds__(256) void k_env_observe_rec(EnvDev V, const Rollout
             const int i = (int)(q / V.E), f = (int)(q - (size_t)i * V.E);      // f fastest: coalesced rows
             const int pos = ES.open_len[i] - 1;
             if (pos < 0 || pos >= ES.T) continue;
-            uint32_t sw0 = 0x01010101u, sw1; int p0x = 0, p0y = 0, p1x, p1y;
+            uint32_t sw0, sw1; int p0x, p0y, p1x, p1y;
             load_state(V, i, &sw1, &p1x, &p1y);
-            if (V.kind == DQN_ENV_TESTMDP) sw0 = *(const uint32_t*)(V.tm_prev + i * 4); else { p0x = V.gw_prev[i * 2]; p0y = V.gw_prev[i * 2 + 1]; }
+            load_prev(V, i, &sw0, &p0x, &p0y);
             const size_t dst = ((size_t)i * ES.T + pos) * V.E + f;
             ES.st_s[dst] = obs_elem(V, sw0, p0x, p0y, f, &b);
             ES.st_sp[dst] = obs_elem(V, sw1, p1x, p1y, f, &b);

@@ -418,6 +418,52 @@ function envs_create_testmdp!(e::Engine, images::Matrix{UInt8}, o_stack, max_tim
         check(ccall((:dqn_envs_create, LIB), Cint, (Ptr{Cvoid}, Ref{EnvSpec}), e.h, spec))
     end
 end
+# ---- tabular environments (dqn_tabular_env): any discrete POMDPs.jl problem as its matrices, so that it runs on the device loop.  Julia arrays are column-major:
+# an array indexed [sp, a, s] IS the header's row-major [S][A][S]
+struct TabularEnv
+    n_envs::Int32; max_episode_length::Int32; seed::UInt64
+    n_states::Int32; n_obs::Int32
+    T::Ptr{Float32}; Z::Ptr{Float32}; Z0::Ptr{Float32}; R::Ptr{Float32}; terminal::Ptr{UInt8}; b0::Ptr{Float32}; features::Ptr{Float32}
+end
+function tabulate(problem::Union{MDP,POMDP})
+    ss = ordered_states(problem); as = ordered_actions(problem); S = length(ss); A = length(as)
+    ispomdp = problem isa POMDP
+    os = ispomdp ? ordered_observations(problem) : ss; O = ispomdp ? length(os) : 0
+    T = zeros(Float32, S, A, S); R = zeros(Float32, S, A, S); term = zeros(UInt8, S); b0 = zeros(Float32, S)
+    Z = zeros(Float32, max(O, 1), S, A); Z0 = zeros(Float32, max(O, 1), S)
+    for (si, s) in enumerate(ss)
+        term[si] = isterminal(problem, s) ? 1 : 0
+        b0[si] = pdf(initialstate(problem), s)
+        for (ai, a) in enumerate(as)
+            term[si] == 1 && continue                     # rows of terminal states are exempt from the row-sum check
+            d = transition(problem, s, a)
+            for (spi, sp) in enumerate(ss)
+                T[spi, ai, si] = pdf(d, sp)
+                R[spi, ai, si] = reward(problem, s, a, sp)
+            end
+        end
+    end
+    if ispomdp
+        for (ai, a) in enumerate(as), (spi, sp) in enumerate(ss), (oi, o) in enumerate(os)
+            Z[oi, spi, ai] = pdf(observation(problem, a, sp), o)
+        end
+        # the observation after a reset: POMDPCommonRLEnv draws it from initialobs where the model defines one.  tabulate does not ask for initialobs: it APPROXIMATES
+        # Z0[s] by the first ordered action's observation model (exact for TigerPOMDP, whose first action is listen; DESIGN 6.2.2)
+        for (si, s) in enumerate(ss), (oi, o) in enumerate(os)
+            Z0[oi, si] = Z[oi, si, 1]
+        end
+    end
+    feat = ispomdp ? reduce(hcat, [vec(convert_o(Vector{Float32}, o, problem)) for o in os]) : reduce(hcat, [vec(convert_s(Vector{Float32}, s, problem)) for s in ss])
+    (T = T, Z = Z, Z0 = Z0, R = R, terminal = term, b0 = b0, features = Matrix{Float32}(feat), n_states = S, n_obs = O)
+end
+function envs_create_tabular!(e::Engine, problem::Union{MDP,POMDP}; n_envs, max_episode_length = 100, seed = 0)
+    t = tabulate(problem)
+    GC.@preserve t begin
+        pz = t.n_obs > 0 ? pointer(t.Z) : Ptr{Float32}(C_NULL); pz0 = t.n_obs > 0 ? pointer(t.Z0) : Ptr{Float32}(C_NULL)
+        spec = TabularEnv(n_envs, max_episode_length, seed, t.n_states, t.n_obs, pointer(t.T), pz, pz0, pointer(t.R), pointer(t.terminal), pointer(t.b0), pointer(t.features))
+        check(ccall((:dqn_envs_create_tabular, LIB), Cint, (Ptr{Cvoid}, Ref{TabularEnv}), e.h, spec))
+    end
+end
 function evaluate(e::Engine, n_eval, max_episode_length; seed = 0)                   # basic_evaluation (src/evaluation_policy.jl:17-42) on the device
     r = Ref{Float64}(0); st = Ref{Float64}(0)
     check(ccall((:dqn_evaluate, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, UInt64, Ref{Float64}, Ref{Float64}), e.h, n_eval, max_episode_length, seed, r, st))

@@ -250,7 +250,7 @@ int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32_t* a_out /
  *    Recur state as it found it (src/solver.jl:137-139).  dqn_episode_export / dqn_get_counters after a rollout describe the committed ring; open episodes
  *    are not part of a checkpoint.
  *  - dqn_evaluate leaves the training copies, the policy state, the ring, the open episodes and the counters exactly as they were. */
-enum { DQN_ENV_TESTMDP = 0, DQN_ENV_GRIDWORLD = 1 };
+enum { DQN_ENV_TESTMDP = 0, DQN_ENV_GRIDWORLD = 1, DQN_ENV_TABULAR = 2 };      /* DQN_ENV_TABULAR has its own spec and entry point, dqn_envs_create_tabular below */
 typedef struct {
     int32_t kind;               /* DQN_ENV_* */
     int32_t n_envs;
@@ -276,6 +276,40 @@ typedef struct {
 } dqn_rollout_cfg;
 typedef struct { int64_t episodes; double reward_sum; int64_t train_steps; float last_loss, last_grad_norm; } dqn_rollout_stats;
 int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* spec);
+/* ---- tabular environments: any discrete MDP / POMDP given as its matrices (TigerPOMDP, BabyPOMDP, SimpleGridWorld, the POMDPModels zoo) on the device loop.
+ * The tables are copied to HBM at creation (the caller's pointers are not kept); afterwards the set behaves exactly as one made by dqn_envs_create: dqn_rollout,
+ * dqn_evaluate, dqn_envs_reset, dqn_envs_peek, dqn_envs_info and the lifecycle rules above apply unchanged, on feed-forward and recurrent engines.  The acting step
+ * takes the general four-launch tail (dqn_envs_info: fused_tail = 0).
+ *
+ * One step of copy i at vector step t (POMDPTools' MDPCommonRLEnv / POMDPCommonRLEnv; third-party, recalled): sp ~ T[s][a]; o ~ Z[a][sp] (an MDP: o = sp);
+ * r = R[s][a][sp]; done = terminal[sp].  The observation of the transition's s is the feature row of the observation index held before the step, that of sp the
+ * feature row of o.  Reset: s ~ b0, then o ~ Z0[s] (an MDP: o = s).
+ *
+ * THE SAMPLING LAW.  At creation the host turns every distribution row (T[s][a][:], Z[a][sp][:], Z0[s][:], b0[:]) into a cumulative row with a plain fp32 loop in
+ * ascending index order (acc = acc + p; no contraction, no device kernel).  A draw is u = u01(philox(seed, t, i, purpose)) with the counter layout and u01 of the
+ * built-in kinds ((r >> 8) * 2^-24).  The pick is the first j with u < cdf[j].  If no j qualifies (the row's fp32 sum lies at or below u) the pick is the last j
+ * with cdf[j] > cdf[j - 1] (cdf[0] > 0 for j = 0) -- so an entry of probability zero is never picked.  (A row without any positive entry -- possible only for T at
+ * a terminal state, reachable only if b0 puts mass there -- picks index 0.)  The device finds j by binary search over the cumulative row; a cumulative row of
+ * non-negative fp32 terms is non-decreasing, so this is the j of the linear scan that defines the law.  Purposes 1-6 belong to the built-in kinds (1 explore or not,
+ * 2 random action, 3-4 SimpleGridWorld move, 5-6 SimpleGridWorld reset); the tabular kind draws with the four below.
+ *
+ * Refused, each with a message naming the offending value: n_states outside 1..1024, n_obs outside 0..1024; n_envs outside what the engine kind allows (above);
+ * a missing table, or Z / Z0 given with n_obs == 0; a negative or non-finite probability; a row whose sum, taken in double, is further than 1e-3 from 1 (rows of T at
+ * terminal states are exempt); a non-finite reward or feature; an engine with a u8 replay (feature rows are floats); an engine with a communicator or created under
+ * DQN_SIM_WORLD -- and dqn_comm_init once such a set exists (no exchange path has run with it). */
+enum { DQN_ENV_RAND_TAB_NEXT = 7, DQN_ENV_RAND_TAB_OBS = 8, DQN_ENV_RAND_TAB_INIT = 9, DQN_ENV_RAND_TAB_INIT_OBS = 10 };      /* next state, observation, initial state, initial observation */
+typedef struct {
+    int32_t n_envs, max_episode_length; uint64_t seed;
+    int32_t n_states, n_obs;      /* S; O = 0: an MDP, the observation index IS the state index */
+    const float*   T;             /* [S][A][S]  P(sp | s, a),  A = hparams.n_actions */
+    const float*   Z;             /* [A][S][O]  P(o | a, sp);  NULL iff O == 0 */
+    const float*   Z0;            /* [S][O]     P(o | s) of the observation after a reset; NULL iff O == 0 */
+    const float*   R;             /* [S][A][S]  reward(s, a, sp) */
+    const uint8_t* terminal;      /* [S] */
+    const float*   b0;            /* [S] initial-state distribution */
+    const float*   features;      /* [O ? O : S][E]  convert_o / convert_s row per index, E = obs_c*obs_h*obs_w */
+} dqn_tabular_env;
+int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* spec);
 int dqn_envs_reset(dqn_engine_t* e);
 int dqn_rollout(dqn_engine_t* e, int n_vector_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* stats_or_null);
 /* basic_evaluation (src/evaluation_policy.jl:17-42; cadence src/solver.jl:101-122) batched on the device: n_eval
