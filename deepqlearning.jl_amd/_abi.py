@@ -91,6 +91,16 @@ class RolloutCfg(C.Structure):
                 ("eps_start", C.c_float), ("eps_stop", C.c_float), ("eps_steps", C.c_float), ("cadence_env_steps", C.c_int32), ("t0", C.c_int64)]
 
 
+class Exploration(C.Structure):
+    """dqn_exploration (include/dqn_mi355x.h): per-vector-step eps (kind 0) or softmax temperature (kind 1), evaluated on the host."""
+    _fields_ = [("kind", C.c_int32), ("n_values", C.c_int32), ("values", C.c_void_p)]
+
+
+EXPLORE_EPS_GREEDY, EXPLORE_SOFTMAX = 0, 1
+ENV_RAND_SOFTMAX = 11
+_EXPLORE_KINDS = {"eps": EXPLORE_EPS_GREEDY, "softmax": EXPLORE_SOFTMAX}
+
+
 class RolloutStats(C.Structure):
     _fields_ = [("episodes", C.c_int64), ("reward_sum", C.c_double), ("train_steps", C.c_int64),
                 ("last_loss", C.c_float), ("last_grad_norm", C.c_float)]
@@ -162,6 +172,7 @@ PROTOS = {
     "envs_create_tabular": [_vp, _P(TabularEnv)],
     "envs_reset": [_vp],
     "rollout": [_vp, C.c_int, _P(RolloutCfg), _P(RolloutStats)],
+    "rollout_explore": [_vp, C.c_int, _P(RolloutCfg), _P(Exploration), _P(RolloutStats)],
     "envs_peek": [_vp, _f32p, _i32p, _f32p, _u8p],
     "envs_info": [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "evaluate": [_vp, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p],
@@ -503,11 +514,21 @@ class Handle:
     def envs_reset(self):
         self._check(self.f["envs_reset"](self._h))
 
-    def rollout(self, n_steps, t0=1, train_freq=4, target_update_freq=500, eps=(1.0, 0.01, 5000.0), stats=True, env_step_cadence=False):
-        """env_step_cadence: train_freq / target_update_freq count ENV steps as in the reference's loop (src/solver.jl:136-145) instead of vector steps"""
+    def rollout(self, n_steps, t0=1, train_freq=4, target_update_freq=500, eps=(1.0, 0.01, 5000.0), stats=True, env_step_cadence=False, explore=None):
+        """env_step_cadence: train_freq / target_update_freq count ENV steps as in the reference's loop (src/solver.jl:136-145) instead of vector steps.
+        explore = ("eps" | "softmax", values): dqn_rollout_explore -- values[j] is eps / the temperature of vector step t0 + j (n_steps values, or one for a constant),
+        rounded to fp32 here; `eps` is then ignored.  A kind given as an int is passed through (the library refuses what it does not know)."""
         cfg = RolloutCfg(int(train_freq), int(target_update_freq), float(eps[0]), float(eps[1]), float(eps[2]), 1 if env_step_cadence else 0, int(t0))
         st = RolloutStats()
-        self._check(self.f["rollout"](self._h, int(n_steps), C.byref(cfg), C.byref(st) if stats else None))
+        if explore is not None:
+            if "rollout_explore" not in self.f:
+                raise DQNError("this library does not export rollout_explore")
+            kind, values = explore
+            vals = None if values is None else np.ascontiguousarray(np.atleast_1d(values), np.float32)
+            x = Exploration(int(_EXPLORE_KINDS.get(kind, kind)), 0 if vals is None else int(vals.size), None if vals is None else vals.ctypes.data)
+            self._check(self.f["rollout_explore"](self._h, int(n_steps), C.byref(cfg), C.byref(x), C.byref(st) if stats else None))
+        else:
+            self._check(self.f["rollout"](self._h, int(n_steps), C.byref(cfg), C.byref(st) if stats else None))
         return dict(episodes=st.episodes, reward_sum=st.reward_sum, train_steps=st.train_steps, loss=st.last_loss, grad_norm=st.last_grad_norm) if stats else None
 
     def evaluate(self, n_eval, max_episode_length=100, seed=0):

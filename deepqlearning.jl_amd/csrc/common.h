@@ -912,7 +912,10 @@ struct EnvDev {
     // index is the state index.  Per copy: state, observation index, observation index before the step
     int tb_S, tb_O; const float *tb_T, *tb_Z, *tb_Z0, *tb_R, *tb_b0, *tb_feat; const unsigned char* tb_term; int *tb_s, *tb_o, *tb_oprev;
 };
-struct RolloutDev { long long t, widx; float eps_start, eps_stop, eps_steps; int pad; };     // t, widx: values of the LAST completed vector step
+// t, widx: values of the LAST completed vector step.  Exploration: xtab == nullptr is the linear eps law of (eps_start, eps_stop, eps_steps); else
+// vector step t reads xtab[clamp(t - xtab_t0, 0, xtab_n - 1)] -- eps (xkind = DQN_EXPLORE_EPS_GREEDY) or the softmax temperature (DQN_EXPLORE_SOFTMAX).  Only the
+// general tail (k_env_step) reads the three x* fields; the fused tail (act_head.hip) serves the linear law and is never launched with a table
+struct RolloutDev { long long t, widx; float eps_start, eps_stop, eps_steps; int xkind; const float* xtab; long long xtab_t0; int xtab_n, pad; };
 struct ReplayMeta { long long cap, cap2; int* a; float* r; unsigned char* done; float* tree; StepState* state; float eps, alpha; };
 void launch_env_observe(hipStream_t st, const EnvDev& V, void* rows, int rows_u8, float* x);
 struct ActHeads { HeadSrc val, adv; int dueling; float* q_out; int* amax; };     // last-layer outputs of the acting forward (adv doubles as the plain Q head)

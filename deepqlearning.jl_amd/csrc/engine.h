@@ -113,6 +113,10 @@ struct dqn_engine {
     struct ActProg { std::vector<Step> steps; int n = 0; bool fused_tail = false; hipGraphExec_t graph = nullptr; std::vector<void*> allocs; int state_gen = -1, state_flip = -1;
                      hipGraphExec_t cycle = nullptr; int cycle_F = 0; bool cycle_train = false;
                      hipGraphExec_t envc = nullptr; int envc_due = 0; };      // envc: one vector step of the reference's cadence (the acting step + its `envc_due` pipelined train steps) as ONE graph
+    // act_gen: the training set's acting program with the general four-launch tail, built only where `act` has the fused one and a rollout explores by table
+    // (dqn_rollout_explore): both are kept, neither is rebuilt when calls alternate.  xtab: that entry point's table in HBM (engine-owned, grown on demand; the
+    // pointer travels in the RolloutDev record, not in a kernel argument, so growing it leaves the captured graphs valid)
+    ActProg act_gen; float* xtab = nullptr; size_t xtab_cap = 0;
     ActProg act, evalp; std::vector<Step>* sink = nullptr; std::vector<void*>* alloc_sink = nullptr; RolloutDev *roll = nullptr, *eval_roll = nullptr;
     EnvDev eval_env{}; int eval_n = 0;
     std::vector<Step> prog; size_t prog_post_begin = 0, prog_pre1_end = 0; bool prog_built = false, prio_forked = false, prio_in_bwd = false;

@@ -343,7 +343,7 @@ static void drop_act_graphs(dqn_engine::ActProg& a) {
 void drop_graphs(dqn_engine* e) {
     for (auto& sg : e->graphs) hipGraphExecDestroy(sg.g);
     e->graphs.clear(); e->mid_big_warm = false;
-    drop_act_graphs(e->act); drop_act_graphs(e->evalp);
+    drop_act_graphs(e->act); drop_act_graphs(e->act_gen); drop_act_graphs(e->evalp);
 }
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a) {
     drop_act_graphs(a);
@@ -1023,7 +1023,7 @@ extern "C" int dqn_get_last_indices(dqn_engine_t* e, int64_t* idx) { if (!e) ret
 // ---------------------------------------------------------------- policy (src/policy.jl:38-64)
 int policy_ws(dqn_engine* e, int n) {
     if (n <= e->pol_n) return 0;
-    HIPCHK(hipStreamSynchronize(e->stream)); free_policy_ws(e); drop_act(e, e->act); drop_act(e, e->evalp);
+    HIPCHK(hipStreamSynchronize(e->stream)); free_policy_ws(e); drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
     size_t need = 1;   // split-K partials of the widest forward at n columns
     for (int i = 0; i < e->nl; i++) { const size_t sf = dqn_nchunks(e->L[i].K, e->L[i].fwd_kc); if (sf > 1) need = std::max(need, sf * (size_t)e->L[i].out_feat * n); }
     if (need > e->partials_elems) { drop_graphs(e); hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * need); e->partials_elems = need; }

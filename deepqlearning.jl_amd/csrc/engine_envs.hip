@@ -19,7 +19,8 @@ void free_envs(dqn_engine* e) {
     hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
     e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false;
     free_env_arrays(e->eval_env); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
-    drop_act(e, e->act); drop_act(e, e->evalp);
+    drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
+    hipFree(e->xtab); e->xtab = nullptr; e->xtab_cap = 0;
     free_eval_state(e);
     EpStage& S = e->ep_stage;      // the open episodes go with the env set; the committed ring is the engine's
     hipFree(S.st_s); hipFree(S.st_sp); hipFree(S.st_a); hipFree(S.st_r); hipFree(S.st_done); hipFree(S.open_len); memset(&S, 0, sizeof S);
@@ -216,7 +217,8 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
 }
 // the acting program: online net forward on the n columns of pol_x (batch-innermost), then Q columns + first-max argmax
 // (action(policy, obs), src/policy.jl:38-64) -- the same tiled kernels and the same plan as the train step, compiled once per n
-static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs) {
+// general: keep the four-launch tail where the fused one would apply (a rollout that explores by table)
+static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs, bool general = false) {
     const int n = V.n;
     if (e->hp.recurrence) return build_act_program_rec(e, ap, V, rs);      // act_head.hip and the GEMM grouping below stay feed-forward only
     if (ap.n == n) return 0;
@@ -235,7 +237,7 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
     bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
     const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
-    bool use_ah = !e->opt.no_act_head && levels.size() >= 2 && !any_padded && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
+    bool use_ah = !general && !e->opt.no_act_head && levels.size() >= 2 && !any_padded && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
     if (use_ah) {
         const LayerDev& La = e->L[lq]; ah_pa = La.src; ah_pv = lvh >= 0 ? e->L[lvh].src : -1;
         bool ok = La.kind == DQN_LAYER_DENSE && ah_pa >= 0 && (lvh < 0 || (e->L[lvh].kind == DQN_LAYER_DENSE && ah_pv >= 0 && ah_pv != ah_pa));
@@ -359,10 +361,35 @@ static int envc_graph(dqn_engine* e, dqn_engine::ActProg& ap, int due) {
             return 0; }, &ap.envc)) return -1;
     ap.envc_due = due; return 0;
 }
+// dqn_rollout_explore's table.  explore_check refuses before anything is enqueued; explore_upload copies the values into the engine's buffer (grown on demand) and
+// names them in the record every RolloutDev of the call is copied from.  x == nullptr: the linear law (xtab stays null)
+static int explore_check(const dqn_exploration* x, int n_steps) {
+    if (!x) return 0;
+    if (x->kind != DQN_EXPLORE_EPS_GREEDY && x->kind != DQN_EXPLORE_SOFTMAX) return fail("exploration: unknown kind %d (0: eps-greedy, 1: softmax)", x->kind);
+    if (x->n_values != 1 && x->n_values != n_steps) return fail("exploration: n_values = %d is neither 1 nor n_vector_steps = %d", x->n_values, n_steps);
+    if (!x->values) return fail("exploration: values is NULL (n_values = %d)", x->n_values);
+    for (int j = 0; j < x->n_values; j++) {
+        const float v = x->values[j];
+        if (x->kind == DQN_EXPLORE_EPS_GREEDY && !(v >= 0.0f && v <= 1.0f)) return fail("exploration: eps values[%d] = %g is outside [0, 1]", j, (double)v);
+        if (x->kind == DQN_EXPLORE_SOFTMAX && !(v > 0.0f && std::isfinite(v))) return fail("exploration: temperature values[%d] = %g is not a finite positive number", j, (double)v);
+    }
+    return 0;
+}
+static int explore_upload(dqn_engine* e, const dqn_exploration* x, long long t0, RolloutDev& h) {
+    if (!x) return 0;
+    const size_t m = (size_t)x->n_values;
+    if (m > e->xtab_cap) {
+        HIPCHK(hipStreamSynchronize(e->stream)); hipFree(e->xtab); e->xtab = nullptr; e->xtab_cap = 0;
+        const size_t cap = std::max<size_t>(256, 2 * m); DM(e->xtab, cap); e->xtab_cap = cap;
+    }
+    HIPCHK(hipMemcpyAsync(e->xtab, x->values, m * sizeof(float), hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));      // the caller's array is not kept
+    h.xkind = x->kind; h.xtab = e->xtab; h.xtab_t0 = t0; h.xtab_n = x->n_values;
+    return 0;
+}
 // dqn_rollout on a recurrent engine: the acting step (graph or launches), then -- when train steps are due and the ring holds a batch of episodes -- the sampled
 // recurrent step(s) with the host SplitMix sampler, whose mirror of the ring (ep_size, ep_widx, ep_len_host) is refreshed from the device before the draw.  No cycle
 // or whole-step graphs: the draw is a host decision.  The train step works on its own sequence buffers and leaves the policy's Recur state alone (src/solver.jl:137-139).
-static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) {
+static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, const dqn_exploration* x, dqn_rollout_stats* out) {
     EnvDev& V = e->env; const int n = V.n;
     if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before dqn_rollout");
     if (e->comm) return fail("device environments on a recurrent engine are single-device: this engine has a communicator");
@@ -370,6 +397,7 @@ static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, d
     if (build_act_program(e, e->act, V, e->roll)) return -1;
     if (cfg->train_freq > 0 && build_program(e)) return -1;
     RolloutDev h; memset(&h, 0, sizeof h); h.t = cfg->t0 - 1; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
+    if (explore_upload(e, x, cfg->t0, h)) return -1;
     { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
       HIPCHK(hipMemcpyAsync(e->roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); if (ep_mirror_push(e)) return -1; }
     launch_env_observe(e->stream, V, nullptr, 0, e->pol_x);
@@ -402,20 +430,27 @@ static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, d
     }
     return 0;
 }
-extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) { if (!e) return fail("null engine handle");
+extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) { return dqn_rollout_explore(e, n_steps, cfg, nullptr, out); }
+// x == NULL: dqn_rollout.  Else the exploration table is validated (nothing is enqueued by a refused call), uploaded, and named by the RolloutDev records
+extern "C" int dqn_rollout_explore(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, const dqn_exploration* x, dqn_rollout_stats* out) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
     if (cfg->t0 < 1) return fail("t0 counts from 1 (src/solver.jl:82)");
-    if (e->hp.recurrence) return rollout_rec(e, n_steps, cfg, out);
+    if (explore_check(x, n_steps)) return -1;
+    if (e->hp.recurrence) return rollout_rec(e, n_steps, cfg, x, out);
     EnvDev& V = e->env; const int n = V.n;
     if (build_act_program(e, e->act, V, e->roll)) return -1;
+    // a table is read by the general tail only: where the set's program has the fused one, its general twin runs this call (both stay built)
+    if (x && e->act.fused_tail && build_act_program(e, e->act_gen, V, e->roll, true)) return -1;
+    dqn_engine::ActProg& act = (x && e->act.fused_tail) ? e->act_gen : e->act;
     if (cfg->train_freq > 0 && build_program(e)) return -1;       // may reallocate split-K workspaces: before any capture
-    RolloutDev h; h.t = cfg->t0 - 1; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps; h.pad = 0;
+    RolloutDev h; memset(&h, 0, sizeof h); h.t = cfg->t0 - 1; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
+    if (explore_upload(e, x, cfg->t0, h)) return -1;
     { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);      // one record per group of four copies (k_act_head ticks its group's), record 0 = the four-launch tail's
       HIPCHK(hipMemcpyAsync(e->roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream)); }   // hs lives in this scope
     launch_env_observe(e->stream, V, nullptr, 0, e->pol_x);
     const bool graph = e->hp.use_graph && !e->profiling;
-    if (graph && act_graph(e, e->act)) return -1;
+    if (graph && act_graph(e, act)) return -1;
     long long trained = 0;
     // whole cycles -- train_freq acting steps ending on a train step (or 4 acting steps when nothing trains) -- replay as ONE graph where the
     // schedule allows it: single device, the train step due exactly at the cycle's last step, the replay already holding a batch, no target sync
@@ -430,14 +465,14 @@ extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* 
             // the whole vector step as one graph where every vector step owes the same number of train steps and the replay holds a batch once this step's experiences are in
             if (graph && single && !e->tiny && cfg->train_freq > 0 && n % cfg->train_freq == 0 && n / cfg->train_freq <= 64 && std::min(e->cap, e->size + n) >= e->B) {
                 const int due_c = n / cfg->train_freq;
-                if (envc_graph(e, e->act, due_c)) return -1;
-                HIPCHK(hipGraphLaunch(e->act.envc, e->stream));
+                if (envc_graph(e, act, due_c)) return -1;
+                HIPCHK(hipGraphLaunch(act.envc, e->stream));
                 e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); trained += due_c;
                 if (cfg->target_update_freq > 0 && (t * n) / cfg->target_update_freq != ((t - 1) * n) / cfg->target_update_freq) { if (dqn_sync_target(e)) return -1; }
                 continue;
             }
-            if (graph) HIPCHK(hipGraphLaunch(e->act.graph, e->stream));
-            else for (auto& s : e->act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
+            if (graph) HIPCHK(hipGraphLaunch(act.graph, e->stream));
+            else for (auto& s : act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
             e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n);
             const long long due = cfg->train_freq > 0 ? (t * n) / cfg->train_freq - ((t - 1) * n) / cfg->train_freq : 0;
             if (due > 0 && e->size >= e->B) { if (dqn_train_steps(e, (int)due, nullptr, nullptr)) return -1; trained += due; }      // back to back: the pipelined gather applies
@@ -449,16 +484,16 @@ extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* 
             bool ok = cfg->train_freq > 0 ? (tl % cfg->train_freq == 0 && std::min(e->cap, e->size + (long long)F * n) >= e->B) : true;
             if (cfg->target_update_freq > 0) for (long long u = t; u < tl; u++) ok = ok && (u % cfg->target_update_freq != 0);
             if (ok) {
-                if (cycle_graph(e, e->act, F, cfg->train_freq > 0)) return -1;
-                HIPCHK(hipGraphLaunch(e->act.cycle, e->stream));
+                if (cycle_graph(e, act, F, cfg->train_freq > 0)) return -1;
+                HIPCHK(hipGraphLaunch(act.cycle, e->stream));
                 for (int f = 0; f < F; f++) { e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); }
                 if (cfg->train_freq > 0) trained++;
                 if (cfg->target_update_freq > 0 && tl % cfg->target_update_freq == 0) { if (dqn_sync_target(e)) return -1; }
                 k += F - 1; continue;
             }
         }
-        if (graph) HIPCHK(hipGraphLaunch(e->act.graph, e->stream));
-        else for (auto& s : e->act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
+        if (graph) HIPCHK(hipGraphLaunch(act.graph, e->stream));
+        else for (auto& s : act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
         e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n);
         if (cfg->train_freq > 0 && t % cfg->train_freq == 0 && e->size >= e->B) { if (run_step(e, true)) return -1; trained++; }     // :134-139
         if (cfg->target_update_freq > 0 && t % cfg->target_update_freq == 0) { if (dqn_sync_target(e)) return -1; }                // :142-145

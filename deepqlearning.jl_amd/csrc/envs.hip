@@ -32,6 +32,26 @@ __device__ __forceinline__ int cdf_pick(const float* __restrict__ cdf, int n, fl
     }
     return base;
 }
+// SoftmaxPolicy (the law: include/dqn_mi355x.h; POMDPTools' SoftmaxPolicy.action, third-party, recalled): q(k) = the copy's Q value of action k, recomputed per pass
+// (the same operations on the same operands: the same bits) instead of kept in a per-lane array.  z_k = q_k / tau, m = max z, w_k = expf(z_k - m), c_k = c_{k-1} + w_k
+// ascending, target = u * c_{nA-1}: the first k with target < c_k, else the last k at which c still rose -- cdf_pick's rule on a cumulative row that is never stored.
+// The trip counts depend on nA alone (uniform across the lanes); the result always lies in [0, nA - 1]
+template <class QF>
+__device__ __forceinline__ int softmax_pick(QF q, int nA, float tau, float u) {
+    float m = q(0) / tau;
+    for (int k = 1; k < nA; k++) { const float z = q(k) / tau; m = z > m ? z : m; }
+    float tot = 0.0f;
+    for (int k = 0; k < nA; k++) tot = tot + expf(q(k) / tau - m);
+    const float target = u * tot;
+    float c = 0.0f; int first = -1, rose = 0;
+    for (int k = 0; k < nA; k++) {
+        const float cn = c + expf(q(k) / tau - m);
+        if (cn > c) rose = k;
+        if (first < 0 && target < cn) first = k;
+        c = cn;
+    }
+    return first >= 0 ? first : rose;
+}
 enum { TAB_NEXT = DQN_ENV_RAND_TAB_NEXT, TAB_OBS = DQN_ENV_RAND_TAB_OBS, TAB_INIT = DQN_ENV_RAND_TAB_INIT, TAB_INIT_OBS = DQN_ENV_RAND_TAB_INIT_OBS };
 
 // element f of the observation of an env in state (sw = the 4 TestMDP state bytes packed little-endian | px, py; tabular: px = the observation index).  No local
@@ -167,6 +187,13 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
     const long long start = REC ? 0 : (rs->widx + n) % R.cap;
     float eps = rs->eps_start - (float)t * ((rs->eps_start - rs->eps_stop) / rs->eps_steps);     // LinearDecaySchedule, fp32
     if (!(rs->eps_steps > 0.0f) || eps < rs->eps_stop) eps = rs->eps_stop;
+    // a table of per-step values (dqn_rollout_explore) replaces the linear law: eps itself, or the softmax temperature.  Uniform: every thread reads the same record
+    const float* const xtab = rs->xtab; const bool softmax = xtab && rs->xkind == DQN_EXPLORE_SOFTMAX; float tau = 1.0f;
+    if (xtab) {
+        long long j = (long long)t - rs->xtab_t0; j = j < 0 ? 0 : j; j = j >= rs->xtab_n ? rs->xtab_n - 1 : j;
+        const float xv = xtab[j];
+        if (softmax) tau = xv; else eps = xv;
+    }
     // head outputs of the acting forward -> LDS in one round of independent loads (split-K slabs included); the per-env
     // reduction below then adds them in canonical (ascending-slab) order out of LDS
     __shared__ float hl[ENV_HEAD_LDS];
@@ -226,11 +253,12 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
         else if (V.kind == DQN_ENV_TABULAR) V.tb_oprev[i] = V.tb_o[i];
         else { V.gw_prev[i * 2] = V.gw_pos[i * 2]; V.gw_prev[i * 2 + 1] = V.gw_pos[i * 2 + 1]; }
         int a = 0;
-        {   // Q column without per-lane arrays (they would live in scratch): advantages are re-read for the second pass
-            auto adv_k = [&](int k) -> float {
-                return in_lds ? hl[(k * Sa) * n + i] : head_val(Hd.adv, k, i);
-            };
-            float v = 0.0f, mean = 0.0f;
+        float v = 0.0f, mean = 0.0f;
+        // Q column without per-lane arrays (they would live in scratch): advantages are re-read for the second pass
+        auto adv_k = [&](int k) -> float {
+            return in_lds ? hl[(k * Sa) * n + i] : head_val(Hd.adv, k, i);
+        };
+        {
             if (Hd.dueling) {
                 v = in_lds ? hl[(Sa * V.nA) * n + i] : head_val(Hd.val, 0, i);
                 float sum = adv_k(0);
@@ -245,7 +273,8 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
             }
             Hd.amax[i] = a;
         }
-        if (u01(env_rand(V.seed, t, i, 1u)) < eps) a = (int)(env_rand(V.seed, t, i, 2u) % (uint32_t)V.nA);
+        if (softmax) a = softmax_pick([&](int k) -> float { const float ak = adv_k(k); return Hd.dueling ? (v + ak) - mean : ak; }, V.nA, tau, u01(env_rand(V.seed, t, i, DQN_ENV_RAND_SOFTMAX)));
+        else if (u01(env_rand(V.seed, t, i, 1u)) < eps) a = (int)(env_rand(V.seed, t, i, 2u) % (uint32_t)V.nA);
         float r; unsigned char done;
         if (V.kind == DQN_ENV_TESTMDP) {
             signed char* s = V.tm_s + i * 4;

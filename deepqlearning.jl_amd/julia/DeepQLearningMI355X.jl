@@ -469,11 +469,38 @@ function evaluate(e::Engine, n_eval, max_episode_length; seed = 0)              
     check(ccall((:dqn_evaluate, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, UInt64, Ref{Float64}, Ref{Float64}), e.h, n_eval, max_episode_length, seed, r, st))
     r[], st[]
 end
+# ---- exploration on the device loop (dqn_exploration / dqn_rollout_explore): POMDPTools' EpsGreedyPolicy and SoftmaxPolicy with any schedule.  The schedule is
+# evaluated HERE, per vector step, and rounded to Float32; the device only reads the table.  A LinearDecaySchedule (or a constant eps) stays on dqn_rollout's own fp32
+# law, so existing trajectories do not move
+struct Exploration
+    kind::Int32; n_values::Int32; values::Ptr{Float32}
+end
+const EXPLORE_EPS_GREEDY = Int32(0)
+const EXPLORE_SOFTMAX = Int32(1)
+# (kind, values) for vector steps t0 .. t0 + n - 1, or `nothing` where dqn_rollout's linear law serves the policy
+exploration_table(p::POMDPTools.SoftmaxPolicy, t0, n) = (EXPLORE_SOFTMAX, Float32[p.temperature(t) for t in t0:t0+n-1])
+function exploration_table(p::POMDPTools.EpsGreedyPolicy, t0, n)
+    p.eps isa POMDPTools.LinearDecaySchedule && return nothing
+    (EXPLORE_EPS_GREEDY, Float32[p.eps(t) for t in t0:t0+n-1])
+end
+linear_eps(p::POMDPTools.EpsGreedyPolicy) = p.eps isa POMDPTools.LinearDecaySchedule ? (Float32(p.eps.start), Float32(p.eps.stop), Float32(p.eps.steps)) : (1f0, 0.01f0, 5000f0)
+linear_eps(p) = (1f0, 0.01f0, 5000f0)
 # env_step_cadence = true: train_freq / target_update_freq count ENV steps as dqn_train! does (src/solver.jl:136-145) -- n / train_freq train steps per vector step
-function rollout!(e::Engine, n_steps; t0 = 1, train_freq = 4, target_update_freq = 500, eps = (1f0, 0.01f0, 5000f0), env_step_cadence = false)
+# explore = an exploration policy: its eps / temperature schedule drives the call (eps is then ignored unless the policy's schedule is a LinearDecaySchedule)
+function rollout!(e::Engine, n_steps; t0 = 1, train_freq = 4, target_update_freq = 500, eps = (1f0, 0.01f0, 5000f0), env_step_cadence = false, explore = nothing)
     st = RolloutStats()
-    check(ccall((:dqn_rollout, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{RolloutCfg}, Ref{RolloutStats}), e.h, n_steps,
-                RolloutCfg(train_freq, target_update_freq, eps[1], eps[2], eps[3], env_step_cadence ? 1 : 0, t0), st))
+    tab = explore === nothing ? nothing : exploration_table(explore, t0, n_steps)
+    explore === nothing || tab !== nothing || (eps = linear_eps(explore))
+    cfg = RolloutCfg(train_freq, target_update_freq, eps[1], eps[2], eps[3], env_step_cadence ? 1 : 0, t0)
+    if tab === nothing
+        check(ccall((:dqn_rollout, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{RolloutCfg}, Ref{RolloutStats}), e.h, n_steps, cfg, st))
+    else
+        kind, vals = tab
+        GC.@preserve vals begin
+            x = Exploration(kind, length(vals), pointer(vals))
+            check(ccall((:dqn_rollout_explore, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{RolloutCfg}, Ref{Exploration}, Ref{RolloutStats}), e.h, n_steps, cfg, x, st))
+        end
+    end
     st
 end
 

@@ -10,7 +10,7 @@ behaviour as src/DeepQLearning.jl:19-33 exports -- driving the HIP engine throug
                                  update_priorities, populate_replay_buffer, is_full, max_size
     NNPolicy(AbstractNNPolicy)   src/policy.jl:1-76: getnetwork, resetstate, actionmap, action, actionvalues, value
     basic_evaluation             src/evaluation_policy.jl:17-42
-    EpsGreedyPolicy / LinearDecaySchedule   POMDPTools (third-party; the exploration policy the reference's tests use)
+    EpsGreedyPolicy / SoftmaxPolicy / LinearDecaySchedule   POMDPTools (third-party, recalled; the exploration policies the reference's users pass)
 
 Environments follow envs.py (reset / observe / act / terminated on n lock-stepped copies; the reference steps n=1).
 Errors are DQNError carrying the reference's strings.  There is no CPU fallback.
@@ -55,6 +55,62 @@ class EpsGreedyPolicy:
 
     def loginfo(self, t):
         return {"eps": self.eps(t)}
+
+
+def softmax_pick(q, tau, u):
+    """The softmax law of include/dqn_mi355x.h in NumPy fp32, for one Q column: z = q / tau, m = max z, w = exp(z - m), c = running sum in ascending k,
+    target = u * c[-1]; the first k with target < c[k], else the last k at which c still rose (a weight that underflowed to zero is never picked)."""
+    q, tau, u = np.asarray(q, np.float32), np.float32(tau), np.float32(u)
+    z = q / tau
+    w = np.exp(z - z.max(), dtype=np.float32)
+    c, acc, rose = [], np.float32(0), 0
+    for k in range(q.size):
+        nxt = np.float32(acc + w[k])
+        if nxt > acc:
+            rose = k
+        acc = nxt
+        c.append(acc)
+    target = np.float32(u * acc)
+    for k in range(q.size):
+        if target < c[k]:
+            return k
+    return rose
+
+
+class SoftmaxPolicy:
+    """POMDPTools' SoftmaxPolicy (third-party; recalled): a ~ softmax(Q(obs) / temperature(t)); temperature is a number, a schedule or any function of the step."""
+
+    def __init__(self, env, temperature, rng=None):
+        self.n_actions = env.n_actions
+        self.schedule = temperature
+        self.temperature = temperature if callable(temperature) else (lambda t, v=temperature: v)
+        self.rng = rng if rng is not None else np.random.default_rng(1)
+
+    def action(self, policy, t, obs):
+        """action(exploration_policy, policy, t, obs) for a batch of n observations: one uniform draw per observation, the law of softmax_pick"""
+        q = np.asarray(policy.actionvalues(obs), np.float32)
+        tau = float(self.temperature(t))
+        if not (tau > 0 and np.isfinite(tau)):
+            raise DQNError(f"SoftmaxPolicy: temperature({t}) = {tau} is not a finite positive number")
+        u = self.rng.random(q.shape[0], dtype=np.float32)
+        return np.array([softmax_pick(q[i], tau, u[i]) for i in range(q.shape[0])], np.int64)
+
+    def loginfo(self, t):
+        return {"temperature": self.temperature(t)}
+
+
+def exploration_table(pol, t0, n_steps):
+    """What the device loop is told for vector steps t0 .. t0 + n_steps - 1: dict(eps=(start, stop, steps)) for a LinearDecaySchedule or a plain number (the
+    engine's own fp32 law: existing trajectories stay bit-identical), else dict(explore=(kind, fp32 values)) with the schedule evaluated here, step by step."""
+    if isinstance(pol, SoftmaxPolicy):
+        return dict(explore=("softmax", np.array([pol.temperature(t) for t in range(t0, t0 + n_steps)], np.float32)))
+    sch = getattr(pol, "schedule", None)
+    if isinstance(sch, LinearDecaySchedule):
+        return dict(eps=(sch.start, sch.stop, sch.steps))
+    if not callable(sch):
+        v = float(pol.eps(1))
+        return dict(eps=(v, v, 1.0))
+    return dict(explore=("eps", np.array([pol.eps(t) for t in range(t0, t0 + n_steps)], np.float32)))
 
 
 # ------------------------------------------------------------------ replay protocol
@@ -382,17 +438,11 @@ def populate_episode_replay_device(solver, env, engine):
 
 def dqn_train_device(solver, env, policy, replay):
     """dqn_train! (src/solver.jl:59-178) with the env loop on the device: `env` is only the SPEC (images, grid, rewards) of the
-    env.n copies that dqn_envs_create builds in HBM; exploration uses the engine's Philox eps-greedy with the solver's
-    LinearDecaySchedule.  Differences from the host loop: evaluation runs right at t % eval_freq == 0 (not at the next
+    env.n copies that dqn_envs_create builds in HBM; exploration uses the engine's Philox draws: eps-greedy with the solver's
+    LinearDecaySchedule (or number) on the engine's own law, any other eps schedule or a SoftmaxPolicy as a per-step table (exploration_table).  Differences from the host loop: evaluation runs right at t % eval_freq == 0 (not at the next
     episode end); the default basic_evaluation runs on the device too (dqn_evaluate), a user-supplied one on the host copy."""
     e = policy.engine
     e.sync_target()
-    sch = getattr(solver.exploration_policy, "schedule", None)
-    if isinstance(sch, LinearDecaySchedule):
-        eps = (sch.start, sch.stop, sch.steps)
-    else:
-        v = float(solver.exploration_policy.eps(1))
-        eps = (v, v, 1.0)
     if solver.recurrence and not envs.is_tabular(env):           # (a tabular env was prefilled on the host, initialize_replay_buffer)
         populate_episode_replay_device(solver, env, e)      # then the env set is created again under the solver's seed; committed episodes stay
     e.envs_create(env, n_envs=env.n, max_episode_length=solver.max_episode_length, seed=solver.seed)
@@ -402,7 +452,7 @@ def dqn_train_device(solver, env, policy, replay):
     save_next = False                                  # set at t % save_freq == 0, consumed at the next evaluation (src/solver.jl:109-113,150-152)
     while t <= solver.max_steps:
         nxt = min(min((t + m - 1) // m * m for m in marks), solver.max_steps)      # run up to the next eval/log/save boundary
-        st = e.rollout(nxt - t + 1, t0=t, train_freq=solver.train_freq, target_update_freq=solver.target_update_freq, eps=eps)
+        st = e.rollout(nxt - t + 1, t0=t, train_freq=solver.train_freq, target_update_freq=solver.target_update_freq, **exploration_table(solver.exploration_policy, t, nxt - t + 1))
         t = nxt + 1
         d_eps, d_rew = st["episodes"] - episodes, st["reward_sum"] - reward_sum
         episodes, reward_sum = st["episodes"], st["reward_sum"]
@@ -420,7 +470,8 @@ def dqn_train_device(solver, env, policy, replay):
                 save_next = False
         if nxt % solver.log_freq == 0 and solver.verbose:
             avg = d_rew / d_eps if d_eps else float("nan")
-            print(f"{nxt:5d} / {solver.max_steps:5d} eps {max(eps[1], eps[0] - nxt * (eps[0] - eps[1]) / eps[2]):0.3f} |  avgR {avg:1.3f} | "
+            name, val = next(iter(solver.exploration_policy.loginfo(nxt).items()))
+            print(f"{nxt:5d} / {solver.max_steps:5d} {name} {val:0.3f} |  avgR {avg:1.3f} | "
                   f"Loss {st['loss']:2.3e} | Grad {st['grad_norm']:2.3e} | EvalR {scores_eval:1.3f}")
     if model_saved and solver.verbose:
         restore_best_model(solver, policy)

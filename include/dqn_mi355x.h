@@ -312,6 +312,28 @@ typedef struct {
 int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* spec);
 int dqn_envs_reset(dqn_engine_t* e);
 int dqn_rollout(dqn_engine_t* e, int n_vector_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* stats_or_null);
+/* ---- exploration by table: POMDPTools' two exploration policies, EpsGreedyPolicy and SoftmaxPolicy, each with any schedule (a number, a LinearDecaySchedule, any
+ * function of the step).  The HOST evaluates the schedule and rounds it to fp32; the device only reads the table: values[j] is eps (DQN_EXPLORE_EPS_GREEDY) or the
+ * temperature tau (DQN_EXPLORE_SOFTMAX) of vector step cfg->t0 + j; n_values is n_vector_steps, or 1 for a constant.  x == NULL is exactly dqn_rollout; with x given
+ * cfg->eps_* are ignored.  Feed-forward and recurrent engines, the three env kinds, both cadences, every graph mode; dqn_evaluate stays greedy.  A rollout with a
+ * table takes the general four-launch tail (the fused tail, act_head.hip, serves the linear law only); dqn_envs_info keeps reporting what dqn_rollout uses.
+ *
+ * EPS TABLE.  rand < eps ? random action : greedy stays as it is (purposes 1 and 2, u01(...) < eps); only eps changes, to values[t - t0].  eps = 1 always
+ * explores (u01 < 1), eps = 0 never does.
+ *
+ * SOFTMAX (POMDPTools' SoftmaxPolicy.action: vals ./ tau, subtract the maximum, exp, normalise, weighted sample -- third-party, recalled and not executed here).  In
+ * fp32, on the Q column q_0 .. q_{nA-1} the step computes anyway (what dqn_envs_peek's actions are the argmax of when nothing explores):
+ *     z_k = q_k / tau (IEEE division);  m = max_k z_k;  w_k = expf(z_k - m) (the device library's expf, no fast intrinsic);  c_k = c_{k-1} + w_k in ascending k (c_{-1} = 0);
+ *     target = u * c_{nA-1},  u = u01(philox(seed, t, i, DQN_ENV_RAND_SOFTMAX)).
+ * The pick is the first k with target < c_k.  If none qualifies, the last k with c_k > c_{k-1} -- so an action whose weight underflowed to zero is never picked (the
+ * rule of the tabular kind's draws).  On a recurrent engine nothing else changes: every vector step advances every copy's Recur state.
+ *
+ * Refused before anything is enqueued, each with a message naming the offending value and its index: an unknown kind; n_values neither 1 nor n_vector_steps; NULL
+ * values; eps outside [0, 1] or NaN; tau <= 0 or not finite.  A refused call leaves the env set as it was. */
+enum { DQN_EXPLORE_EPS_GREEDY = 0, DQN_EXPLORE_SOFTMAX = 1 };
+enum { DQN_ENV_RAND_SOFTMAX = 11 };            /* Philox purpose of the softmax draw; 1-10 are taken */
+typedef struct { int32_t kind; int32_t n_values; const float* values; } dqn_exploration;
+int dqn_rollout_explore(dqn_engine_t* e, int n_vector_steps, const dqn_rollout_cfg* cfg, const dqn_exploration* x, dqn_rollout_stats* stats_or_null);
 /* basic_evaluation (src/evaluation_policy.jl:17-42; cadence src/solver.jl:101-122) batched on the device: n_eval
  * further copies of the MDP given to dqn_envs_create each run ONE greedy episode (while !done && step <= max_episode_length); returns
  * the average undiscounted return (Float64 sum of the Float32 rewards, as r_tot) and the average step count. */
