@@ -48,6 +48,8 @@ def julia_param_shapes(net):
         elif l.kind == "rnn":    # Flux 0.14 Recur(RNNCell): Wi, Wh, b, state0 = h0 as an (out, 1) matrix
             h = l.n_out
             out += [((h, l.n_in), h * l.n_in), ((h, h), h * h), ((h,), h), ((h, 1), h)]
+        elif l.kind == "layernorm":   # Flux 0.14 LayerNorm(n): diag = Scale(n): scale (n), then bias (n)
+            out += [((l.n,), l.n), ((l.n,), l.n)]
         elif l.kind in ("maxpool", "meanpool"):   # Flux.params(MaxPool / MeanPool) is empty: the file holds no array for the layer
             continue
         else:

@@ -41,6 +41,11 @@ static inline __host__ __device__ bool is_recurrent(int kind) { return kind == D
 // Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
 static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
 static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind); }      // the layer's output is a (cout, oh, ow) map
+// Flux LayerNorm (layernorm.hip): K = N = n features in and out, a parameter block of 2n floats (scale at w_off, bias at b_off = w_off + n -- NOT K * N weights: layer_wn),
+// the fp32 bit pattern of eps in cin (0 = 1f-5); launched alone on its level, as pools are
+static inline __host__ __device__ bool is_ln(int kind) { return kind == DQN_LAYER_LAYERNORM; }
+static inline float ln_eps(const LayerDev& L) { if (L.cin == 0) return 1e-5f; float f; memcpy(&f, &L.cin, sizeof f); return f; }
+static inline __host__ __device__ size_t layer_wn(const LayerDev& L) { return is_ln(L.kind) ? (size_t)L.N : (size_t)L.K * L.N; }      // floats in front of the layer's bias
 // a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 
@@ -741,6 +746,7 @@ struct DrqnColsArgs {
 // the column-group size of the fused recurrent step for this network, 0 = not covered (the twin restates this rule: oracle/dqn_ref.c fused_cg)
 static inline int drqn_fused_cg(const LayerDev* L, int nl, int E, int B, int T, int nA, int dueling, int double_q, int recurrence) {
     if (!recurrence) return 0;
+    for (int i = 0; i < nl; i++) if (is_ln(L[i].kind)) return 0;      // a network with a LayerNorm layer takes the multi-launch recurrent program
     const int duel = dueling ? 1 : 0;
     if (nl != (duel ? 3 : 2) || L[0].kind != DQN_LAYER_LSTM || L[0].stream != DQN_STREAM_BASE || L[0].src >= 0) return 0;
     const int H = L[0].H, N = 4 * H;
@@ -986,6 +992,11 @@ void launch_gemm_dwdx(hipStream_t st, const LayerDev& Lw, int nprob, const float
 // (reduce == false leaves split-K partial slabs in `partials` for the caller's batched k_reduce_multi)
 // pool.hip: MaxPool / MeanPool over Y[feature][column]; the backward gathers dY per input element and applies the producing layer's activation derivative
 void launch_pool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/);
+// layernorm.hip: Flux LayerNorm over Y[feature][column].  stat (optional): [2][ncols] floats, mu then sigma per column, kept by the online pass for the backward
+void launch_ln_fwd(hipStream_t st, const LayerDev& L, const float* P, const float* X, int ldx, int col0, int ncols, float* Y /*[n][ncols]*/, float* stat);
+// dpre[n][B] = dY .* act'(y) (written by the layer above); X[n][ld] the layer's input (online net, s columns 0 .. B); stat[2][ld_stat] from the forward.
+// dX[n][B] = (gradient of the law) .* act_src'(X); g_scale[n], g_bias[n] = the column sums.  Two launches
+void launch_ln_bwd(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, float* dX, int act_src, float* g_scale, float* g_bias);
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
                      float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');

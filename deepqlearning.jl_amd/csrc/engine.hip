@@ -99,6 +99,19 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             l.cin = l.cout = c; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
             l.ih = h; l.iw = w; l.oh = (h - l.kh) / l.sh + 1; l.ow = (w - l.kw) / l.sw + 1;      // trailing rows / columns no window covers are dropped
             l.K = 0; l.N = 0; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
+        } else if (is_ln(l.kind)) {      // Flux LayerNorm(n, act; affine = true, eps) (layernorm.hip): per column over the n incoming features; K = N = n, parameters scale (n), bias (n)
+            if (prev < 0) return fail("layer %d: LayerNorm cannot be the first layer (it must directly follow a Dense or recurrent layer)", i);
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: LayerNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (has_map(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
+            if (is_ln(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a LayerNorm layer)", i, prev);
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: LayerNorm n_in %d != n_out %d (both carry the size n)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_out < 2) return fail("layer %d: LayerNorm size n = %d must be >= 2 (over one feature sigma is identically 0 and the gradient is NaN)", i, d[i].n_out);
+            if (d[i].n_in != l.in_feat) return fail("layer %d: LayerNorm size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID) return fail("layer %d: LayerNorm activation %d is not one of DQN_ACT_*", i, d[i].act);
+            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: LayerNorm uses n_in, n_out, act and cin (the bit pattern of eps) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
+            l.cin = d[i].cin;      // the fp32 bit pattern of eps, 0 = the default 1f-5 (ln_eps)
+            { const float eps = ln_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: LayerNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].cin); }
+            l.K = l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
@@ -117,8 +130,9 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
             l.h0_off = off; off += l.H; if (has_c) { l.c0_off = off; off += l.H; } off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
         } else {
-            l.ew_off = eoff; eoff += (size_t)l.K * l.N; l.eb_off = eoff; eoff += l.N;
-            off = (off + 3) / 4 * 4; l.w_off = off; off += (size_t)l.K * l.N; l.b_off = off; off += l.N;
+            const size_t wn = layer_wn(l);      // K * N weights; a LayerNorm's scale vector (N)
+            l.ew_off = eoff; eoff += wn; l.eb_off = eoff; eoff += l.N;
+            off = (off + 3) / 4 * 4; l.w_off = off; off += wn; l.b_off = off; off += l.N;
         }
         if (l.stream == DQN_STREAM_BASE) *lb = i; else if (l.stream == DQN_STREAM_VAL) *lv = i; else *la = i;
     }
@@ -128,6 +142,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             return fail("DeepQLearningError: the qnetwork provided is incompatible with dueling");   // src/dueling.jl:47
     } else if (*lb < 0 || L[*lb].out_feat != hp->n_actions) return fail("network output size != n_actions");
     if (!hp->dueling && is_pool(L[*lb].kind)) return fail("layer %d: a MaxPool / MeanPool layer cannot be the network's output layer", *lb);
+    if (!hp->dueling && is_ln(L[*lb].kind)) return fail("layer %d: a LayerNorm layer cannot be the network's output layer", *lb);
     if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
     return 0;
 }
@@ -155,6 +170,7 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
     bool rec = false; for (int i = 0; i < n; i++) rec = rec || is_recurrent(L[i].kind);
     for (int i = 0; i < n; i++) {
         out[i].fwd_kc = 0;
+        if (is_ln(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: the layer's sums have one fixed order (layernorm.hip)
         // (small batches only: at B >= 128 the 3 B columns of a step already fill the chip -- 512 workgroups for the 3136 -> 512 layers of config 5 --
         // and the split only bought slab traffic plus a reduce launch: 16 us of the 807 us step, r03_g)
         if (L[i].K > 1024 && B < 128) { const int s = (L[i].K + 511) / 512; int kc = (L[i].K + s - 1) / s; kc = (kc + 3) / 4 * 4; out[i].fwd_kc = kc; }
@@ -246,13 +262,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
                        (((long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("DQN_SIM_WORLD: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
+    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
     if (!plan) { default_plan(e->L, e->nl, e->B, defp, hp); plan = defp; }
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
-        if (is_pool(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool layer's plan entry is ignored
+        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm layer's plan entry is ignored
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
@@ -595,6 +612,7 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name) {
     prof_begin(e, name);
     if (is_pool(l.kind)) launch_pool_fwd(e->stream, l, X, ldx, col0, ncols, Y);
+    else if (is_ln(l.kind)) launch_ln_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, nullptr);
     else if (is_padded(l)) launch_cpad_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma, 0);      // the policy workspace holds floats
     else if (!(e->hp.use_mfma && launch_mfma_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials)))
         launch_valu_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials);
@@ -1099,6 +1117,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     // ... and none with a padded convolution either (conv_pad.hip)
     for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
+    for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;

@@ -190,6 +190,7 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
     if (!eval) ap.steps.push_back({"recur_reset", [=](dqn_engine* en) { launch_recur_reset(en->stream, Vc.pending, n, RS); }});
     auto fwd = [](dqn_engine* en, const LayerDev& l, const float* P, const float* X, int n, float* Y, bool mf) {      // fwd_layer without its profiling bracket (the step has its own)
         if (is_pool(l.kind)) launch_pool_fwd(en->stream, l, X, n, 0, n, Y);
+        else if (is_ln(l.kind)) launch_ln_fwd(en->stream, l, P, X, n, 0, n, Y, nullptr);
         else if (is_padded(l)) launch_cpad_fwd(en->stream, l, P, X, n, 0, n, Y, mf ? 1 : 0, 0);
         else if (!(mf && launch_mfma_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials))) launch_valu_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials);
     };
@@ -236,8 +237,9 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     // (the conditions of the train step's fused reduce + head launch, engine_program.hip); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
     bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
+    bool any_ln = false; for (int i = 0; i < e->nl; i++) any_ln = any_ln || is_ln(e->L[i].kind);      // ... and so does a network with a LayerNorm layer (layernorm.hip): fused_tail = 0
     const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
-    bool use_ah = !general && !e->opt.no_act_head && levels.size() >= 2 && !any_padded && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
+    bool use_ah = !general && !e->opt.no_act_head && levels.size() >= 2 && !any_padded && !any_ln && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
     if (use_ah) {
         const LayerDev& La = e->L[lq]; ah_pa = La.src; ah_pv = lvh >= 0 ? e->L[lvh].src : -1;
         bool ok = La.kind == DQN_LAYER_DENSE && ah_pa >= 0 && (lvh < 0 || (e->L[lvh].kind == DQN_LAYER_DENSE && ah_pv >= 0 && ah_pv != ah_pa));
@@ -260,6 +262,11 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
         if (is_pool(e->L[lv[0]].kind)) {      // a pool layer: one launch on the n columns (pool.hip), never grouped with a GEMM layer
             const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
             ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, n, 0, n, Y); }});
+            continue;
+        }
+        if (is_ln(e->L[lv[0]].kind)) {      // a LayerNorm layer: one launch on the n columns (layernorm.hip), never grouped
+            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = e->pol_act[L.src]; float* Y = e->pol_act[l];
+            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_ln_fwd(en->stream, L, P, X, n, 0, n, Y, nullptr); }});
             continue;
         }
         if (is_padded(e->L[lv[0]])) {      // a padded conv: one launch on the n columns (conv_pad.hip), never grouped

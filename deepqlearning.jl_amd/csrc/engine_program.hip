@@ -35,7 +35,7 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
     segs.clear();
 }
 const char* pname(dqn_engine* e, const char* op, int kind, int i) {
-    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
+    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
 int build_program(dqn_engine* e) {
     if (e->prog_built) return 0;
@@ -45,6 +45,10 @@ int build_program(dqn_engine* e) {
     e->prog_names.reserve(512);
     const int B = e->Bc /* columns of one sequence set: batch_size, or T*batch_size for DRQN */, ncon = e->ncon, ld0 = 2 * B, Bb = e->B, T = e->T;
     const bool mf = e->hp.use_mfma != 0, rec = e->hp.recurrence != 0;
+    // a LayerNorm layer (layernorm.hip) is launched alone, as a pool is; every fusion below that pairs a layer with a neighbour or swallows the whole step (the fused recurrent
+    // step, the single-workgroup step, the fused reduce + head launches) DECLINES a network that holds one, by name, instead of relying on its own shape tests
+    bool has_ln = false; for (int i = 0; i < e->nl; i++) has_ln = has_ln || is_ln(e->L[i].kind);
+    float* ln_stat[DQN_MAX_LAYERS] = {};      // per LayerNorm layer: (mu, sigma) of the online pass's columns, kept for the backward
     // forward views: an LSTM layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (a dense layer
     // K = n_in, N = 4H writing gx_*); the recurrence then runs as T small launches.
     LayerDev LV[DQN_MAX_LAYERS]; float *fwd_on[DQN_MAX_LAYERS], *fwd_tg[DQN_MAX_LAYERS];
@@ -62,7 +66,7 @@ int build_program(dqn_engine* e) {
         if (cgm) {
             if (!rec || !all_same) return fail("plan: column-group dW chunks (dw_kc < 0) need recurrence = true and the same dw_kc on every layer");
             const int nset = e->hp.double_q ? 3 : 2; const LayerDev& L0 = e->L[0];
-            bool ok = drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
+            bool ok = !has_ln && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
             if (ok) { ok = dqn_nchunks(L0.K, L0.fwd_kc) == 1; for (int i = 1; i < e->nl; i++) ok = ok && dqn_nchunks(e->L[i].N, e->L[i].dx_kc) == 1; }
             if (!ok) return fail("plan: column-group dW chunks (dw_kc = %d) need a network the fused recurrent step covers -- Chain(flattenbatch, LSTM, Dense) with or without the dueling split, "
                                  "H a multiple of 8 up to 64, unsplit input projection and head dX, ONE device without a communicator -- use dw_kc >= 0 (plan = NULL picks a plan that fits; with a communicator dqn_comm_init re-derives it)", -cgm);
@@ -110,7 +114,7 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
-    if (!rec && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
+    if (!rec && !has_ln && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
         (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
         bool ok = true; size_t fl = 0;
         TinyArgs a; memset(&a, 0, sizeof a);
@@ -177,7 +181,7 @@ int build_program(dqn_engine* e) {
     // k_reduce_multi (384 workgroups) + k_head_td (B workgroups)
     bool fuse_rh = false, rh_pm = false; int rh_pa = -1, rh_pv = -1, rh_S = 0; const float* rh_part[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // [stream][net]
     const float* rh_partT[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    if (fuse_heads && levels.size() >= 2 && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
+    if (fuse_heads && !has_ln && levels.size() >= 2 && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
         const LayerDev& La = e->L[ha_l]; rh_pa = La.src; rh_pv = hv_l >= 0 ? e->L[hv_l].src : -1;
         bool ok = rh_pa >= 0 && (hv_l < 0 || (rh_pv >= 0 && rh_pv != rh_pa));
         const auto& pl = levels[levels.size() - 2];
@@ -211,6 +215,17 @@ int build_program(dqn_engine* e) {
                 float** act = net ? e->act_tg : e->act_on;
                 const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
                 e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, ldx, col0, ncols, Y); }});
+            }
+            continue;
+        }
+        if (is_ln(e->L[lv[0]].kind)) {      // a LayerNorm layer (base chain only, so alone on its level): one launch per pass; the online pass keeps (mu, sigma) per column for the backward
+            const int l = lv[0]; const LayerDev L = e->L[l];
+            float* stat = ln_stat[l] = palloc(e, (size_t)2 * ncon);
+            for (int net = 0; net < 2; net++) {
+                float** act = net ? e->act_tg : e->act_on; const float* P = net ? e->p_tg : e->p_on;
+                const float* X = act[L.src]; const int ldx = net ? B : ncon, ncols = net ? B : ncon; float* Y = act[l]; float* st = net ? nullptr : stat;
+                if (net == 1 && e->opt.probe_no_tg) continue;
+                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_ln_fwd(en->stream, L, P, X, ldx, 0, ncols, Y, st); }});
             }
             continue;
         }
@@ -401,7 +416,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -515,6 +530,15 @@ int build_program(dqn_engine* e) {
                     const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act;
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
                 }
+                continue;
+            }
+            if (is_ln(L.kind)) {
+                // the layer above wrote dpre = dY .* act'(y) into this layer's dact through its own dX epilogue (this layer's activation is `act` like any other's).  Two launches
+                // (layernorm.hip): dX with the producing layer's activation derivative -- a recurrent producer's `act` is IDENTITY, so its dact is the cell's dH -- and the column
+                // sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
+                const float* P = e->p_on; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act; const float* stat = ln_stat[l];
+                float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
+                e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
                 continue;
             }
             if (is_padded(L)) {
@@ -651,7 +675,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;

@@ -564,7 +564,7 @@ __global__ void k_convert_params(const LayerDev* __restrict__ layers, int nl, co
     size_t j = i;
     for (int l = 0; l < nl; l++) {
         const LayerDev& L = layers[l];
-        const size_t wn = (size_t)L.K * L.N;
+        const size_t wn = layer_wn(L);      // a LayerNorm's scale vector sits where a GEMM layer's weights do
         if (i >= L.ew_off && i < L.ew_off + wn) {
             size_t e = i - L.ew_off;
             if (L.kind == DQN_LAYER_CONV) {      // external ((co*cin + ci)*kh + yy)*kw + xx, yy/xx un-flipped

@@ -69,6 +69,12 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.MeanPool
         any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MeanPool with pad=0 only")
         return LayerDesc(6, 0, stream, 0, 0, 0, 0, l.k[2], l.k[1], l.stride[2], l.stride[1])
+    elseif l isa Flux.LayerNorm      # Flux 0.14 fields λ, diag, ϵ, size, affine; Flux.params order diag.scale, diag.bias == the ABI's LayerNorm block
+        # normalise(x; dims, ϵ) = (x .- μ) ./ (σ .+ ϵ) with the uncorrected σ: ϵ is added OUTSIDE the root -- the engine runs this law, not torch's sqrt(var + eps).
+        # n in both size slots, the Float32 bit pattern of ϵ in cin (as a Conv's pad rides in n_in / n_out)
+        length(l.size) == 1 || throw("DeepQLearningError: the MI355X engine supports LayerNorm(n) with an integer n only, got size=$(l.size)")
+        (l.affine && l.diag isa Flux.Scale) || throw("DeepQLearningError: the MI355X engine supports LayerNorm with affine=true only")
+        return LayerDesc(7, ACT[l.λ], stream, l.size[1], l.size[1], reinterpret(Int32, Float32(l.ϵ)), 0, 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.LSTMCell     # Flux.params order Wi, Wh, b, state0 (h0, c0) == the ABI's LSTM block
         return LayerDesc(2, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (Flux's GRUv3 has another block: unsupported)
@@ -76,7 +82,7 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 function lower(q)

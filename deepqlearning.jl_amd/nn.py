@@ -113,6 +113,34 @@ class MeanPool(_Pool):
     kind = "meanpool"
 
 
+class LayerNorm:
+    """Flux 0.14 LayerNorm(n, λ = identity; affine = true, eps = 1f-5) on a feature vector of length n, per batch column (Flux's `normalise`; recalled, not executed here):
+    μ = mean(x), σ = sqrt(mean((x - μ)²)) (uncorrected), y = λ.(scale .* (x - μ) / (σ + eps) .+ bias) -- eps is added to σ OUTSIDE the root, which is not torch's
+    sqrt(var + eps).  Flux.params: diag.scale (n, ones), diag.bias (n, zeros).  Directly behind a Dense or recurrent layer, base chain only."""
+    kind = "layernorm"
+
+    def __init__(self, n, act=identity, eps=1e-5, affine=True):
+        if isinstance(n, (tuple, list)):
+            raise _abi.DQNError(f"DeepQLearningError: LayerNorm(size={tuple(n)!r}): a tuple size (normalisation over several dimensions) is not supported; the MI355X engine "
+                                "normalises a feature vector, LayerNorm(n) with an integer n")
+        if not affine:
+            raise _abi.DQNError(f"DeepQLearningError: LayerNorm({n}; affine=false) is not supported; the MI355X engine runs the layer with its scale and bias (affine=true)")
+        self.n, self.act, self.eps = int(n), act, float(eps)
+        if self.n < 2:
+            raise _abi.DQNError(f"DeepQLearningError: LayerNorm({self.n}): n must be >= 2 (over one feature σ is identically 0 and the gradient is NaN)")
+        with np.errstate(over="ignore"):
+            e32 = np.float32(self.eps)
+        if not (np.isfinite(e32) and e32 > 0):
+            raise _abi.DQNError(f"DeepQLearningError: LayerNorm({self.n}; eps={eps!r}): eps must be finite and > 0 in Float32")
+        self.n_in = self.n_out = self.n      # what a following Dense / the dueling split reads
+
+    def __repr__(self):
+        return f"LayerNorm({self.n}, act={self.act}, eps={self.eps!r})"
+
+    def shapes(self):   # Flux.params order: diag.scale, diag.bias
+        return [(self.n,), (self.n,)]
+
+
 class LSTM:
     """Flux LSTM(in, out) = Recur(LSTMCell): params Wi (4out,in), Wh (4out,out), b (4out, forget gate bias 1), state0 (h0, c0)."""
     kind = "lstm"
@@ -206,8 +234,8 @@ def lower(net):
     def add(chain, stream):
         for l in chain:
             d = _abi.LayerDesc()
-            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
             d.act, d.stream = l.act, stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -217,6 +245,9 @@ def lower(net):
                 d.kind, d.n_in, d.n_out = _abi.LAYER_GRU, l.n_in, l.n_out
             elif l.kind == "rnn":       # act carries the cell's σ
                 d.kind, d.n_in, d.n_out = _abi.LAYER_RNN, l.n_in, l.n_out
+            elif l.kind == "layernorm":      # n in both size slots; the fp32 bit pattern of eps rides in cin (as a Conv's pad rides in n_in / n_out)
+                d.kind, d.n_in, d.n_out = _abi.LAYER_LAYERNORM, l.n, l.n
+                d.cin = int(np.float32(l.eps).view(np.int32))
             elif l.kind in ("maxpool", "meanpool"):      # cin == cout == channels of the incoming map
                 d.kind = _abi.LAYER_MAXPOOL if l.kind == "maxpool" else _abi.LAYER_MEANPOOL
                 d.cin = d.cout = chan[0]
@@ -253,6 +284,9 @@ def glorot_params(net, seed=1):
     parts = []
     for l in all_layers(net):
         if l.kind in ("maxpool", "meanpool"):      # no parameters
+            continue
+        if l.kind == "layernorm":      # Flux Scale(n): scale = ones, bias = zeros
+            parts += [np.ones(l.n, np.float32), np.zeros(l.n, np.float32)]
             continue
         if l.kind == "lstm":
             h = l.n_out

@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7 };
 enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3 };
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
@@ -63,7 +63,12 @@ typedef struct {
                                           symmetric zero padding per axis, 0 <= pad_h <= kh - 1, 0 <= pad_w <= kw - 1 (0, 0 = no padding); output map
                                           (H + 2 pad_h - kh) / sh + 1 by (W + 2 pad_w - kw) / sw + 1; a padded Conv is base chain only and single GPU only;
                                           MaxPool((kh,kw); stride=(sh,sw)) / MeanPool(...), pad 0: cin == cout == channels of the incoming map (or both 0: the engine fills them in), act = IDENTITY,
-                                          no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored */
+                                          no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored;
+                                          LayerNorm(n, act; affine = true, eps) (Flux 0.14 `normalise`, recalled, not executed): n_in == n_out == n >= 2 == the incoming feature count, act = the
+                                          layer's activation, stream = BASE, cin = the fp32 BIT PATTERN of eps (0 = the default 1f-5; finite and > 0), every other slot 0.  Per batch column
+                                          mu = mean(x), sigma = sqrt(mean((x - mu)^2)), y = act(scale * (x - mu) / (sigma + eps) + bias): eps is added to sigma OUTSIDE the root (not torch's
+                                          sqrt(var + eps)).  Parameters in Flux.params order: scale (n), bias (n).  Directly behind a Dense or recurrent layer, base chain only, never the
+                                          output layer, single GPU only; its plan entry is ignored.  A column with sigma = 0 has a finite forward (x_hat = 0); its backward is undefined */
 } dqn_layer_desc;
 
 /* Summation-order plan of one layer: the K dimension of each contraction is cut
