@@ -158,7 +158,10 @@ template <class T> static int dmalloc(T** p, size_t n) {
 // engine.hip
 void drop_graphs(dqn_engine* e);
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a);
-void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name);
+// one layer's forward launched alone on the given columns, by kind: THE place (with emit_forward, engine_program.hip) where the forward side learns a new layer kind.
+// xu8: X is the byte arena of a u8 replay (padded convs only); ln_stat: where a LayerNorm layer keeps (mu, sigma) per column, or null; partials: split-K workspace of the GEMM kinds
+void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials);
+void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name);      // ... inside a profiling bracket
 void enqueue_step(dqn_engine* e, const StepKey& k);
 int capture_graph(dqn_engine* e, const char* what, const std::function<int()>& body, hipGraphExec_t* out);      // the one stream capture of the library
 int run_phase(dqn_engine* e, const StepKey& k, bool eager = false);      // the cached graph of k (captured on first use), or k enqueued eagerly
@@ -180,6 +183,32 @@ void add_valu(dqn_engine* e, std::vector<VTask>& pend, const VTask& t);
 void flush_valu(dqn_engine* e, std::vector<VTask>& pend, const char* name, const PrioArgs* prio = nullptr);
 void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name);
 const char* pname(dqn_engine* e, const char* op, int kind, int i);
+typedef std::vector<std::vector<int>> Levels;
+Levels net_levels(const dqn_engine* e);      // the launch levels of the network: the base chain one layer per level, then the (value, advantage) layers pairwise
+LayerDev gx_view(const LayerDev& l);         // a recurrent layer's batched part: its bias-free input projection Gx = Wi*x as a dense layer K = n_in, N = ngates*H
+// the layout half of the fused reduce + head launches (red_head.hip, act_head.hip): the dense heads ha (and hv, or -1) sit alone on the last level, their dense producers alone
+// on the level before, with equal width and split count, and the heads' plan chunks are 32 long and tile K exactly.  Returns the producers' split count S (0: another layout)
+int fused_head_layout(const dqn_engine* e, const Levels& levels, int ha, int hv, int* pa, int* pv);
+// One network pass of emit_forward, as data: the parameter vector, where the observation columns are, the activations a layer reads (in[src]) and writes (out[l]: differs
+// from in[l] for a recurrent layer, whose batched part writes its gx_* view) -- dense in the column, leading dimension = ncols -- and the tag of its single-pass launch names
+struct FwdPass { const float* P; const float* x0; int ldx0, col0; float* const* in; float* const* out; int ncols; const char* tag; };
+struct FwdEmit {
+    // ---- in
+    const char *gemm = nullptr, *valu = nullptr, *reduce = nullptr;      // launch-name prefixes of the grouped GEMM launch, the VALU task table and the split-K reduce of a level
+    bool skip_last = false;                // the last level runs inside the caller's fused head launch
+    int prod[2] = {-1, -1};                // the heads' producer layers (advantage / single stream, value) whose slabs or activations that launch reads unreduced ...
+    bool pm_ok = false;                    // ... and whether it reads slabs piece-major (GFwdProb::pm)
+    bool last_on_the_fly = false;          // the consumer of the last level reduces split-K slabs itself (HeadSrc::S > 1)
+    bool byte_arena = false;               // LayerDev::xu8 holds for the observation columns of these passes
+    const bool* wantT = nullptr;           // layers whose consumer reads a transposed copy [column][feature] of their output (null: none)
+    // ---- out (the arrays are the caller's)
+    float* (*actT)[2] = nullptr;           // per (layer, pass): the transposed copy of a wantT layer (needed with wantT)
+    float** ln_stat = nullptr;             // per LayerNorm layer: (mu, sigma) of the FIRST pass's columns, allocated here and kept for the backward (null: not kept)
+    HeadSrc (*head)[2] = nullptr;          // per (layer, pass): where the layer's output is found
+    const float *part[2][2] = {}, *partT[2][2] = {}; bool pm = false;      // per (producer stream, pass): slabs or finished activation, its transposed copy; slabs were written piece-major
+};
+// the forward launches of levels [li0, li1) into the current sink, for every pass: THE statement of the forward selection rules (train step and acting programs)
+void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, const std::vector<FwdPass>& passes, FwdEmit& E);
 int build_program(dqn_engine* e);
 // engine_envs.hip
 void free_envs(dqn_engine* e);

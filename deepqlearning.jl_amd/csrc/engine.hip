@@ -609,13 +609,15 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 }
 
 // ---------------------------------------------------------------- the train step
+void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials) {
+    if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
+    else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
+    else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
+    else if (!(use_mfma && launch_mfma_fwd(st, l, P, X, ldx, col0, ncols, Y, partials))) launch_valu_fwd(st, l, P, X, ldx, col0, ncols, Y, partials);
+}
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name) {
     prof_begin(e, name);
-    if (is_pool(l.kind)) launch_pool_fwd(e->stream, l, X, ldx, col0, ncols, Y);
-    else if (is_ln(l.kind)) launch_ln_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, nullptr);
-    else if (is_padded(l)) launch_cpad_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma, 0);      // the policy workspace holds floats
-    else if (!(e->hp.use_mfma && launch_mfma_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials)))
-        launch_valu_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->partials);
+    launch_layer_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma != 0, 0 /* the policy workspace holds floats */, nullptr, e->partials);
     prof_end(e);
 }
 
@@ -1084,8 +1086,7 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
         const LayerDev& l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src];
         if (is_recurrent(l.kind)) {      // one Recur step: Gx = Wi*x (bias-free view), then the cell with the carried h (and c)
             const CellOps* C = cell_ops(l.kind);
-            LayerDev V = l; V.kind = DQN_LAYER_DENSE; V.out_feat = l.N; V.b_off = l.z_off; V.act = DQN_ACT_IDENTITY;
-            fwd_layer(e, V, P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
+            fwd_layer(e, gx_view(l), P, X, n, 0, n, e->pol_gx[i], "policy_fwd");
             CellFwdArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.T = 1; a.nseq = 1; a.act = l.cell_act;
             CellSeq& q = a.s[0]; q.Gx = e->pol_gx[i]; q.Hout = e->pol_act[i]; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off;
             q.hprev = e->pol_h[i][fl]; q.hp_ld = n; q.hp_bs = 1;

@@ -188,20 +188,14 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
     const bool mf = e->hp.use_mfma != 0; const float* P = e->p_on;
     const RecurState RS = recur_state(e, eval); const EnvDev Vc = V; const EpStage ES = e->ep_stage;
     if (!eval) ap.steps.push_back({"recur_reset", [=](dqn_engine* en) { launch_recur_reset(en->stream, Vc.pending, n, RS); }});
-    auto fwd = [](dqn_engine* en, const LayerDev& l, const float* P, const float* X, int n, float* Y, bool mf) {      // fwd_layer without its profiling bracket (the step has its own)
-        if (is_pool(l.kind)) launch_pool_fwd(en->stream, l, X, n, 0, n, Y);
-        else if (is_ln(l.kind)) launch_ln_fwd(en->stream, l, P, X, n, 0, n, Y, nullptr);
-        else if (is_padded(l)) launch_cpad_fwd(en->stream, l, P, X, n, 0, n, Y, mf ? 1 : 0, 0);
-        else if (!(mf && launch_mfma_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials))) launch_valu_fwd(en->stream, l, P, X, n, 0, n, Y, en->partials);
-    };
     int k = 0;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src]; float* Y = e->pol_act[i];
-        if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l.kind, i), [=](dqn_engine* en) { fwd(en, l, P, X, n, Y, mf); }}); continue; }
+        if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l.kind, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, l, P, X, n, 0, n, Y, mf, 0, nullptr, en->partials); }}); continue; }
         const CellOps* C = cell_ops(l.kind);
-        LayerDev Vw = l; Vw.kind = DQN_LAYER_DENSE; Vw.out_feat = l.N; Vw.b_off = l.z_off; Vw.act = DQN_ACT_IDENTITY;      // Gx = Wi*x (bias-free view)
+        const LayerDev Vw = gx_view(l);
         float* gx = eval ? e->eval_gx[i] : e->pol_gx[i]; float* h = RS.h[k]; float* c = RS.c[k]; k++;
-        ap.steps.push_back({pname(e, "act_gx", l.kind, i), [=](dqn_engine* en) { fwd(en, Vw, P, X, n, gx, mf); }});
+        ap.steps.push_back({pname(e, "act_gx", l.kind, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, Vw, P, X, n, 0, n, gx, mf, 0, nullptr, en->partials); }});
         CellFwdArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.T = 1; a.nseq = 1; a.act = l.cell_act;
         CellSeq& q = a.s[0]; q.Gx = gx; q.Hout = Y; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off; q.hprev = h; q.hp_ld = n; q.hp_bs = 1;
         if (C->has_c) { q.Cst = c; q.cprev = c; q.cp_ld = n; q.cp_bs = 1; }
@@ -217,7 +211,8 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
     ap.n = n; ap.fused_tail = false; ap.state_gen = gen; ap.state_flip = flip; return 0;
 }
 // the acting program: online net forward on the n columns of pol_x (batch-innermost), then Q columns + first-max argmax
-// (action(policy, obs), src/policy.jl:38-64) -- the same tiled kernels and the same plan as the train step, compiled once per n
+// (action(policy, obs), src/policy.jl:38-64) -- the train step's forward emitter (emit_forward, engine_program.hip) with one pass: the same tiled kernels, plan and
+// selection rules, compiled once per n
 // general: keep the four-launch tail where the fused one would apply (a rollout that explores by table)
 static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs, bool general = false) {
     const int n = V.n;
@@ -227,106 +222,31 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     drop_act(e, ap);
     e->prog_names.reserve(512);
     e->sink = &ap.steps; e->alloc_sink = &ap.allocs;
-    const bool mf = e->hp.use_mfma != 0;
-    std::vector<std::vector<int>> levels; std::vector<int> val, adv;
-    for (int i = 0; i < e->nl; i++) { if (e->L[i].stream == DQN_STREAM_BASE) levels.push_back({i}); else if (e->L[i].stream == DQN_STREAM_VAL) val.push_back(i); else adv.push_back(i); }
-    for (size_t j = 0; j < std::max(val.size(), adv.size()); j++) { std::vector<int> lv; if (j < val.size()) lv.push_back(val[j]); if (j < adv.size()) lv.push_back(adv[j]); levels.push_back(lv); }
+    const Levels levels = net_levels(e);
     const float* P = e->p_on;
-    HeadSrc head[DQN_MAX_LAYERS];
+    HeadSrc head[DQN_MAX_LAYERS][2];      // [layer][0]: the acting forward is one pass
     // the fused tail (act_head.hip): reduce of the heads' producers + heads + Q / argmax + eps-greedy + act! + add_exp!'s per-experience part in ONE launch, where the shapes allow
-    // (the conditions of the train step's fused reduce + head launch, engine_program.hip); else k_reduce_multi + the heads' forward + k_env_step
+    // (the layout of the train step's fused reduce + head launch, fused_head_layout, + this kernel's own test); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
     bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
     bool any_ln = false; for (int i = 0; i < e->nl; i++) any_ln = any_ln || is_ln(e->L[i].kind);      // ... and so does a network with a LayerNorm layer (layernorm.hip): fused_tail = 0
     const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
-    bool use_ah = !general && !e->opt.no_act_head && levels.size() >= 2 && !any_padded && !any_ln && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0; bool ah_pm = false; const float* ah_part[2] = {nullptr, nullptr};
-    if (use_ah) {
-        const LayerDev& La = e->L[lq]; ah_pa = La.src; ah_pv = lvh >= 0 ? e->L[lvh].src : -1;
-        bool ok = La.kind == DQN_LAYER_DENSE && ah_pa >= 0 && (lvh < 0 || (e->L[lvh].kind == DQN_LAYER_DENSE && ah_pv >= 0 && ah_pv != ah_pa));
-        auto in_lv = [&](const std::vector<int>& v, int l) { for (int x : v) if (x == l) return true; return false; };
-        const auto& hl = levels.back(); const auto& pl = levels[levels.size() - 2];
-        if (ok) ok = (int)hl.size() == (lvh >= 0 ? 2 : 1) && in_lv(hl, lq) && (lvh < 0 || in_lv(hl, lvh)) && (int)pl.size() == (lvh >= 0 ? 2 : 1) && in_lv(pl, ah_pa) && (lvh < 0 || in_lv(pl, ah_pv));
-        if (ok) {
-            const LayerDev& Pa = e->L[ah_pa]; ah_S = dqn_nchunks(Pa.K, Pa.fwd_kc);
-            ok = Pa.kind == DQN_LAYER_DENSE && Pa.N == La.K && dqn_chunk_len(La.K, La.fwd_kc) == 32 && dqn_nchunks(La.K, La.fwd_kc) * 32 == La.K;
-            if (ok && lvh >= 0) { const LayerDev& Pv = e->L[ah_pv]; const LayerDev& Lv = e->L[lvh];
-                ok = Pv.kind == DQN_LAYER_DENSE && Pv.N == Pa.N && dqn_nchunks(Pv.K, Pv.fwd_kc) == ah_S && dqn_chunk_len(Lv.K, Lv.fwd_kc) == 32 && Lv.K == La.K; }
-            if (ok) ok = act_head_ok(n, La.K, ah_S, e->nA, lvh >= 0 ? 2 : 1, La.N, lvh >= 0 ? e->L[lvh].N : 0);
-        }
-        use_ah = ok;
-    }
-    for (size_t li = 0; li < levels.size(); li++) {
-        const auto& lv = levels[li]; const bool last = li + 1 == levels.size();
-        if (use_ah && last) break;                          // the head level runs inside k_act_head
-        const bool ah_prod = use_ah && li + 2 == levels.size();      // this level = the heads' producers: their slabs stay unreduced
-        if (is_pool(e->L[lv[0]].kind)) {      // a pool layer: one launch on the n columns (pool.hip), never grouped with a GEMM layer
-            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
-            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, n, 0, n, Y); }});
-            continue;
-        }
-        if (is_ln(e->L[lv[0]].kind)) {      // a LayerNorm layer: one launch on the n columns (layernorm.hip), never grouped
-            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = e->pol_act[L.src]; float* Y = e->pol_act[l];
-            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_ln_fwd(en->stream, L, P, X, n, 0, n, Y, nullptr); }});
-            continue;
-        }
-        if (is_padded(e->L[lv[0]])) {      // a padded conv: one launch on the n columns (conv_pad.hip), never grouped
-            const int l = lv[0]; const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; float* Y = e->pol_act[l];
-            HeadSrc h; h.p = Y; h.ld = n; h.S = 1; h.per_s = 0; h.bias = P + L.b_off; h.act = L.act; head[l] = h;
-            ap.steps.push_back({pname(e, "act_fwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, P, X, n, 0, n, Y, mf ? 1 : 0, 0); }});
-            continue;
-        }
-        struct Prob { int l; const float* X; float *Y, *part; int S; };
-        std::vector<Prob> pr;
-        for (int l : lv) { const LayerDev& L = e->L[l]; Prob q; q.l = l; q.X = L.src < 0 ? e->pol_x : e->pol_act[L.src]; q.Y = e->pol_act[l]; q.S = dqn_nchunks(L.K, L.fwd_kc);
-                           q.part = q.S > 1 ? palloc(e, (size_t)q.S * L.out_feat * n) : nullptr; pr.push_back(q); }
-        bool geo = true; for (int l : lv) geo = geo && same_geo(e->L[lv[0]], e->L[l]);
-        std::vector<bool> done(pr.size(), false);
-        auto emit_gemm = [&](const std::vector<int>& ids, const char* name) {
-            const LayerDev L = e->L[pr[ids[0]].l]; const int np = (int)ids.size();
-            struct A { const float *W[4], *bias[4], *X[4]; int ldx[4], col0[4], ncols[4]; float* out[4]; } a;
-            for (int i = 0; i < np; i++) { const Prob& q = pr[ids[i]]; const LayerDev& Lq = e->L[q.l]; a.W[i] = P + Lq.w_off; a.bias[i] = P + Lq.b_off; a.X[i] = q.X; a.ldx[i] = n; a.col0[i] = 0; a.ncols[i] = n; a.out[i] = q.S > 1 ? q.part : q.Y; }
-            // slabs only k_act_head reads are written piece-major (GFwdProb::pm), when ONE launch produces them all
-            const int pm = (ah_prod && ah_S > 1 && np == (int)pr.size() && !e->opt.no_rh_pm) ? 1 : 0; if (pm) ah_pm = true;
-            ap.steps.push_back({name, [=](dqn_engine* en) { launch_gemm_fwd(en->stream, L, np, a.W, a.bias, a.X, a.ldx, a.col0, a.ncols, a.out, nullptr, pm); }});
-            for (int id : ids) done[id] = true;
-        };
-        if (mf && pr.size() <= 4) {
-            int ldx[4], c0[4], nc[4]; std::vector<int> all;
-            for (size_t i = 0; i < pr.size(); i++) { all.push_back((int)i); ldx[i] = n; c0[i] = 0; nc[i] = n; }
-            if (geo && gemm_fwd_eligible(e->L[lv[0]], (int)pr.size(), ldx, c0, nc)) emit_gemm(all, pname(e, "act_fwd", e->L[lv[0]].kind, lv[0]));
-            else for (size_t i = 0; i < pr.size(); i++) if (gemm_fwd_eligible(e->L[pr[i].l], 1, ldx, c0, nc)) emit_gemm({(int)i}, pname(e, "act_fwd", e->L[pr[i].l].kind, pr[i].l));
-        }
-        std::vector<VTask> pend;
-        for (size_t i = 0; i < pr.size(); i++) {
-            if (done[i]) continue;
-            const Prob q = pr[i]; const LayerDev L = e->L[q.l];
-            if (mf && mfma_fwd_ok(L, n)) ap.steps.push_back({pname(e, "act_fwd", L.kind, q.l), [=](dqn_engine* en) { launch_mfma_fwd(en->stream, L, P, q.X, n, 0, n, q.Y, q.part, false); }});
-            else { VTask t; memset(&t, 0, sizeof t); t.kind = 0; t.L = L; t.P = P; t.X = q.X; t.ldx = n; t.col0 = 0; t.ncols = n; t.S = q.S; t.kc = dqn_chunk_len(L.K, L.fwd_kc); t.out = q.S > 1 ? q.part : q.Y; add_valu(e, pend, t); }
-        }
-        flush_valu(e, pend, pname(e, "act_fwd_valu", e->L[lv[0]].kind, lv[0]));
-        std::vector<RSeg> segs;
-        for (const Prob& q : pr) {
-            const LayerDev& L = e->L[q.l];
-            HeadSrc h; h.p = q.Y; h.ld = n; h.S = 1; h.per_s = 0; h.bias = P + L.b_off; h.act = L.act;
-            if (ah_prod) { ah_part[q.l == ah_pa ? 0 : 1] = q.S > 1 ? q.part : q.Y; head[q.l] = h; continue; }      // reduced inside k_act_head (S == 1: the finished activation)
-            if (q.S > 1) {
-                if (last) { h.p = q.part; h.S = q.S; h.per_s = (unsigned long long)L.out_feat * n; }      // reduced on the fly by k_env_step
-                else { RSeg r; memset(&r, 0, sizeof r); r.part = q.part; r.S = q.S; r.elems = (unsigned long long)L.out_feat * n; r.mode = 0; r.bias = P + L.b_off; r.per_n = L.npos * n; r.act = L.act; r.out = q.Y; segs.push_back(r); }
-            }
-            head[q.l] = h;
-        }
-        emit_reduce(e, segs, pname(e, "act_reduce", e->L[lv[0]].kind, lv[0]));
-    }
+    bool use_ah = !general && !e->opt.no_act_head && !any_padded && !any_ln && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
+    if (use_ah) { ah_S = fused_head_layout(e, levels, lq, lvh, &ah_pa, &ah_pv); use_ah = ah_S > 0 && act_head_ok(n, e->L[lq].K, ah_S, e->nA, lvh >= 0 ? 2 : 1, e->L[lq].N, lvh >= 0 ? e->L[lvh].N : 0); }
+    // one pass on the n columns of pol_x; the last level's consumer (k_env_step) reduces split-K slabs on the fly; no transposed copies, no byte arena, no LayerNorm statistics
+    FwdEmit fe; fe.gemm = "act_fwd"; fe.valu = "act_fwd_valu"; fe.reduce = "act_reduce"; fe.skip_last = use_ah /* the head level runs inside k_act_head */; fe.last_on_the_fly = true; fe.head = head;
+    if (use_ah) { fe.prod[0] = ah_pa; fe.prod[1] = ah_pv; fe.pm_ok = ah_S > 1 && !e->opt.no_rh_pm; }
+    emit_forward(e, levels, 0, levels.size(), {{P, e->pol_x, n, 0, e->pol_act, e->pol_act, n, "act_fwd"}}, fe);
     ReplayMeta R; R.cap = e->cap; R.cap2 = e->cap2; R.a = e->ra; R.r = e->rr; R.done = e->rdone; R.tree = e->tree; R.state = e->state; R.eps = e->hp.prio_eps; R.alpha = e->hp.prio_alpha;
     const bool u8 = e->hp.obs_dtype == DQN_OBS_U8;
     void *srows = e->s_rows, *sprows = e->sp_rows; float* px = e->pol_x; const long long cap = e->cap; const EnvDev Vc = V;
     if (use_ah) {
         ActHeadArgs h; memset(&h, 0, sizeof h);
         const LayerDev& La = e->L[lq];
-        h.n = n; h.nA = e->nA; h.K = La.K; h.S = ah_S; h.nstream = lvh >= 0 ? 2 : 1; h.NO = e->nA + (lvh >= 0 ? 1 : 0); h.pm = ah_pm ? 1 : 0;
+        h.n = n; h.nA = e->nA; h.K = La.K; h.S = ah_S; h.nstream = lvh >= 0 ? 2 : 1; h.NO = e->nA + (lvh >= 0 ? 1 : 0); h.pm = fe.pm ? 1 : 0;
         for (int st = 0; st < 2; st++) {
             const int hl_ = (st == 1 && lvh >= 0) ? lvh : lq, pl_ = (st == 1 && lvh >= 0) ? ah_pv : ah_pa; const LayerDev& H = e->L[hl_]; const LayerDev& Pl = e->L[pl_]; ActHeadStream& T = h.st[st];
-            T.part = ah_part[(st == 1 && lvh >= 0) ? 1 : 0]; T.pbias = P + Pl.b_off; T.pact = Pl.act; T.W = P + H.w_off; T.hbias = P + H.b_off; T.N = H.N; T.hact = H.act;
+            T.part = fe.part[(st == 1 && lvh >= 0) ? 1 : 0][0]; T.pbias = P + Pl.b_off; T.pact = Pl.act; T.W = P + H.w_off; T.hbias = P + H.b_off; T.N = H.N; T.hact = H.act;
         }
         const int Gc = n / 4, NC = La.K / 32;
         h.partials = palloc(e, (size_t)Gc * 4 * h.NO * NC); h.tickets = (unsigned*)palloc(e, (size_t)Gc);
@@ -338,7 +258,7 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
         ap.n = n; ap.fused_tail = true; return 0;
     }
     e->sink = nullptr; e->alloc_sink = nullptr; ap.fused_tail = false;
-    ActHeads Hd; memset(&Hd, 0, sizeof Hd); Hd.adv = head[lq]; if (e->hp.dueling) Hd.val = head[e->last_val]; Hd.dueling = e->hp.dueling; Hd.q_out = e->pol_q; Hd.amax = e->pol_a;
+    ActHeads Hd; memset(&Hd, 0, sizeof Hd); Hd.adv = head[lq][0]; if (e->hp.dueling) Hd.val = head[e->last_val][0]; Hd.dueling = e->hp.dueling; Hd.q_out = e->pol_q; Hd.amax = e->pol_a;
     // act!, add_exp!, observe, episode bookkeeping
     ap.steps.push_back({"env_step_commit", [=](dqn_engine* en) { launch_env_step(en->stream, Vc, rs, Hd, R); }});
     ap.steps.push_back({"env_observe", [=](dqn_engine* en) { launch_env_observe2(en->stream, Vc, rs, u8, srows, sprows, cap, px); }});

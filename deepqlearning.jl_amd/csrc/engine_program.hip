@@ -37,6 +37,121 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
 const char* pname(dqn_engine* e, const char* op, int kind, int i) {
     char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
+Levels net_levels(const dqn_engine* e) {
+    Levels levels; std::vector<int> val, adv;
+    for (int i = 0; i < e->nl; i++) { if (e->L[i].stream == DQN_STREAM_BASE) levels.push_back({i}); else if (e->L[i].stream == DQN_STREAM_VAL) val.push_back(i); else adv.push_back(i); }
+    for (size_t j = 0; j < std::max(val.size(), adv.size()); j++) { std::vector<int> lv; if (j < val.size()) lv.push_back(val[j]); if (j < adv.size()) lv.push_back(adv[j]); levels.push_back(lv); }
+    return levels;
+}
+LayerDev gx_view(const LayerDev& l) { LayerDev v = l; v.kind = DQN_LAYER_DENSE; v.out_feat = l.N; v.b_off = l.z_off; v.act = DQN_ACT_IDENTITY; return v; }
+int fused_head_layout(const dqn_engine* e, const Levels& levels, int ha, int hv, int* pa, int* pv) {
+    if (levels.size() < 2 || ha < 0) return 0;
+    const int ns = hv >= 0 ? 2 : 1; const LayerDev& La = e->L[ha]; *pa = La.src; *pv = hv >= 0 ? e->L[hv].src : -1;
+    auto in_lv = [](const std::vector<int>& v, int l) { for (int x : v) if (x == l) return true; return false; };
+    const auto& hl = levels.back(); const auto& pl = levels[levels.size() - 2];
+    bool ok = La.kind == DQN_LAYER_DENSE && *pa >= 0 && (hv < 0 || (e->L[hv].kind == DQN_LAYER_DENSE && *pv >= 0 && *pv != *pa));
+    ok = ok && (int)hl.size() == ns && in_lv(hl, ha) && (hv < 0 || in_lv(hl, hv)) && (int)pl.size() == ns && in_lv(pl, *pa) && (hv < 0 || in_lv(pl, *pv));
+    if (!ok) return 0;
+    const LayerDev& Pa = e->L[*pa]; const int S = dqn_nchunks(Pa.K, Pa.fwd_kc);
+    ok = Pa.kind == DQN_LAYER_DENSE && Pa.N == La.K && dqn_chunk_len(La.K, La.fwd_kc) == 32 && dqn_nchunks(La.K, La.fwd_kc) * 32 == La.K;
+    if (ok && hv >= 0) { const LayerDev& Pv = e->L[*pv]; const LayerDev& Lv = e->L[hv];
+        ok = Pv.kind == DQN_LAYER_DENSE && Pv.N == Pa.N && dqn_nchunks(Pv.K, Pv.fwd_kc) == S && dqn_chunk_len(Lv.K, Lv.fwd_kc) == 32 && Lv.K == La.K; }
+    return ok ? S : 0;
+}
+void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, const std::vector<FwdPass>& passes, FwdEmit& E) {
+    const bool mf = e->hp.use_mfma != 0; auto& prog = e->sink ? *e->sink : e->prog; const int np = (int)passes.size();
+    auto view = [&](int l) { LayerDev V = is_recurrent(e->L[l].kind) ? gx_view(e->L[l]) : e->L[l]; if (!E.byte_arena) V.xu8 = 0; return V; };
+    auto prod_stream = [&](int l) { return l == E.prod[0] ? 0 : l == E.prod[1] ? 1 : -1; };
+    struct Prob { int l, pass; const float *P, *X; int ldx, col0, ncols; float *Y, *part; int S; };
+    auto prob = [&](int l, int pi) {      // layer l on pass pi; the split-K slabs are allocated by the caller
+        const FwdPass& ps = passes[pi]; const int src = e->L[l].src; Prob q; q.l = l; q.pass = pi; q.P = ps.P; q.ncols = ps.ncols; q.Y = ps.out[l]; q.part = nullptr; q.S = 1;
+        q.X = src < 0 ? ps.x0 : ps.in[src]; q.ldx = src < 0 ? ps.ldx0 : ps.ncols; q.col0 = src < 0 ? ps.col0 : 0;
+        return q;
+    };
+    for (size_t li = li0; li < li1; li++) {
+        const auto& lv = levels[li]; const bool last = li + 1 == levels.size();
+        if (E.skip_last && last) continue;
+        if (is_pool(e->L[lv[0]].kind) || is_ln(e->L[lv[0]].kind) || is_padded(e->L[lv[0]])) {
+            // a layer launched alone on its level (base chain only): one launch per pass, never grouped with a GEMM layer -- a pool (pool.hip), a LayerNorm layer (layernorm.hip:
+            // the first pass keeps (mu, sigma) per column for the backward), a padded conv (conv_pad.hip walks the plan chunks itself)
+            const int l = lv[0]; const LayerDev L = view(l);
+            float* stat0 = (is_ln(L.kind) && E.ln_stat) ? (E.ln_stat[l] = palloc(e, (size_t)2 * passes[0].ncols)) : nullptr;
+            for (int pi = 0; pi < np; pi++) {
+                const Prob q = prob(l, pi); float* stat = pi == 0 ? stat0 : nullptr;
+                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;
+                prog.push_back({pname(e, passes[pi].tag, L.kind, l), [=](dqn_engine* en) { launch_layer_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, mf, L.xu8, stat, nullptr); }});
+            }
+            continue;
+        }
+        std::vector<Prob> pr;
+        for (int l : lv) for (int pi = 0; pi < np; pi++) {
+            const LayerDev L = view(l); Prob q = prob(l, pi);
+            q.S = dqn_nchunks(L.K, L.fwd_kc); q.part = q.S > 1 ? palloc(e, (size_t)q.S * L.out_feat * q.ncols) : nullptr;
+            pr.push_back(q);
+        }
+        bool geo = true; for (int l : lv) geo = geo && same_geo(view(lv[0]), view(l));
+        std::vector<bool> done(pr.size(), false);
+        auto emit_gemm = [&](const std::vector<int>& ids, const char* name, int pm) {
+            const LayerDev L = view(pr[ids[0]].l); const int n = (int)ids.size();
+            struct A { const float *W[4], *bias[4], *X[4]; int ldx[4], col0[4], ncols[4]; float* out[4]; float* outT[4]; } a;
+            bool any_t = false;
+            for (int i = 0; i < n; i++) {
+                const Prob& q = pr[ids[i]]; const LayerDev Lq = view(q.l); a.W[i] = q.P + Lq.w_off; a.bias[i] = q.P + Lq.b_off; a.X[i] = q.X; a.ldx[i] = q.ldx; a.col0[i] = q.col0; a.ncols[i] = q.ncols; a.out[i] = q.S > 1 ? q.part : q.Y;
+                // an UNSPLIT dense layer that feeds k_head_td writes the transposed copy of its output itself (r04: without it the head kernel read its columns one 64-byte
+                // sector per element at B = 512 -- 11 us of its 25); split-K layers get theirs from the reduce launch below
+                a.outT[i] = nullptr;
+                if (E.wantT && E.wantT[q.l] && q.S == 1 && Lq.kind == DQN_LAYER_DENSE) { a.outT[i] = E.actT[q.l][q.pass] = palloc(e, (size_t)Lq.out_feat * q.ncols); any_t = true; }
+            }
+            if (any_t) for (int i = 0; i < n; i++) if (!a.outT[i]) { any_t = false; for (int j = 0; j < n; j++) { if (a.outT[j]) E.actT[pr[ids[j]].l][pr[ids[j]].pass] = nullptr; a.outT[j] = nullptr; } break; }      // all problems of the launch or none
+            prog.push_back({name, [=](dqn_engine* en) { launch_gemm_fwd(en->stream, L, n, a.W, a.bias, a.X, a.ldx, a.col0, a.ncols, a.out, any_t ? a.outT : nullptr, pm); }});
+        };
+        // the grouping rule: ALL problems of the level in one LDS-tiled launch when they number at most four, share the geometry and are eligible; else one launch per layer
+        // over that layer's passes, where eligible; the leftovers go to the direct MFMA launch or the level's VALU task table
+        std::vector<std::pair<std::vector<int>, const char*>> groups;
+        if (mf && pr.size() <= 4) {
+            int ldx[4], c0[4], nc[4]; std::vector<int> all;
+            for (size_t i = 0; i < pr.size(); i++) { all.push_back((int)i); ldx[i] = pr[i].ldx; c0[i] = pr[i].col0; nc[i] = pr[i].ncols; }
+            if (geo && gemm_fwd_eligible(view(lv[0]), (int)pr.size(), ldx, c0, nc)) groups.push_back({all, pname(e, E.gemm, e->L[lv[0]].kind, lv[0])});
+            else for (size_t i = 0; i < pr.size(); i += np)
+                if (gemm_fwd_eligible(view(pr[i].l), np, ldx + i, c0 + i, nc + i)) groups.push_back({std::vector<int>(all.begin() + i, all.begin() + i + np), pname(e, E.gemm, e->L[pr[i].l].kind, pr[i].l)});
+        }
+        for (auto& g : groups) for (int id : g.first) done[id] = true;
+        // split-K slabs that only the fused head launch reads are written piece-major (GFwdProb::pm).  That launch takes ONE flag for all its streams, so the layout is decided
+        // once per level: every problem of the level is a split producer's AND sits in an LDS-tiled launch (the direct MFMA launch and the VALU tasks write [S][N][columns])
+        bool pm_all = E.pm_ok; for (size_t i = 0; i < pr.size(); i++) pm_all = pm_all && done[i] && prod_stream(pr[i].l) >= 0 && pr[i].S > 1;
+        if (pm_all) E.pm = true;
+        for (auto& g : groups) emit_gemm(g.first, g.second, pm_all ? 1 : 0);
+        std::vector<VTask> pend;
+        for (size_t i = 0; i < pr.size(); i++) {
+            if (done[i]) continue;
+            const Prob q = pr[i]; const LayerDev L = view(q.l);
+            if (mf && mfma_fwd_ok(L, q.ncols)) {
+                prog.push_back({pname(e, passes[q.pass].tag, L.kind, q.l), [=](dqn_engine* en) { launch_mfma_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, q.part, false); }});
+            } else {
+                VTask t; memset(&t, 0, sizeof t); t.kind = 0; t.L = L; t.P = q.P; t.X = q.X; t.ldx = q.ldx; t.col0 = q.col0; t.ncols = q.ncols; t.S = q.S; t.kc = dqn_chunk_len(L.K, L.fwd_kc);
+                t.out = q.S > 1 ? q.part : q.Y; add_valu(e, pend, t);
+            }
+        }
+        flush_valu(e, pend, pname(e, E.valu, e->L[lv[0]].kind, lv[0]));
+        std::vector<RSeg> segs;
+        for (const Prob& q : pr) {
+            const LayerDev L = view(q.l); const int st = prod_stream(q.l);
+            HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = q.P + L.b_off; h.act = L.act;
+            if (st >= 0) { E.part[st][q.pass] = q.S > 1 ? q.part : q.Y;      // reduced inside the fused head launch (S == 1: the finished activation)
+                           E.partT[st][q.pass] = (q.S > 1 || !E.actT) ? nullptr : E.actT[q.l][q.pass]; }
+            else if (q.S > 1) {
+                // the last level's split-K slabs are reduced inside its consumer only while that is cheaper than a reduce launch (the train step's single-workgroup TD kernel at
+                // small batches; at B = 512 the 7680 head values x 16 slabs belong on many workgroups)
+                if (last && E.last_on_the_fly) { h.p = q.part; h.S = q.S; h.per_s = (unsigned long long)L.out_feat * q.ncols; }
+                else { RSeg r; memset(&r, 0, sizeof r); r.part = q.part; r.S = q.S; r.elems = (unsigned long long)L.out_feat * q.ncols; r.mode = 0; r.bias = q.P + L.b_off; r.per_n = L.npos * q.ncols; r.act = L.act; r.out = q.Y;
+                       if (E.wantT && E.wantT[q.l]) { r.outT = E.actT[q.l][q.pass] = palloc(e, (size_t)L.out_feat * q.ncols); r.ncolsT = q.ncols; }
+                       segs.push_back(r); }
+            }
+            E.head[q.l][q.pass] = h;
+        }
+        emit_reduce(e, segs, pname(e, E.reduce, e->L[lv[0]].kind, lv[0]));
+    }
+}
 int build_program(dqn_engine* e) {
     if (e->prog_built) return 0;
     HIPCHK(hipSetDevice(e->device));
@@ -49,16 +164,11 @@ int build_program(dqn_engine* e) {
     // step, the single-workgroup step, the fused reduce + head launches) DECLINES a network that holds one, by name, instead of relying on its own shape tests
     bool has_ln = false; for (int i = 0; i < e->nl; i++) has_ln = has_ln || is_ln(e->L[i].kind);
     float* ln_stat[DQN_MAX_LAYERS] = {};      // per LayerNorm layer: (mu, sigma) of the online pass's columns, kept for the backward
-    // forward views: an LSTM layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (a dense layer
-    // K = n_in, N = 4H writing gx_*); the recurrence then runs as T small launches.
-    LayerDev LV[DQN_MAX_LAYERS]; float *fwd_on[DQN_MAX_LAYERS], *fwd_tg[DQN_MAX_LAYERS];
-    for (int i = 0; i < e->nl; i++) {
-        LV[i] = e->L[i]; fwd_on[i] = e->act_on[i]; fwd_tg[i] = e->act_tg[i];
-        if (is_recurrent(e->L[i].kind)) { LV[i].kind = DQN_LAYER_DENSE; LV[i].out_feat = LV[i].N; LV[i].b_off = LV[i].z_off; LV[i].act = DQN_ACT_IDENTITY; fwd_on[i] = e->gx_on[i]; fwd_tg[i] = e->gx_tg[i]; }
-    }
-    std::vector<std::vector<int>> levels; std::vector<int> val, adv;
-    for (int i = 0; i < e->nl; i++) { if (e->L[i].stream == DQN_STREAM_BASE) levels.push_back({i}); else if (e->L[i].stream == DQN_STREAM_VAL) val.push_back(i); else adv.push_back(i); }
-    for (size_t j = 0; j < std::max(val.size(), adv.size()); j++) { std::vector<int> lv; if (j < val.size()) lv.push_back(val[j]); if (j < adv.size()) lv.push_back(adv[j]); levels.push_back(lv); }
+    // forward outputs: a recurrent layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (gx_view, writing gx_*); the recurrence then
+    // runs as T small launches (or one).
+    float *fwd_on[DQN_MAX_LAYERS], *fwd_tg[DQN_MAX_LAYERS];
+    for (int i = 0; i < e->nl; i++) { const bool r = is_recurrent(e->L[i].kind); fwd_on[i] = r ? e->gx_on[i] : e->act_on[i]; fwd_tg[i] = r ? e->gx_tg[i] : e->act_tg[i]; }
+    const Levels levels = net_levels(e);
     // ---------------- recurrent networks with column-group dW chunks (plan dw_kc = -cg): the step is ONE column-parallel launch + the Adam launch (drqn_cols.hip; BASELINE config 4)
     {
         int cgm = 0; bool all_same = true;
@@ -147,13 +257,13 @@ int build_program(dqn_engine* e) {
     // first layer (they convert byte / 255 inside their tile loads): the gather writes 1 byte per element instead of 4 and the first layer reads
     // a quarter of the bytes.  Everything else (VALU / direct-MFMA fallbacks, heads fed by the observation, the operand all-gather) needs floats.
     e->arena_u8 = false;
-    for (int i = 0; i < e->nl; i++) { e->L[i].xu8 = 0; LV[i].xu8 = 0; }
+    for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0;
     if (e->hp.obs_dtype == DQN_OBS_U8 && !rec && mf && B % 4 == 0 && e->E % 4 == 0 && levels.size() > 1) {
         int n_src = 0; for (int i = 0; i < e->nl; i++) if (e->L[i].src < 0) n_src++;
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
         if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && !is_pool(e->L[l0].kind) /* pool.hip reads floats: a pool as the first layer keeps the fp32 arena */ && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
-            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || (gemm_fwd_eligible(LV[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; LV[l0].xu8 = 1; }
+            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || (gemm_fwd_eligible(e->L[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; }
     }
     // ---------------- small batches: the head level (forwards of both nets), the TD kernel and the head layers' dX run as ONE launch with a
     // workgroup per batch column (k_head_td); the heads' dW/db and the loss fold ride as tail tasks of the next backward launch
@@ -179,135 +289,26 @@ int build_program(dqn_engine* e) {
     // ---------------- r05: when the head layers sit on dense hidden layers whose forward ran split-K, the split-K reduce AND the head level are ONE chip-filling launch
     // (red_head.hip: workgroup = 4 batch columns x stream x plan chunk of 32 hidden rows, the last arriver of a column group does TD + the heads' dX) instead of
     // k_reduce_multi (384 workgroups) + k_head_td (B workgroups)
-    bool fuse_rh = false, rh_pm = false; int rh_pa = -1, rh_pv = -1, rh_S = 0; const float* rh_part[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};      // [stream][net]
-    const float* rh_partT[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    if (fuse_heads && !has_ln && levels.size() >= 2 && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
-        const LayerDev& La = e->L[ha_l]; rh_pa = La.src; rh_pv = hv_l >= 0 ? e->L[hv_l].src : -1;
-        bool ok = rh_pa >= 0 && (hv_l < 0 || (rh_pv >= 0 && rh_pv != rh_pa));
-        const auto& pl = levels[levels.size() - 2];
-        auto in_pl = [&](int l) { for (int x : pl) if (x == l) return true; return false; };
-        if (ok) ok = in_pl(rh_pa) && (hv_l < 0 || in_pl(rh_pv)) && (int)pl.size() == (hv_l >= 0 ? 2 : 1);
-        if (ok) {
-            const LayerDev& Pa = e->L[rh_pa]; const int S = dqn_nchunks(Pa.K, Pa.fwd_kc); rh_S = S;
-            // S > 1: k_red_head (split-K producers, small batches).  S == 1 -- finished activations of an unsplit forward, i.e. large batches: k_head_cols4, one workgroup per
-            // column group (k_red_head's (group, stream, chunk) decomposition is SLOWER there: 27.4 vs 21.3 us for k_head_td at B = 512, profiles/history/r05_k_cfg5_red_head_ab.txt --
-            // 4096 workgroups each staging both streams' head weights)
-            ok = Pa.kind == DQN_LAYER_DENSE && (S > 1 || e->opt.no_head_cols4 != 1) && dqn_chunk_len(La.K, La.fwd_kc) == 32 && dqn_nchunks(La.K, La.fwd_kc) * 32 == La.K;
-            if (ok && hv_l >= 0) { const LayerDev& Pv = e->L[rh_pv]; const LayerDev& Lv = e->L[hv_l];
-                ok = Pv.kind == DQN_LAYER_DENSE && Pv.N == Pa.N && dqn_nchunks(Pv.K, Pv.fwd_kc) == S && dqn_chunk_len(Lv.K, Lv.fwd_kc) == 32 && Lv.K == La.K; }
-            if (ok) ok = red_head_ok(B, La.K, S, e->nA, hv_l >= 0 ? 2 : 1, La.N, hv_l >= 0 ? e->L[hv_l].N : 0);
-        }
-        fuse_rh = ok;
+    bool fuse_rh = false; int rh_pa = -1, rh_pv = -1, rh_S = 0;
+    if (fuse_heads && !has_ln && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
+        rh_S = fused_head_layout(e, levels, ha_l, hv_l, &rh_pa, &rh_pv);
+        // S > 1: k_red_head (split-K producers, small batches).  S == 1 -- finished activations of an unsplit forward, i.e. large batches: k_head_cols4, one workgroup per
+        // column group (k_red_head's (group, stream, chunk) decomposition is SLOWER there: 27.4 vs 21.3 us for k_head_td at B = 512, profiles/history/r05_k_cfg5_red_head_ab.txt --
+        // 4096 workgroups each staging both streams' head weights)
+        fuse_rh = rh_S > 0 && (rh_S > 1 || e->opt.no_head_cols4 != 1) && red_head_ok(B, e->L[ha_l].K, rh_S, e->nA, hv_l >= 0 ? 2 : 1, e->L[ha_l].N, hv_l >= 0 ? e->L[hv_l].N : 0);
     }
     // k_head_td and k_head_cols4 (unsplit producers) read their input columns out of transposed copies
     if (fuse_heads && (!fuse_rh || rh_S == 1)) for (int l : levels.back()) if (e->L[l].src >= 0) wantT[e->L[l].src] = true;
     HeadSrc head[DQN_MAX_LAYERS][2];   // per (layer, net): where k_td finds the layer's output
     // ---------------- forward: online net on [s ; sp] (src/solver.jl:210,220), target net on sp (:211)
+    std::vector<FwdPass> passes = {{e->p_on, e->x0, ld0, 0, e->act_on, fwd_on, ncon, "fwd_on"}, {e->p_tg, e->x0, ld0, B, e->act_tg, fwd_tg, B, "fwd_tg"}};
+    if (e->opt.probe_no_tg) passes.pop_back();      // TIMING PROBE (wrong numbers, right schedule): the forward launches without the target network's problems
+    FwdEmit fe; fe.gemm = "fwd"; fe.valu = "fwd_valu"; fe.reduce = "fwd_reduce"; fe.skip_last = fuse_heads /* computed inside k_head_td */; fe.byte_arena = true;
+    if (fuse_rh) { fe.prod[0] = rh_pa; fe.prod[1] = rh_pv; fe.pm_ok = rh_S > 1 && !e->opt.no_rh_pm; }
+    fe.last_on_the_fly = !rec && e->B <= 64; fe.wantT = wantT; fe.actT = actT; fe.ln_stat = ln_stat; fe.head = head;
     for (size_t li = 0; li < levels.size(); li++) {
-        // the head layers' split-K slabs are reduced inside the single-workgroup TD kernel only while that is cheaper than a reduce
-        // launch (small batches); at B = 512 the 7680 head values x 16 slabs belong on many workgroups
-        const auto& lv = levels[li]; const bool last = li + 1 == levels.size() && !rec && e->B <= 64;
-        if (fuse_heads && li + 1 == levels.size()) continue;      // computed inside k_head_td
-        if (is_pool(e->L[lv[0]].kind)) {      // a pool layer (always alone on its level: base chain only) is one launch per pass, never grouped with a GEMM layer
-            const int l = lv[0]; const LayerDev L = e->L[l];
-            for (int net = 0; net < 2; net++) {
-                if (net == 1 && e->opt.probe_no_tg) continue;
-                float** act = net ? e->act_tg : e->act_on;
-                const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
-                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_pool_fwd(en->stream, L, X, ldx, col0, ncols, Y); }});
-            }
-            continue;
-        }
-        if (is_ln(e->L[lv[0]].kind)) {      // a LayerNorm layer (base chain only, so alone on its level): one launch per pass; the online pass keeps (mu, sigma) per column for the backward
-            const int l = lv[0]; const LayerDev L = e->L[l];
-            float* stat = ln_stat[l] = palloc(e, (size_t)2 * ncon);
-            for (int net = 0; net < 2; net++) {
-                float** act = net ? e->act_tg : e->act_on; const float* P = net ? e->p_tg : e->p_on;
-                const float* X = act[L.src]; const int ldx = net ? B : ncon, ncols = net ? B : ncon; float* Y = act[l]; float* st = net ? nullptr : stat;
-                if (net == 1 && e->opt.probe_no_tg) continue;
-                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_ln_fwd(en->stream, L, P, X, ldx, 0, ncols, Y, st); }});
-            }
-            continue;
-        }
-        if (is_padded(e->L[lv[0]])) {      // a padded conv (base chain only, so alone on its level): one launch per pass (conv_pad.hip walks the plan chunks itself), never grouped
-            const int l = lv[0]; const LayerDev L = LV[l]; const int xu8 = L.xu8;
-            for (int net = 0; net < 2; net++) {
-                float** act = net ? e->act_tg : e->act_on; const float* P = net ? e->p_tg : e->p_on;
-                const float* X = L.src < 0 ? e->x0 : act[L.src]; const int ldx = L.src < 0 ? ld0 : (net ? B : ncon), col0 = (L.src < 0 && net) ? B : 0, ncols = net ? B : ncon; float* Y = act[l];
-                HeadSrc h; h.p = Y; h.ld = ncols; h.S = 1; h.per_s = 0; h.bias = P + L.b_off; h.act = L.act; head[l][net] = h;
-                if (net == 1 && e->opt.probe_no_tg) continue;
-                e->prog.push_back({pname(e, net ? "fwd_tg" : "fwd_on", L.kind, l), [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, P, X, ldx, col0, ncols, Y, mf ? 1 : 0, xu8); }});
-            }
-            continue;
-        }
-        struct Prob { int l, net; const float *P, *X; int ldx, col0, ncols; float *Y, *part; int S; };
-        std::vector<Prob> pr;
-        const bool probe_no_tg = e->opt.probe_no_tg != 0;      // TIMING PROBE (wrong numbers, right schedule): the forward launches without the target network's problems
-        for (int l : lv) for (int net = 0; net < 2; net++) {
-            if (net == 1 && probe_no_tg) { if (wantT[l]) actT[l][1] = palloc(e, (size_t)LV[l].out_feat * B); continue; }
-            const LayerDev& L = LV[l]; Prob q; q.l = l; q.net = net; q.P = net ? e->p_tg : e->p_on;
-            float** act = net ? e->act_tg : e->act_on;
-            q.X = L.src < 0 ? e->x0 : act[L.src]; q.ldx = L.src < 0 ? ld0 : (net ? B : ncon); q.col0 = (L.src < 0 && net) ? B : 0; q.ncols = net ? B : ncon;
-            q.Y = net ? fwd_tg[l] : fwd_on[l]; q.S = dqn_nchunks(L.K, L.fwd_kc); q.part = q.S > 1 ? palloc(e, (size_t)q.S * L.out_feat * q.ncols) : nullptr;
-            pr.push_back(q);
-        }
-        bool geo = true; for (int l : lv) geo = geo && same_geo(LV[lv[0]], LV[l]);
-        std::vector<bool> done(pr.size(), false);
-        auto emit_gemm = [&](const std::vector<int>& ids, const char* name) {
-            const LayerDev L = LV[pr[ids[0]].l]; const int n = (int)ids.size();
-            struct A { const float *W[4], *bias[4], *X[4]; int ldx[4], col0[4], ncols[4]; float* out[4]; float* outT[4]; } a;
-            bool any_t = false;
-            for (int i = 0; i < n; i++) {
-                const Prob& q = pr[ids[i]]; const LayerDev& Lq = LV[q.l]; a.W[i] = q.P + Lq.w_off; a.bias[i] = q.P + Lq.b_off; a.X[i] = q.X; a.ldx[i] = q.ldx; a.col0[i] = q.col0; a.ncols[i] = q.ncols; a.out[i] = q.S > 1 ? q.part : q.Y;
-                // an UNSPLIT dense layer that feeds k_head_td writes the transposed copy of its output itself (r04: without it the head kernel read its columns one 64-byte
-                // sector per element at B = 512 -- 11 us of its 25); split-K layers get theirs from the reduce launch below
-                a.outT[i] = nullptr;
-                if (wantT[q.l] && q.S == 1 && Lq.kind == DQN_LAYER_DENSE) { a.outT[i] = actT[q.l][q.net] = palloc(e, (size_t)Lq.out_feat * q.ncols); any_t = true; }
-            }
-            if (any_t) for (int i = 0; i < n; i++) if (!a.outT[i]) { any_t = false; for (int j = 0; j < n; j++) { if (a.outT[j]) actT[pr[ids[j]].l][pr[ids[j]].net] = nullptr; a.outT[j] = nullptr; } break; }      // all problems of the launch or none
-            // split-K slabs that only k_red_head reads are written piece-major (GFwdProb::pm): every problem of the launch belongs to the head's producer layers
-            bool pm_all = fuse_rh && rh_S > 1 && !e->opt.no_rh_pm; for (int i = 0; i < n; i++) pm_all = pm_all && (pr[ids[i]].l == rh_pa || pr[ids[i]].l == rh_pv) && pr[ids[i]].S > 1;
-            if (pm_all) rh_pm = true;
-            const int pm = pm_all ? 1 : 0;
-            e->prog.push_back({name, [=](dqn_engine* en) { launch_gemm_fwd(en->stream, L, n, a.W, a.bias, a.X, a.ldx, a.col0, a.ncols, a.out, any_t ? a.outT : nullptr, pm); }});
-            for (int id : ids) done[id] = true;
-        };
-        if (mf) {
-            std::vector<int> all; int ldx[4], c0[4], nc[4];
-            for (size_t i = 0; i < pr.size() && i < 4; i++) { all.push_back((int)i); ldx[i] = pr[i].ldx; c0[i] = pr[i].col0; nc[i] = pr[i].ncols; }
-            if (geo && pr.size() <= 4 && gemm_fwd_eligible(LV[lv[0]], (int)pr.size(), ldx, c0, nc)) emit_gemm(all, pname(e, "fwd", e->L[lv[0]].kind, lv[0]));
-            else for (size_t i = 0; i + 1 < pr.size(); i += 2) {
-                int l2[2] = {pr[i].ldx, pr[i + 1].ldx}, c2[2] = {pr[i].col0, pr[i + 1].col0}, n2[2] = {pr[i].ncols, pr[i + 1].ncols};
-                if (gemm_fwd_eligible(LV[pr[i].l], 2, l2, c2, n2)) emit_gemm({(int)i, (int)i + 1}, pname(e, "fwd", e->L[pr[i].l].kind, pr[i].l));
-            }
-        }
-        std::vector<VTask> pend;
-        for (size_t i = 0; i < pr.size(); i++) {
-            if (done[i]) continue;
-            const Prob q = pr[i]; const LayerDev L = LV[q.l];
-            if (mf && mfma_fwd_ok(L, q.ncols)) {
-                e->prog.push_back({pname(e, q.net ? "fwd_tg" : "fwd_on", L.kind, q.l), [=](dqn_engine* en) { launch_mfma_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, q.part, false); }});
-            } else {
-                VTask t; memset(&t, 0, sizeof t); t.kind = 0; t.L = L; t.P = q.P; t.X = q.X; t.ldx = q.ldx; t.col0 = q.col0; t.ncols = q.ncols; t.S = q.S; t.kc = dqn_chunk_len(L.K, L.fwd_kc);
-                t.out = q.S > 1 ? q.part : q.Y; add_valu(e, pend, t);
-            }
-        }
-        flush_valu(e, pend, pname(e, "fwd_valu", e->L[lv[0]].kind, lv[0]));
-        std::vector<RSeg> segs;
-        for (const Prob& q : pr) {
-            const LayerDev& L = LV[q.l];
-            HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = q.P + L.b_off; h.act = L.act;
-            if (fuse_rh && (q.l == rh_pa || q.l == rh_pv)) { rh_part[q.l == rh_pa ? 0 : 1][q.net] = q.S > 1 ? q.part : q.Y;      // reduced inside k_red_head (S == 1: the finished activation)
-                                                             rh_partT[q.l == rh_pa ? 0 : 1][q.net] = q.S > 1 ? nullptr : actT[q.l][q.net]; }
-            else if (q.S > 1) {
-                if (last) { h.p = q.part; h.S = q.S; h.per_s = (unsigned long long)L.out_feat * q.ncols; }   // reduced on the fly by k_td
-                else { RSeg r; memset(&r, 0, sizeof r); r.part = q.part; r.S = q.S; r.elems = (unsigned long long)L.out_feat * q.ncols; r.mode = 0; r.bias = q.P + L.b_off; r.per_n = L.npos * q.ncols; r.act = L.act; r.out = q.Y;
-                       if (wantT[q.l]) { r.outT = actT[q.l][q.net] = palloc(e, (size_t)L.out_feat * q.ncols); r.ncolsT = q.ncols; }
-                       segs.push_back(r); }
-            }
-            head[q.l][q.net] = h;
-        }
-        emit_reduce(e, segs, pname(e, "fwd_reduce", e->L[lv[0]].kind, lv[0]));
+        emit_forward(e, levels, li, li + 1, passes, fe);
+        const auto& lv = levels[li];
         if (is_recurrent(e->L[lv[0]].kind)) {
             // the recurrence: each launch advances the online s-sequence, the online sp-sequence (double-Q) and the target sp-sequence from the reset
             // state (Flux.reset!, src/solver.jl:249-250,271) -- ONE launch for the whole recurrence where the cell's whole-sequence kernels fit, else T
@@ -336,6 +337,7 @@ int build_program(dqn_engine* e) {
             }
         }
     }
+    if (e->opt.probe_no_tg) for (int l = 0; l < e->nl; l++) if (wantT[l] && actT[l][0]) actT[l][1] = palloc(e, (size_t)e->L[l].out_feat * B);      // (never written: the head kernel still gets a buffer)
     // ---------------- dueling reduce + argmax + Bellman target + TD + Huber + dL/dQ + priority update
     {
         TdArgs t; memset(&t, 0, sizeof t);
@@ -349,11 +351,11 @@ int build_program(dqn_engine* e) {
         if (fuse_rh) {
             RedHeadArgs h; memset(&h, 0, sizeof h);
             const LayerDev& La = e->L[ha_l];
-            h.B = B; h.nA = e->nA; h.K = La.K; h.S = dqn_nchunks(e->L[rh_pa].K, e->L[rh_pa].fwd_kc); h.ncon = ncon; h.nstream = hv_l >= 0 ? 2 : 1; h.NO = e->nA + (hv_l >= 0 ? 1 : 0); h.double_q = e->hp.double_q;
-            h.gamma = e->hp.gamma; h.pm = rh_pm ? 1 : 0;
+            h.B = B; h.nA = e->nA; h.K = La.K; h.S = rh_S; h.ncon = ncon; h.nstream = hv_l >= 0 ? 2 : 1; h.NO = e->nA + (hv_l >= 0 ? 1 : 0); h.double_q = e->hp.double_q;
+            h.gamma = e->hp.gamma; h.pm = fe.pm ? 1 : 0;
             for (int st = 0; st < h.nstream; st++) {
                 const int hl_ = st == 0 ? ha_l : hv_l, pl_ = st == 0 ? rh_pa : rh_pv; const LayerDev& H = e->L[hl_]; const LayerDev& P = e->L[pl_]; RedHeadStream& T = h.st[st];
-                T.part[0] = rh_part[st][0]; T.part[1] = rh_part[st][1]; T.partT[0] = rh_partT[st][0]; T.partT[1] = rh_partT[st][1]; T.pbias[0] = e->p_on + P.b_off; T.pbias[1] = e->p_tg + P.b_off; T.pact = P.act;
+                T.part[0] = fe.part[st][0]; T.part[1] = fe.part[st][1]; T.partT[0] = fe.partT[st][0]; T.partT[1] = fe.partT[st][1]; T.pbias[0] = e->p_on + P.b_off; T.pbias[1] = e->p_tg + P.b_off; T.pact = P.act;
                 T.W[0] = e->p_on + H.w_off; T.W[1] = e->p_tg + H.w_off; T.hbias[0] = e->p_on + H.b_off; T.hbias[1] = e->p_tg + H.b_off; T.N = H.N; T.hact = H.act;
                 T.y_on = e->act_on[pl_]; T.dpre = e->dact[hl_]; T.dsrc = e->dact[pl_];
             }
@@ -440,6 +442,14 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- backward of the online net on the s columns (Zygote through src/solver.jl:219-225)
     std::vector<RSeg> final_segs;   // dW split-K slabs: nothing reads the gradient before Adam, so ONE reduce launch at the end
+    // where the (K+1) x N gradient block of a layer (or of a recurrent layer's Wi | b / Wh | junk view) lands: its range of the flat gradient, or -- S > 1 plan chunks -- S slabs,
+    // registered here for the final reduce.  The ONE place that decides it; the order of the calls is the order of final_segs, which adam_segs and dp_pack read
+    auto dw_dst = [&](const LayerDev& L, int S) {
+        if (S <= 1) return e->grad + L.w_off;
+        float* part = palloc(e, (size_t)S * (L.K + 1) * L.N);
+        RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = e->grad + L.w_off; final_segs.push_back(r);
+        return part;
+    };
     // ---------------- Adam overlap (single GPU).  A layer's gradient is final once the launch of its level has run (fused heads: once the launch
     // carrying their dW tail tasks has run), and from then on nothing reads its parameters (its dX ran at its own level).  So the Adam update of
     // every such layer -- stream (unsplit dW) or slab reduce + update (split-K dW) -- rides as TAIL workgroups of the NEXT backward launch: the
@@ -505,10 +515,8 @@ int build_program(dqn_engine* e) {
             for (int l : lv) {
                 const LayerDev L = e->L[l];
                 const int S = dqn_nchunks(B, L.dw_kc);      // large batches: plan chunks of the B-long chains, slabs summed with the other dW slabs
-                float* part = S > 1 ? palloc(e, (size_t)S * (L.K + 1) * L.N) : nullptr;
                 VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = L; t.X = L.src < 0 ? e->x0 : e->act_on[L.src]; t.ldx = L.src < 0 ? ld0 : ncon; t.dpre = e->dact[l]; t.B = B; t.S = S; t.kc = dqn_chunk_len(B, L.dw_kc);
-                t.out = S > 1 ? part : e->grad + L.w_off; tail_pend.push_back(t);
-                if (S > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = e->grad + L.w_off; final_segs.push_back(r); }
+                t.out = dw_dst(L, S); tail_pend.push_back(t);
             }
             VTask f; memset(&f, 0, sizeof f); f.kind = 3; f.dpre = hl_buf; f.B = B; f.out = &e->state->loss; tail_pend.push_back(f);
             continue;
@@ -544,10 +552,8 @@ int build_program(dqn_engine* e) {
             if (is_padded(L)) {
                 // a padded conv's backward (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then
                 // -- unless the layer reads the observation -- dX with the producing layer's activation derivative.  Two launches of the layer's own, never grouped
-                const int S = dqn_nchunks(L.npos * B, L.dw_kc); float* grad = e->grad;
-                float* part = S > 1 ? palloc(e, (size_t)S * (L.K + 1) * L.N) : nullptr; float* dst = S > 1 ? part : grad + L.w_off; const int xu8 = L.xu8;
+                float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8;
                 e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
-                if (S > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = grad + L.w_off; final_segs.push_back(r); }
                 if (wants_dx(l)) {
                     const float* P = e->p_on; float* out = e->dact[L.src]; const float* ysrc = e->act_on[L.src]; const int act_src = e->L[L.src].act;
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, ysrc, ncon, act_src, mf ? 1 : 0); }});
@@ -569,13 +575,13 @@ int build_program(dqn_engine* e) {
                     if (C->seq_fits(L.H, Bb, T) && !stepwise(e->opt, L.kind)) { snprintf(op, sizeof op, "%s_bwd_seq", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_seq(en->stream, a); }}); }
                     else for (int t = T - 1; t >= 0; t--) { CellBwdArgs at = a; at.t = t; snprintf(op, sizeof op, "%s_bwd", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_step(en->stream, at); }}); }
                 }
-                LayerDev Vi = L; Vi.kind = DQN_LAYER_DENSE; Vi.out_feat = L.N; Vi.act = DQN_ACT_IDENTITY;                    // Wi | b  : (K+1) x N
+                LayerDev Vi = gx_view(L); Vi.b_off = L.b_off;                                                                 // Wi | b  : (K+1) x N (the bias row is real here)
                 LayerDev Vh = Vi; Vh.K = L.H; Vh.in_feat = L.H; Vh.w_off = L.wh_off; Vh.b_off = L.wh_off + (size_t)L.H * L.N;  // Wh | junk
                 const float* dGi = e->dG[l]; const float* dGw = dGh;      // the Wi | b and dX operand, the Wh operand
                 float* wh_dst = nullptr; int wh_S = 1;      // where the Wh | junk block (or its slabs) lands
                 auto emit_dw1 = [&](const LayerDev V, const float* Xv, int ldv, const float* dG, const char* nm) {
                     const int S = dqn_nchunks(B, V.dw_kc);
-                    float* part = S > 1 ? palloc(e, (size_t)S * (V.K + 1) * V.N) : nullptr; float* dst = S > 1 ? part : grad + V.w_off;
+                    float* dst = dw_dst(V, S); float* part = S > 1 ? dst : nullptr;
                     // small recurrent layers (config 4: (25+1) x 128 and (32+1) x 128 weights, 256 columns): the two dW contractions as VALU tasks of ONE launch
                     // (15 us) beat two LDS-tiled MFMA launches of 13 us each (r03: 113.4 -> 102.7 us/step); the MFMA tiles win once the sample chains get long
                     const bool small_dw = B <= 256 && (size_t)(V.K + 1) * V.N <= 16384;
@@ -583,7 +589,6 @@ int build_program(dqn_engine* e) {
                         e->prog.push_back({nm, [=](dqn_engine* en) { launch_gemm_dw(en->stream, V, 1, a.X, ldv, a.d, B, a.o); }}); }
                     else if (mf && !small_dw && mfma_dw_ok(V, B)) e->prog.push_back({nm, [=](dqn_engine* en) { launch_mfma_dw(en->stream, V, Xv, ldv, dG, B, grad, part, false); }});
                     else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = V; t.X = Xv; t.ldx = ldv; t.dpre = dG; t.B = B; t.S = S; t.kc = dqn_chunk_len(B, V.dw_kc); t.out = dst; add_valu(e, pend, t); }
-                    if (S > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(V.K + 1) * V.N; r.mode = 2; r.out = grad + V.w_off; final_segs.push_back(r); }
                     if (V.w_off == L.wh_off) { wh_dst = dst; wh_S = S; }
                 };
                 emit_dw1(Vh, e->hprev_buf[l], B, dGw, pname(e, "dw_wh", L.kind, l));      // first: its junk bias row is then overwritten by nothing that matters
@@ -604,28 +609,22 @@ int build_program(dqn_engine* e) {
                 }
                 continue;
             }
-            if (!dp_layer[l]) {   // dW / db  (layers flagged for the gather exchange get theirs after the collective)
-                const int S = dqn_nchunks(L.npos * B, L.dw_kc);
-                float* part = S > 1 ? palloc(e, (size_t)S * (L.K + 1) * L.N) : nullptr;
-                float* grad = e->grad;
-                float* dst = S > 1 ? part : grad + L.w_off;
-                if (mf && gemm_dw_eligible(L, B, ldx)) {
-                    // sibling layers of this level with identical geometry and the same input share ONE launch
-                    if (k == (int)lv.size() - 1 && lv.size() == 2 && same_geo(e->L[lv[0]], e->L[lv[1]]) && e->L[lv[0]].dw_kc == e->L[lv[1]].dw_kc) {
-                        const LayerDev L0 = e->L[lv[0]]; const int S0 = S;
-                        float* part0 = S0 > 1 ? palloc(e, (size_t)S0 * (L0.K + 1) * L0.N) : nullptr;
-                        flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 2; dwl.ldx = ldx; dwl.name = pname(e, "dw2", L.kind, l);
-                        dwl.X[0] = X; dwl.d[0] = dpre; dwl.o[0] = dst; dwl.X[1] = X; dwl.d[1] = e->dact[lv[0]]; dwl.o[1] = S0 > 1 ? part0 : grad + L0.w_off;
-                        if (S0 > 1) { RSeg r; memset(&r, 0, sizeof r); r.part = part0; r.S = S0; r.elems = (unsigned long long)(L0.K + 1) * L0.N; r.mode = 2; r.out = grad + L0.w_off; final_segs.push_back(r); }
-                        dw_done_sibling = true;
-                    } else if (!(dw_done_sibling && k == 0 && lv.size() == 2)) {
-                        flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 1; dwl.ldx = ldx; dwl.name = pname(e, "dw", L.kind, l);
-                        dwl.X[0] = dwl.X[1] = X; dwl.d[0] = dwl.d[1] = dpre; dwl.o[0] = dwl.o[1] = dst;
-                    }
+            if (!dp_layer[l] && !(dw_done_sibling && k == 0)) {   // dW / db  (layers flagged for the gather exchange get theirs after the collective; a second sibling got its in the pair's launch)
+                const int S = dqn_nchunks(L.npos * B, L.dw_kc); float* grad = e->grad;
+                const bool lds = mf && gemm_dw_eligible(L, B, ldx);
+                // sibling layers of this level with identical geometry and the same input share ONE launch (the sibling's slabs enter final_segs first)
+                const bool pair = lds && k == (int)lv.size() - 1 && lv.size() == 2 && same_geo(e->L[lv[0]], e->L[lv[1]]) && e->L[lv[0]].dw_kc == e->L[lv[1]].dw_kc;
+                float* dst0 = pair ? dw_dst(e->L[lv[0]], S) : nullptr; float* dst = dw_dst(L, S);
+                if (pair) {
+                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 2; dwl.ldx = ldx; dwl.name = pname(e, "dw2", L.kind, l);
+                    dwl.X[0] = X; dwl.d[0] = dpre; dwl.o[0] = dst; dwl.X[1] = X; dwl.d[1] = e->dact[lv[0]]; dwl.o[1] = dst0;
+                    dw_done_sibling = true;
+                } else if (lds) {
+                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 1; dwl.ldx = ldx; dwl.name = pname(e, "dw", L.kind, l);
+                    dwl.X[0] = dwl.X[1] = X; dwl.d[0] = dwl.d[1] = dpre; dwl.o[0] = dwl.o[1] = dst;
                 }
-                else if (mf && mfma_dw_ok(L, B)) e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_mfma_dw(en->stream, L, X, ldx, dpre, B, grad, part, false); }});
+                else if (mf && mfma_dw_ok(L, B)) { float* part = S > 1 ? dst : nullptr; e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_mfma_dw(en->stream, L, X, ldx, dpre, B, grad, part, false); }}); }
                 else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = L; t.X = X; t.ldx = ldx; t.dpre = dpre; t.B = B; t.S = S; t.kc = dqn_chunk_len(L.npos * B, L.dw_kc); t.out = dst; add_valu(e, pend, t); }
-                if (S > 1 && !(dw_done_sibling && k == 0 && lv.size() == 2)) { RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)(L.K + 1) * L.N; r.mode = 2; r.out = grad + L.w_off; final_segs.push_back(r); }
             }
             if (!wants_dx(l)) continue;
             // dX, then act' of the producing layer; the two streams of a dueling net meet at the base output (dX_val + dX_adv)

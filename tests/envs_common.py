@@ -31,6 +31,12 @@ def gridworld_mlp_dueling():
     return O.Network((2,), b, v, a)
 
 
+def gridworld_mlp_unequal_streams():
+    """value hidden width 32, advantage hidden width 64: the two hidden layers share their level but not their geometry, so the acting forward never groups them into one launch
+    (and the fused acting tail, which wants equal widths, does not apply)"""
+    return O.Network((2,), [O.Dense(2, 32, R)], [O.Dense(32, 32, R), O.Dense(32, 1, I)], [O.Dense(32, 64, R), O.Dense(64, 4, I)])
+
+
 def same_params(handles, net, seed=3):
     p = O.Network.flatten(O.init_params(net, seed=seed))
     rng = np.random.default_rng(seed)

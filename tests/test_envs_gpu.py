@@ -117,17 +117,24 @@ def test_rollout_with_fused_acting_head_bit_exact(pkg, envs, monkeypatch, n_envs
     np.testing.assert_array_equal(outs[0][0], outs[1][0]); np.testing.assert_array_equal(outs[0][1], outs[1][1])
 
 
-@pytest.mark.parametrize("case", ["wide_fc_dueling", "wide_fc_dueling_u8", "wide_fc_dueling_s13", "wide_fc_plain", "wide_fc_dueling_uniform", "gridworld", "gridworld_1024", "small_fc_dueling"])
+@pytest.mark.parametrize("case", ["wide_fc_dueling", "wide_fc_dueling_u8", "wide_fc_dueling_s13", "wide_fc_plain", "wide_fc_dueling_uniform", "gridworld", "gridworld_1024", "small_fc_dueling", "gridworld_unequal_streams", "gridworld_unequal_streams_16",
+                                  "wide_fc_dueling_u8_b32"])
 def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
     """r06: the acting step's tail as ONE launch -- k_act_head (act_head.hip): split-K reduce of the heads' producers + heads + Q / argmax + eps-greedy +
     act! + add_exp!'s per-experience part, one wave per (four copies, stream, plan chunk) with a ticketed last arriver -- and the sum-tree ancestors as workgroup 0 of the observe
     launch.  Trajectories, replay (rows, metadata, priorities incl. a wrapping ring), episode statistics, parameters and evaluation equal the twin's bit for bit, and the
     four-launch tail (DQN_NO_ACT_HEAD=1) walks the same trajectory.  Cases: split-K dueling streams (the Nature shape class; f32 and u8 rows; 13 slabs; uniform replay without double-Q), a plain Q head (one stream),
-    the GridWorld MLP (unsplit producers, one chunk), a dueling net whose producers are unsplit."""
+    the GridWorld MLP (unsplit producers, one chunk), a dueling net whose producers are unsplit, and a dueling GridWorld MLP whose streams' hidden layers differ in width (32 / 64),
+    so that they share a level but not a geometry: at 4 copies every layer takes the direct-MFMA / VALU launches, at 16 copies each hidden layer takes an LDS-tiled launch of its own; the
+    fused tail never applies there, so both settings run the four-launch tail.  wide_fc_dueling_u8_b32: a batch of 32 puts the train step's first layer on the byte arena, while the acting
+    programs read float columns -- also the evaluation set's, built after the train program, at 16 copies (a multiple of the LDS-tiled launch's column tile)."""
     grid = case.startswith("gridworld")      # (gridworld_1024: the largest copy count, 256 groups = every RolloutDev record in use)
-    net = {"wide_fc_dueling": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s13": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_uniform": EC.testmdp_wide_fc_dueling, "wide_fc_plain": EC.testmdp_wide_fc_plain,
-           "gridworld": EC.gridworld_mlp_dueling, "gridworld_1024": EC.gridworld_mlp_dueling, "small_fc_dueling": EC.testmdp_conv_dueling}[case]()
-    n_envs = {"wide_fc_dueling": 8, "wide_fc_dueling_u8": 12, "wide_fc_dueling_s13": 8, "wide_fc_dueling_uniform": 8, "wide_fc_plain": 4, "gridworld": 64, "gridworld_1024": 1024, "small_fc_dueling": 8}[case]
+    unequal, b32 = case.startswith("gridworld_unequal_streams"), case.endswith("b32")
+    net = {"wide_fc_dueling": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8_b32": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s13": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_uniform": EC.testmdp_wide_fc_dueling, "wide_fc_plain": EC.testmdp_wide_fc_plain,
+           "gridworld": EC.gridworld_mlp_dueling, "gridworld_1024": EC.gridworld_mlp_dueling, "small_fc_dueling": EC.testmdp_conv_dueling,
+           "gridworld_unequal_streams": EC.gridworld_mlp_unequal_streams, "gridworld_unequal_streams_16": EC.gridworld_mlp_unequal_streams}[case]()
+    n_envs = {"wide_fc_dueling": 8, "wide_fc_dueling_u8": 12, "wide_fc_dueling_s13": 8, "wide_fc_dueling_uniform": 8, "wide_fc_plain": 4, "gridworld": 64, "gridworld_1024": 1024, "small_fc_dueling": 8, "gridworld_unequal_streams": 4, "gridworld_unequal_streams_16": 16,
+              "wide_fc_dueling_u8_b32": 16}[case]
     # plan edits (the twin takes the same plan): 13 slabs per hidden layer (the 16-slab instantiation of the launch); 32-row chunks for the plain net's 64-input head (the default
     # plan leaves it unsplit, which the launch does not cover)
     plan_edit = {"wide_fc_dueling_s13": lambda pl: [(128, dx, dw) if fk == 392 else (fk, dx, dw) for fk, dx, dw in pl],
@@ -137,14 +144,14 @@ def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
         if not fused:
             monkeypatch.setenv("DQN_NO_ACT_HEAD", "1")
         extra = dict(prioritized_replay=0, double_q=0) if case.endswith("uniform") else {}      # uniform replay (add_exp! with priority 0f0, no pre-drawn batches), plain Q targets
-        g, t, hp = make_pair(pkg, net, B=8, cap=(3000 if n_envs == 1024 else 1024) if grid else 80, plan_edit=plan_edit, obs_dtype=1 if case.endswith("u8") else 0, **extra)
+        g, t, hp = make_pair(pkg, net, B=32 if b32 else 8, cap=(3000 if n_envs == 1024 else 1024) if grid else 80, plan_edit=plan_edit, obs_dtype=1 if "u8" in case else 0, **extra)
         monkeypatch.delenv("DQN_NO_ACT_HEAD", raising=False)
         EC.same_params([g, t], net)
         spec = envs.SimpleGridWorld(n=n_envs) if grid else envs.TestMDP((14, 12) if case == "small_fc_dueling" else (20, 20), 4, 6, n=n_envs, seed=3)
         for h in (g, t):
             h.envs_create(spec, max_episode_length=20 if grid else 100, seed=17)
         compare_state(g, t)
-        assert g.envs_info() == (n_envs, fused), "the schedule under test is not the one this case names"
+        assert g.envs_info() == (n_envs, fused and not unequal), "the schedule under test is not the one this case names"
         t0 = 1
         for chunk, cad in ((1, False), (4, False), (3, True), (9, False), (5, True), (6, False)):      # the 80-slot ring wraps; episodes end every 5 steps (TestMDP) / within 20 (GridWorld)
             kw = dict(t0=t0, train_freq=2 if cad else 3, target_update_freq=7, eps=(0.6, 0.05, 15.0), env_step_cadence=cad)      # cad: n / 2 train steps per vector step, the whole vector step as one graph
@@ -154,11 +161,14 @@ def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
             compare_state(g, t)
             np.testing.assert_array_equal(g.get_params(0), t.get_params(0))
             np.testing.assert_array_equal(g.get_params(1), t.get_params(1))
-        idx = (np.arange(8, dtype=np.int64) * 7) % int(g.replay_size()[0])
+        idx = (np.arange(32 if b32 else 8, dtype=np.int64) * 7) % int(g.replay_size()[0])
         for x, y in zip(g.get_batch(idx), t.get_batch(idx)):
             np.testing.assert_array_equal(x, y)
         assert g.evaluate(8, 50, seed=5) == t.evaluate(8, 50, seed=5)
         assert g.evaluate(4, 30, seed=6) == t.evaluate(4, 30, seed=6)
+        if b32:
+            assert g.batch_arena_elem_bytes() == 1, "the case is written for the byte arena"
+            assert g.evaluate(16, 30, seed=7) == t.evaluate(16, 30, seed=7)
         compare_state(g, t)
         outs.append((g.get_params(0), g.replay_priorities(), g.envs_peek()))
         g.close(); t.close()
