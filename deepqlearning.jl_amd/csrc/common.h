@@ -788,8 +788,9 @@ void launch_gemm_fwd(hipStream_t st, const LayerDev& L, int nprob, const float* 
 
 // ---- DRQN: EpisodeReplayBuffer gather and recurrent TD (drqn.hip); the recurrent cells -- LSTM (drqn.hip), GRU (gru.hip), RNN (rnn.hip).
 // Every cell is decomposed the same way: Gx = Wi*x over all T*B columns by the dense kernels, the recurrence and BPTT by the cell's own kernels
-// (one launch per time step, or one whole-sequence launch where <cell>_seq_fits), dW / dX by the dense kernels.  The three cells share the
-// argument structs below and the engine reaches them through the cell table (cell_ops).
+// (one launch per time step, or one whole-sequence launch where the cell's seq_fits says so), dW / dX by the dense kernels.  The three cells share
+// the argument structs below AND their kernels: cell.h holds one template per kernel form, each cell file a struct with the cell's arithmetic and
+// its entry of the cell table (cell_ops), through which the engine reaches them.
 struct CellSeq {          // one sequence set: B columns starting at column c0 (+ t*B) of [*][ld] arrays
     const float* Gx; float* Hout;             // all cells: the input projection [N][ld], the output h [H][ld]
     float* Cst; int ld, c0;                   // Cst: LSTM, the cell state c [H][ld]
@@ -811,22 +812,6 @@ struct CellBwdArgs {      // BPTT over the online s-sequence, all [*][TB] arrays
     float *dhn, *dh2;        // [H][B]: dh_{t-1}; LSTM dc_{t-1}, GRU dh .* z of the current step (per-step launches only)
     float *g_h0, *g_c0;      // state0 gradients; g_c0: LSTM, else null
 };
-void launch_lstm_step_t(hipStream_t st, const CellFwdArgs& a, int t);
-void launch_lstm_bwd_step(hipStream_t st, const CellBwdArgs& a);
-// whole-sequence variants (small cells: Wh and one step's state in LDS); the backward ones fold the state0 gradient too
-bool lstm_seq_fits(int H, int B, int T);
-void launch_lstm_seq(hipStream_t st, const CellFwdArgs& a);
-void launch_lstm_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
-void launch_gru_step_t(hipStream_t st, const CellFwdArgs& a, int t);
-void launch_gru_bwd_step(hipStream_t st, const CellBwdArgs& a);
-bool gru_seq_fits(int H, int B, int T);
-void launch_gru_seq(hipStream_t st, const CellFwdArgs& a);
-void launch_gru_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
-void launch_rnn_step_t(hipStream_t st, const CellFwdArgs& a, int t);
-void launch_rnn_bwd_step(hipStream_t st, const CellBwdArgs& a);
-bool rnn_seq_fits(int H, int B, int T);
-void launch_rnn_seq(hipStream_t st, const CellFwdArgs& a);
-void launch_rnn_bwd_seq(hipStream_t st, const CellBwdArgs& a);   // a.t ignored
 // the cell table: all that the engine's host code knows about a recurrent layer kind
 struct CellOps {
     const char *name, *display;      // program step names ("<name>_seq", "<name>_bwd", ...); error messages
@@ -835,20 +820,17 @@ struct CellOps {
     bool has_c;                      // carries a cell state c beside h: c0 in the parameter block, Cst / cprev / cprev_out / g_c0, the policy's second state
     bool two_dG;                     // BPTT writes dGh apart from dG (dG buffer [2N][TB])
     bool clear_junk;                 // the junk bias row of the Wh | junk dW pass is not a copy of db and may raise max |g|: cleared after the level's dW
-    bool (*seq_fits)(int H, int B, int T);
+    bool (*seq_fits)(int H, int B, int T);      // whole-sequence variants (small cells: Wh and one step's state in LDS); launch_bwd_seq folds the state0 gradient too and ignores a.t
     void (*launch_step)(hipStream_t, const CellFwdArgs&, int t);
     void (*launch_seq)(hipStream_t, const CellFwdArgs&);
     void (*launch_bwd_step)(hipStream_t, const CellBwdArgs&);
     void (*launch_bwd_seq)(hipStream_t, const CellBwdArgs&);
 };
+const CellOps *lstm_cell_ops(), *gru_cell_ops(), *rnn_cell_ops();      // each defined by its cell file, from its cell struct (cell.h cell_ops_entry)
 static inline const CellOps* cell_ops(int kind) {      // kind: is_recurrent
-    static const CellOps tab[] = {
-        {"lstm", "LSTM", 4, false, true, false, false, lstm_seq_fits, launch_lstm_step_t, launch_lstm_seq, launch_lstm_bwd_step, launch_lstm_bwd_seq},
-        {"gru", "GRU", 3, false, false, true, true, gru_seq_fits, launch_gru_step_t, launch_gru_seq, launch_gru_bwd_step, launch_gru_bwd_seq},
-        {"rnn", "RNN", 1, true, false, false, false, rnn_seq_fits, launch_rnn_step_t, launch_rnn_seq, launch_rnn_bwd_step, launch_rnn_bwd_seq},
-    };
+    static const CellOps* const tab[] = {lstm_cell_ops(), gru_cell_ops(), rnn_cell_ops()};
     static_assert(DQN_LAYER_GRU == DQN_LAYER_LSTM + 1 && DQN_LAYER_RNN == DQN_LAYER_LSTM + 2, "cell table order");
-    return &tab[kind - DQN_LAYER_LSTM];
+    return tab[kind - DQN_LAYER_LSTM];
 }
 struct EpGatherArgs {
     const float *ep_s, *ep_sp; const int* ep_a; const float* ep_r; const unsigned char* ep_done; const int* ep_len;

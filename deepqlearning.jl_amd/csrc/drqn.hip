@@ -1,6 +1,6 @@
 // drqn.hip -- DRQN on the device (BASELINE config 4):
 //   EpisodeReplayBuffer sample  src/episode_replay.jl:71-95   -> k_gather_episodes (prefix-copy quirk reproduced)
-//   recurrent batch_train!      src/solver.jl:239-287         -> k_lstm_step (x T), k_td_drqn, k_lstm_bwd_step (x T)
+//   recurrent batch_train!      src/solver.jl:239-287         -> k_cell_step<LstmCell> (x T), k_td_drqn, k_cell_bwd_step<LstmCell> (x T)
 //   Flux LSTM (third-party; recalled): g = Wi*x .+ Wh*h .+ b, gates input/forget/cell/output,
 //   c' = sigm(f).*c .+ sigm(i).*tanh(g), h' = sigm(o).*tanh(c'), trainable state0 (h0, c0).
 // Columns are (time-major) t*B + b, so every feed-forward layer of the network runs ONCE over all T*B columns with the
@@ -36,215 +36,39 @@ void launch_gather_episodes(hipStream_t st, const EpGatherArgs& a) {
     hipLaunchKernelGGL(k_gather_episodes, dim3(blocks), dim3(256), 0, st, a);
 }
 
-// ------------------------------------------------------------------ one LSTM time step for up to 3 sequence sets
-__global__ void k_lstm_step(CellFwdArgs A, int t) {
-    const int per = A.H * A.B;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= per * A.nseq) return;
-    const CellSeq& S = A.s[i / per];
-    const int e = i % per, u = e / A.B, b = e % A.B, H = A.H, N = 4 * H;
-    const int col = S.c0 + t * A.B + b;
-    float g[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        const int n = q * H + u; float ch = 0.0f;
-        for (int j = 0; j < H; j++) ch = fmaf(S.hprev[(size_t)j * S.hp_ld + (size_t)b * S.hp_bs], S.Wh[(size_t)j * N + n], ch);
-        g[q] = (S.Gx[(size_t)n * S.ld + col] + ch) + S.bias[n];
+// ------------------------------------------------------------------ the LSTM cell (cell.h: what a cell struct provides, and the kernels built from it)
+// Gates i, f, g, o, all early; the thread of gate 0 finishes c', tanh(c'), h'.  BPTT reads back the four gates, tanh(c), c_{t-1} and the head gradient.
+// The whole-sequence kernels serve small LSTMs (config 4: H = 32, B = 32, T = 8): H*CB ~ 256 outputs per step keeps one wave per SIMD busy and the
+// double-precision sigm / tanh (most of a step's instructions) spread over 4x more CUs.
+struct LstmCell {
+    static constexpr int NG = 4, NE = 4, FIN = 0;
+    static constexpr bool HAS_C = true, TWO_DG = false, ADD_DH = false;
+    static constexpr size_t SEQ_LDS = 64 * 1024;
+    static __device__ __forceinline__ float gate_act(int q, float pre) { return q == 2 ? tanh_f(pre) : sigm_f(pre); }
+    static __device__ __forceinline__ CellFwd finish(const float* a, float, float, float, float, float cp, int) {
+        const float ig = a[0], fg = a[1], gg = a[2], og = a[3];
+        const float t1 = fg * cp; const float t2 = ig * gg; const float c = t1 + t2; const float tc = tanh_f(c); const float h = og * tc;
+        return {h, c, 0.0f, tc};
     }
-    const float ig = sigm_f(g[0]), fg = sigm_f(g[1]), gg = tanh_f(g[2]), og = sigm_f(g[3]);
-    const float cp = S.cprev[(size_t)u * S.cp_ld + (size_t)b * S.cp_bs];
-    const float t1 = fg * cp; const float t2 = ig * gg; const float c = t1 + t2; const float tc = tanh_f(c); const float h = og * tc;
-    S.Hout[(size_t)u * S.ld + col] = h; S.Cst[(size_t)u * S.ld + col] = c;
-    if (S.gates) {
-        const size_t k = (size_t)S.keep_c0 + t * A.B + b; const size_t kl = S.keep_ld;
-        S.gates[(size_t)(0 * H + u) * kl + k] = ig; S.gates[(size_t)(1 * H + u) * kl + k] = fg; S.gates[(size_t)(2 * H + u) * kl + k] = gg; S.gates[(size_t)(3 * H + u) * kl + k] = og;
-        S.aux[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = S.hprev[(size_t)u * S.hp_ld + (size_t)b * S.hp_bs]; S.cprev_out[(size_t)u * kl + k] = cp;
-    }
-}
-void launch_lstm_step_t(hipStream_t st, const CellFwdArgs& a, int t) {
-    const int n = a.H * a.B * a.nseq;
-    hipLaunchKernelGGL(k_lstm_step, dim3((n + 255) / 256), dim3(256), 0, st, a, t);
-}
-
-// ------------------------------------------------------------------ one BPTT step (single workgroup: dh_{t-1} needs all 4H gate gradients of step t)
-__global__ __launch_bounds__(1024) void k_lstm_bwd_step(CellBwdArgs A) {
-    const int H = A.H, B = A.B, TB = A.TB, N = 4 * H, t = A.t, per = H * B;
-    for (int e = threadIdx.x; e < per; e += blockDim.x) {
-        const int u = e / B, b = e % B; const size_t k = (size_t)t * B + b;
-        const float ig = A.gates[(size_t)u * TB + k], fg = A.gates[(size_t)(H + u) * TB + k], gg = A.gates[(size_t)(2 * H + u) * TB + k], og = A.gates[(size_t)(3 * H + u) * TB + k];
-        const float tc = A.aux[(size_t)u * TB + k], cprev = A.cprev[(size_t)u * TB + k];
-        const float dhn = t == A.T - 1 ? 0.0f : A.dhn[e], dcn = t == A.T - 1 ? 0.0f : A.dh2[e];
-        const float dh = A.dH[(size_t)u * TB + k] + dhn;
-        const float dov = dh * tc; const float t1 = dh * og; const float t2 = tc * tc; const float t3 = 1.0f - t2; const float t4 = t1 * t3; const float dc = dcn + t4;
-        const float di = dc * gg, df = dc * cprev, dgc = dc * ig; A.dh2[e] = dc * fg;
-        const float a1 = di * ig, a2 = 1.0f - ig; A.dG[(size_t)u * TB + k] = a1 * a2;
-        const float b1 = df * fg, b2 = 1.0f - fg; A.dG[(size_t)(H + u) * TB + k] = b1 * b2;
-        const float c1 = gg * gg, c2 = 1.0f - c1; A.dG[(size_t)(2 * H + u) * TB + k] = dgc * c2;
-        const float d1 = dov * og, d2 = 1.0f - og; A.dG[(size_t)(3 * H + u) * TB + k] = d1 * d2;
-    }
-    __syncthreads();
-    for (int e = threadIdx.x; e < per; e += blockDim.x) {     // dh_{t-1}[j][b] = sum_n dG[n][t,b] Wh[j][n], n ascending
-        const int j = e / B, b = e % B; const size_t k = (size_t)t * B + b;
-        float acc = 0.0f;
-        for (int n = 0; n < N; n++) acc = fmaf(A.dG[(size_t)n * TB + k], A.Wh[(size_t)j * N + n], acc);
-        A.dhn[e] = acc;
-    }
-    if (t == 0) {                                              // trainable state0: gradient summed over the batch, ascending b
-        __syncthreads();
-        for (int u = threadIdx.x; u < H; u += blockDim.x) state0_fold<true>(u, B, A.dhn, A.dh2, A.g_h0, A.g_c0);
-    }
-}
-void launch_lstm_bwd_step(hipStream_t st, const CellBwdArgs& a) {
-    int bs = ((a.H * a.B + 63) / 64) * 64; if (bs > 1024) bs = 1024;
-    hipLaunchKernelGGL(k_lstm_bwd_step, dim3(1), dim3(bs), 0, st, a);
-}
-
-// ------------------------------------------------------------------ whole-sequence kernels for small LSTMs (config 4: H = 32, B = 32, T = 8)
-// The per-step launches above cost a dispatch and a cold walk over Wh per time step.  When Wh (H x 4H) and one step's state fit in
-// LDS, ONE launch runs the whole recurrence: workgroup s owns sequence set s (online s, online sp, target sp), keeps Wh, the bias
-// and the (h, c) state in LDS and walks t = 0..T-1; the arithmetic per output -- and therefore every bit -- is that of k_lstm_step.
-// Batch columns are independent in the recurrence, so a sequence set is further split into groups of CB columns (cell_cb; one workgroup
-// each, its own LDS copy of Wh): H*CB ~ 256 outputs per step keeps one wave per SIMD busy and the double-precision sigm/tanh
-// (most of a step's instructions) spread over 4x more CUs.
-bool lstm_seq_fits(int H, int B, int T) {     // both kernels within 64 KB of dynamic LDS; the gate-parallel forward wants whole waves per gate
-    const int cb = cell_cb(H, B);
-    const size_t fwd = (size_t)H * 4 * H + 4 * H + 7 * (size_t)H * cb, bwd = (size_t)H * (4 * H + 1) + 6 * (size_t)H * cb;
-    return fwd <= 16384 && bwd <= 16384 && (H * cb) % 64 == 0 && H * cb <= 256 && T <= 64;
-}
-
-// r03: (1) the FOUR gates of an output advance on four threads (thread = (gate, unit, column): one 32-deep chain and ONE Float64 sigm/tanh each
-// instead of four chains and five transcendentals in sequence), the gates meet in LDS and the (unit, column) thread of gate 0 finishes c, tanh(c), h;
-// (2) the input projections Gx of ALL time steps are requested before the recurrence starts (they do not depend on it) -- one round trip instead of one
-// per time step.  Per-element arithmetic unchanged (same chains, same association), so every bit is k_lstm_step's.  TT: compile-time bound on T.
-template <int TT>
-__global__ __launch_bounds__(1024) void k_lstm_seq(CellFwdArgs A, int CB) {
-    extern __shared__ float lds[];
-    const int H = A.H, B = A.B, N = 4 * H, per = H * CB, T = A.T, nsplit = B / CB;
-    float* Wh_s = lds;                 // [H][4H]
-    float* bias_s = Wh_s + H * N;      // [4H]
-    float* h_s = bias_s + N;           // [2][H*CB]
-    float* c_s = h_s + 2 * per;        // [H*CB]
-    float* g_s = c_s + per;            // [4][H*CB] activated gates of the current step
-    const CellSeq& S = A.s[blockIdx.x / nsplit];
-    const int b0 = (blockIdx.x % nsplit) * CB;
-    for (int i = threadIdx.x; i < H * N; i += blockDim.x) Wh_s[i] = S.Wh[i];
-    for (int i = threadIdx.x; i < N; i += blockDim.x) bias_s[i] = S.bias[i];
-    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB; h_s[e] = S.hprev[u]; c_s[e] = S.cprev[u]; }      // Flux.reset!: state0 broadcast over the batch
-    const int q = threadIdx.x / per, e = threadIdx.x - q * per;      // gate, (unit, column) element; per is a multiple of 64, so a wave has one gate
-    const bool on = q < 4;
-    const int u = e / CB, bl = e - u * CB, b = b0 + bl;
-    float gxr[TT];
-#pragma unroll
-    for (int t = 0; t < TT; t++) gxr[t] = (on && t < T) ? S.Gx[(size_t)(q * H + u) * S.ld + S.c0 + t * B + b] : 0.0f;
-    __syncthreads();
-    int cur = 0;
-#pragma unroll
-    for (int t = 0; t < TT; t++) {
-        if (t >= T) break;
-        const float* hp = h_s + cur * per; float* hn = h_s + (cur ^ 1) * per;
-        const int col = S.c0 + t * B + b;
-        if (on) {
-            float ch = 0.0f;
-            const float* wr = Wh_s + q * H + u;
-#pragma unroll 8
-            for (int j = 0; j < H; j++) ch = fmaf(hp[j * CB + bl], wr[j * N], ch);
-            const float g = (gxr[t] + ch) + bias_s[q * H + u];
-            const float act = q == 2 ? tanh_f(g) : sigm_f(g);
-            g_s[q * per + e] = act;
-            if (S.gates) S.gates[(size_t)(q * H + u) * S.keep_ld + (size_t)S.keep_c0 + t * B + b] = act;
-        }
-        __syncthreads();
-        if (q == 0) {
-            const float ig = g_s[e], fg = g_s[per + e], gg = g_s[2 * per + e], og = g_s[3 * per + e];
-            const float cp = c_s[e];
-            const float t1 = fg * cp; const float t2 = ig * gg; const float c = t1 + t2; const float tc = tanh_f(c); const float h = og * tc;
-            S.Hout[(size_t)u * S.ld + col] = h; S.Cst[(size_t)u * S.ld + col] = c;
-            if (S.gates) { const size_t k = (size_t)S.keep_c0 + t * B + b; const size_t kl = S.keep_ld; S.aux[(size_t)u * kl + k] = tc; S.hprev_out[(size_t)u * kl + k] = hp[e]; S.cprev_out[(size_t)u * kl + k] = cp; }
-            hn[e] = h; c_s[e] = c;
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-}
-void launch_lstm_seq(hipStream_t st, const CellFwdArgs& a) {
-    const int cb = cell_cb(a.H, a.B);
-    const size_t lds = ((size_t)a.H * 4 * a.H + 4 * a.H + 7 * (size_t)a.H * cb) * sizeof(float);
-    const int bs = 4 * a.H * cb;                      // 4 gates x (unit, column) elements; lstm_seq_fits: H * cb is a multiple of 64 and <= 256
-    if (a.T <= 8) hipLaunchKernelGGL((k_lstm_seq<8>), dim3(a.nseq * (a.B / cb)), dim3(bs), lds, st, a, cb);
-    else if (a.T <= 32) hipLaunchKernelGGL((k_lstm_seq<32>), dim3(a.nseq * (a.B / cb)), dim3(bs), lds, st, a, cb);
-    else hipLaunchKernelGGL((k_lstm_seq<64>), dim3(a.nseq * (a.B / cb)), dim3(bs), lds, st, a, cb);      // lstm_seq_fits: T <= 64
-}
-
-// BPTT over the whole s-sequence, one workgroup per group of CB columns (same arithmetic as T calls of k_lstm_bwd_step); the
-// trainable state0's gradient (a sum over ALL columns, ascending b) is folded by k_state0_grad (cell.h) afterwards.
-// PF: the seven stashed values of EVERY time step are requested before the loop (T <= 8: 56 registers) instead of one step ahead -- their round trip
-// was longer than a step's arithmetic (r03: 4.6 us per time step)
-template <bool PF>
-__global__ __launch_bounds__(1024) void k_lstm_bwd_seq(CellBwdArgs A, int CB) {
-    extern __shared__ float lds[];
-    const int H = A.H, B = A.B, TB = A.TB, N = 4 * H, per = H * CB, b0 = blockIdx.x * CB;
-    const int NP = N + 1;              // padded row stride: lanes of one wave hold different rows j of Wh at the same n -- stride 4H put all of them on ONE bank (8-way conflict on every read of the 128-deep chain)
-    float* Wh_s = lds;                 // [H][4H + 1]
-    float* dG_s = Wh_s + H * NP;       // [4H][CB]
-    float* dhn_s = dG_s + N * CB;      // [H*CB]
-    float* dcn_s = dhn_s + per;        // [H*CB]
-    for (int i = threadIdx.x; i < H * N; i += blockDim.x) Wh_s[(i / N) * NP + i % N] = A.Wh[i];
-    for (int e = threadIdx.x; e < per; e += blockDim.x) { dhn_s[e] = 0.0f; dcn_s[e] = 0.0f; }
-    __syncthreads();
-    // one (u, column) element per thread (per <= blockDim by construction); the seven stashed values of step t-1 are requested
-    // while step t's dh chain runs, so their latency is off the serial path
-    const int e = threadIdx.x; const bool on = e < per;
-    const int u = on ? e / CB : 0, bl = on ? e - u * CB : 0;
     struct St { float ig, fg, gg, og, tc, cprev, dH; };
-    auto fetch = [&](int t) { St s; const size_t k = (size_t)t * B + b0 + bl;
+    static __device__ __forceinline__ St fetch(const CellBwdArgs& A, int u, size_t k) {
+        const int H = A.H, TB = A.TB; St s;
         s.ig = A.gates[(size_t)u * TB + k]; s.fg = A.gates[(size_t)(H + u) * TB + k]; s.gg = A.gates[(size_t)(2 * H + u) * TB + k]; s.og = A.gates[(size_t)(3 * H + u) * TB + k];
-        s.tc = A.aux[(size_t)u * TB + k]; s.cprev = A.cprev[(size_t)u * TB + k]; s.dH = A.dH[(size_t)u * TB + k]; return s; };
-    St all[PF ? 8 : 1];
-    if constexpr (PF) {
-#pragma unroll
-        for (int t = 0; t < 8; t++) if (t < A.T) all[t] = fetch(t);
+        s.tc = A.aux[(size_t)u * TB + k]; s.cprev = A.cprev[(size_t)u * TB + k]; s.dH = A.dH[(size_t)u * TB + k]; return s;
     }
-    St nx; if constexpr (!PF) nx = fetch(A.T - 1);
-#pragma unroll
-    for (int tt = 0; tt < (PF ? 8 : 1 << 30); tt++) {
-        const int t = (PF ? 7 : A.T - 1) - tt;
-        if (t < 0) break;
-        if (PF && t >= A.T) continue;
-        St c; if constexpr (PF) c = all[PF ? t : 0]; else c = nx;
-        if (on) {
-            const size_t k = (size_t)t * B + b0 + bl;
-            const float ig = c.ig, fg = c.fg, gg = c.gg, og = c.og, tc = c.tc, cprev = c.cprev;
-            const float dhn = t == A.T - 1 ? 0.0f : dhn_s[e], dcn = t == A.T - 1 ? 0.0f : dcn_s[e];
-            const float dh = c.dH + dhn;
-            const float dov = dh * tc; const float t1 = dh * og; const float t2 = tc * tc; const float t3 = 1.0f - t2; const float t4 = t1 * t3; const float dc = dcn + t4;
-            const float di = dc * gg, df = dc * cprev, dgc = dc * ig; dcn_s[e] = dc * fg;
-            const float a1 = di * ig, a2 = 1.0f - ig, v0 = a1 * a2;
-            const float b1 = df * fg, b2 = 1.0f - fg, v1 = b1 * b2;
-            const float c1 = gg * gg, c2 = 1.0f - c1, v2 = dgc * c2;
-            const float d1 = dov * og, d2 = 1.0f - og, v3 = d1 * d2;
-            A.dG[(size_t)u * TB + k] = v0; A.dG[(size_t)(H + u) * TB + k] = v1; A.dG[(size_t)(2 * H + u) * TB + k] = v2; A.dG[(size_t)(3 * H + u) * TB + k] = v3;
-            dG_s[u * CB + bl] = v0; dG_s[(H + u) * CB + bl] = v1; dG_s[(2 * H + u) * CB + bl] = v2; dG_s[(3 * H + u) * CB + bl] = v3;
-        }
-        if constexpr (!PF) { if (t > 0) nx = fetch(t - 1); }
-        __syncthreads();
-        if (on) {                                                  // dh_{t-1}[j][b] = sum_n dG[n][t,b] Wh[j][n], n ascending  (j == u)
-            float acc = 0.0f;
-#pragma unroll 8
-            for (int n = 0; n < N; n++) acc = fmaf(dG_s[n * CB + bl], Wh_s[u * NP + n], acc);
-            dhn_s[e] = acc;
-        }
-        __syncthreads();
+    static __device__ __forceinline__ float bwd(const St& s, float dhn, float dcn, int, float* dG, float*) {
+        const float ig = s.ig, fg = s.fg, gg = s.gg, og = s.og, tc = s.tc, cprev = s.cprev;
+        const float dh = s.dH + dhn;
+        const float dov = dh * tc; const float t1 = dh * og; const float t2 = tc * tc; const float t3 = 1.0f - t2; const float t4 = t1 * t3; const float dc = dcn + t4;
+        const float di = dc * gg, df = dc * cprev, dgc = dc * ig; const float carry = dc * fg;
+        const float a1 = di * ig, a2 = 1.0f - ig; dG[0] = a1 * a2;
+        const float b1 = df * fg, b2 = 1.0f - fg; dG[1] = b1 * b2;
+        const float c1 = gg * gg, c2 = 1.0f - c1; dG[2] = dgc * c2;
+        const float d1 = dov * og, d2 = 1.0f - og; dG[3] = d1 * d2;
+        return carry;
     }
-    for (int e = threadIdx.x; e < per; e += blockDim.x) { const int u = e / CB, bl = e - u * CB; A.dhn[u * B + b0 + bl] = dhn_s[e]; A.dh2[u * B + b0 + bl] = dcn_s[e]; }
-}
-void launch_lstm_bwd_seq(hipStream_t st, const CellBwdArgs& a) {
-    const int cb = cell_cb(a.H, a.B);
-    const size_t lds = ((size_t)a.H * (4 * a.H + 1) + 6 * (size_t)a.H * cb) * sizeof(float);
-    int bs = ((a.H * cb + 63) / 64) * 64; if (bs > 1024) bs = 1024;
-    if (a.T <= 8) hipLaunchKernelGGL((k_lstm_bwd_seq<true>), dim3(a.B / cb), dim3(bs), lds, st, a, cb);
-    else hipLaunchKernelGGL((k_lstm_bwd_seq<false>), dim3(a.B / cb), dim3(bs), lds, st, a, cb);
-    launch_state0_grad(st, a);
-}
+};
+const CellOps* lstm_cell_ops() { static const CellOps ops = cell_ops_entry<LstmCell>("lstm", "LSTM", false, false, launch_cell_seq<LstmCell>); return &ops; }
 
 // ------------------------------------------------------------------ recurrent TD: targets, masked Huber / B / T, dL/dQ  (src/solver.jl:259-282)
 __device__ __forceinline__ float head_at(const HeadSrc& h, int n, int col) { return h.p[(size_t)n * h.ld + col]; }
