@@ -50,7 +50,7 @@ def julia_param_shapes(net):
             out += [((h, l.n_in), h * l.n_in), ((h, h), h * h), ((h,), h), ((h, 1), h)]
         elif l.kind == "layernorm":   # Flux 0.14 LayerNorm(n): diag = Scale(n): scale (n), then bias (n)
             out += [((l.n,), l.n), ((l.n,), l.n)]
-        elif l.kind in ("maxpool", "meanpool"):   # Flux.params(MaxPool / MeanPool) is empty: the file holds no array for the layer
+        elif l.kind in ("maxpool", "meanpool", "dropout"):   # Flux.params(MaxPool / MeanPool / Dropout) is empty: the file holds no array for the layer
             continue
         else:
             raise ValueError(f"unsupported layer kind {l.kind}")

@@ -46,6 +46,12 @@ static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LA
 static inline __host__ __device__ bool is_ln(int kind) { return kind == DQN_LAYER_LAYERNORM; }
 static inline float ln_eps(const LayerDev& L) { if (L.cin == 0) return 1e-5f; float f; memcpy(&f, &L.cin, sizeof f); return f; }
 static inline __host__ __device__ size_t layer_wn(const LayerDev& L) { return is_ln(L.kind) ? (size_t)L.N : (size_t)L.K * L.N; }      // floats in front of the layer's bias
+// Flux Dropout(p) (dropout.hip): parameter-free (K = N = 0 as a pool's), out_feat = in_feat = n; the Float64 bit pattern of p in (cin = low word, cout = high word).  Launched
+// alone on its level in the ONE active pass (online network, s columns of the train step); in every other pass it is the identity and costs nothing: the layer's target /
+// policy activation pointer IS its producer's (engine.hip), so its consumer reads the producer's output
+static inline __host__ __device__ bool is_do(int kind) { return kind == DQN_LAYER_DROPOUT; }
+static inline double do_p(const LayerDev& L) { const uint64_t b = (uint64_t)(uint32_t)L.cin | ((uint64_t)(uint32_t)L.cout << 32); double p; memcpy(&p, &b, sizeof p); return p; }
+#define DQN_DO_TAG 0x44520000u      /* word 3 of the mask counter, | layer index ("DR"; the sampler's tag is 0x5A4D504C, the environments use small purpose codes) */
 // a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 
@@ -747,6 +753,7 @@ struct DrqnColsArgs {
 static inline int drqn_fused_cg(const LayerDev* L, int nl, int E, int B, int T, int nA, int dueling, int double_q, int recurrence) {
     if (!recurrence) return 0;
     for (int i = 0; i < nl; i++) if (is_ln(L[i].kind)) return 0;      // a network with a LayerNorm layer takes the multi-launch recurrent program
+    for (int i = 0; i < nl; i++) if (is_do(L[i].kind)) return 0;      // ... and so does a network with a Dropout layer
     const int duel = dueling ? 1 : 0;
     if (nl != (duel ? 3 : 2) || L[0].kind != DQN_LAYER_LSTM || L[0].stream != DQN_STREAM_BASE || L[0].src >= 0) return 0;
     const int H = L[0].H, N = 4 * H;
@@ -979,6 +986,11 @@ void launch_ln_fwd(hipStream_t st, const LayerDev& L, const float* P, const floa
 // dpre[n][B] = dY .* act'(y) (written by the layer above); X[n][ld] the layer's input (online net, s columns 0 .. B); stat[2][ld_stat] from the forward.
 // dX[n][B] = (gradient of the law) .* act_src'(X); g_scale[n], g_bias[n] = the column sums.  Two launches
 void launch_ln_bwd(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, float* dX, int act_src, float* g_scale, float* g_bias);
+// dropout.hip: the ACTIVE pass of a Dropout layer.  X, Y: [n][ld], the first C columns get the mask of train step k = st->step (read on the device: graphs and
+// dqn_train_steps replay it; the step's TD launch has not bumped it yet), the columns C .. ncols are copied; layer: the layer's index (the counter's tag)
+void launch_do_fwd(hipStream_t stream, int n, double p, unsigned long long seed, int layer, const StepState* st, const float* X, float* Y, int ld, int ncols, int C);
+// dX[n][C] = (keep ? dY * scale : +0) .* act_src'(Ysrc), Ysrc[n][ld] the producing layer's own, unmasked output; runs behind the TD launch, which bumped st->step: k = st->step - 1
+void launch_do_bwd(hipStream_t stream, int n, double p, unsigned long long seed, int layer, const StepState* st, const float* dY, const float* Ysrc, int ld, int C, float* dX, int act_src);
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
                      float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');

@@ -200,6 +200,7 @@ struct FwdEmit {
     bool pm_ok = false;                    // ... and whether it reads slabs piece-major (GFwdProb::pm)
     bool last_on_the_fly = false;          // the consumer of the last level reduces split-K slabs itself (HeadSrc::S > 1)
     bool byte_arena = false;               // LayerDev::xu8 holds for the observation columns of these passes
+    int do_cols = 0;                       // Dropout layers are ACTIVE on the leading do_cols columns of the FIRST pass (the train step: online network, s); 0: inactive everywhere, no launch
     const bool* wantT = nullptr;           // layers whose consumer reads a transposed copy [column][feature] of their output (null: none)
     // ---- out (the arrays are the caller's)
     float* (*actT)[2] = nullptr;           // per (layer, pass): the transposed copy of a wantT layer (needed with wantT)

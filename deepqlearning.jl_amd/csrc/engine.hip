@@ -112,6 +112,20 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             l.cin = d[i].cin;      // the fp32 bit pattern of eps, 0 = the default 1f-5 (ln_eps)
             { const float eps = ln_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: LayerNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].cin); }
             l.K = l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (is_do(l.kind)) {      // Flux Dropout(p), dims = : (dropout.hip): per element of the n incoming features; no parameters (K = N = 0 as a pool's), p's Float64 bits in (cin, cout)
+            if (prev < 0) return fail("layer %d: Dropout cannot be the first layer (it must directly follow a Dense, recurrent or LayerNorm layer; dropout on the observation is not supported)", i);
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Dropout layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (has_map(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
+            if (is_do(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Dropout layer)", i, prev);
+            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: Dropout has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: Dropout n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: Dropout size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
+            if (d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: Dropout uses n_in, n_out, cin and cout (the Float64 bit pattern of p) only; kh / kw / sh / sw = %d / %d / %d / %d must be 0", i, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
+            l.cin = d[i].cin; l.cout = d[i].cout;      // the Float64 bit pattern of p, low word then high word (do_p)
+            { const double p = do_p(l);
+              if (!(p >= 0.0) || !(p < 1.0)) return fail("layer %d: Dropout p = %g (bit pattern 0x%08x%08x) must be finite with 0 <= p < 1%s", i, p, (unsigned)d[i].cout, (unsigned)d[i].cin,
+                                                         p == 1.0 ? " (p = 1 drops every feature: Q would be constant)" : ""); }
+            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
@@ -143,6 +157,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
     } else if (*lb < 0 || L[*lb].out_feat != hp->n_actions) return fail("network output size != n_actions");
     if (!hp->dueling && is_pool(L[*lb].kind)) return fail("layer %d: a MaxPool / MeanPool layer cannot be the network's output layer", *lb);
     if (!hp->dueling && is_ln(L[*lb].kind)) return fail("layer %d: a LayerNorm layer cannot be the network's output layer", *lb);
+    if (!hp->dueling && is_do(L[*lb].kind)) return fail("layer %d: a Dropout layer cannot be the network's output layer", *lb);
     if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
     return 0;
 }
@@ -171,6 +186,7 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
     for (int i = 0; i < n; i++) {
         out[i].fwd_kc = 0;
         if (is_ln(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: the layer's sums have one fixed order (layernorm.hip)
+        if (is_do(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: a Dropout layer's plan entry is all zeros
         // (small batches only: at B >= 128 the 3 B columns of a step already fill the chip -- 512 workgroups for the 3136 -> 512 layers of config 5 --
         // and the split only bought slab traffic plus a reduce launch: 16 us of the 807 us step, r03_g)
         if (L[i].K > 1024 && B < 128) { const int s = (L[i].K + 511) / 512; int kc = (L[i].K + s - 1) / s; kc = (kc + 3) / 4 * 4; out[i].fwd_kc = kc; }
@@ -263,13 +279,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("DQN_SIM_WORLD: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
+    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
     if (!plan) { default_plan(e->L, e->nl, e->B, defp, hp); plan = defp; }
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
-        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm layer's plan entry is ignored
+        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind) || is_do(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's plan entry is ignored
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
@@ -320,7 +337,9 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     size_t pmax = 1, jmax = 1;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev& l = e->L[i];
-        DM(e->act_on[i], (size_t)l.out_feat * e->ncon); DM(e->act_tg[i], (size_t)l.out_feat * Bc); DM(e->dact[i], (size_t)l.out_feat * Bc);
+        DM(e->act_on[i], (size_t)l.out_feat * e->ncon); DM(e->dact[i], (size_t)l.out_feat * Bc);
+        if (is_do(l.kind)) e->act_tg[i] = e->act_tg[l.src];      // inactive in the target pass: the consumer reads the producer's output (an alias, never freed)
+        else DM(e->act_tg[i], (size_t)l.out_feat * Bc);
         const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
         const size_t sw = dqn_nchunks(l.npos * Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
         const size_t sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
@@ -370,7 +389,7 @@ void drop_act(dqn_engine* e, dqn_engine::ActProg& a) {
 }
 static void free_policy_ws(dqn_engine* e) {
     hipFree(e->pol_obs); hipFree(e->pol_x); hipFree(e->pol_q); hipFree(e->pol_a);
-    for (int i = 0; i < e->nl; i++) { hipFree(e->pol_act[i]); e->pol_act[i] = nullptr; }
+    for (int i = 0; i < e->nl; i++) { if (!is_do(e->L[i].kind)) hipFree(e->pol_act[i]); e->pol_act[i] = nullptr; }      // (a Dropout layer's is its producer's)
     e->pol_obs = e->pol_x = e->pol_q = nullptr; e->pol_a = nullptr; e->pol_n = 0;
 }
 extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
@@ -389,7 +408,7 @@ extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     for (int k = 0; k < 4; k++) if (e->draw_ev[k]) hipEventDestroy(e->draw_ev[k]);
     hipFree(e->pub_ctr);
     hipFree(e->st_a); hipFree(e->st_r); hipFree(e->st_done); hipFree(e->st_td); hipFree(e->idx); hipFree(e->idx_pre); hipFree(e->x0);
-    for (int i = 0; i < e->nl; i++) { hipFree(e->act_on[i]); hipFree(e->act_tg[i]); hipFree(e->dact[i]); }
+    for (int i = 0; i < e->nl; i++) { hipFree(e->act_on[i]); if (!is_do(e->L[i].kind)) hipFree(e->act_tg[i]); hipFree(e->dact[i]); }
     hipFree(e->join_tmp); hipFree(e->partials); hipFree(e->gmax_part); hipFree(e->w_is); hipFree(e->td); hipFree(e->q_on_s); hipFree(e->q_on_sp); hipFree(e->q_tg_sp);
     hipFree(e->ytarget); hipFree(e->best); hipFree(e->gb_rows); hipFree(e->gb_r); hipFree(e->gb_done); hipFree(e->gb_w); hipFree(e->gb_a); hipFree(e->gb_idx);
     hipFree(e->gb_r2); hipFree(e->gb_done2); hipFree(e->gb_w2); hipFree(e->gb_a2);
@@ -610,6 +629,7 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 
 // ---------------------------------------------------------------- the train step
 void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials) {
+    if (is_do(l.kind)) return;      // inactive everywhere but the train step's online pass on s (emit_forward): the identity, and Y IS X (the layer's activation aliases its producer's)
     if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
     else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
@@ -1048,7 +1068,7 @@ int policy_ws(dqn_engine* e, int n) {
     for (int i = 0; i < e->nl; i++) { const size_t sf = dqn_nchunks(e->L[i].K, e->L[i].fwd_kc); if (sf > 1) need = std::max(need, sf * (size_t)e->L[i].out_feat * n); }
     if (need > e->partials_elems) { drop_graphs(e); hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * need); e->partials_elems = need; }
     DM(e->pol_obs, (size_t)n * e->E); DM(e->pol_x, (size_t)n * e->E); DM(e->pol_q, (size_t)n * e->nA); DM(e->pol_a, n);
-    for (int i = 0; i < e->nl; i++) DM(e->pol_act[i], (size_t)e->L[i].out_feat * n);
+    for (int i = 0; i < e->nl; i++) { if (is_do(e->L[i].kind)) e->pol_act[i] = e->pol_act[e->L[i].src]; else DM(e->pol_act[i], (size_t)e->L[i].out_feat * n); }      // Dropout: inactive when acting, the producer's output
     e->pol_n = n; return 0;
 }
 int policy_state(dqn_engine* e, int n, bool force_reset) {
@@ -1093,7 +1113,7 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
             if (C->has_c) { q.Cst = e->pol_c[i][fl ^ 1]; q.cprev = e->pol_c[i][fl]; q.cp_ld = n; q.cp_bs = 1; }
             C->launch_step(e->stream, a, 0);
             HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
-        } else fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");
+        } else if (!is_do(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");      // a Dropout layer is the identity here: no launch
     }
     if (e->hp.recurrence) e->pol_flip ^= 1;
     const int lq = e->hp.dueling ? e->last_adv : e->last_base;
@@ -1119,6 +1139,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
+    for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;

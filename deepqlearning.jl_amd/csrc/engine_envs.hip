@@ -191,6 +191,7 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
     int k = 0;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src]; float* Y = e->pol_act[i];
+        if (is_do(l.kind)) continue;      // a Dropout layer is the identity when acting: nothing is emitted, pol_act[i] is its producer's
         if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l.kind, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, l, P, X, n, 0, n, Y, mf, 0, nullptr, en->partials); }}); continue; }
         const CellOps* C = cell_ops(l.kind);
         const LayerDev Vw = gx_view(l);
@@ -231,7 +232,8 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
     bool any_ln = false; for (int i = 0; i < e->nl; i++) any_ln = any_ln || is_ln(e->L[i].kind);      // ... and so does a network with a LayerNorm layer (layernorm.hip): fused_tail = 0
     const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
-    bool use_ah = !general && !e->opt.no_act_head && !any_padded && !any_ln && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
+    bool any_do = false; for (int i = 0; i < e->nl; i++) any_do = any_do || is_do(e->L[i].kind);      // ... and a network with a Dropout layer (dropout.hip; nothing is emitted for the layer itself): fused_tail = 0
+    bool use_ah = !general && !e->opt.no_act_head && !any_padded && !any_ln && !any_do && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
     if (use_ah) { ah_S = fused_head_layout(e, levels, lq, lvh, &ah_pa, &ah_pv); use_ah = ah_S > 0 && act_head_ok(n, e->L[lq].K, ah_S, e->nA, lvh >= 0 ? 2 : 1, e->L[lq].N, lvh >= 0 ? e->L[lvh].N : 0); }
     // one pass on the n columns of pol_x; the last level's consumer (k_env_step) reduces split-K slabs on the fly; no transposed copies, no byte arena, no LayerNorm statistics
     FwdEmit fe; fe.gemm = "act_fwd"; fe.valu = "act_fwd_valu"; fe.reduce = "act_reduce"; fe.skip_last = use_ah /* the head level runs inside k_act_head */; fe.last_on_the_fly = true; fe.head = head;

@@ -35,7 +35,7 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
     segs.clear();
 }
 const char* pname(dqn_engine* e, const char* op, int kind, int i) {
-    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
+    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : is_do(kind) ? "do" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
 Levels net_levels(const dqn_engine* e) {
     Levels levels; std::vector<int> val, adv;
@@ -71,6 +71,18 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
     for (size_t li = li0; li < li1; li++) {
         const auto& lv = levels[li]; const bool last = li + 1 == levels.size();
         if (E.skip_last && last) continue;
+        if (is_do(e->L[lv[0]].kind)) {
+            // a Dropout layer (dropout.hip; base chain only, so alone on its level) is ACTIVE in one pass only: the first pass of the train step, on its leading E.do_cols columns
+            // (online network, s).  There it writes a buffer of its own -- the producer's output must survive for the producer's backward -- and copies the s' columns behind
+            // them.  Every other pass (target, acting, evaluation) emits NOTHING: the layer's activation pointer of that pass is its producer's (engine.hip)
+            const int l = lv[0]; const LayerDev L = e->L[l];
+            for (int pi = 0; pi < np; pi++) { const Prob q = prob(l, pi); HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = nullptr; h.act = DQN_ACT_IDENTITY; E.head[l][pi] = h; }
+            if (E.do_cols > 0) {
+                const Prob q = prob(l, 0); const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
+                prog.push_back({pname(e, passes[0].tag, L.kind, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
+            }
+            continue;
+        }
         if (is_pool(e->L[lv[0]].kind) || is_ln(e->L[lv[0]].kind) || is_padded(e->L[lv[0]])) {
             // a layer launched alone on its level (base chain only): one launch per pass, never grouped with a GEMM layer -- a pool (pool.hip), a LayerNorm layer (layernorm.hip:
             // the first pass keeps (mu, sigma) per column for the backward), a padded conv (conv_pad.hip walks the plan chunks itself)
@@ -163,6 +175,8 @@ int build_program(dqn_engine* e) {
     // a LayerNorm layer (layernorm.hip) is launched alone, as a pool is; every fusion below that pairs a layer with a neighbour or swallows the whole step (the fused recurrent
     // step, the single-workgroup step, the fused reduce + head launches) DECLINES a network that holds one, by name, instead of relying on its own shape tests
     bool has_ln = false; for (int i = 0; i < e->nl; i++) has_ln = has_ln || is_ln(e->L[i].kind);
+    // ... and so does a Dropout layer (dropout.hip), which those fused launches would have to mask in one of their passes and not in the others
+    bool has_do = false; for (int i = 0; i < e->nl; i++) has_do = has_do || is_do(e->L[i].kind);
     float* ln_stat[DQN_MAX_LAYERS] = {};      // per LayerNorm layer: (mu, sigma) of the online pass's columns, kept for the backward
     // forward outputs: a recurrent layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (gx_view, writing gx_*); the recurrence then
     // runs as T small launches (or one).
@@ -176,7 +190,7 @@ int build_program(dqn_engine* e) {
         if (cgm) {
             if (!rec || !all_same) return fail("plan: column-group dW chunks (dw_kc < 0) need recurrence = true and the same dw_kc on every layer");
             const int nset = e->hp.double_q ? 3 : 2; const LayerDev& L0 = e->L[0];
-            bool ok = !has_ln && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
+            bool ok = !has_ln && !has_do && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
             if (ok) { ok = dqn_nchunks(L0.K, L0.fwd_kc) == 1; for (int i = 1; i < e->nl; i++) ok = ok && dqn_nchunks(e->L[i].N, e->L[i].dx_kc) == 1; }
             if (!ok) return fail("plan: column-group dW chunks (dw_kc = %d) need a network the fused recurrent step covers -- Chain(flattenbatch, LSTM, Dense) with or without the dueling split, "
                                  "H a multiple of 8 up to 64, unsplit input projection and head dX, ONE device without a communicator -- use dw_kc >= 0 (plan = NULL picks a plan that fits; with a communicator dqn_comm_init re-derives it)", -cgm);
@@ -224,7 +238,7 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
-    if (!rec && !has_ln && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
+    if (!rec && !has_ln && !has_do && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
         (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
         bool ok = true; size_t fl = 0;
         TinyArgs a; memset(&a, 0, sizeof a);
@@ -290,7 +304,7 @@ int build_program(dqn_engine* e) {
     // (red_head.hip: workgroup = 4 batch columns x stream x plan chunk of 32 hidden rows, the last arriver of a column group does TD + the heads' dX) instead of
     // k_reduce_multi (384 workgroups) + k_head_td (B workgroups)
     bool fuse_rh = false; int rh_pa = -1, rh_pv = -1, rh_S = 0;
-    if (fuse_heads && !has_ln && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
+    if (fuse_heads && !has_ln && !has_do && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
         rh_S = fused_head_layout(e, levels, ha_l, hv_l, &rh_pa, &rh_pv);
         // S > 1: k_red_head (split-K producers, small batches).  S == 1 -- finished activations of an unsplit forward, i.e. large batches: k_head_cols4, one workgroup per
         // column group (k_red_head's (group, stream, chunk) decomposition is SLOWER there: 27.4 vs 21.3 us for k_head_td at B = 512, profiles/history/r05_k_cfg5_red_head_ab.txt --
@@ -305,7 +319,7 @@ int build_program(dqn_engine* e) {
     if (e->opt.probe_no_tg) passes.pop_back();      // TIMING PROBE (wrong numbers, right schedule): the forward launches without the target network's problems
     FwdEmit fe; fe.gemm = "fwd"; fe.valu = "fwd_valu"; fe.reduce = "fwd_reduce"; fe.skip_last = fuse_heads /* computed inside k_head_td */; fe.byte_arena = true;
     if (fuse_rh) { fe.prod[0] = rh_pa; fe.prod[1] = rh_pv; fe.pm_ok = rh_S > 1 && !e->opt.no_rh_pm; }
-    fe.last_on_the_fly = !rec && e->B <= 64; fe.wantT = wantT; fe.actT = actT; fe.ln_stat = ln_stat; fe.head = head;
+    fe.last_on_the_fly = !rec && e->B <= 64; fe.wantT = wantT; fe.actT = actT; fe.ln_stat = ln_stat; fe.do_cols = B /* the s columns of the online pass */; fe.head = head;
     for (size_t li = 0; li < levels.size(); li++) {
         emit_forward(e, levels, li, li + 1, passes, fe);
         const auto& lv = levels[li];
@@ -418,7 +432,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -538,6 +552,14 @@ int build_program(dqn_engine* e) {
                     const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act;
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
                 }
+                continue;
+            }
+            if (is_do(L.kind)) {
+                // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (the layer has no activation); the backward regenerates the forward's
+                // mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on that layer's own,
+                // unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation
+                const float* Ysrc = e->act_on[L.src]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act; const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
+                e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_do_bwd(en->stream, L.out_feat, p, seed, l, stt, dpre, Ysrc, ncon, B, out, act_src); }});
                 continue;
             }
             if (is_ln(L.kind)) {
@@ -674,7 +696,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;

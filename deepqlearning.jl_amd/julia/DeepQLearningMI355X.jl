@@ -75,6 +75,14 @@ function lower_layer(l, stream)::LayerDesc
         length(l.size) == 1 || throw("DeepQLearningError: the MI355X engine supports LayerNorm(n) with an integer n only, got size=$(l.size)")
         (l.affine && l.diag isa Flux.Scale) || throw("DeepQLearningError: the MI355X engine supports LayerNorm with affine=true only")
         return LayerDesc(7, ACT[l.λ], stream, l.size[1], l.size[1], reinterpret(Int32, Float32(l.ϵ)), 0, 0, 0, 0, 0)
+    elseif l isa Flux.Dropout      # Flux 0.14 fields p, dims, active, rng; no parameters (Flux.params skips the layer)
+        # automatic mode (active === nothing): the layer is active only under Flux.gradient -- the engine masks the online forward on s and nothing else.  A forced mode
+        # (trainmode! / testmode!) is not the reference's behaviour.  p crosses as its Float64 bit pattern, low word in cin, high word in cout (Float32(0.1) would move
+        # 1 / (1 - p) off Flux's value); n_in = n_out = 0: the engine takes the incoming feature count.  The mask is the engine's own counter-based law, not l.rng
+        l.dims === Colon() || throw("DeepQLearningError: the MI355X engine supports Dropout with dims = : only, got dims=$(l.dims)")
+        l.active === nothing || throw("DeepQLearningError: the MI355X engine supports Dropout in Flux's automatic mode only (active = nothing), got active=$(l.active): a forced train / test mode is not the reference's behaviour")
+        bits = reinterpret(UInt64, Float64(l.p))
+        return LayerDesc(8, 0, stream, 0, 0, reinterpret(Int32, UInt32(bits & 0xffffffff)), reinterpret(Int32, UInt32(bits >> 32)), 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.LSTMCell     # Flux.params order Wi, Wh, b, state0 (h0, c0) == the ABI's LSTM block
         return LayerDesc(2, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (Flux's GRUv3 has another block: unsupported)
@@ -82,7 +90,7 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 function lower(q)

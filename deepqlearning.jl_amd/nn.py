@@ -116,7 +116,7 @@ class MeanPool(_Pool):
 class LayerNorm:
     """Flux 0.14 LayerNorm(n, λ = identity; affine = true, eps = 1f-5) on a feature vector of length n, per batch column (Flux's `normalise`; recalled, not executed here):
     μ = mean(x), σ = sqrt(mean((x - μ)²)) (uncorrected), y = λ.(scale .* (x - μ) / (σ + eps) .+ bias) -- eps is added to σ OUTSIDE the root, which is not torch's
-    sqrt(var + eps).  Flux.params: diag.scale (n, ones), diag.bias (n, zeros).  Directly behind a Dense or recurrent layer, base chain only."""
+    sqrt(var + eps).  Flux.params: diag.scale (n, ones), diag.bias (n, zeros).  Directly behind a Dense or recurrent layer (or the Dropout that follows one), base chain only."""
     kind = "layernorm"
 
     def __init__(self, n, act=identity, eps=1e-5, affine=True):
@@ -139,6 +139,27 @@ class LayerNorm:
 
     def shapes(self):   # Flux.params order: diag.scale, diag.bias
         return [(self.n,), (self.n,)]
+
+
+class Dropout:
+    """Flux 0.14 Dropout(p; dims = :) on a feature vector, per batch column, in Flux's automatic mode (recalled, not executed here): active only under Flux.gradient --
+    in the train step's online forward on s, y = keep ? x * Float32(1 / (1 - p)) : 0 -- and the identity in every other pass (online on s', target, acting, evaluation,
+    after restore_best_model).  The mask is the engine's own counter-based law, not Julia's RNG.  No parameters: Flux.params skips the layer.
+    Directly behind a Dense, recurrent or LayerNorm layer, base chain only, never the first or the output layer."""
+    kind = "dropout"
+
+    def __init__(self, p, dims=None):
+        if dims is not None and dims != ":":
+            raise _abi.DQNError(f"DeepQLearningError: Dropout({p!r}; dims={dims!r}) is not supported; the MI355X engine drops single elements (dims = :)")
+        self.p, self.act = float(p), identity
+        if not (np.isfinite(self.p) and 0.0 <= self.p < 1.0):
+            raise _abi.DQNError(f"DeepQLearningError: Dropout({p!r}): p must be finite with 0 <= p < 1" + (" (p = 1 drops every feature: Q would be constant)" if self.p == 1.0 else ""))
+
+    def __repr__(self):
+        return f"Dropout({self.p!r})"
+
+    def shapes(self):   # Flux.params holds nothing for a Dropout layer
+        return []
 
 
 class LSTM:
@@ -234,8 +255,8 @@ def lower(net):
     def add(chain, stream):
         for l in chain:
             d = _abi.LayerDesc()
-            if getattr(l, "kind", None) not in ("dense", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
             d.act, d.stream = l.act, stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -248,6 +269,10 @@ def lower(net):
             elif l.kind == "layernorm":      # n in both size slots; the fp32 bit pattern of eps rides in cin (as a Conv's pad rides in n_in / n_out)
                 d.kind, d.n_in, d.n_out = _abi.LAYER_LAYERNORM, l.n, l.n
                 d.cin = int(np.float32(l.eps).view(np.int32))
+            elif l.kind == "dropout":      # n_in == n_out == 0: the engine fills in the incoming feature count; p crosses as its Float64 bit pattern, low word in cin, high in cout
+                bits = int(np.float64(l.p).view(np.uint64))
+                d.kind = _abi.LAYER_DROPOUT
+                d.cin, d.cout = int(np.uint32(bits & 0xFFFFFFFF).view(np.int32)), int(np.uint32(bits >> 32).view(np.int32))
             elif l.kind in ("maxpool", "meanpool"):      # cin == cout == channels of the incoming map
                 d.kind = _abi.LAYER_MAXPOOL if l.kind == "maxpool" else _abi.LAYER_MEANPOOL
                 d.cin = d.cout = chan[0]
@@ -283,7 +308,7 @@ def glorot_params(net, seed=1):
     rng = np.random.default_rng(seed)
     parts = []
     for l in all_layers(net):
-        if l.kind in ("maxpool", "meanpool"):      # no parameters
+        if l.kind in ("maxpool", "meanpool", "dropout"):      # no parameters
             continue
         if l.kind == "layernorm":      # Flux Scale(n): scale = ones, bias = zeros
             parts += [np.ones(l.n, np.float32), np.zeros(l.n, np.float32)]

@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8 };
 enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3 };
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
@@ -67,8 +67,18 @@ typedef struct {
                                           LayerNorm(n, act; affine = true, eps) (Flux 0.14 `normalise`, recalled, not executed): n_in == n_out == n >= 2 == the incoming feature count, act = the
                                           layer's activation, stream = BASE, cin = the fp32 BIT PATTERN of eps (0 = the default 1f-5; finite and > 0), every other slot 0.  Per batch column
                                           mu = mean(x), sigma = sqrt(mean((x - mu)^2)), y = act(scale * (x - mu) / (sigma + eps) + bias): eps is added to sigma OUTSIDE the root (not torch's
-                                          sqrt(var + eps)).  Parameters in Flux.params order: scale (n), bias (n).  Directly behind a Dense or recurrent layer, base chain only, never the
-                                          output layer, single GPU only; its plan entry is ignored.  A column with sigma = 0 has a finite forward (x_hat = 0); its backward is undefined */
+                                          sqrt(var + eps)).  Parameters in Flux.params order: scale (n), bias (n).  Directly behind a Dense or recurrent layer (or the Dropout layer that follows one), base chain only, never the
+                                          output layer, single GPU only; its plan entry is ignored.  A column with sigma = 0 has a finite forward (x_hat = 0); its backward is undefined;
+                                          Dropout(p), dims = : (Flux 0.14 automatic mode, recalled, not executed): n_in == n_out == the incoming feature count (or both 0: the engine fills them
+                                          in), act = IDENTITY, stream = BASE, p as its Float64 BIT PATTERN, low word in cin, high word in cout (finite, 0 <= p < 1), every other slot 0.
+                                          No parameters (Flux.params skips the layer); its plan entry is all zeros and ignored.  ACTIVE only in the online network's pass on the s columns
+                                          of a train step (the forward Flux.gradient differentiates): y = keep ? x * Float32(1 / (1 - p)) : +0, dX = keep ? dY * scale : +0 with the same
+                                          mask regenerated; the IDENTITY, at no cost, in every other pass (online on s', target, dqn_forward, dqn_greedy_action, the device loops,
+                                          dqn_evaluate).  The mask is the engine's own law (Julia's RNG is not matched): Philox4x32-10 keyed by hparams.seed on the counter
+                                          {k lo, k hi, q, 0x44520000 | layer index}, k = train steps completed before this one, q = f * ceil(C / 4) + col / 4 over the C active columns
+                                          (col = t * B + b in a recurrent step), the four output words for columns 4 (col / 4) + 0..3, u = (word >> 8) * 2^-24, keep <=> (double)u >= p.
+                                          Directly behind a Dense, recurrent or LayerNorm layer (a LayerNorm may follow it), base chain only, never the first or the output layer,
+                                          single GPU only */
 } dqn_layer_desc;
 
 /* Summation-order plan of one layer: the K dimension of each contraction is cut
