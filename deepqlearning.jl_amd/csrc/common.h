@@ -90,38 +90,95 @@ static inline __host__ __device__ int dqn_chunk_len(int K, int kc) { return (kc 
 // tanh / sigmoid through Float64 (Flux's Float32 activations round once): OUT OF LINE.  Inlined at every use -- four per epilogue vector, in every kernel -- these two bodies
 // were most of the code of the forward kernels (k_fwd_lds<2>: 1185 instructions without them, ~10 000 with) and stood, as branch targets nobody takes at relu / identity
 // layers, between the instructions that run (r05: same-box A/B of a build without them: +1.4 % steps/s at config 2).  Same arithmetic, same bits.
+//
+// THE ACTIVATION LAW (include/dqn_mi355x.h carries the table for users; this is the one place that computes it).  x: the fp32 pre-activation, y: the stored fp32 output;
+// the engine keeps only y, so every derivative is a function of y (NNlib writes its rules the same way: deriv_elu(Ω), deriv_selu(Ω), (1 - abs(Ω))^2, ...).  The forwards with a
+// transcendental or a division go through Float64 and round once, as tanh / sigmoid do; the three select-only ones (leakyrelu, relu6, hardtanh) are plain fp32.
+// NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu α = 1; selu's λ, α below.  Codes >= DQN_ACT_TANH take the out-of-line path: identity / relu layers pay one range
+// compare inline, nothing else (docs/history/activations.md has the instruction counts).
+#define DQN_SELU_LAMBDA 1.0507009873554805
+#define DQN_SELU_ALPHA 1.6732632423543772
+#define DQN_SELU_LAMBDA_ALPHA 1.7580993408473766
 __device__ __attribute__((noinline)) static float act_slow(float y, int act) {
-    if (act == DQN_ACT_TANH) return (float)tanh((double)y);
-    return (float)(1.0 / (1.0 + exp(-(double)y)));
-}
-__device__ __forceinline__ float act_f(float y, int act) {
-#ifdef DQN_PROBE_NO_TRANS      /* TIMING PROBE (r05): tanh / sigmoid compiled out */
-    return act == DQN_ACT_RELU ? (y > 0.0f ? y : 0.0f) : y;
-#else
-    if (act == DQN_ACT_RELU) return y > 0.0f ? y : 0.0f;
-    if (act == DQN_ACT_TANH || act == DQN_ACT_SIGMOID) return act_slow(y, act);
-    return y;
-#endif
-}
-__device__ __forceinline__ float dact_f(float dy, float y, int act) {
+    const double x = (double)y;
     switch (act) {
-    case DQN_ACT_RELU: return y > 0.0f ? dy : 0.0f;
-    case DQN_ACT_TANH: { float t = y * y; float u = 1.0f - t; return dy * u; }
-    case DQN_ACT_SIGMOID: { float u = 1.0f - y; float t = y * u; return dy * t; }
+    case DQN_ACT_TANH: return (float)tanh(x);
+    case DQN_ACT_SIGMOID: return (float)(1.0 / (1.0 + exp(-x)));
+    case DQN_ACT_LEAKYRELU: return y > 0.0f ? y : 0.01f * y;
+    case DQN_ACT_ELU: return y >= 0.0f ? y : (float)expm1(x);
+    case DQN_ACT_SELU: return (float)(DQN_SELU_LAMBDA * (y > 0.0f ? x : DQN_SELU_ALPHA * expm1(x)));
+    case DQN_ACT_SOFTPLUS: return (float)(log1p(exp(-fabs(x))) + (x > 0.0 ? x : 0.0));
+    case DQN_ACT_SOFTSIGN: return (float)(x / (1.0 + fabs(x)));
+    case DQN_ACT_RELU6: return fminf(fmaxf(y, 0.0f), 6.0f);
+    case DQN_ACT_HARDTANH: return fmaxf(-1.0f, fminf(1.0f, y));
+    default: return y;
+    }
+}
+// the derivatives of the codes >= DQN_ACT_LEAKYRELU from the stored output, in fp32 (softplus: σ(x) = 1 - e^(-y) through Float64, rounded once).  tanh' and sigmoid' are
+// two multiplies each and stay in dact_f's inline switch, where they always were
+__device__ __forceinline__ float dact_new(float dy, float y, int act) {
+    switch (act) {
+    case DQN_ACT_LEAKYRELU: return y > 0.0f ? dy : 0.01f * dy;
+    case DQN_ACT_ELU: return y >= 0.0f ? dy : dy * (y + 1.0f);
+    case DQN_ACT_SELU: return y > 0.0f ? (float)DQN_SELU_LAMBDA * dy : dy * (y + (float)DQN_SELU_LAMBDA_ALPHA);
+    case DQN_ACT_SOFTPLUS: return dy * (float)(-expm1(-(double)y));
+    case DQN_ACT_SOFTSIGN: { float u = 1.0f - fabsf(y); float t = u * u; return dy * t; }
+    case DQN_ACT_RELU6: return (y > 0.0f && y < 6.0f) ? dy : 0.0f;
+    case DQN_ACT_HARDTANH: return (y > -1.0f && y < 1.0f) ? dy : 0.0f;
     default: return dy;
     }
 }
-// four values at once: ONE decode of the activation code per vector (the element-wise helpers above cost a switch -- three or four scalar branches -- per element, and a
-// lone wave pays every branch: r04).  V = any 4-component vector type with .x .y .z .w
+// ... OUT OF LINE, for the reason above
+__device__ __attribute__((noinline)) static float dact_slow(float dy, float y, int act) { return dact_new(dy, y, act); }
+__device__ __forceinline__ float act_f(float y, int act) {
+#ifdef DQN_PROBE_NO_TRANS      /* TIMING PROBE (r05): the arithmetic of every code above relu compiled out of the forwards; of every code above sigmoid out of the backwards (dact_f, dact_v4) */
+    return act == DQN_ACT_RELU ? (y > 0.0f ? y : 0.0f) : y;
+#else
+    if (act == DQN_ACT_RELU) return y > 0.0f ? y : 0.0f;
+    if (act >= DQN_ACT_TANH) return act_slow(y, act);
+    return y;
+#endif
+}
+// CALL = false: dact_new's body in line instead of the call.  For the backward kernels of nn_gemm.hip only, which had no call before and live at the SGPR limit (106): one call
+// anywhere in such a kernel -- taken or not -- costs it the registers the calling convention reserves, and the allocator spills two dozen more scalars to VGPR lanes along
+// the paths that DO run (docs/history/activations.md: dw_conv1 / dw_conv2 of config 2, +0.3 us each).  The body sits behind the default label: relu / identity layers never reach it
+template <bool CALL = true> __device__ __forceinline__ float dact_f(float dy, float y, int act) {
+    switch (act) {
+    case DQN_ACT_IDENTITY: return dy;
+    case DQN_ACT_RELU: return y > 0.0f ? dy : 0.0f;
+    case DQN_ACT_TANH: { float t = y * y; float u = 1.0f - t; return dy * u; }
+    case DQN_ACT_SIGMOID: { float u = 1.0f - y; float t = y * u; return dy * t; }
+#ifdef DQN_PROBE_NO_TRANS
+    default: return dy;
+#else
+    default: if constexpr (CALL) return dact_slow(dy, y, act); else return dact_new(dy, y, act);
+#endif
+    }
+}
+// four values at once: ONE decode of the activation code per vector for identity / relu (the element-wise helpers above cost a switch -- three or four scalar branches -- per
+// element, and a lone wave pays every branch: r04); the codes from tanh upwards decode once here and once more per element in act_f / dact_f.  V = any 4-component vector type with .x .y .z .w
 template <class V> __device__ __forceinline__ void act_v4(V& v, float bias, int act) {
     const float a = v.x + bias, b = v.y + bias, c = v.z + bias, d = v.w + bias;
     if (act == DQN_ACT_RELU) { v.x = a > 0.0f ? a : 0.0f; v.y = b > 0.0f ? b : 0.0f; v.z = c > 0.0f ? c : 0.0f; v.w = d > 0.0f ? d : 0.0f; }
-    else if (act == DQN_ACT_TANH || act == DQN_ACT_SIGMOID) { v.x = act_f(a, act); v.y = act_f(b, act); v.z = act_f(c, act); v.w = act_f(d, act); }
+    else if (act >= DQN_ACT_TANH) { v.x = act_f(a, act); v.y = act_f(b, act); v.z = act_f(c, act); v.w = act_f(d, act); }
     else { v.x = a; v.y = b; v.z = c; v.w = d; }
 }
-template <class V> __device__ __forceinline__ void dact_v4(V& v, const V& y, int act) {
+template <bool CALL = true, class V> __device__ __forceinline__ void dact_v4(V& v, const V& y, int act) {
     if (act == DQN_ACT_RELU) { v.x = y.x > 0.0f ? v.x : 0.0f; v.y = y.y > 0.0f ? v.y : 0.0f; v.z = y.z > 0.0f ? v.z : 0.0f; v.w = y.w > 0.0f ? v.w : 0.0f; }
-    else if (act == DQN_ACT_TANH || act == DQN_ACT_SIGMOID) { v.x = dact_f(v.x, y.x, act); v.y = dact_f(v.y, y.y, act); v.z = dact_f(v.z, y.z, act); v.w = dact_f(v.w, y.w, act); }
+    else if (CALL || act <= DQN_ACT_SIGMOID) {
+        if (act >= DQN_ACT_TANH) { v.x = dact_f<CALL>(v.x, y.x, act); v.y = dact_f<CALL>(v.y, y.y, act); v.z = dact_f<CALL>(v.z, y.z, act); v.w = dact_f<CALL>(v.w, y.w, act); }
+    }
+#ifndef DQN_PROBE_NO_TRANS
+    else {      // CALL == false and a code above sigmoid: ONE copy of dact_new's body per vector, not four.  The loop is kept rolled; each turn handles the element in .x and
+                // rotates the vector by one (eight v_mov per turn, on a path relu / identity / tanh / sigmoid layers never take); after four turns every element is back in place
+        V u = y;
+#pragma clang loop unroll(disable)
+        for (int i = 0; i < 4; i++) {
+            const float r = dact_new(v.x, u.x, act);
+            v.x = v.y; v.y = v.z; v.z = v.w; v.w = r; { const float t = u.x; u.x = u.y; u.y = u.z; u.z = u.w; u.w = t; }
+        }
+    }
+#endif
 }
 // (float)b / 255.0f for a byte b (u8 observations, test/test_env.jl:59) in TWO operations beside the conversion instead of the ~10-instruction IEEE division:
 // 1/255 = r_hi + r_lo with r_hi = 0x1.01p-8 (9 significant bits: b * r_hi is exact for b < 256) and r_lo = fl(1/255 - r_hi), so fma(b, r_lo, b * r_hi) rounds

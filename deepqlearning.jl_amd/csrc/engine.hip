@@ -78,6 +78,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         l.in_feat = c * h * w;
         if (l.kind == DQN_LAYER_CONV) {
             l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);      // every kernel decodes the code on trust: an unknown one would train with some other law
             if (l.cin != c) return fail("layer %d: conv cin %d != incoming channels %d", i, l.cin, c);
             // pad = (ph, pw) rides in the n_in / n_out slots (zero in every pad-0 descriptor): symmetric zero padding, at most kernel - 1 per axis (conv_pad.hip)
             l.ph = d[i].n_in; l.pw = d[i].n_out;
@@ -107,7 +108,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (d[i].n_in != d[i].n_out) return fail("layer %d: LayerNorm n_in %d != n_out %d (both carry the size n)", i, d[i].n_in, d[i].n_out);
             if (d[i].n_out < 2) return fail("layer %d: LayerNorm size n = %d must be >= 2 (over one feature sigma is identically 0 and the gradient is NaN)", i, d[i].n_out);
             if (d[i].n_in != l.in_feat) return fail("layer %d: LayerNorm size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID) return fail("layer %d: LayerNorm activation %d is not one of DQN_ACT_*", i, d[i].act);
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: LayerNorm activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: LayerNorm uses n_in, n_out, act and cin (the bit pattern of eps) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
             l.cin = d[i].cin;      // the fp32 bit pattern of eps, 0 = the default 1f-5 (ln_eps)
             { const float eps = ln_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: LayerNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].cin); }
@@ -127,9 +128,11 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                                                          p == 1.0 ? " (p = 1 drops every feature: Q would be constant)" : ""); }
             l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
         } else if (l.kind == DQN_LAYER_DENSE) {
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Dense activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
             l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (is_recurrent(l.kind)) {      // the cell's activation (CellOps::has_act) goes to cell_act, never to act (the cell's kernels apply it)
+        } else if (is_recurrent(l.kind)) {      // the cell's activation (CellOps::has_act) goes to cell_act, never to act (the cell's kernels apply it); an RNN cell's σ is one of the
+                                                // first four codes: cell.h states the cell's arithmetic on its own, and the codes above DQN_ACT_SIGMOID are Dense / Conv / LayerNorm epilogues only
             const CellOps* C = cell_ops(l.kind);
             if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
             if (l.stream != DQN_STREAM_BASE) return fail("%s layers are supported in the base chain only", C->display);

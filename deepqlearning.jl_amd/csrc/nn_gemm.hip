@@ -1185,7 +1185,7 @@ __device__ __forceinline__ void dx_units_body(const LayerDev& L, const GDxArgs& 
         }
         if (si == 0) v = tot; else { v.x = v.x + tot.x; v.y = v.y + tot.y; v.z = v.z + tot.z; v.w = v.w + tot.w; }
     }
-    if (A.ysrc) { v.x = dact_f(v.x, y_e.x, A.act_src); v.y = dact_f(v.y, y_e.y, A.act_src); v.z = dact_f(v.z, y_e.z, A.act_src); v.w = dact_f(v.w, y_e.w, A.act_src); }
+    if (A.ysrc) dact_v4<false>(v, y_e, A.act_src);      // (<false>: no call in this kernel, common.h)
     const size_t featx = dense ? (size_t)fl : (size_t)fl * L.ih * L.iw + ip;
     st_out4(reinterpret_cast<f32x4*>(A.out + featx * B + b0 + 16 * mt + 4 * kq), v, L.opt & DQN_LOPT_ST_WT);
 }
@@ -1327,7 +1327,7 @@ __device__ __forceinline__ void dx_lds_body_wide(const LayerDev& L, const GDxArg
             if (A.nsrc > 1) { const f32x4 o = acc[1][ft][ml]; v.x = v.x + o.x; v.y = v.y + o.y; v.z = v.z + o.z; v.w = v.w + o.w; }
             if (S == 1 && A.ysrc) {
                 const f32x4 y = *reinterpret_cast<const f32x4*>(A.ysrc + feat * A.ldy + bcol);
-                dact_v4(v, y, A.act_src);
+                dact_v4<false>(v, y, A.act_src);
             }
             st_out4(reinterpret_cast<f32x4*>(A.out + (size_t)s * per_s + feat * B + bcol), v, L.opt & DQN_LOPT_ST_WT);
         }

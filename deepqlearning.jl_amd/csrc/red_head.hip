@@ -38,7 +38,8 @@ __device__ __forceinline__ f32x4r ld_sc1_x4(const float* p) { f32x4r v; asm vola
 __device__ __forceinline__ void st_sc1(float* p, float v) { __hip_atomic_store(gptr(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ float ld_sc1(const float* p) { return __hip_atomic_load(gptr(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
-// activations: TRANS == false instantiations know only identity / relu (selects, no code) -- the Float64 tanh / sigmoid bodies of act_f / dact_f inlined at every use made
+// activations: TRANS == false instantiations know only identity / relu (selects, no code); every code >= DQN_ACT_TANH takes the TRANS == true ones (launch_red_head) -- the
+// Float64 tanh / sigmoid bodies of act_f / dact_f inlined at every use made
 // the kernel 5600 instructions of branchy code that each last arriver walks ONCE, cold in the instruction cache (r05 stamps: 3 us for six dX items per lane)
 template <bool TRANS> __device__ __forceinline__ float rh_act(float y, int a) { if constexpr (TRANS) return act_f(y, a); else return a == DQN_ACT_RELU ? (y > 0.0f ? y : 0.0f) : y; }
 template <bool TRANS> __device__ __forceinline__ float rh_dact(float dy, float y, int a) { if constexpr (TRANS) return dact_f(dy, y, a); else return a == DQN_ACT_RELU ? (y > 0.0f ? dy : 0.0f) : dy; }
@@ -551,7 +552,7 @@ void launch_red_head(hipStream_t st, const RedHeadArgs& a, const RedHeadArgs* a_
     const size_t lds = red_head_lds_bytes(a);
     const unsigned grid = (unsigned)((a.B / 4) * (a.K / 32) * a.nstream);
     (void)a_dev;
-    auto tr = [](int x) { return x == DQN_ACT_TANH || x == DQN_ACT_SIGMOID; };
+    auto tr = [](int x) { return x >= DQN_ACT_TANH; };      // every code with out-of-line arithmetic (common.h act_slow / dact_slow)
     const bool trans = tr(a.st[0].pact) || tr(a.st[0].hact) || (a.nstream > 1 && (tr(a.st[1].pact) || tr(a.st[1].hact)));
     if (a.S == 1) {      // unsplit producers (large batches): one workgroup per column group, no hand-off
         const size_t l4 = head_cols4_lds_bytes(a);

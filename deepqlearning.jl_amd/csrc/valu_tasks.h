@@ -136,7 +136,7 @@ __device__ __forceinline__ void valu_dx_body(const LayerDev& L, const float* __r
     }
     if (S == 1) {
         if (addend) acc = addend[e] + acc;
-        if (ysrc) acc = dact_f(acc, ysrc[(size_t)feat * ldy + b], act_src);
+        if (ysrc) acc = dact_f<false>(acc, ysrc[(size_t)feat * ldy + b], act_src);      // (<false>: this body is compiled into the tails of nn_gemm.hip's backward kernels, which take no call: common.h)
         out[e] = acc;
     } else out[(size_t)s * per_s + e] = acc;
 }

@@ -51,9 +51,23 @@ end
 
 check(rc) = rc == 0 ? nothing : throw(unsafe_string(ccall((:dqn_last_error, LIB), Cstring, ())))  # reference errors are thrown Strings
 
-const ACT = Dict(identity => 0, relu => 1, tanh => 2, sigmoid => 3)
+# DQN_ACT_* (include/dqn_mi355x.h has the table of the eleven laws).  NNlib's default parameters only: leakyrelu(x) = leakyrelu(x, 0.01), elu(x) = elu(x, 1)
+const ACT = Dict(identity => 0, relu => 1, tanh => 2, sigmoid => 3, leakyrelu => 4, elu => 5, selu => 6, softplus => 7, softsign => 8, relu6 => 9, hardtanh => 10)
+const ACT_SUPPORTED = "identity / relu / tanh / sigmoid / leakyrelu / elu / selu / softplus / softsign / relu6 / hardtanh"
+const ACT_NEEDS_X = (gelu, swish, mish, hardswish)      # not monotone: the derivative is no function of the output
+# the activation a layer carries: σ of a Dense / Conv / RNN cell, λ of a LayerNorm; nothing for the layers without one
+layer_act(l) = (l isa Dense || l isa Conv) ? l.σ : l isa Flux.LayerNorm ? l.λ : (l isa Flux.Recur && l.cell isa Flux.RNNCell) ? l.cell.σ : nothing
+# the one check of a layer's activation: lower_layer calls it first, so that every ACT[...] lookup below it is a hit (a bare lookup died on a KeyError with no explanation).
+# Throws the DeepQLearningError that names what is supported, and why the rest is not
+function check_act(l)
+    f = layer_act(l)
+    (f === nothing || haskey(ACT, f)) && return nothing
+    any(g -> f === g, ACT_NEEDS_X) && throw("DeepQLearningError: unsupported activation $(f) on $(typeof(l)): it is not monotone, so its derivative needs the pre-activation, and the MI355X engine keeps only each layer's output and differentiates from it (supported: $(ACT_SUPPORTED))")
+    throw("DeepQLearningError: unsupported activation $(f) on $(typeof(l)) (supported: $(ACT_SUPPORTED)); default parameters only: a closure such as x -> leakyrelu(x, 0.2f0) or x -> elu(x, 2f0) has no code")
+end
 
 function lower_layer(l, stream)::LayerDesc
+    check_act(l)
     if l isa Dense
         return LayerDesc(0, ACT[l.σ], stream, size(l.weight, 2), size(l.weight, 1), 0, 0, 0, 0, 0, 0)
     elseif l isa Conv
@@ -87,7 +101,7 @@ function lower_layer(l, stream)::LayerDesc
         return LayerDesc(2, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     elseif l isa Flux.Recur && l.cell isa Flux.GRUCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's GRU block (Flux's GRUv3 has another block: unsupported)
         return LayerDesc(3, 0, stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
-    elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ
+    elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ (the engine accepts the first four codes there)
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
     throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")

@@ -11,6 +11,36 @@ import numpy as np
 from . import _abi
 
 identity, relu, tanh, sigmoid = _abi.ACT_IDENTITY, _abi.ACT_RELU, _abi.ACT_TANH, _abi.ACT_SIGMOID
+# NNlib's default parameters only: leakyrelu(x) = leakyrelu(x, 0.01), elu(x) = elu(x, 1) (include/dqn_mi355x.h has the table of all eleven)
+leakyrelu, elu, selu, softplus, softsign, relu6, hardtanh = (_abi.ACT_LEAKYRELU, _abi.ACT_ELU, _abi.ACT_SELU, _abi.ACT_SOFTPLUS, _abi.ACT_SOFTSIGN, _abi.ACT_RELU6,
+                                                             _abi.ACT_HARDTANH)
+ACT_NAMES = ("identity", "relu", "tanh", "sigmoid", "leakyrelu", "elu", "selu", "softplus", "softsign", "relu6", "hardtanh")      # index = DQN_ACT_* code
+
+
+class _UnsupportedActivation:
+    """a name Flux users write that the engine cannot run: a sentinel `lower` refuses with the reason"""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return self.name
+
+
+# not monotone: the derivative is no function of the output y, and the engine keeps only y (every backward epilogue differentiates from it)
+gelu, swish, mish, hardswish = (_UnsupportedActivation(n) for n in ("gelu", "swish", "mish", "hardswish"))
+
+
+def _act_code(l):
+    """the DQN_ACT_* code of a layer's activation, or the DeepQLearningError that names what is supported"""
+    a = l.act
+    supported = " / ".join(ACT_NAMES)
+    if isinstance(a, _UnsupportedActivation):
+        raise _abi.DQNError(f"DeepQLearningError: unsupported activation {a.name} on {l!r}: {a.name} is not monotone, so its derivative needs the pre-activation, and the "
+                            f"MI355X engine keeps only each layer's output y and differentiates from it (supported: {supported})")
+    if isinstance(a, (int, np.integer)) and not isinstance(a, bool) and 0 <= int(a) < len(ACT_NAMES):
+        return int(a)
+    raise _abi.DQNError(f"DeepQLearningError: unsupported activation {a!r} on {l!r} (supported: {supported}, with NNlib's default parameters only)")
 
 
 class flattenbatch:  # src/helpers.jl:6-8 -- a no-op marker: the engine flattens between Conv and Dense
@@ -23,6 +53,9 @@ class Dense:
 
     def __init__(self, n_in, n_out, act=identity):
         self.n_in, self.n_out, self.act = int(n_in), int(n_out), act
+
+    def __repr__(self):
+        return f"Dense({self.n_in}, {self.n_out}, act={self.act})"
 
     def shapes(self):  # host array shapes in Julia memory order: weight (out,in) == C (in,out); bias (out,)
         return [(self.n_in, self.n_out), (self.n_out,)]
@@ -257,7 +290,7 @@ def lower(net):
             d = _abi.LayerDesc()
             if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
                 raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
-            d.act, d.stream = l.act, stream
+            d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
             elif l.kind == "lstm":

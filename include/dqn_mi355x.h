@@ -42,7 +42,28 @@ extern "C" {
 typedef struct dqn_engine dqn_engine_t;
 
 enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8 };
-enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3 };
+/* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
+ * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
+ * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
+ *   code          forward                                                        dx from (dy, y), fp32
+ *   IDENTITY   0  x                                                              dy
+ *   RELU       1  x > 0 ? x : 0                                                  y > 0 ? dy : 0
+ *   TANH       2  (float)tanh((double)x)                                         dy * (1 - y * y)
+ *   SIGMOID    3  (float)(1 / (1 + exp(-(double)x)))                             dy * (y * (1 - y))
+ *   LEAKYRELU  4  x > 0 ? x : 0.01f * x                                          y > 0 ? dy : 0.01f * dy
+ *   ELU        5  x >= 0 ? x : (float)expm1((double)x)                           y >= 0 ? dy : dy * (y + 1)
+ *   SELU       6  (float)(L * (x > 0 ? x : A * expm1((double)x)))                y > 0 ? (float)L * dy : dy * (y + (float)LA)
+ *   SOFTPLUS   7  (float)(log1p(exp(-fabs((double)x))) + max((double)x, 0))      dy * (float)(-expm1(-(double)y))        (sigmoid(x) = 1 - exp(-y))
+ *   SOFTSIGN   8  (float)((double)x / (1 + fabs((double)x)))                     dy * ((1 - |y|) * (1 - |y|))
+ *   RELU6      9  min(max(x, 0), 6)                                              (y > 0 && y < 6) ? dy : 0
+ *   HARDTANH  10  max(-1, min(1, x))                                             (y > -1 && y < 1) ? dy : 0
+ * A Dense, Conv or LayerNorm layer takes any of the eleven; any other code is refused at dqn_plan_default / dqn_engine_create by layer index and code.  An RNN layer's
+ * cell activation stays one of the first four (IDENTITY .. SIGMOID): the cell states its arithmetic on its own.  gelu, swish, mish and hardswish are not monotone: their
+ * derivative needs the pre-activation, which the engine does not keep; parametrised forms (leakyrelu(x, 0.2), elu(x, 2)) have no code.  NNlib's definitions are recalled,
+ * not executed: elu's x >= 0, selu's x > 0 and leakyrelu's derivative taken at x > 0 are what only a maintainer with Julia can pin. */
+enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3, DQN_ACT_LEAKYRELU = 4, DQN_ACT_ELU = 5, DQN_ACT_SELU = 6, DQN_ACT_SOFTPLUS = 7,
+       DQN_ACT_SOFTSIGN = 8, DQN_ACT_RELU6 = 9, DQN_ACT_HARDTANH = 10 };
+#define DQN_ACT_LAST DQN_ACT_HARDTANH
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
 enum { DQN_NET_ONLINE = 0, DQN_NET_TARGET = 1 };
@@ -53,7 +74,7 @@ enum { DQN_NET_ONLINE = 0, DQN_NET_TARGET = 1 };
  * flattenbatch (src/helpers.jl:6-8) is implicit between a Conv and a Dense. */
 typedef struct {
     int32_t kind;   /* DQN_LAYER_* */
-    int32_t act;    /* DQN_ACT_*; for an RNN layer the cell's activation */
+    int32_t act;    /* DQN_ACT_* (Dense, Conv, LayerNorm: any of the eleven); for an RNN layer the cell's activation, one of the first four */
     int32_t stream; /* DQN_STREAM_*; all BASE when dueling == 0 */
     int32_t n_in, n_out;               /* Dense(in,out); LSTM(in,out) = Flux Recur(LSTMCell): params Wi (4out,in), Wh (4out,out), b (4out), state0 h0, c0;
                                           GRU(in,out) = Flux Recur(GRUCell): params Wi (3out,in), Wh (3out,out), b (3out), state0 h0;
