@@ -33,6 +33,7 @@ struct LayerDev {
     int opt;                           // per-ENGINE experiment switches the kernel launchers look at (DQN_LOPT_*, set at dqn_engine_create from EngineOpts): no process-wide state
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
     int ph, pw;                        // Conv: symmetric zero padding per axis (dqn_layer_desc n_in / n_out slots); ih, iw stay the UNPADDED map, oh = (ih + 2 ph - kh) / sh + 1
+    int src2;                          // DQN_LAYER_SKIPADD: the block's entry P, the producer the block's first inner layer reads (src = the last inner layer K); -1 on every other layer
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
@@ -52,6 +53,11 @@ static inline __host__ __device__ size_t layer_wn(const LayerDev& L) { return is
 static inline __host__ __device__ bool is_do(int kind) { return kind == DQN_LAYER_DROPOUT; }
 static inline double do_p(const LayerDev& L) { const uint64_t b = (uint64_t)(uint32_t)L.cin | ((uint64_t)(uint32_t)L.cout << 32); double p; memcpy(&p, &b, sizeof p); return p; }
 #define DQN_DO_TAG 0x44520000u      /* word 3 of the mask counter, | layer index ("DR"; the sampler's tag is 0x5A4D504C, the environments use small purpose codes) */
+// the join of a Flux SkipConnection(layers, +) block (skip.hip): y = y_K + y_P, K = src the block's last inner layer, P = src2 the producer its first inner layer F reads.
+// Parameter-free (K = N = 0), no activation, cin = m the number of inner layers (the m layers in front of it); launched alone on its level in EVERY pass.  Its backward is two
+// launches: at the join dact[K] = dY .* act_K'(y_K) (an alias of dact[join] where act_K is IDENTITY: engine.hip), at the entry dact[P] = (dF + dY) .* act_P'(y_P) behind F's
+// input-gradient launch, which therefore runs with the IDENTITY epilogue (src_act, engine_program.hip)
+static inline __host__ __device__ bool is_skip(int kind) { return kind == DQN_LAYER_SKIPADD; }
 // a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 
@@ -811,6 +817,7 @@ static inline int drqn_fused_cg(const LayerDev* L, int nl, int E, int B, int T, 
     if (!recurrence) return 0;
     for (int i = 0; i < nl; i++) if (is_ln(L[i].kind)) return 0;      // a network with a LayerNorm layer takes the multi-launch recurrent program
     for (int i = 0; i < nl; i++) if (is_do(L[i].kind)) return 0;      // ... and so does a network with a Dropout layer
+    for (int i = 0; i < nl; i++) if (is_skip(L[i].kind)) return 0;      // ... and a network with a skip block (skip.hip): a producer with two consumers
     const int duel = dueling ? 1 : 0;
     if (nl != (duel ? 3 : 2) || L[0].kind != DQN_LAYER_LSTM || L[0].stream != DQN_STREAM_BASE || L[0].src >= 0) return 0;
     const int H = L[0].H, N = 4 * H;
@@ -1048,6 +1055,13 @@ void launch_ln_bwd(hipStream_t st, const LayerDev& L, const float* P, const floa
 void launch_do_fwd(hipStream_t stream, int n, double p, unsigned long long seed, int layer, const StepState* st, const float* X, float* Y, int ld, int ncols, int C);
 // dX[n][C] = (keep ? dY * scale : +0) .* act_src'(Ysrc), Ysrc[n][ld] the producing layer's own, unmasked output; runs behind the TD launch, which bumped st->step: k = st->step - 1
 void launch_do_bwd(hipStream_t stream, int n, double p, unsigned long long seed, int layer, const StepState* st, const float* dY, const float* Ysrc, int ld, int C, float* dX, int act_src);
+// skip.hip: the join of a SkipConnection(+) block.  Y = A[n][lda] + X[n][ldx] on the columns col0 .. col0 + ncols of the two operands; Y[n][ncols] is dense (column j of the
+// window is column j of Y).  One fp32 add per element
+void launch_skip_fwd(hipStream_t stream, int n, const float* A, int lda, const float* X, int ldx, int col0, int ncols, float* Y);
+// dK[n][B] = dY[n][B] .* act_K'(Yk), Yk[n][ld] the last inner layer's stored output (not launched where act_K is IDENTITY: dK IS dY)
+void launch_skip_bwd_join(hipStream_t stream, int n, const float* dY, const float* Yk, int ld, int B, float* dK, int act_k);
+// dP[n][B] = (dF[n][B] + dY[n][B]) .* act_P'(Yp), dF the raw input gradient of the first inner layer, Yp[n][ld] the entry's stored output; dP may be dF (element-wise in place)
+void launch_skip_bwd_entry(hipStream_t stream, int n, const float* dF, const float* dY, const float* Yp, int ld, int B, float* dP, int act_p);
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
                      float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');

@@ -160,8 +160,19 @@ void drop_graphs(dqn_engine* e);
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a);
 // one layer's forward launched alone on the given columns, by kind: THE place (with emit_forward, engine_program.hip) where the forward side learns a new layer kind.
 // xu8: X is the byte arena of a u8 replay (padded convs only); ln_stat: where a LayerNorm layer keeps (mu, sigma) per column, or null; partials: split-K workspace of the GEMM kinds
-void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials);
-void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name);      // ... inside a profiling bracket
+// X2, ldx2: the second operand of a skip block's join (the output of the block's entry, LayerDev::src2; X is the last inner layer's), null for every other kind
+void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials, const float* X2 = nullptr, int ldx2 = 0);
+void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name, const float* X2 = nullptr, int ldx2 = 0);      // ... inside a profiling bracket
+// a skip block's join whose last inner layer has no activation: the join's backward is the identity, so dact[join] IS dact[src] (one buffer; engine.hip allocates, skip.hip)
+static inline bool skip_dact_alias(const dqn_engine* e, int i) { return is_skip(e->L[i].kind) && e->L[e->L[i].src].act == DQN_ACT_IDENTITY; }
+// the activation whose derivative layer l's input-gradient launch applies in its epilogue: its producer's -- unless that producer is the entry P of a skip block (then l is
+// the block's first inner layer and P has a second consumer, the join): the launch writes the RAW gradient and the block's entry launch (skip.hip) takes P's derivative
+// once, after the sum.  THE statement of the rule: every dX site of engine_program.hip goes through it
+static inline int src_act(const dqn_engine* e, int l) {
+    const int s = e->L[l].src;
+    for (int j = 0; j < e->nl; j++) if (is_skip(e->L[j].kind) && e->L[j].src2 == s) return DQN_ACT_IDENTITY;
+    return e->L[s].act;
+}
 void enqueue_step(dqn_engine* e, const StepKey& k);
 int capture_graph(dqn_engine* e, const char* what, const std::function<int()>& body, hipGraphExec_t* out);      // the one stream capture of the library
 int run_phase(dqn_engine* e, const StepKey& k, bool eager = false);      // the cached graph of k (captured on first use), or k enqueued eagerly

@@ -67,7 +67,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
     *lb = *lv = *la = -1; size_t off = 0, eoff = 0;
     for (int i = 0; i < n; i++) {
         LayerDev& l = L[i]; memset(&l, 0, sizeof l);
-        l.kind = d[i].kind; l.act = d[i].act; l.stream = d[i].stream;
+        l.kind = d[i].kind; l.act = d[i].act; l.stream = d[i].stream; l.src2 = -1;
         int prev;
         if (l.stream == DQN_STREAM_BASE) prev = *lb; else if (l.stream == DQN_STREAM_VAL) prev = *lv >= 0 ? *lv : *lb; else prev = *la >= 0 ? *la : *lb;
         l.src = prev;
@@ -127,6 +127,27 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
               if (!(p >= 0.0) || !(p < 1.0)) return fail("layer %d: Dropout p = %g (bit pattern 0x%08x%08x) must be finite with 0 <= p < 1%s", i, p, (unsigned)d[i].cout, (unsigned)d[i].cin,
                                                          p == 1.0 ? " (p = 1 drops every feature: Q would be constant)" : ""); }
             l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (is_skip(l.kind)) {      // the join of a Flux SkipConnection(layers, +) block (skip.hip): y = y_K + y_P; cin = m, the number of inner layers (the m descriptors in front)
+            const int m = d[i].cin;
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a skip block is supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: a skip block's join has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
+            if (m < 1) return fail("layer %d: a skip block holds at least one inner layer (cin = m = %d must be >= 1)", i, m);
+            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: a skip block's join uses n_in, n_out and cin (the number of inner layers) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
+            if (m > i) return fail("layer %d: the skip block's %d inner layers would start before the first layer (the block cannot be the first layer: its input is never the observation)", i, m);
+            for (int j = i - m; j < i; j++) {
+                if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
+                if (is_skip(L[j].kind)) return fail("layer %d: the skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
+                if (is_recurrent(L[j].kind)) return fail("layer %d: the skip block holds a recurrent layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only", i, j);
+                if (has_map(L[j].kind)) return fail("layer %d: the skip block holds a Conv / MaxPool / MeanPool layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (convolutional residual blocks are not supported)", i, j);
+            }
+            const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
+            if (pp < 0) return fail("layer %d: the skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the output of a Dense, recurrent, LayerNorm or Dropout layer or of another skip block)", i, i - m);
+            if (has_map(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a Conv / MaxPool / MeanPool layer); a skip block stands on a feature vector (convolutional residual blocks are not supported)", i, pp);
+            if (L[prev].out_feat != L[pp].out_feat) return fail("layer %d: the skip block maps %d features to %d; SkipConnection(layers, +) needs layers: n -> n", i, L[pp].out_feat, L[prev].out_feat);
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: skip block n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: skip block size n = %d != the block's features %d", i, d[i].n_in, l.in_feat);
+            l.cin = m; l.src2 = pp;
+            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Dense activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
@@ -161,6 +182,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
     if (!hp->dueling && is_pool(L[*lb].kind)) return fail("layer %d: a MaxPool / MeanPool layer cannot be the network's output layer", *lb);
     if (!hp->dueling && is_ln(L[*lb].kind)) return fail("layer %d: a LayerNorm layer cannot be the network's output layer", *lb);
     if (!hp->dueling && is_do(L[*lb].kind)) return fail("layer %d: a Dropout layer cannot be the network's output layer", *lb);
+    if (!hp->dueling && is_skip(L[*lb].kind)) return fail("layer %d: a skip block cannot be the network's output layer", *lb);
     if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
     return 0;
 }
@@ -190,6 +212,7 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
         out[i].fwd_kc = 0;
         if (is_ln(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: the layer's sums have one fixed order (layernorm.hip)
         if (is_do(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: a Dropout layer's plan entry is all zeros
+        if (is_skip(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // ... and so is a skip block's join's
         // (small batches only: at B >= 128 the 3 B columns of a step already fill the chip -- 512 workgroups for the 3136 -> 512 layers of config 5 --
         // and the split only bought slab traffic plus a reduce launch: 16 us of the 807 us step, r03_g)
         if (L[i].K > 1024 && B < 128) { const int s = (L[i].K + 511) / 512; int kc = (L[i].K + s - 1) / s; kc = (kc + 3) / 4 * 4; out[i].fwd_kc = kc; }
@@ -283,13 +306,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
+    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_skip(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a skip block; data-parallel replicas of a network with skip blocks are not supported (single GPU only)", i);
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
     if (!plan) { default_plan(e->L, e->nl, e->B, defp, hp); plan = defp; }
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
-        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind) || is_do(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's plan entry is ignored
+        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind) || is_do(e->L[i].kind) || is_skip(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's / skip join's plan entry is ignored
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
@@ -340,7 +364,9 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     size_t pmax = 1, jmax = 1;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev& l = e->L[i];
-        DM(e->act_on[i], (size_t)l.out_feat * e->ncon); DM(e->dact[i], (size_t)l.out_feat * Bc);
+        DM(e->act_on[i], (size_t)l.out_feat * e->ncon);
+        if (skip_dact_alias(e, i)) e->dact[i] = e->dact[l.src];      // a skip join behind an inner chain that ends without an activation: dK IS dY (an alias, never freed; skip.hip)
+        else DM(e->dact[i], (size_t)l.out_feat * Bc);
         if (is_do(l.kind)) e->act_tg[i] = e->act_tg[l.src];      // inactive in the target pass: the consumer reads the producer's output (an alias, never freed)
         else DM(e->act_tg[i], (size_t)l.out_feat * Bc);
         const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
@@ -411,7 +437,7 @@ extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     for (int k = 0; k < 4; k++) if (e->draw_ev[k]) hipEventDestroy(e->draw_ev[k]);
     hipFree(e->pub_ctr);
     hipFree(e->st_a); hipFree(e->st_r); hipFree(e->st_done); hipFree(e->st_td); hipFree(e->idx); hipFree(e->idx_pre); hipFree(e->x0);
-    for (int i = 0; i < e->nl; i++) { hipFree(e->act_on[i]); if (!is_do(e->L[i].kind)) hipFree(e->act_tg[i]); hipFree(e->dact[i]); }
+    for (int i = 0; i < e->nl; i++) { hipFree(e->act_on[i]); if (!is_do(e->L[i].kind)) hipFree(e->act_tg[i]); if (!skip_dact_alias(e, i)) hipFree(e->dact[i]); }
     hipFree(e->join_tmp); hipFree(e->partials); hipFree(e->gmax_part); hipFree(e->w_is); hipFree(e->td); hipFree(e->q_on_s); hipFree(e->q_on_sp); hipFree(e->q_tg_sp);
     hipFree(e->ytarget); hipFree(e->best); hipFree(e->gb_rows); hipFree(e->gb_r); hipFree(e->gb_done); hipFree(e->gb_w); hipFree(e->gb_a); hipFree(e->gb_idx);
     hipFree(e->gb_r2); hipFree(e->gb_done2); hipFree(e->gb_w2); hipFree(e->gb_a2);
@@ -631,16 +657,17 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 }
 
 // ---------------------------------------------------------------- the train step
-void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials) {
+void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials, const float* X2, int ldx2) {
+    if (is_skip(l.kind)) { launch_skip_fwd(st, l.out_feat, X, ldx, X2, ldx2, col0, ncols, Y); return; }      // X: the last inner layer's output, X2: the block's entry's
     if (is_do(l.kind)) return;      // inactive everywhere but the train step's online pass on s (emit_forward): the identity, and Y IS X (the layer's activation aliases its producer's)
     if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
     else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
     else if (!(use_mfma && launch_mfma_fwd(st, l, P, X, ldx, col0, ncols, Y, partials))) launch_valu_fwd(st, l, P, X, ldx, col0, ncols, Y, partials);
 }
-void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name) {
+void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name, const float* X2, int ldx2) {
     prof_begin(e, name);
-    launch_layer_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma != 0, 0 /* the policy workspace holds floats */, nullptr, e->partials);
+    launch_layer_fwd(e->stream, l, P, X, ldx, col0, ncols, Y, e->hp.use_mfma != 0, 0 /* the policy workspace holds floats */, nullptr, e->partials, X2, ldx2);
     prof_end(e);
 }
 
@@ -1116,7 +1143,8 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
             if (C->has_c) { q.Cst = e->pol_c[i][fl ^ 1]; q.cprev = e->pol_c[i][fl]; q.cp_ld = n; q.cp_bs = 1; }
             C->launch_step(e->stream, a, 0);
             HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
-        } else if (!is_do(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");      // a Dropout layer is the identity here: no launch
+        } else if (is_skip(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd", e->pol_act[l.src2], n);      // a skip join: the last inner layer's output + the block's entry's
+        else if (!is_do(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");      // a Dropout layer is the identity here: no launch
     }
     if (e->hp.recurrence) e->pol_flip ^= 1;
     const int lq = e->hp.dueling ? e->last_adv : e->last_base;
@@ -1143,6 +1171,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
     for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
     for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
+    for (int i = 0; i < e->nl; i++) if (is_skip(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a skip block; data-parallel replicas of a network with skip blocks are not supported (single GPU only)", i);
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;

@@ -35,7 +35,7 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
     segs.clear();
 }
 const char* pname(dqn_engine* e, const char* op, int kind, int i) {
-    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : is_do(kind) ? "do" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
+    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : is_do(kind) ? "do" : is_skip(kind) ? "skip" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
 Levels net_levels(const dqn_engine* e) {
     Levels levels; std::vector<int> val, adv;
@@ -80,6 +80,18 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             if (E.do_cols > 0) {
                 const Prob q = prob(l, 0); const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
                 prog.push_back({pname(e, passes[0].tag, L.kind, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
+            }
+            continue;
+        }
+        if (is_skip(e->L[lv[0]].kind)) {
+            // the join of a skip block (skip.hip; base chain only, so alone on its level): in EVERY pass y = (the last inner layer's stored output) + (the stored output of the
+            // block's entry, LayerDev::src2) on that pass's own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online
+            // pass and its producer's (the alias) everywhere else.  One launch per pass
+            const int l = lv[0]; const LayerDev L = e->L[l];
+            for (int pi = 0; pi < np; pi++) {
+                const Prob q = prob(l, pi); const float* X2 = passes[pi].in[L.src2];
+                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = nullptr; h.act = DQN_ACT_IDENTITY; E.head[l][pi] = h;
+                prog.push_back({pname(e, passes[pi].tag, L.kind, l), [=](dqn_engine* en) { launch_skip_fwd(en->stream, L.out_feat, q.X, q.ldx, X2, q.ncols, q.col0, q.ncols, q.Y); }});
             }
             continue;
         }
@@ -177,6 +189,8 @@ int build_program(dqn_engine* e) {
     bool has_ln = false; for (int i = 0; i < e->nl; i++) has_ln = has_ln || is_ln(e->L[i].kind);
     // ... and so does a Dropout layer (dropout.hip), which those fused launches would have to mask in one of their passes and not in the others
     bool has_do = false; for (int i = 0; i < e->nl; i++) has_do = has_do || is_do(e->L[i].kind);
+    // ... and a skip block (skip.hip), whose entry has two consumers and whose join reads two producers: none of those launches has a second operand or a second gradient
+    bool has_skip = false; for (int i = 0; i < e->nl; i++) has_skip = has_skip || is_skip(e->L[i].kind);
     float* ln_stat[DQN_MAX_LAYERS] = {};      // per LayerNorm layer: (mu, sigma) of the online pass's columns, kept for the backward
     // forward outputs: a recurrent layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (gx_view, writing gx_*); the recurrence then
     // runs as T small launches (or one).
@@ -190,7 +204,7 @@ int build_program(dqn_engine* e) {
         if (cgm) {
             if (!rec || !all_same) return fail("plan: column-group dW chunks (dw_kc < 0) need recurrence = true and the same dw_kc on every layer");
             const int nset = e->hp.double_q ? 3 : 2; const LayerDev& L0 = e->L[0];
-            bool ok = !has_ln && !has_do && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
+            bool ok = !has_ln && !has_do && !has_skip && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
             if (ok) { ok = dqn_nchunks(L0.K, L0.fwd_kc) == 1; for (int i = 1; i < e->nl; i++) ok = ok && dqn_nchunks(e->L[i].N, e->L[i].dx_kc) == 1; }
             if (!ok) return fail("plan: column-group dW chunks (dw_kc = %d) need a network the fused recurrent step covers -- Chain(flattenbatch, LSTM, Dense) with or without the dueling split, "
                                  "H a multiple of 8 up to 64, unsplit input projection and head dX, ONE device without a communicator -- use dw_kc >= 0 (plan = NULL picks a plan that fits; with a communicator dqn_comm_init re-derives it)", -cgm);
@@ -238,7 +252,7 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
-    if (!rec && !has_ln && !has_do && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
+    if (!rec && !has_ln && !has_do && !has_skip && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
         (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
         bool ok = true; size_t fl = 0;
         TinyArgs a; memset(&a, 0, sizeof a);
@@ -304,7 +318,7 @@ int build_program(dqn_engine* e) {
     // (red_head.hip: workgroup = 4 batch columns x stream x plan chunk of 32 hidden rows, the last arriver of a column group does TD + the heads' dX) instead of
     // k_reduce_multi (384 workgroups) + k_head_td (B workgroups)
     bool fuse_rh = false; int rh_pa = -1, rh_pv = -1, rh_S = 0;
-    if (fuse_heads && !has_ln && !has_do && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
+    if (fuse_heads && !has_ln && !has_do && !has_skip && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
         rh_S = fused_head_layout(e, levels, ha_l, hv_l, &rh_pa, &rh_pv);
         // S > 1: k_red_head (split-K producers, small batches).  S == 1 -- finished activations of an unsplit forward, i.e. large batches: k_head_cols4, one workgroup per
         // column group (k_red_head's (group, stream, chunk) decomposition is SLOWER there: 27.4 vs 21.3 us for k_head_td at B = 512, profiles/history/r05_k_cfg5_red_head_ab.txt --
@@ -400,7 +414,7 @@ int build_program(dqn_engine* e) {
                 if (L.src < 0) { H.X[0] = H.X[1] = e->x0; H.ldx[0] = H.ldx[1] = ld0; H.c0[0] = 0; H.c0[1] = B; }
                 else { H.X[0] = e->act_on[L.src]; H.ldx[0] = ncon; H.c0[0] = 0; H.X[1] = e->act_tg[L.src]; H.ldx[1] = B; H.c0[1] = 0; H.XT[0] = actT[L.src][0]; H.XT[1] = actT[L.src][1]; }
                 H.dpre = e->dact[l];
-                if (L.src >= 0) { H.dsrc = e->dact[L.src]; H.ysrc = e->act_on[L.src]; H.ldy = ncon; H.act_src = e->L[L.src].act; }
+                if (L.src >= 0) { H.dsrc = e->dact[L.src]; H.ysrc = e->act_on[L.src]; H.ldy = ncon; H.act_src = src_act(e, l); }
             };
             fill(h.adv, ha_l);
             if (hv_l >= 0) { fill(h.val, hv_l); h.join = (e->L[hv_l].src == e->L[ha_l].src && e->L[ha_l].src >= 0) ? 1 : 0; }
@@ -432,7 +446,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_skip(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -545,11 +559,28 @@ int build_program(dqn_engine* e) {
             const int l = lv[k]; const LayerDev L = e->L[l];
             const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon;
             float* dpre = e->dact[l];
+            for (int j = l + 1; j < e->nl; j++) if (is_skip(e->L[j].kind) && j - e->L[j].cin == l) {
+                // this layer is the FIRST inner layer of the skip block that joins at j: its input-gradient launch below, whatever its kind, runs with the IDENTITY epilogue
+                // (src_act) and leaves the raw dF in dact[P].  Behind every launch of this level the block's entry launch (skip.hip) adds the join's dY and takes P's
+                // derivative once, after the sum, in place:  dact[P] = (dF + dY) .* act_P'(y_P)
+                const int pp = e->L[j].src2; const LayerDev Pl = e->L[pp]; float* dP = e->dact[pp]; const float* dYj = e->dact[j]; const float* Yp = e->act_on[pp];
+                post_level.push_back({pname(e, "bwd_entry", DQN_LAYER_SKIPADD, j), [=](dqn_engine* en) { launch_skip_bwd_entry(en->stream, Pl.out_feat, dP, dYj, Yp, ncon, B, dP, Pl.act); }});
+            }
+            if (is_skip(L.kind)) {
+                // the layer above wrote dY into this layer's dact through an identity epilogue (the join has no activation).  The join hands it to the block's last inner layer
+                // K with K's activation derivative on K's stored output; where K has no activation that is the identity and dact[K] IS dact[l] (engine.hip): no launch.  The
+                // other half of the join's backward, the + dY at the block's entry, runs behind the first inner layer's level (above)
+                if (!skip_dact_alias(e, l)) {
+                    const LayerDev Kl = e->L[L.src]; const float* Yk = e->act_on[L.src]; float* dK = e->dact[L.src];
+                    e->prog.push_back({pname(e, "bwd_join", L.kind, l), [=](dqn_engine* en) { launch_skip_bwd_join(en->stream, Kl.out_feat, dpre, Yk, ncon, B, dK, Kl.act); }});
+                }
+                continue;
+            }
             if (is_pool(L.kind)) {
                 // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (a pool has no activation); the pool's backward gathers it per
                 // input element and applies the producing layer's activation derivative.  No parameters, so no dW; a pool on the observation has no input gradient to compute
                 if (wants_dx(l)) {
-                    const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act;
+                    const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = src_act(e, l);
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
                 }
                 continue;
@@ -558,7 +589,7 @@ int build_program(dqn_engine* e) {
                 // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (the layer has no activation); the backward regenerates the forward's
                 // mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on that layer's own,
                 // unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation
-                const float* Ysrc = e->act_on[L.src]; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act; const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
+                const float* Ysrc = e->act_on[L.src]; float* out = e->dact[L.src]; const int act_src = src_act(e, l); const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
                 e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_do_bwd(en->stream, L.out_feat, p, seed, l, stt, dpre, Ysrc, ncon, B, out, act_src); }});
                 continue;
             }
@@ -566,7 +597,7 @@ int build_program(dqn_engine* e) {
                 // the layer above wrote dpre = dY .* act'(y) into this layer's dact through its own dX epilogue (this layer's activation is `act` like any other's).  Two launches
                 // (layernorm.hip): dX with the producing layer's activation derivative -- a recurrent producer's `act` is IDENTITY, so its dact is the cell's dH -- and the column
                 // sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
-                const float* P = e->p_on; float* out = e->dact[L.src]; const int act_src = e->L[L.src].act; const float* stat = ln_stat[l];
+                const float* P = e->p_on; float* out = e->dact[L.src]; const int act_src = src_act(e, l); const float* stat = ln_stat[l];
                 float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
                 e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
                 continue;
@@ -577,7 +608,7 @@ int build_program(dqn_engine* e) {
                 float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8;
                 e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
                 if (wants_dx(l)) {
-                    const float* P = e->p_on; float* out = e->dact[L.src]; const float* ysrc = e->act_on[L.src]; const int act_src = e->L[L.src].act;
+                    const float* P = e->p_on; float* out = e->dact[L.src]; const float* ysrc = e->act_on[L.src]; const int act_src = src_act(e, l);
                     e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, ysrc, ncon, act_src, mf ? 1 : 0); }});
                 }
                 continue;
@@ -620,7 +651,7 @@ int build_program(dqn_engine* e) {
                     post_level.push_back({pname(e, "gru_junk_clear", L.kind, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
                 }
                 if (wants_dx(l)) {
-                    const int src = L.src; const int act_src = e->L[src].act; float* out = e->dact[src]; const float* ysrc = e->act_on[src]; const float* P = e->p_on;
+                    const int src = L.src; const int act_src = src_act(e, l); float* out = e->dact[src]; const float* ysrc = e->act_on[src]; const float* P = e->p_on;
                     const int S = (mf && gemm_dx_internal_chunks(Vi, B, ncon)) ? 1 : dqn_nchunks(Vi.N, Vi.dx_kc);      // internal: the launch combines its plan chunks itself
                     float* part = S > 1 ? palloc(e, (size_t)S * Vi.in_feat * B) : nullptr;
                     if (mf && gemm_dx_eligible(Vi, B, ncon)) { struct A1 { const float* W[1]; const float* d[1]; } a; a.W[0] = P + Vi.w_off; a.d[0] = dGi; float* dst = S > 1 ? part : out; const float* ys = S > 1 ? nullptr : ysrc;
@@ -652,7 +683,7 @@ int build_program(dqn_engine* e) {
             // dX, then act' of the producing layer; the two streams of a dueling net meet at the base output (dX_val + dX_adv)
             const int src = L.src; const bool is_join = e->hp.dueling && src == e->last_base && L.stream != DQN_STREAM_BASE;
             const bool dense = L.kind == DQN_LAYER_DENSE; const int S_plan = dense ? dqn_nchunks(L.N, L.dx_kc) : 1;
-            const float* P = e->p_on; const int act_src = e->L[src].act;
+            const float* P = e->p_on; const int act_src = src_act(e, l);
             const bool join_lds = is_join && lv.size() == 2 && mf && same_geo(e->L[lv[0]], e->L[lv[1]]) && e->L[lv[0]].dx_kc == e->L[lv[1]].dx_kc &&
                                   gemm_dx_eligible(L, B, ncon, 2) && (S_plan == 1 || gemm_dx_internal_chunks(L, B, ncon, 2));
             if (join_lds) {
@@ -696,7 +727,7 @@ int build_program(dqn_engine* e) {
             bool later = false;
             for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
                 const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
+                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_skip(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
             }
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;

@@ -104,17 +104,36 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ (the engine accepts the first four codes there)
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+    l isa Flux.Parallel && throw("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (SkipConnection(+) / Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
+# Flux 0.14 SkipConnection(layers, connection), fields layers, connection: layers(x) .+ x for connection === +.  No parameters of its own (Flux.params yields the inner
+# layers' in order, which flatparams below follows) and no activation.  Lowered as the inner layers' descriptors, then ONE join descriptor of kind 9 directly behind them:
+# cin = m, the number of inner descriptors; n_in = n_out = 0: the engine takes the feature count.  The engine checks the placement (base chain, on a feature vector, never
+# first or last, n -> n); what it cannot see is refused here by name: another connection (vcat, *, a closure), a nested block, an inner layer that is not Dense / LayerNorm / Dropout
+function lower_skip!(descs, l, stream)
+    l.connection === (+) || throw("DeepQLearningError: SkipConnection(layers, $(l.connection)) is not supported; the MI355X engine runs SkipConnection with the connection + only (vcat, *, closures and Parallel are not supported)")
+    inner = l.layers isa Flux.Chain ? collect(l.layers.layers) : Any[l.layers]
+    m = 0
+    for x in inner
+        is_glue(x) && continue
+        x isa Flux.SkipConnection && throw("DeepQLearningError: a SkipConnection inside a SkipConnection is not supported (nested skip blocks)")
+        (x isa Dense || x isa Flux.LayerNorm || x isa Flux.Dropout) || throw("DeepQLearningError: unsupported layer $(typeof(x)) inside a SkipConnection (its inner layers are Dense, LayerNorm and Dropout layers only)")
+        push!(descs, lower_layer(x, stream)); m += 1
+    end
+    m >= 1 || throw("DeepQLearningError: SkipConnection(Chain(), +) holds no layer; the MI355X engine needs at least one inner layer")
+    push!(descs, LayerDesc(9, 0, stream, 0, 0, m, 0, 0, 0, 0, 0))
+end
+lower_into!(descs, l, stream) = is_glue(l) ? descs : l isa Flux.SkipConnection ? lower_skip!(descs, l, stream) : push!(descs, lower_layer(l, stream))
 function lower(q)
     descs = LayerDesc[]
     if q isa DeepQLearning.DuelingNetwork
         for (chain, s) in ((q.base, 0), (q.val, 1), (q.adv, 2)), l in chain.layers
-            is_glue(l) || push!(descs, lower_layer(l, Int32(s)))
+            lower_into!(descs, l, Int32(s))
         end
     else
-        for l in q.layers; is_glue(l) || push!(descs, lower_layer(l, Int32(0))); end
+        for l in q.layers; lower_into!(descs, l, Int32(0)); end
     end
     descs
 end

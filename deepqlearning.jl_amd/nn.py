@@ -6,6 +6,8 @@ dqn_layer_desc records and handed to the HIP engine.
 """
 from __future__ import annotations
 
+import operator
+
 import numpy as np
 
 from . import _abi
@@ -250,6 +252,41 @@ class Chain:
         return len(self.layers)
 
 
+class SkipConnection:
+    """Flux 0.14 SkipConnection(layers, +) on a feature vector (recalled, not executed here): y = layers(x) .+ x.  No parameters and no activation of its own: Flux.params
+    yields the inner layers' parameters in order.  `layers` is a Chain (or one layer) of Dense, LayerNorm and Dropout layers that maps n -> n; the connection is `+` only
+    ("+" or operator.add).  The block stands in the base chain behind a Dense, recurrent, LayerNorm or Dropout layer or another block: never first, never behind a
+    Conv / pool, never the output layer (DESIGN.md section 4 "Skip connections").  create_dueling_network treats it as a non-Dense layer."""
+    kind = "skip"
+
+    def __init__(self, layers, connection):
+        if not (connection == "+" or connection is operator.add):
+            name = connection if isinstance(connection, str) else getattr(connection, "__name__", None) or repr(connection)
+            raise _abi.DQNError(f"DeepQLearningError: SkipConnection(layers, {name}) is not supported; the MI355X engine runs SkipConnection with the connection + only "
+                                "(vcat, *, closures and Parallel are not supported)")
+        self.layers = layers if isinstance(layers, Chain) else Chain(layers)
+        self.connection, self.act = "+", identity
+        if len(self.layers) < 1:
+            raise _abi.DQNError("DeepQLearningError: SkipConnection(Chain(), +) holds no layer; the MI355X engine needs at least one inner layer")
+
+    def __repr__(self):
+        return f"SkipConnection(Chain({', '.join(repr(l) for l in self.layers)}), +)"
+
+    def shapes(self):   # Flux.params holds nothing for the block itself: the inner layers' arrays come from all_layers
+        return []
+
+
+class Parallel:
+    """Flux Parallel(connection, layers...): named so that the refusal can name it; the MI355X engine does not run it."""
+    kind = "parallel"
+
+    def __init__(self, connection, *layers):
+        self.connection, self.layers = connection, layers
+
+    def __repr__(self):
+        return "Parallel(...)"
+
+
 class DuelingNetwork:
     """src/dueling.jl:1-6: base, val, adv chains; Flux.params order = base, val, adv."""
 
@@ -284,12 +321,51 @@ def lower(net):
     """Chain | DuelingNetwork -> (list[LayerDesc], dueling flag)."""
     out = []
     chan = [0]      # channels of the map the next layer reads (0 in front of the first Conv: the engine takes the observation's)
+    top = None if isinstance(net, DuelingNetwork) else net      # the chain whose last layer is the network's output layer (a dueling base chain's is not)
+
+    def add_skip(blk, stream, first, prev_kind, is_last):
+        # SkipConnection(Chain(inner...), +): the inner layers' descriptors, then ONE join descriptor (kind SKIPADD, cin = m the number of inner layers, n_in = n_out = 0: the
+        # engine fills in the feature count).  The placement rules are stated here by name; the engine's build_layers holds them again for C callers
+        if stream != _abi.STREAM_BASE:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} is supported in the base chain only (not in a value / advantage stream)")
+        if first:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the first layer: a skip block's input is never the observation (it must follow a Dense, recurrent, LayerNorm or Dropout layer or another skip block)")
+        if prev_kind in ("conv", "maxpool", "meanpool"):
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot follow a Conv / MaxPool / MeanPool layer: a skip block stands on a feature vector (convolutional residual blocks are not supported)")
+        if is_last:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the network's output layer")
+        n_first = n_last = None
+        for l in blk.layers:
+            k = getattr(l, "kind", None)
+            if k == "skip":
+                raise _abi.DQNError(f"DeepQLearningError: a SkipConnection inside a SkipConnection is not supported (nested skip blocks): {blk!r}")
+            if k in ("lstm", "gru", "rnn"):
+                raise _abi.DQNError(f"DeepQLearningError: a recurrent layer inside a SkipConnection is not supported (its inner layers are Dense, LayerNorm and Dropout layers only): {blk!r}")
+            if k in ("conv", "maxpool", "meanpool"):
+                raise _abi.DQNError(f"DeepQLearningError: a Conv / MaxPool / MeanPool layer inside a SkipConnection is not supported (its inner layers are Dense, LayerNorm and Dropout layers only; convolutional residual blocks are not supported): {blk!r}")
+            if k not in ("dense", "layernorm", "dropout"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} inside a SkipConnection (Dense / LayerNorm / Dropout only)")
+            if k != "dropout":
+                n_first = l.n_in if n_first is None else n_first
+                n_last = l.n_out
+        if n_first is not None and n_first != n_last:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} maps {n_first} features to {n_last}; SkipConnection(layers, +) needs layers: n -> n")
+        add(blk.layers, stream)
+        d = _abi.LayerDesc()
+        d.kind, d.act, d.stream, d.cin = _abi.LAYER_SKIPADD, _abi.ACT_IDENTITY, stream, len(blk.layers)
+        out.append(d)
 
     def add(chain, stream):
-        for l in chain:
+        layers = list(chain)
+        for i, l in enumerate(layers):
             d = _abi.LayerDesc()
+            if getattr(l, "kind", None) == "parallel":
+                raise _abi.DQNError("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
+            if getattr(l, "kind", None) == "skip":
+                add_skip(l, stream, not out, getattr(layers[i - 1], "kind", None) if i > 0 else None, i + 1 == len(layers) and chain is top)
+                continue
             if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (SkipConnection(+) / Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
             d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -332,7 +408,13 @@ def isrecurrent(m):
 
 
 def all_layers(net):
-    return list(net.base) + list(net.val) + list(net.adv) if isinstance(net, DuelingNetwork) else list(net)
+    """the layers in Flux.params order; a SkipConnection block contributes its inner layers (the join has no parameters)."""
+    def flat(chain):
+        out = []
+        for l in chain:
+            out += flat(l.layers) if getattr(l, "kind", None) == "skip" else [l]
+        return out
+    return flat(net.base) + flat(net.val) + flat(net.adv) if isinstance(net, DuelingNetwork) else flat(net)
 
 
 def glorot_params(net, seed=1):

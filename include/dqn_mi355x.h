@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -99,7 +99,18 @@ typedef struct {
                                           {k lo, k hi, q, 0x44520000 | layer index}, k = train steps completed before this one, q = f * ceil(C / 4) + col / 4 over the C active columns
                                           (col = t * B + b in a recurrent step), the four output words for columns 4 (col / 4) + 0..3, u = (word >> 8) * 2^-24, keep <=> (double)u >= p.
                                           Directly behind a Dense, recurrent or LayerNorm layer (a LayerNorm may follow it), base chain only, never the first or the output layer,
-                                          single GPU only */
+                                          single GPU only;
+                                          SKIPADD, the join of a SkipConnection(layers, +) block (Flux 0.14, recalled, not executed): layers(x) .+ x.  ONE descriptor placed directly
+                                          AFTER the descriptors of the block's inner layers: cin = m >= 1, the number of inner layers (the m descriptors immediately before it, same
+                                          stream); n_in == n_out == the feature count n (or both 0: the engine fills them in), act = IDENTITY, stream = BASE, every other slot 0.
+                                          No parameters (Flux.params yields the inner layers' in order); its plan entry is all zeros and ignored.  In EVERY pass
+                                          y = y_K + y_P, one fp32 add per element: y_K the stored output of the last inner layer K (after K's activation), y_P the stored output of
+                                          the producer P that the first inner layer F reads (after P's; a Dropout's masked output in its active pass, its producer's elsewhere).
+                                          Backward: dact[K] = dY .* act_K'(y_K); F's input gradient dF is taken raw and dact[P] = (dF + dY) .* act_P'(y_P) -- P's derivative once,
+                                          after the sum.  The inner layers are Dense, LayerNorm and Dropout layers (no recurrent layer, Conv, pool or nested block) and map n -> n;
+                                          P is a Dense, recurrent, LayerNorm or Dropout layer or the join of a preceding block: never the observation (the block is never the first
+                                          layer), never a Conv / pool map (convolutional residual blocks are not supported); the block is never the output layer.  LayerNorm and
+                                          Dropout may be the first inner layer and may directly follow a join.  Base chain only, single GPU only */
 } dqn_layer_desc;
 
 /* Summation-order plan of one layer: the K dimension of each contraction is cut
