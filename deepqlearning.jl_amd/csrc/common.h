@@ -60,6 +60,48 @@ static inline double do_p(const LayerDev& L) { const uint64_t b = (uint64_t)(uin
 static inline __host__ __device__ bool is_skip(int kind) { return kind == DQN_LAYER_SKIPADD; }
 // a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
+// ---- what the engine's host code knows about a layer kind, ONE row per kind ("own-level kinds"), keyed on the layer: a padded Conv is a row of its own.
+// The own-level rows come first, in the order in which the single-GPU refusals name them (refuse_replicas, engine.hip)
+struct KindTraits {
+    const char* tag;           // the launch-name piece (pname, engine_program.hip)
+    bool own_level;            // launched alone on its level in every pass it runs in, never grouped into the GEMM / VALU / reduce launches of emit_forward
+    bool contracts;            // has a summation-order plan; false: the plan entry is all zeros and ignored
+    bool dw_carrier;           // its dW may be an LDS-tiled launch that carries the priority block (dw_carrier_ok, engine_program.hip)
+    bool declines_fusion;      // a network that holds one takes the general train programs: no fused recurrent step, no tiny_step, no k_red_head / k_head_cols4 ...
+    bool declines_act_tail;    // ... and the general acting tail (fused_tail = 0).  Wider by the padded Conv; a pool declines neither (general_only)
+    bool output_ok;            // may be the network's output layer
+    const char *a_noun, *plural;      // what the refusals call it (plain text, printed through %s); plural != null: single GPU only (dqn_comm_init and DQN_SIM_WORLD refuse the network)
+};
+enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
+static inline int kind_row(const LayerDev& L) {
+    switch (L.kind) {
+    case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: return KT_POOL;
+    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: return KT_SKIP;
+    case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
+    }
+}
+static inline const KindTraits& kind_traits(const LayerDev& L) {
+    static const KindTraits T[] = {
+        //                    tag     own_level contracts dw_carrier declines_fusion declines_act_tail output_ok
+        /* KT_CPAD      */ {"conv",    true,     true,     false,     false,          true,             true,  "a Conv with pad", "padded convolutions"},
+        /* KT_POOL      */ {"pool",    true,     false,    false,     false,          false,            false, "a MaxPool / MeanPool layer", "pool layers"},
+        /* KT_LN        */ {"ln",      true,     false,    false,     true,           true,             false, "a LayerNorm layer", "LayerNorm layers"},
+        /* KT_DO        */ {"do",      true,     false,    false,     true,           true,             false, "a Dropout layer", "Dropout layers"},
+        /* KT_SKIP      */ {"skip",    true,     false,    false,     true,           true,             false, "a skip block", "skip blocks"},
+        /* KT_CONV      */ {"conv",    false,    true,     true,      false,          false,            true,  nullptr, nullptr},
+        /* KT_DENSE     */ {"dense",   false,    true,     true,      false,          false,            true,  nullptr, nullptr},
+        /* KT_RECURRENT */ {"dense",   false,    true,     false,     false,          false,            true,  nullptr, nullptr},      // named after its batched part, the dense view Gx = Wi*x (gx_view)
+    };
+    static_assert(sizeof T / sizeof T[0] == KT_RECURRENT + 1, "one row per KT_* code, in the enum's order");
+    return T[kind_row(L)];
+}
+// THE whole-network fusion rule: a network that holds a declining kind takes the general programs.  Stated by name instead of relied on through the fused launches' own shape
+// tests: a LayerNorm is launched alone, a Dropout layer would have to be masked in one of a fused launch's passes and not in the others, a skip block's entry has two
+// consumers and its join two producers.  acting: the rule of the acting program's fused tail (act_head.hip)
+static inline bool general_only(const LayerDev* L, int nl, bool acting = false) {
+    for (int i = 0; i < nl; i++) { const KindTraits& t = kind_traits(L[i]); if (acting ? t.declines_act_tail : t.declines_fusion) return true; }
+    return false;
+}
 
 // device-resident mutable state of one engine (one instance in HBM)
 struct StepState {
@@ -815,9 +857,7 @@ struct DrqnColsArgs {
 // the column-group size of the fused recurrent step for this network, 0 = not covered (the twin restates this rule: oracle/dqn_ref.c fused_cg)
 static inline int drqn_fused_cg(const LayerDev* L, int nl, int E, int B, int T, int nA, int dueling, int double_q, int recurrence) {
     if (!recurrence) return 0;
-    for (int i = 0; i < nl; i++) if (is_ln(L[i].kind)) return 0;      // a network with a LayerNorm layer takes the multi-launch recurrent program
-    for (int i = 0; i < nl; i++) if (is_do(L[i].kind)) return 0;      // ... and so does a network with a Dropout layer
-    for (int i = 0; i < nl; i++) if (is_skip(L[i].kind)) return 0;      // ... and a network with a skip block (skip.hip): a producer with two consumers
+    if (general_only(L, nl)) return 0;      // a network with a LayerNorm layer, a Dropout layer or a skip block takes the multi-launch recurrent program
     const int duel = dueling ? 1 : 0;
     if (nl != (duel ? 3 : 2) || L[0].kind != DQN_LAYER_LSTM || L[0].stream != DQN_STREAM_BASE || L[0].src >= 0) return 0;
     const int H = L[0].H, N = 4 * H;

@@ -193,7 +193,7 @@ bool same_geo(const LayerDev& a, const LayerDev& b);
 void add_valu(dqn_engine* e, std::vector<VTask>& pend, const VTask& t);
 void flush_valu(dqn_engine* e, std::vector<VTask>& pend, const char* name, const PrioArgs* prio = nullptr);
 void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name);
-const char* pname(dqn_engine* e, const char* op, int kind, int i);
+const char* pname(dqn_engine* e, const char* op, const LayerDev& L, int i);      // "<op>_<the kind's tag><i>" (KindTraits::tag)
 typedef std::vector<std::vector<int>> Levels;
 Levels net_levels(const dqn_engine* e);      // the launch levels of the network: the base chain one layer per level, then the (value, advantage) layers pairwise
 LayerDev gx_view(const LayerDev& l);         // a recurrent layer's batched part: its bias-free input projection Gx = Wi*x as a dense layer K = n_in, N = ngates*H

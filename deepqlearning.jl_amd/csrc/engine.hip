@@ -61,6 +61,16 @@ extern "C" int dqn_hparams_default(dqn_hparams* hp) {
     return 0;
 }
 
+// THE single-GPU rule: the exchange paths (operand all-gather, all-reduce) have never run with an own-level kind's launches in the program -- refused instead of claimed.
+// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
+static int refuse_replicas(const char* who, const LayerDev* L, int nl) {
+    for (int r = 0; r < KT_OWN_LEVEL; r++) for (int i = 0; i < nl; i++) {
+        const KindTraits& t = kind_traits(L[i]); if (kind_row(L[i]) != r || !t.plural) continue;
+        char pad[32] = ""; if (r == KT_CPAD) snprintf(pad, sizeof pad, " (%d, %d)", L[i].ph, L[i].pw);      // the padded conv's message also says which pad
+        return fail("%s: layer %d is %s%s; data-parallel replicas of a network with %s are not supported (single GPU only)", who, i, t.a_noun, pad, t.plural);
+    }
+    return 0;
+}
 // geometry of every layer; shared by dqn_plan_default (host only) and dqn_engine_create
 static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, LayerDev* L, int* lb, int* lv, int* la, size_t* P, size_t* Pint) {
     if (n <= 0 || n > DQN_MAX_LAYERS) return fail("bad layer count %d", n);
@@ -179,10 +189,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         if (*lv < 0 || *la < 0 || L[*lv].out_feat != 1 || L[*la].out_feat != hp->n_actions)
             return fail("DeepQLearningError: the qnetwork provided is incompatible with dueling");   // src/dueling.jl:47
     } else if (*lb < 0 || L[*lb].out_feat != hp->n_actions) return fail("network output size != n_actions");
-    if (!hp->dueling && is_pool(L[*lb].kind)) return fail("layer %d: a MaxPool / MeanPool layer cannot be the network's output layer", *lb);
-    if (!hp->dueling && is_ln(L[*lb].kind)) return fail("layer %d: a LayerNorm layer cannot be the network's output layer", *lb);
-    if (!hp->dueling && is_do(L[*lb].kind)) return fail("layer %d: a Dropout layer cannot be the network's output layer", *lb);
-    if (!hp->dueling && is_skip(L[*lb].kind)) return fail("layer %d: a skip block cannot be the network's output layer", *lb);
+    if (!hp->dueling && !kind_traits(L[*lb]).output_ok) return fail("layer %d: %s cannot be the network's output layer", *lb, kind_traits(L[*lb]).a_noun);
     if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
     return 0;
 }
@@ -210,9 +217,7 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
     bool rec = false; for (int i = 0; i < n; i++) rec = rec || is_recurrent(L[i].kind);
     for (int i = 0; i < n; i++) {
         out[i].fwd_kc = 0;
-        if (is_ln(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: the layer's sums have one fixed order (layernorm.hip)
-        if (is_do(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: a Dropout layer's plan entry is all zeros
-        if (is_skip(L[i].kind)) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // ... and so is a skip block's join's
+        if (!kind_traits(L[i]).contracts) { out[i].dx_kc = out[i].dw_kc = 0; continue; }      // nothing to contract: a pool and a skip join have no sums, a Dropout layer none either, a LayerNorm's have one fixed order (layernorm.hip); the entry is all zeros
         // (small batches only: at B >= 128 the 3 B columns of a step already fill the chip -- 512 workgroups for the 3136 -> 512 layers of config 5 --
         // and the split only bought slab traffic plus a reduce launch: 16 us of the 807 us step, r03_g)
         if (L[i].K > 1024 && B < 128) { const int s = (L[i].K + 511) / 512; int kc = (L[i].K + s - 1) / s; kc = (kc + 3) / 4 * 4; out[i].fwd_kc = kc; }
@@ -302,18 +307,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     { const int lopt = (e->opt.fwd_m32 > 0 ? DQN_LOPT_FWD_M32 : 0) | (e->opt.fwd_m32 == 0 ? DQN_LOPT_NO_FWD_M32 : 0) | (e->opt.no_fwd_wres ? DQN_LOPT_NO_FWD_WRES : 0) |
                        ((std::min(255, std::max(0, e->opt.dw_split / 16)) & 0xff) << 8) | 
                        (((long long)hp->batch_size * (hp->recurrence ? hp->trace_length : 1) <= 64) ? DQN_LOPT_ST_WT : 0); for (int i = 0; i < e->nl; i++) e->L[i].opt = lopt; }
-    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("DQN_SIM_WORLD: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
-    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
-    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
-    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
-    if (e->opt.sim_world >= 1) for (int i = 0; i < e->nl; i++) if (is_skip(e->L[i].kind)) return fail("DQN_SIM_WORLD: layer %d is a skip block; data-parallel replicas of a network with skip blocks are not supported (single GPU only)", i);
+    if (e->opt.sim_world >= 1 && refuse_replicas("DQN_SIM_WORLD", e->L, e->nl)) return -1;
     if (e->opt.sim_world >= 1 && !hp->recurrence) { e->sim_world = e->opt.sim_world; e->world = e->opt.sim_world; }   // tests: one process plays k identical ranks
     dqn_layer_plan defp[DQN_MAX_LAYERS];
     e->plan_defaulted = plan == nullptr;
     if (!plan) { default_plan(e->L, e->nl, e->B, defp, hp); plan = defp; }
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
-        if (is_pool(e->L[i].kind) || is_ln(e->L[i].kind) || is_do(e->L[i].kind) || is_skip(e->L[i].kind)) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's / skip join's plan entry is ignored
+        if (!kind_traits(e->L[i]).contracts) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's / skip join's plan entry is ignored
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
@@ -1143,8 +1144,7 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
             if (C->has_c) { q.Cst = e->pol_c[i][fl ^ 1]; q.cprev = e->pol_c[i][fl]; q.cp_ld = n; q.cp_bs = 1; }
             C->launch_step(e->stream, a, 0);
             HIPCHK(hipMemcpyAsync(e->pol_h[i][fl ^ 1], e->pol_act[i], (size_t)l.H * n * 4, hipMemcpyDeviceToDevice, e->stream));
-        } else if (is_skip(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd", e->pol_act[l.src2], n);      // a skip join: the last inner layer's output + the block's entry's
-        else if (!is_do(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd");      // a Dropout layer is the identity here: no launch
+        } else if (!is_do(l.kind)) fwd_layer(e, l, P, X, n, 0, n, e->pol_act[i], "policy_fwd", is_skip(l.kind) ? e->pol_act[l.src2] : nullptr, n);      // a Dropout layer is the identity here: no launch; a skip join adds the output of the block's entry
     }
     if (e->hp.recurrence) e->pol_flip ^= 1;
     const int lq = e->hp.dueling ? e->last_adv : e->last_base;
@@ -1165,13 +1165,7 @@ extern "C" int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32
 // ---------------------------------------------------------------- data-parallel replicas
 extern "C" int dqn_comm_unique_id(void* id128) { if (rccl_load()) return -1; const int rc = g_rccl.GetUniqueId(id128); return rc ? fail("ncclGetUniqueId failed (%d)", rc) : 0; }
 extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int world) { if (!e) return fail("null engine handle");
-    // MaxPool / MeanPool networks: the exchange paths (operand all-gather, all-reduce) have never run with a pool level in the program -- refused instead of claimed
-    // ... and none with a padded convolution either (conv_pad.hip)
-    for (int i = 0; i < e->nl; i++) if (is_padded(e->L[i])) return fail("dqn_comm_init: layer %d is a Conv with pad (%d, %d); data-parallel replicas of a network with padded convolutions are not supported (single GPU only)", i, e->L[i].ph, e->L[i].pw);
-    for (int i = 0; i < e->nl; i++) if (is_pool(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a MaxPool / MeanPool layer; data-parallel replicas of a network with pool layers are not supported (single GPU only)", i);
-    for (int i = 0; i < e->nl; i++) if (is_ln(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a LayerNorm layer; data-parallel replicas of a network with LayerNorm layers are not supported (single GPU only)", i);
-    for (int i = 0; i < e->nl; i++) if (is_do(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a Dropout layer; data-parallel replicas of a network with Dropout layers are not supported (single GPU only)", i);
-    for (int i = 0; i < e->nl; i++) if (is_skip(e->L[i].kind)) return fail("dqn_comm_init: layer %d is a skip block; data-parallel replicas of a network with skip blocks are not supported (single GPU only)", i);
+    if (refuse_replicas("dqn_comm_init", e->L, e->nl)) return -1;
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;

@@ -193,15 +193,15 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
         const LayerDev l = e->L[i]; const float* X = l.src < 0 ? e->pol_x : e->pol_act[l.src]; float* Y = e->pol_act[i];
         if (is_do(l.kind)) continue;      // a Dropout layer is the identity when acting: nothing is emitted, pol_act[i] is its producer's
         const float* X2 = is_skip(l.kind) ? e->pol_act[l.src2] : nullptr;      // a skip join adds the output of the block's entry
-        if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l.kind, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, l, P, X, n, 0, n, Y, mf, 0, nullptr, en->partials, X2, n); }}); continue; }
+        if (!is_recurrent(l.kind)) { ap.steps.push_back({pname(e, "act_fwd", l, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, l, P, X, n, 0, n, Y, mf, 0, nullptr, en->partials, X2, n); }}); continue; }
         const CellOps* C = cell_ops(l.kind);
         const LayerDev Vw = gx_view(l);
         float* gx = eval ? e->eval_gx[i] : e->pol_gx[i]; float* h = RS.h[k]; float* c = RS.c[k]; k++;
-        ap.steps.push_back({pname(e, "act_gx", l.kind, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, Vw, P, X, n, 0, n, gx, mf, 0, nullptr, en->partials); }});
+        ap.steps.push_back({pname(e, "act_gx", l, i), [=](dqn_engine* en) { launch_layer_fwd(en->stream, Vw, P, X, n, 0, n, gx, mf, 0, nullptr, en->partials); }});
         CellFwdArgs a; memset(&a, 0, sizeof a); a.H = l.H; a.B = n; a.T = 1; a.nseq = 1; a.act = l.cell_act;
         CellSeq& q = a.s[0]; q.Gx = gx; q.Hout = Y; q.ld = n; q.c0 = 0; q.Wh = P + l.wh_off; q.bias = P + l.b_off; q.hprev = h; q.hp_ld = n; q.hp_bs = 1;
         if (C->has_c) { q.Cst = c; q.cprev = c; q.cp_ld = n; q.cp_bs = 1; }
-        ap.steps.push_back({pname(e, "act_cell", l.kind, i), [=](dqn_engine* en) { C->launch_step(en->stream, a, 0); launch_state_copy(en->stream, Y, h, l.H * n); }});
+        ap.steps.push_back({pname(e, "act_cell", l, i), [=](dqn_engine* en) { C->launch_step(en->stream, a, 0); launch_state_copy(en->stream, Y, h, l.H * n); }});
     }
     const int lq = e->hp.dueling ? e->last_adv : e->last_base;
     auto head_of = [&](int l) { HeadSrc h; h.p = e->pol_act[l]; h.ld = n; h.S = 1; h.per_s = 0; h.bias = P + e->L[l].b_off; h.act = e->L[l].act; return h; };
@@ -230,12 +230,9 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
     // the fused tail (act_head.hip): reduce of the heads' producers + heads + Q / argmax + eps-greedy + act! + add_exp!'s per-experience part in ONE launch, where the shapes allow
     // (the layout of the train step's fused reduce + head launch, fused_head_layout, + this kernel's own test); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
-    bool any_padded = false; for (int i = 0; i < e->nl; i++) any_padded = any_padded || is_padded(e->L[i]);      // a network with a padded conv keeps the general acting program
-    bool any_ln = false; for (int i = 0; i < e->nl; i++) any_ln = any_ln || is_ln(e->L[i].kind);      // ... and so does a network with a LayerNorm layer (layernorm.hip): fused_tail = 0
     const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
-    bool any_do = false; for (int i = 0; i < e->nl; i++) any_do = any_do || is_do(e->L[i].kind);      // ... and a network with a Dropout layer (dropout.hip; nothing is emitted for the layer itself): fused_tail = 0
-    bool any_skip = false; for (int i = 0; i < e->nl; i++) any_skip = any_skip || is_skip(e->L[i].kind);      // ... and a network with a skip block (skip.hip): fused_tail = 0
-    bool use_ah = !general && !e->opt.no_act_head && !any_padded && !any_ln && !any_do && !any_skip && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
+    // ... and so does a network with a padded conv, a LayerNorm layer, a Dropout layer (nothing is emitted for the layer itself) or a skip block (common.h general_only): fused_tail = 0
+    bool use_ah = !general && !e->opt.no_act_head && !general_only(e->L, e->nl, true) && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
     if (use_ah) { ah_S = fused_head_layout(e, levels, lq, lvh, &ah_pa, &ah_pv); use_ah = ah_S > 0 && act_head_ok(n, e->L[lq].K, ah_S, e->nA, lvh >= 0 ? 2 : 1, e->L[lq].N, lvh >= 0 ? e->L[lvh].N : 0); }
     // one pass on the n columns of pol_x; the last level's consumer (k_env_step) reduces split-K slabs on the fly; no transposed copies, no byte arena, no LayerNorm statistics
     FwdEmit fe; fe.gemm = "act_fwd"; fe.valu = "act_fwd_valu"; fe.reduce = "act_reduce"; fe.skip_last = use_ah /* the head level runs inside k_act_head */; fe.last_on_the_fly = true; fe.head = head;

@@ -34,9 +34,11 @@ void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name) {
     (e->sink ? *e->sink : e->prog).push_back({name, [=](dqn_engine* en) { launch_reduce_multi(en->stream, dev, n, blocks); }});
     segs.clear();
 }
-const char* pname(dqn_engine* e, const char* op, int kind, int i) {
-    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind == DQN_LAYER_CONV ? "conv" : is_pool(kind) ? "pool" : is_ln(kind) ? "ln" : is_do(kind) ? "do" : is_skip(kind) ? "skip" : "dense", i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
+const char* pname(dqn_engine* e, const char* op, const LayerDev& L, int i) {
+    char b[32]; snprintf(b, sizeof b, "%s_%s%d", op, kind_traits(L).tag, i); e->prog_names.push_back(b); return e->prog_names.back().c_str();
 }
+// layer l may be an LDS-tiled dW launch that carries the priority block: a GEMM kind (no own-level kind, no recurrent layer) whose dW the tiled kernel takes.  ld: its input's leading dimension
+static bool dw_carrier_ok(const dqn_engine* e, int l, int B, int ld) { return kind_traits(e->L[l]).dw_carrier && gemm_dw_eligible(e->L[l], B, ld); }
 Levels net_levels(const dqn_engine* e) {
     Levels levels; std::vector<int> val, adv;
     for (int i = 0; i < e->nl; i++) { if (e->L[i].stream == DQN_STREAM_BASE) levels.push_back({i}); else if (e->L[i].stream == DQN_STREAM_VAL) val.push_back(i); else adv.push_back(i); }
@@ -71,39 +73,25 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
     for (size_t li = li0; li < li1; li++) {
         const auto& lv = levels[li]; const bool last = li + 1 == levels.size();
         if (E.skip_last && last) continue;
-        if (is_do(e->L[lv[0]].kind)) {
-            // a Dropout layer (dropout.hip; base chain only, so alone on its level) is ACTIVE in one pass only: the first pass of the train step, on its leading E.do_cols columns
-            // (online network, s).  There it writes a buffer of its own -- the producer's output must survive for the producer's backward -- and copies the s' columns behind
-            // them.  Every other pass (target, acting, evaluation) emits NOTHING: the layer's activation pointer of that pass is its producer's (engine.hip)
-            const int l = lv[0]; const LayerDev L = e->L[l];
-            for (int pi = 0; pi < np; pi++) { const Prob q = prob(l, pi); HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = nullptr; h.act = DQN_ACT_IDENTITY; E.head[l][pi] = h; }
-            if (E.do_cols > 0) {
-                const Prob q = prob(l, 0); const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
-                prog.push_back({pname(e, passes[0].tag, L.kind, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
-            }
-            continue;
-        }
-        if (is_skip(e->L[lv[0]].kind)) {
-            // the join of a skip block (skip.hip; base chain only, so alone on its level): in EVERY pass y = (the last inner layer's stored output) + (the stored output of the
-            // block's entry, LayerDev::src2) on that pass's own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online
-            // pass and its producer's (the alias) everywhere else.  One launch per pass
-            const int l = lv[0]; const LayerDev L = e->L[l];
-            for (int pi = 0; pi < np; pi++) {
-                const Prob q = prob(l, pi); const float* X2 = passes[pi].in[L.src2];
-                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = nullptr; h.act = DQN_ACT_IDENTITY; E.head[l][pi] = h;
-                prog.push_back({pname(e, passes[pi].tag, L.kind, l), [=](dqn_engine* en) { launch_skip_fwd(en->stream, L.out_feat, q.X, q.ldx, X2, q.ncols, q.col0, q.ncols, q.Y); }});
-            }
-            continue;
-        }
-        if (is_pool(e->L[lv[0]].kind) || is_ln(e->L[lv[0]].kind) || is_padded(e->L[lv[0]])) {
-            // a layer launched alone on its level (base chain only): one launch per pass, never grouped with a GEMM layer -- a pool (pool.hip), a LayerNorm layer (layernorm.hip:
-            // the first pass keeps (mu, sigma) per column for the backward), a padded conv (conv_pad.hip walks the plan chunks itself)
-            const int l = lv[0]; const LayerDev L = view(l);
+        if (kind_traits(e->L[lv[0]]).own_level) {
+            // a layer launched alone on its level (base chain only): one launch per pass it is active in, never grouped with a GEMM layer.  Per kind:
+            //   a pool (pool.hip), a padded conv (conv_pad.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
+            //   the join of a skip block (skip.hip): every pass, y = (the last inner layer's stored output) + (the stored output of the block's entry, LayerDev::src2) on that pass's
+            //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
+            //   a Dropout layer (dropout.hip): ACTIVE in the first pass of the train step only, on its leading E.do_cols columns (online network, s): it writes a buffer of its own -- the producer's output
+            //     must survive for the producer's backward -- and copies the s' columns behind them.  Every other pass emits NOTHING: the layer's activation pointer there is its producer's (engine.hip)
+            const int l = lv[0]; const LayerDev L = view(l); const bool dropout = is_do(L.kind), join = is_skip(L.kind);
             float* stat0 = (is_ln(L.kind) && E.ln_stat) ? (E.ln_stat[l] = palloc(e, (size_t)2 * passes[0].ncols)) : nullptr;
             for (int pi = 0; pi < np; pi++) {
-                const Prob q = prob(l, pi); float* stat = pi == 0 ? stat0 : nullptr;
-                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;
-                prog.push_back({pname(e, passes[pi].tag, L.kind, l), [=](dqn_engine* en) { launch_layer_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, mf, L.xu8, stat, nullptr); }});
+                const Prob q = prob(l, pi);
+                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = (dropout || join) ? nullptr : q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;      // (a Dropout layer, a join: no parameters, IDENTITY)
+                if (dropout) {
+                    const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
+                    if (pi == 0 && C > 0) prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
+                    continue;
+                }
+                float* stat = pi == 0 ? stat0 : nullptr; const float* X2 = join ? passes[pi].in[L.src2] : nullptr;
+                prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_layer_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, mf, L.xu8, stat, nullptr, X2, q.ncols); }});
             }
             continue;
         }
@@ -135,9 +123,9 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
         if (mf && pr.size() <= 4) {
             int ldx[4], c0[4], nc[4]; std::vector<int> all;
             for (size_t i = 0; i < pr.size(); i++) { all.push_back((int)i); ldx[i] = pr[i].ldx; c0[i] = pr[i].col0; nc[i] = pr[i].ncols; }
-            if (geo && gemm_fwd_eligible(view(lv[0]), (int)pr.size(), ldx, c0, nc)) groups.push_back({all, pname(e, E.gemm, e->L[lv[0]].kind, lv[0])});
+            if (geo && gemm_fwd_eligible(view(lv[0]), (int)pr.size(), ldx, c0, nc)) groups.push_back({all, pname(e, E.gemm, e->L[lv[0]], lv[0])});
             else for (size_t i = 0; i < pr.size(); i += np)
-                if (gemm_fwd_eligible(view(pr[i].l), np, ldx + i, c0 + i, nc + i)) groups.push_back({std::vector<int>(all.begin() + i, all.begin() + i + np), pname(e, E.gemm, e->L[pr[i].l].kind, pr[i].l)});
+                if (gemm_fwd_eligible(view(pr[i].l), np, ldx + i, c0 + i, nc + i)) groups.push_back({std::vector<int>(all.begin() + i, all.begin() + i + np), pname(e, E.gemm, e->L[pr[i].l], pr[i].l)});
         }
         for (auto& g : groups) for (int id : g.first) done[id] = true;
         // split-K slabs that only the fused head launch reads are written piece-major (GFwdProb::pm).  That launch takes ONE flag for all its streams, so the layout is decided
@@ -150,13 +138,13 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             if (done[i]) continue;
             const Prob q = pr[i]; const LayerDev L = view(q.l);
             if (mf && mfma_fwd_ok(L, q.ncols)) {
-                prog.push_back({pname(e, passes[q.pass].tag, L.kind, q.l), [=](dqn_engine* en) { launch_mfma_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, q.part, false); }});
+                prog.push_back({pname(e, passes[q.pass].tag, L, q.l), [=](dqn_engine* en) { launch_mfma_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, q.part, false); }});
             } else {
                 VTask t; memset(&t, 0, sizeof t); t.kind = 0; t.L = L; t.P = q.P; t.X = q.X; t.ldx = q.ldx; t.col0 = q.col0; t.ncols = q.ncols; t.S = q.S; t.kc = dqn_chunk_len(L.K, L.fwd_kc);
                 t.out = q.S > 1 ? q.part : q.Y; add_valu(e, pend, t);
             }
         }
-        flush_valu(e, pend, pname(e, E.valu, e->L[lv[0]].kind, lv[0]));
+        flush_valu(e, pend, pname(e, E.valu, e->L[lv[0]], lv[0]));
         std::vector<RSeg> segs;
         for (const Prob& q : pr) {
             const LayerDev L = view(q.l); const int st = prod_stream(q.l);
@@ -173,7 +161,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             }
             E.head[q.l][q.pass] = h;
         }
-        emit_reduce(e, segs, pname(e, E.reduce, e->L[lv[0]].kind, lv[0]));
+        emit_reduce(e, segs, pname(e, E.reduce, e->L[lv[0]], lv[0]));
     }
 }
 int build_program(dqn_engine* e) {
@@ -184,13 +172,7 @@ int build_program(dqn_engine* e) {
     e->prog_names.reserve(512);
     const int B = e->Bc /* columns of one sequence set: batch_size, or T*batch_size for DRQN */, ncon = e->ncon, ld0 = 2 * B, Bb = e->B, T = e->T;
     const bool mf = e->hp.use_mfma != 0, rec = e->hp.recurrence != 0;
-    // a LayerNorm layer (layernorm.hip) is launched alone, as a pool is; every fusion below that pairs a layer with a neighbour or swallows the whole step (the fused recurrent
-    // step, the single-workgroup step, the fused reduce + head launches) DECLINES a network that holds one, by name, instead of relying on its own shape tests
-    bool has_ln = false; for (int i = 0; i < e->nl; i++) has_ln = has_ln || is_ln(e->L[i].kind);
-    // ... and so does a Dropout layer (dropout.hip), which those fused launches would have to mask in one of their passes and not in the others
-    bool has_do = false; for (int i = 0; i < e->nl; i++) has_do = has_do || is_do(e->L[i].kind);
-    // ... and a skip block (skip.hip), whose entry has two consumers and whose join reads two producers: none of those launches has a second operand or a second gradient
-    bool has_skip = false; for (int i = 0; i < e->nl; i++) has_skip = has_skip || is_skip(e->L[i].kind);
+    const bool general = general_only(e->L, e->nl);      // declines, by name, every fusion below that pairs a layer with a neighbour or swallows the whole step: the fused recurrent step, the single-workgroup step, the fused reduce + head launches
     float* ln_stat[DQN_MAX_LAYERS] = {};      // per LayerNorm layer: (mu, sigma) of the online pass's columns, kept for the backward
     // forward outputs: a recurrent layer's batched part is its bias-free input projection Gx = Wi*x over ALL columns (gx_view, writing gx_*); the recurrence then
     // runs as T small launches (or one).
@@ -204,7 +186,7 @@ int build_program(dqn_engine* e) {
         if (cgm) {
             if (!rec || !all_same) return fail("plan: column-group dW chunks (dw_kc < 0) need recurrence = true and the same dw_kc on every layer");
             const int nset = e->hp.double_q ? 3 : 2; const LayerDev& L0 = e->L[0];
-            bool ok = !has_ln && !has_do && !has_skip && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
+            bool ok = !general && drqn_fused_cg(e->L, e->nl, e->E, Bb, T, e->nA, e->hp.dueling, e->hp.double_q, 1) > 0 && Bb % cgm == 0 && nset * 4 * L0.H * cgm <= 1024 && !e->comm && !e->sim_world && e->world <= 1;
             if (ok) { ok = dqn_nchunks(L0.K, L0.fwd_kc) == 1; for (int i = 1; i < e->nl; i++) ok = ok && dqn_nchunks(e->L[i].N, e->L[i].dx_kc) == 1; }
             if (!ok) return fail("plan: column-group dW chunks (dw_kc = %d) need a network the fused recurrent step covers -- Chain(flattenbatch, LSTM, Dense) with or without the dueling split, "
                                  "H a multiple of 8 up to 64, unsplit input projection and head dX, ONE device without a communicator -- use dw_kc >= 0 (plan = NULL picks a plan that fits; with a communicator dqn_comm_init re-derives it)", -cgm);
@@ -252,7 +234,7 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
-    if (!rec && !has_ln && !has_do && !has_skip && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
+    if (!rec && !general && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
         (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
         bool ok = true; size_t fl = 0;
         TinyArgs a; memset(&a, 0, sizeof a);
@@ -318,7 +300,7 @@ int build_program(dqn_engine* e) {
     // (red_head.hip: workgroup = 4 batch columns x stream x plan chunk of 32 hidden rows, the last arriver of a column group does TD + the heads' dX) instead of
     // k_reduce_multi (384 workgroups) + k_head_td (B workgroups)
     bool fuse_rh = false; int rh_pa = -1, rh_pv = -1, rh_S = 0;
-    if (fuse_heads && !has_ln && !has_do && !has_skip && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
+    if (fuse_heads && !general && !e->opt.no_red_head && !e->opt.probe_no_tg && !e->opt.head_dbg) {
         rh_S = fused_head_layout(e, levels, ha_l, hv_l, &rh_pa, &rh_pv);
         // S > 1: k_red_head (split-K producers, small batches).  S == 1 -- finished activations of an unsplit forward, i.e. large batches: k_head_cols4, one workgroup per
         // column group (k_red_head's (group, stream, chunk) decomposition is SLOWER there: 27.4 vs 21.3 us for k_head_td at B = 512, profiles/history/r05_k_cfg5_red_head_ab.txt --
@@ -357,11 +339,11 @@ int build_program(dqn_engine* e) {
             char op[24];
             if (C->seq_fits(H, Bb, T) && !stepwise(e->opt, L.kind)) {
                 const CellFwdArgs a = args(0); snprintf(op, sizeof op, "%s_seq", C->name);
-                e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_seq(en->stream, a); }});
+                e->prog.push_back({pname(e, op, L, l), [=](dqn_engine* en) { C->launch_seq(en->stream, a); }});
             } else
             for (int t = 0; t < T; t++) {
                 const CellFwdArgs a = args(t); snprintf(op, sizeof op, "%s_step", C->name);
-                e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_step(en->stream, a, t); }});
+                e->prog.push_back({pname(e, op, L, l), [=](dqn_engine* en) { C->launch_step(en->stream, a, t); }});
             }
         }
     }
@@ -446,7 +428,7 @@ int build_program(dqn_engine* e) {
         bool big_in_bwd = false;
         if (!rec && e->hp.prioritized_replay && Bb > 64 && Bb <= 1024 && mf && !e->comm && !e->sim_world) {
             int carriers = 0;
-            for (const auto& lvq : levels) for (int l2 : lvq) { const LayerDev& L2 = e->L[l2]; if (!is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_skip(L2.kind) && !is_padded(L2) && gemm_dw_eligible(L2, B, L2.src < 0 ? ld0 : ncon)) { carriers++; break; } }
+            for (const auto& lvq : levels) for (int l2 : lvq) if (dw_carrier_ok(e, l2, B, e->L[l2].src < 0 ? ld0 : ncon)) { carriers++; break; }
             big_in_bwd = carriers >= 2;
         }
         e->prio_in_bwd = big_in_bwd;
@@ -511,6 +493,48 @@ int build_program(dqn_engine* e) {
     bool joined = false;
     // a layer's input gradient has a reader unless the layer reads the observation -- directly, or through pool layers only (a pool has no parameters: its dY would feed nothing)
     auto wants_dx = [&](int l) { int s = e->L[l].src; while (s >= 0 && is_pool(e->L[s].kind)) s = e->L[s].src; return s >= 0; };
+    // the backward of the own-level kinds: launches of the layer's own, never grouped.  Returns true where layer l is one (the GEMM path has nothing to add).  Whatever its
+    // kind, l may also be the FIRST inner layer of a skip block: the block's entry launch is queued behind its level (post_level)
+    auto emit_own_level_bwd = [&](int l, std::vector<dqn_engine::Step>& post_level) {
+        const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon; float* dpre = e->dact[l];
+        for (int j = l + 1; j < e->nl; j++) if (is_skip(e->L[j].kind) && j - e->L[j].cin == l) {
+            // this layer is the FIRST inner layer of the skip block that joins at j: its input-gradient launch, whatever its kind, runs with the IDENTITY epilogue
+            // (src_act) and leaves the raw dF in dact[P].  Behind every launch of this level the block's entry launch (skip.hip) adds the join's dY and takes P's
+            // derivative once, after the sum, in place:  dact[P] = (dF + dY) .* act_P'(y_P)
+            const int pp = e->L[j].src2; const LayerDev Pl = e->L[pp]; float* dP = e->dact[pp]; const float* dYj = e->dact[j]; const float* Yp = e->act_on[pp];
+            post_level.push_back({pname(e, "bwd_entry", e->L[j], j), [=](dqn_engine* en) { launch_skip_bwd_entry(en->stream, Pl.out_feat, dP, dYj, Yp, ncon, B, dP, Pl.act); }});
+        }
+        if (!kind_traits(L).own_level) return false;
+        // the layer above wrote its dX into dact[l] through its dX epilogue with this layer's `act`: dY for a pool, a Dropout layer and a join (IDENTITY), dpre = dY .* act'(y) for a LayerNorm and a padded conv
+        const int act_src = L.src >= 0 ? src_act(e, l) : DQN_ACT_IDENTITY; float* out = L.src >= 0 ? e->dact[L.src] : nullptr; const float* Ysrc = L.src >= 0 ? e->act_on[L.src] : nullptr;
+        if (is_skip(L.kind)) {
+            // the join hands dY to the block's last inner layer K with K's activation derivative on K's stored output; where K has no activation that is the identity and
+            // dact[K] IS dact[l] (engine.hip): no launch.  The other half of the join's backward, the + dY at the block's entry, runs behind the first inner layer's level (above)
+            const LayerDev Kl = e->L[L.src];
+            if (!skip_dact_alias(e, l)) e->prog.push_back({pname(e, "bwd_join", L, l), [=](dqn_engine* en) { launch_skip_bwd_join(en->stream, Kl.out_feat, dpre, Ysrc, ncon, B, out, Kl.act); }});
+        } else if (is_pool(L.kind)) {
+            // gathers dY per input element and applies the producing layer's activation derivative.  No parameters, so no dW; a pool on the observation has no input gradient to compute
+            const float* Yp = e->act_on[l];
+            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
+        } else if (is_do(L.kind)) {
+            // regenerates the forward's mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on
+            // that layer's own, unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation
+            const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
+            e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_do_bwd(en->stream, L.out_feat, p, seed, l, stt, dpre, Ysrc, ncon, B, out, act_src); }});
+        } else if (is_ln(L.kind)) {
+            // two launches (layernorm.hip): dX with the producing layer's activation derivative -- a recurrent producer's `act` is IDENTITY, so its dact is the cell's dH -- and the
+            // column sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
+            const float* P = e->p_on; const float* stat = ln_stat[l]; float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
+            e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
+        } else {
+            // a padded conv (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then -- unless the layer
+            // reads the observation -- dX with the producing layer's activation derivative
+            float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8; const float* P = e->p_on;
+            e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
+            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
+        }
+        return true;
+    };
     std::vector<VTask> tail_pend;    // small tasks waiting for a launch to ride on (fused heads: their dW/db and the loss fold)
     auto make_tail = [&](std::vector<VTask>& v) {
         GemmTail t = gemm_no_tail();
@@ -559,60 +583,7 @@ int build_program(dqn_engine* e) {
             const int l = lv[k]; const LayerDev L = e->L[l];
             const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon;
             float* dpre = e->dact[l];
-            for (int j = l + 1; j < e->nl; j++) if (is_skip(e->L[j].kind) && j - e->L[j].cin == l) {
-                // this layer is the FIRST inner layer of the skip block that joins at j: its input-gradient launch below, whatever its kind, runs with the IDENTITY epilogue
-                // (src_act) and leaves the raw dF in dact[P].  Behind every launch of this level the block's entry launch (skip.hip) adds the join's dY and takes P's
-                // derivative once, after the sum, in place:  dact[P] = (dF + dY) .* act_P'(y_P)
-                const int pp = e->L[j].src2; const LayerDev Pl = e->L[pp]; float* dP = e->dact[pp]; const float* dYj = e->dact[j]; const float* Yp = e->act_on[pp];
-                post_level.push_back({pname(e, "bwd_entry", DQN_LAYER_SKIPADD, j), [=](dqn_engine* en) { launch_skip_bwd_entry(en->stream, Pl.out_feat, dP, dYj, Yp, ncon, B, dP, Pl.act); }});
-            }
-            if (is_skip(L.kind)) {
-                // the layer above wrote dY into this layer's dact through an identity epilogue (the join has no activation).  The join hands it to the block's last inner layer
-                // K with K's activation derivative on K's stored output; where K has no activation that is the identity and dact[K] IS dact[l] (engine.hip): no launch.  The
-                // other half of the join's backward, the + dY at the block's entry, runs behind the first inner layer's level (above)
-                if (!skip_dact_alias(e, l)) {
-                    const LayerDev Kl = e->L[L.src]; const float* Yk = e->act_on[L.src]; float* dK = e->dact[L.src];
-                    e->prog.push_back({pname(e, "bwd_join", L.kind, l), [=](dqn_engine* en) { launch_skip_bwd_join(en->stream, Kl.out_feat, dpre, Yk, ncon, B, dK, Kl.act); }});
-                }
-                continue;
-            }
-            if (is_pool(L.kind)) {
-                // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (a pool has no activation); the pool's backward gathers it per
-                // input element and applies the producing layer's activation derivative.  No parameters, so no dW; a pool on the observation has no input gradient to compute
-                if (wants_dx(l)) {
-                    const float* Yp = e->act_on[l]; float* out = e->dact[L.src]; const int act_src = src_act(e, l);
-                    e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
-                }
-                continue;
-            }
-            if (is_do(L.kind)) {
-                // the layer above wrote its dX into this layer's dY (dact[l]) through an identity epilogue (the layer has no activation); the backward regenerates the forward's
-                // mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on that layer's own,
-                // unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation
-                const float* Ysrc = e->act_on[L.src]; float* out = e->dact[L.src]; const int act_src = src_act(e, l); const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
-                e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_do_bwd(en->stream, L.out_feat, p, seed, l, stt, dpre, Ysrc, ncon, B, out, act_src); }});
-                continue;
-            }
-            if (is_ln(L.kind)) {
-                // the layer above wrote dpre = dY .* act'(y) into this layer's dact through its own dX epilogue (this layer's activation is `act` like any other's).  Two launches
-                // (layernorm.hip): dX with the producing layer's activation derivative -- a recurrent producer's `act` is IDENTITY, so its dact is the cell's dH -- and the column
-                // sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
-                const float* P = e->p_on; float* out = e->dact[L.src]; const int act_src = src_act(e, l); const float* stat = ln_stat[l];
-                float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
-                e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
-                continue;
-            }
-            if (is_padded(L)) {
-                // a padded conv's backward (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then
-                // -- unless the layer reads the observation -- dX with the producing layer's activation derivative.  Two launches of the layer's own, never grouped
-                float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8;
-                e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
-                if (wants_dx(l)) {
-                    const float* P = e->p_on; float* out = e->dact[L.src]; const float* ysrc = e->act_on[L.src]; const int act_src = src_act(e, l);
-                    e->prog.push_back({pname(e, "bwd", L.kind, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, ysrc, ncon, act_src, mf ? 1 : 0); }});
-                }
-                continue;
-            }
+            if (emit_own_level_bwd(l, post_level)) continue;
             if (is_recurrent(L.kind)) {
                 // BPTT over the s-sequence: T single-workgroup steps produce dG (gate pre-activation gradients) for all columns,
                 // then Wi|b, Wh and the input gradient are ordinary dense contractions over the T*B columns.
@@ -625,8 +596,8 @@ int build_program(dqn_engine* e) {
                     a.gates = e->gates[l]; a.aux = e->tcb[l]; a.hprev = e->hprev_buf[l]; a.cprev = e->cprev_buf[l]; a.hout = e->act_on[l]; a.ld_h = ncon; a.Wh = e->p_on + L.wh_off;
                     a.dH = dpre; a.dG = e->dG[l]; a.dGh = dGh; a.dhn = e->dhn[l]; a.dh2 = e->dcn[l]; a.g_h0 = grad + L.h0_off; if (C->has_c) a.g_c0 = grad + L.c0_off;
                     char op[24];
-                    if (C->seq_fits(L.H, Bb, T) && !stepwise(e->opt, L.kind)) { snprintf(op, sizeof op, "%s_bwd_seq", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_seq(en->stream, a); }}); }
-                    else for (int t = T - 1; t >= 0; t--) { CellBwdArgs at = a; at.t = t; snprintf(op, sizeof op, "%s_bwd", C->name); e->prog.push_back({pname(e, op, L.kind, l), [=](dqn_engine* en) { C->launch_bwd_step(en->stream, at); }}); }
+                    if (C->seq_fits(L.H, Bb, T) && !stepwise(e->opt, L.kind)) { snprintf(op, sizeof op, "%s_bwd_seq", C->name); e->prog.push_back({pname(e, op, L, l), [=](dqn_engine* en) { C->launch_bwd_seq(en->stream, a); }}); }
+                    else for (int t = T - 1; t >= 0; t--) { CellBwdArgs at = a; at.t = t; snprintf(op, sizeof op, "%s_bwd", C->name); e->prog.push_back({pname(e, op, L, l), [=](dqn_engine* en) { C->launch_bwd_step(en->stream, at); }}); }
                 }
                 LayerDev Vi = gx_view(L); Vi.b_off = L.b_off;                                                                 // Wi | b  : (K+1) x N (the bias row is real here)
                 LayerDev Vh = Vi; Vh.K = L.H; Vh.in_feat = L.H; Vh.w_off = L.wh_off; Vh.b_off = L.wh_off + (size_t)L.H * L.N;  // Wh | junk
@@ -644,21 +615,21 @@ int build_program(dqn_engine* e) {
                     else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = V; t.X = Xv; t.ldx = ldv; t.dpre = dG; t.B = B; t.S = S; t.kc = dqn_chunk_len(B, V.dw_kc); t.out = dst; add_valu(e, pend, t); }
                     if (V.w_off == L.wh_off) { wh_dst = dst; wh_S = S; }
                 };
-                emit_dw1(Vh, e->hprev_buf[l], B, dGw, pname(e, "dw_wh", L.kind, l));      // first: its junk bias row is then overwritten by nothing that matters
-                emit_dw1(Vi, X, ldx, dGi, pname(e, "dw_wi", L.kind, l));
+                emit_dw1(Vh, e->hprev_buf[l], B, dGw, pname(e, "dw_wh", L, l));      // first: its junk bias row is then overwritten by nothing that matters
+                emit_dw1(Vi, X, ldx, dGi, pname(e, "dw_wi", L, l));
                 if (C->clear_junk) {      // the GRU's junk row (sum of dn .* r) is cleared once the level's launches have written it: Adam folds max |g| over it (gru.hip)
                     float* jr = wh_dst + (size_t)L.H * L.N; const int nr = wh_S; const size_t stride = (size_t)(L.H + 1) * L.N; const int n = L.N;
-                    post_level.push_back({pname(e, "gru_junk_clear", L.kind, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
+                    post_level.push_back({pname(e, "gru_junk_clear", L, l), [=](dqn_engine* en) { launch_clear_rows(en->stream, jr, nr, stride, n); }});
                 }
                 if (wants_dx(l)) {
                     const int src = L.src; const int act_src = src_act(e, l); float* out = e->dact[src]; const float* ysrc = e->act_on[src]; const float* P = e->p_on;
                     const int S = (mf && gemm_dx_internal_chunks(Vi, B, ncon)) ? 1 : dqn_nchunks(Vi.N, Vi.dx_kc);      // internal: the launch combines its plan chunks itself
                     float* part = S > 1 ? palloc(e, (size_t)S * Vi.in_feat * B) : nullptr;
                     if (mf && gemm_dx_eligible(Vi, B, ncon)) { struct A1 { const float* W[1]; const float* d[1]; } a; a.W[0] = P + Vi.w_off; a.d[0] = dGi; float* dst = S > 1 ? part : out; const float* ys = S > 1 ? nullptr : ysrc;
-                        e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_gemm_dx(en->stream, Vi, 1, a.W, a.d, B, dst, ys, ncon, act_src); }}); }
-                    else if (mf && mfma_dx_ok(Vi, B, ncon)) e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, Vi, P, dGi, B, out, part, nullptr, ysrc, ncon, act_src, false); }});
+                        e->prog.push_back({pname(e, "dx", L, l), [=](dqn_engine* en) { launch_gemm_dx(en->stream, Vi, 1, a.W, a.d, B, dst, ys, ncon, act_src); }}); }
+                    else if (mf && mfma_dx_ok(Vi, B, ncon)) e->prog.push_back({pname(e, "dx", L, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, Vi, P, dGi, B, out, part, nullptr, ysrc, ncon, act_src, false); }});
                     else { VTask t; memset(&t, 0, sizeof t); t.kind = 2; t.L = Vi; t.P = P; t.dpre = dGi; t.B = B; t.S = S; t.kc = dqn_chunk_len(Vi.N, Vi.dx_kc); t.out = S > 1 ? part : out; t.ysrc = ysrc; t.ldy = ncon; t.act_src = act_src; add_valu(e, pend, t); }
-                    if (S > 1) { flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l)); std::vector<RSeg> one; RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)Vi.in_feat * B; r.mode = 1; r.act = act_src; r.ysrc = ysrc; r.B = B; r.ldy = ncon; r.out = out; one.push_back(r); emit_reduce(e, one, pname(e, "dx_reduce", L.kind, l)); }
+                    if (S > 1) { flush_valu(e, pend, pname(e, "bwd_valu", L, l)); std::vector<RSeg> one; RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)Vi.in_feat * B; r.mode = 1; r.act = act_src; r.ysrc = ysrc; r.B = B; r.ldy = ncon; r.out = out; one.push_back(r); emit_reduce(e, one, pname(e, "dx_reduce", L, l)); }
                 }
                 continue;
             }
@@ -669,14 +640,14 @@ int build_program(dqn_engine* e) {
                 const bool pair = lds && k == (int)lv.size() - 1 && lv.size() == 2 && same_geo(e->L[lv[0]], e->L[lv[1]]) && e->L[lv[0]].dw_kc == e->L[lv[1]].dw_kc;
                 float* dst0 = pair ? dw_dst(e->L[lv[0]], S) : nullptr; float* dst = dw_dst(L, S);
                 if (pair) {
-                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 2; dwl.ldx = ldx; dwl.name = pname(e, "dw2", L.kind, l);
+                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 2; dwl.ldx = ldx; dwl.name = pname(e, "dw2", L, l);
                     dwl.X[0] = X; dwl.d[0] = dpre; dwl.o[0] = dst; dwl.X[1] = X; dwl.d[1] = e->dact[lv[0]]; dwl.o[1] = dst0;
                     dw_done_sibling = true;
                 } else if (lds) {
-                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 1; dwl.ldx = ldx; dwl.name = pname(e, "dw", L.kind, l);
+                    flush_dw(); dwl.on = true; dwl.L = L; dwl.nprob = 1; dwl.ldx = ldx; dwl.name = pname(e, "dw", L, l);
                     dwl.X[0] = dwl.X[1] = X; dwl.d[0] = dwl.d[1] = dpre; dwl.o[0] = dwl.o[1] = dst;
                 }
-                else if (mf && mfma_dw_ok(L, B)) { float* part = S > 1 ? dst : nullptr; e->prog.push_back({pname(e, "dw", L.kind, l), [=](dqn_engine* en) { launch_mfma_dw(en->stream, L, X, ldx, dpre, B, grad, part, false); }}); }
+                else if (mf && mfma_dw_ok(L, B)) { float* part = S > 1 ? dst : nullptr; e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_mfma_dw(en->stream, L, X, ldx, dpre, B, grad, part, false); }}); }
                 else { VTask t; memset(&t, 0, sizeof t); t.kind = 1; t.L = L; t.X = X; t.ldx = ldx; t.dpre = dpre; t.B = B; t.S = S; t.kc = dqn_chunk_len(L.npos * B, L.dw_kc); t.out = dst; add_valu(e, pend, t); }
             }
             if (!wants_dx(l)) continue;
@@ -691,26 +662,26 @@ int build_program(dqn_engine* e) {
                 if (k == (int)lv.size() - 1) {
                     const LayerDev Lv = e->L[lv[0]], La = e->L[lv[1]];
                     flush_dx(); dxl.on = true; dxl.L = Lv; dxl.nsrc = 2; dxl.W[0] = P + Lv.w_off; dxl.d[0] = e->dact[lv[0]]; dxl.W[1] = P + La.w_off; dxl.d[1] = e->dact[lv[1]];
-                    dxl.out = e->dact[src]; dxl.ys = e->act_on[src]; dxl.act_src = act_src; dxl.name = pname(e, "dx_join", L.kind, l);
+                    dxl.out = e->dact[src]; dxl.ys = e->act_on[src]; dxl.act_src = act_src; dxl.name = pname(e, "dx_join", L, l);
                 }
                 continue;
             }
             float* out = e->dact[src]; const float *addend = nullptr, *ysrc = e->act_on[src];
             if (is_join && !joined) { out = e->join_tmp; ysrc = nullptr; joined = true; }
-            else if (is_join) { addend = e->join_tmp; flush_dx(); flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l)); }   // depends on the first stream's dX: an LDS-tiled one still waits in dxl
+            else if (is_join) { addend = e->join_tmp; flush_dx(); flush_valu(e, pend, pname(e, "bwd_valu", L, l)); }   // depends on the first stream's dX: an LDS-tiled one still waits in dxl
             const int S = (mf && !addend && gemm_dx_internal_chunks(L, B, ncon)) ? 1 : S_plan;      // internal: the launch combines its plan chunks itself (no slabs)
             float* part = S > 1 ? palloc(e, (size_t)S * L.in_feat * B) : nullptr;
             if (mf && !addend && gemm_dx_eligible(L, B, ncon)) {
                 flush_dx(); dxl.on = true; dxl.L = L; dxl.nsrc = 1; dxl.W[0] = dxl.W[1] = P + L.w_off; dxl.d[0] = dxl.d[1] = dpre;
-                dxl.out = S > 1 ? part : out; dxl.ys = S > 1 ? nullptr : ysrc; dxl.act_src = act_src; dxl.name = pname(e, "dx", L.kind, l);
+                dxl.out = S > 1 ? part : out; dxl.ys = S > 1 ? nullptr : ysrc; dxl.act_src = act_src; dxl.name = pname(e, "dx", L, l);
                 if (S > 1) flush_dx();   // its partial slabs are reduced right below
             }
-            else if (mf && L.N >= 16 && mfma_dx_ok(L, B, ncon)) e->prog.push_back({pname(e, "dx", L.kind, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, L, P, dpre, B, out, part, addend, ysrc, ncon, act_src, false); }});
+            else if (mf && L.N >= 16 && mfma_dx_ok(L, B, ncon)) e->prog.push_back({pname(e, "dx", L, l), [=](dqn_engine* en) { launch_mfma_dx(en->stream, L, P, dpre, B, out, part, addend, ysrc, ncon, act_src, false); }});
             else { VTask t; memset(&t, 0, sizeof t); t.kind = 2; t.L = L; t.P = P; t.dpre = dpre; t.B = B; t.S = S; t.kc = dqn_chunk_len(L.N, L.dx_kc); t.out = S > 1 ? part : out; t.addend = addend; t.ysrc = ysrc; t.ldy = ncon; t.act_src = act_src; add_valu(e, pend, t); }
             if (S > 1) {
-                flush_valu(e, pend, pname(e, "bwd_valu", L.kind, l));
+                flush_valu(e, pend, pname(e, "bwd_valu", L, l));
                 std::vector<RSeg> one; RSeg r; memset(&r, 0, sizeof r); r.part = part; r.S = S; r.elems = (unsigned long long)L.in_feat * B; r.mode = 1; r.act = act_src; r.addend = addend; r.ysrc = ysrc; r.B = B; r.ldy = ncon; r.out = out; one.push_back(r);
-                emit_reduce(e, one, pname(e, "dx_reduce", L.kind, l));
+                emit_reduce(e, one, pname(e, "dx_reduce", L, l));
             }
         }
         GemmTail tail = gemm_no_tail();
@@ -725,15 +696,12 @@ int build_program(dqn_engine* e) {
             // the block rides as workgroup 0 of this launch.  When a LATER backward launch can carry a workgroup too, the block is SPLIT: update_priorities!
             // here, the draws there -- each half shorter than the dX chains it hides under (r03 ktrace: the whole block lived 11 us, longer than any)
             bool later = false;
-            for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) {
-                const LayerDev& L2 = e->L[l2]; const int ldx2 = L2.src < 0 ? ld0 : ncon;
-                if (mf && !is_recurrent(L2.kind) && !is_pool(L2.kind) && !is_ln(L2.kind) && !is_do(L2.kind) && !is_skip(L2.kind) && !is_padded(L2) && !dp_layer[l2] && gemm_dw_eligible(L2, B, ldx2)) later = true;
-            }
+            for (int lj = li - 1; lj >= 0 && !later; lj--) for (int l2 : levels[lj]) if (mf && !dp_layer[l2] && dw_carrier_ok(e, l2, B, e->L[l2].src < 0 ? ld0 : ncon)) later = true;
             tail.adam = base_job(); tail.adam.prio = prio_args(); tail.has_adam = 1;
             if (later) { tail.adam.prio.phase = 1; prio_draw_pending = true; } else prio_placed = true;
         }
-        if (pg_want && prio_in_adam && !prio_placed && !pend.empty() && !tail.has_adam && !e->prio_in_bwd /* large batches: only the long LDS-tiled launches can hide the block */) { PrioArgs pa = prio_args(); if (prio_draw_pending) { pa.phase = 2; prio_draw_pending = false; } flush_valu(e, pend, pname(e, "bwd_valu", e->L[lv[0]].kind, lv[0]), &pa); prio_placed = true; }
-        flush_valu(e, pend, pname(e, "bwd_valu", e->L[lv[0]].kind, lv[0]));
+        if (pg_want && prio_in_adam && !prio_placed && !pend.empty() && !tail.has_adam && !e->prio_in_bwd /* large batches: only the long LDS-tiled launches can hide the block */) { PrioArgs pa = prio_args(); if (prio_draw_pending) { pa.phase = 2; prio_draw_pending = false; } flush_valu(e, pend, pname(e, "bwd_valu", e->L[lv[0]], lv[0]), &pa); prio_placed = true; }
+        flush_valu(e, pend, pname(e, "bwd_valu", e->L[lv[0]], lv[0]));
         const char* tsuf = (tail.has_adam && adam_job_blocks(tail.adam) == 1 && tail.adam.prio.n > 0) ? "+prio" : "+adam_tail";      // a job that is only the priority block
         auto tailed = [&](const char* base) { if (!tail.has_adam) return base; char nm[80]; snprintf(nm, sizeof nm, "%s%s", base, tsuf); e->prog_names.push_back(nm); return e->prog_names.back().c_str(); };
         if (dwl.on && dxl.on) {      // dW and dX of this level in ONE launch
@@ -834,7 +802,7 @@ int build_program(dqn_engine* e) {
             size_t j = i + 1; for (; j < dpdw.size(); j++) if (!used[j] && dpdw[j].x_off == dpdw[i].x_off && same_geo(dpdw[i].L, dpdw[j].L)) break;
             const bool pair = j < dpdw.size(); if (pair) used[j] = true;
             const DpDw a = dpdw[i], b = pair ? dpdw[j] : dpdw[i]; const int np = pair ? 2 : 1;
-            e->prog.push_back({pname(e, "dp_dw", a.L.kind, (int)i), [=](dqn_engine* en) {
+            e->prog.push_back({pname(e, "dp_dw", a.L, (int)i), [=](dqn_engine* en) {
                 const float* X[2] = {recv + a.x_off, recv + b.x_off}; const float* d[2] = {recv + a.d_off, recv + b.d_off}; float* o[2] = {grad + a.L.w_off, grad + b.L.w_off};
                 launch_gemm_dw(en->stream, a.L, np, X, B, d, W * B, o, /*ldd*/ B, /*tiles per rank*/ B / 32, /*rank stride*/ cnt); }});
         }
