@@ -33,7 +33,7 @@ struct LayerDev {
     int opt;                           // per-ENGINE experiment switches the kernel launchers look at (DQN_LOPT_*, set at dqn_engine_create from EngineOpts): no process-wide state
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
     int ph, pw;                        // Conv: symmetric zero padding per axis (dqn_layer_desc n_in / n_out slots); ih, iw stay the UNPADDED map, oh = (ih + 2 ph - kh) / sh + 1
-    int src2;                          // DQN_LAYER_SKIPADD: the block's entry P, the producer the block's first inner layer reads (src = the last inner layer K); -1 on every other layer
+    int src2;                          // DQN_LAYER_SKIPADD / _MAP: the block's entry P, the producer the block's first inner layer reads (src = the last inner layer K); -1 on every other layer
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
@@ -41,7 +41,7 @@ static inline __host__ __device__ bool is_recurrent(int kind) { return kind == D
 
 // Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
 static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
-static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind); }      // the layer's output is a (cout, oh, ow) map
+static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP; }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow)
 // Flux LayerNorm (layernorm.hip): K = N = n features in and out, a parameter block of 2n floats (scale at w_off, bias at b_off = w_off + n -- NOT K * N weights: layer_wn),
 // the fp32 bit pattern of eps in cin (0 = 1f-5); launched alone on its level, as pools are
 static inline __host__ __device__ bool is_ln(int kind) { return kind == DQN_LAYER_LAYERNORM; }
@@ -57,7 +57,11 @@ static inline double do_p(const LayerDev& L) { const uint64_t b = (uint64_t)(uin
 // Parameter-free (K = N = 0), no activation, cin = m the number of inner layers (the m layers in front of it); launched alone on its level in EVERY pass.  Its backward is two
 // launches: at the join dact[K] = dY .* act_K'(y_K) (an alias of dact[join] where act_K is IDENTITY: engine.hip), at the entry dact[P] = (dF + dY) .* act_P'(y_P) behind F's
 // input-gradient launch, which therefore runs with the IDENTITY epilogue (src_act, engine_program.hip)
-static inline __host__ __device__ bool is_skip(int kind) { return kind == DQN_LAYER_SKIPADD; }
+// DQN_LAYER_SKIPADD_MAP: the same join on a (c, h, w) map, n = c * h * w features in the same layout -- the block's inner layers are padded Convs, its entry a Conv, a pool or
+// another map join; cout, ih, iw, oh, ow carry the map for the layer behind it.  Where K has no activation the forward add runs in the epilogue of K's launch and the
+// entry's + dY in the epilogue of F's input-gradient launch (conv_pad.hip; skip_fused, engine.h); every rule stated for "a join" holds for both kinds
+static inline __host__ __device__ bool is_skip(int kind) { return kind == DQN_LAYER_SKIPADD || kind == DQN_LAYER_SKIPADD_MAP; }
+static inline __host__ __device__ bool is_skip_map(int kind) { return kind == DQN_LAYER_SKIPADD_MAP; }
 // a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 // ---- what the engine's host code knows about a layer kind, ONE row per kind ("own-level kinds"), keyed on the layer: a padded Conv is a row of its own.
@@ -76,7 +80,7 @@ enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_OWN_LEVEL /* rows below: the 
 static inline int kind_row(const LayerDev& L) {
     switch (L.kind) {
     case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: return KT_POOL;
-    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: return KT_SKIP;
+    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;
     case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
     }
 }
@@ -1106,9 +1110,11 @@ void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_f
                      float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');
 // mf = hp.use_mfma (MFMA tiles where the shape allows, the same bits either way); xu8: X is the byte arena of a u8 replay
-void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8);
+// R (or null): the residual operand of a map block's fused join, [out_feat][ldr] read on the columns rcol0 .. rcol0 + ncols: Y = act(tot + bias) + R
+void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8, const float* R = nullptr, int ldr = 0, int rcol0 = 0);
 void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
-void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf);
+// dY (or null): the addend of a map block's fused entry, [in_feat][B]: out = dact(acc + dY, ysrc, act_src).  May be the buffer dpre points at (single inner layer): both are read only
+void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf, const float* dY = nullptr);
 bool mfma_fwd_ok(const LayerDev& L, int ncols);
 bool mfma_dw_ok(const LayerDev& L, int B);
 bool mfma_dx_ok(const LayerDev& L, int B, int ldy);

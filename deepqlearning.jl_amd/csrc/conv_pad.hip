@@ -13,6 +13,14 @@
 // Two forms of each contraction, bit-identical: fp32 MFMA (v_mfma_f32_16x16x4_f32, one wave = one register tile, operands straight from L2 as in nn_mfma.hip) where the
 // channel / column counts tile by 16, one thread per output element otherwise.  A first-layer padded conv may read the BYTE arena of a u8 replay (xu8): value = u8_unit(byte),
 // and a zero byte is an exact 0.
+//
+// Residual epilogues (the join of a convolutional skip block, DQN_LAYER_SKIPADD_MAP; DESIGN.md section 4 "Convolutional skip blocks"), template parameter RES / ADD:
+//   forward   Y = act(tot + bias) + R        R = the stored output of the block's entry P on this pass's columns ([out_feat][ldr], window rcol0): the block's LAST inner
+//                                            layer writes the JOIN's activation; one fp32 add behind the activation, the add skip.hip's k_skip_fwd makes in a launch of its own
+//   dX        out = dact(acc + dY, y_P, act_P)   dY = dact[join] ([in_feat][B]): the block's FIRST inner layer writes dact[P]; the add and the derivative k_skip_bwd_entry makes
+// The same operands in the same order as the separate launches, hence the same bits.  The addend comes straight from global memory (no LDS, no atomics); its loads are issued
+// together, before the first use: in front of the contraction where that costs one register (VALU forms), at the head of the epilogue where it would cost a register tile
+// held across the whole MFMA loop (MT x NT x 4 VGPRs).  RES = ADD = 0 compiles to the kernels without the operand: a padded conv outside a block keeps its code and its bits.
 #include "common.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -25,14 +33,16 @@ template <int U8> __device__ __forceinline__ float ld_x(const void* __restrict__
 }
 
 // ------------------------------------------------------------------ VALU: one thread per output element
-template <int U8>
-__global__ __launch_bounds__(256) void k_cpad_fwd(LayerDev L, const float* __restrict__ P, const void* __restrict__ X, int ldx, int col0, int ncols, float* __restrict__ Y) {
+template <int U8, int RES>
+__global__ __launch_bounds__(256) void k_cpad_fwd(LayerDev L, const float* __restrict__ P, const void* __restrict__ X, int ldx, int col0, int ncols, float* __restrict__ Y,
+                                                  const float* __restrict__ R, int ldr, int rcol0) {
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= (size_t)L.N * L.npos * ncols) return;
     const int col = (int)(t % ncols); const int pos = (int)((t / ncols) % L.npos); const int n = (int)(t / ((size_t)ncols * L.npos));
     const int oy = pos / L.ow, ox = pos % L.ow; const int y0 = oy * L.sh - L.ph, x0 = ox * L.sw - L.pw;
     const float* W = P + L.w_off;
     const int S = dqn_nchunks(L.K, L.fwd_kc), kc = dqn_chunk_len(L.K, L.fwd_kc), khw = L.kh * L.kw;
+    float res = 0.0f; if (RES) res = R[((size_t)n * L.npos + pos) * ldr + rcol0 + col];      // in flight under the contraction
     float tot = 0.0f;
     for (int s = 0; s < S; s++) {
         const int k0 = s * kc, k1 = min(L.K, k0 + kc);
@@ -46,7 +56,8 @@ __global__ __launch_bounds__(256) void k_cpad_fwd(LayerDev L, const float* __res
         }
         tot = s == 0 ? acc : tot + acc;
     }
-    Y[t] = act_f(tot + P[L.b_off + n], L.act);
+    const float y = act_f(tot + P[L.b_off + n], L.act);
+    Y[t] = RES ? y + res : y;
 }
 
 // thread = (chunk, k, n) for k < K, plus the virtual row k == K of the bias gradient; out = slabs [S][(K+1)][N] (S == 1: the gradient block itself)
@@ -72,10 +83,13 @@ __global__ __launch_bounds__(256) void k_cpad_dw(LayerDev L, const void* __restr
     out[(size_t)s * per_s + e] = acc;
 }
 
+// ADD: dY is the join's gradient.  With a single inner layer it IS the buffer dpre points at: both are only read, which __restrict__ allows
+template <int ADD>
 __global__ __launch_bounds__(256) void k_cpad_dx(LayerDev L, const float* __restrict__ P, const float* __restrict__ dpre, int B, float* __restrict__ out,
-                                                 const float* __restrict__ ysrc, int ldy, int act_src) {
+                                                 const float* __restrict__ ysrc, int ldy, int act_src, const float* __restrict__ dY) {
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= (size_t)L.in_feat * B) return;
+    float add = 0.0f; if (ADD) add = dY[e];      // in flight under the contraction
     const int b = (int)(e % B); const int feat = (int)(e / B);
     const float* W = P + L.w_off;
     const int hw = L.ih * L.iw; const int ci = feat / hw, iy = (feat % hw) / L.iw, ix = feat % L.iw;
@@ -91,14 +105,16 @@ __global__ __launch_bounds__(256) void k_cpad_dx(LayerDev L, const float* __rest
         }
     }
     if (have) acc = tot + acc;
+    if (ADD) acc = acc + add;
     if (ysrc) acc = dact_f(acc, ysrc[(size_t)feat * ldy + b], act_src);
     out[e] = acc;
 }
 
 // ------------------------------------------------------------------ MFMA: one wave = one register tile (operand layouts: nn_mfma.hip)
 // forward: task = (channel group, column group, position); the wave walks the plan chunks itself and adds the chunk sums in ascending order
-template <int MT, int NT, int U8>
-__global__ __launch_bounds__(256) void k_cpad_mfma_fwd(LayerDev L, const float* __restrict__ P, const void* __restrict__ X, int ldx, int col0, int ncols, float* __restrict__ Y, int ntasks) {
+template <int MT, int NT, int U8, int RES>
+__global__ __launch_bounds__(256) void k_cpad_mfma_fwd(LayerDev L, const float* __restrict__ P, const void* __restrict__ X, int ldx, int col0, int ncols, float* __restrict__ Y, int ntasks,
+                                                       const float* __restrict__ R, int ldr, int rcol0) {
     extern __shared__ int tap_lds[];      // k -> (ci << 16 | ky << 8 | kx)
     {
         const int khw = L.kh * L.kw;
@@ -165,6 +181,13 @@ __global__ __launch_bounds__(256) void k_cpad_mfma_fwd(LayerDev L, const float* 
                 else { tot[m][t].x = tot[m][t].x + acc[m][t].x; tot[m][t].y = tot[m][t].y + acc[m][t].y; tot[m][t].z = tot[m][t].z + acc[m][t].z; tot[m][t].w = tot[m][t].w + acc[m][t].w; }
             }
     }
+    f32x4 res[RES ? MT : 1][RES ? NT : 1];
+    if (RES) {      // every load of the addend tile before the first use
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int m = 0; m < MT; m++) res[RES ? m : 0][RES ? t : 0] = *reinterpret_cast<const f32x4*>(R + ((size_t)(n0 + 16 * t + l15) * L.npos + pos) * ldr + rcol0 + c0 + 16 * m + 4 * kq);
+    }
 #pragma unroll
     for (int t = 0; t < NT; t++) {
         const int n = n0 + 16 * t + l15;
@@ -173,15 +196,16 @@ __global__ __launch_bounds__(256) void k_cpad_mfma_fwd(LayerDev L, const float* 
         for (int m = 0; m < MT; m++) {
             f32x4 v = tot[m][t];
             act_v4(v, bias, L.act);
+            if (RES) { const f32x4 r = res[RES ? m : 0][RES ? t : 0]; v.x = v.x + r.x; v.y = v.y + r.y; v.z = v.z + r.z; v.w = v.w + r.w; }
             *reinterpret_cast<f32x4*>(Y + ((size_t)n * L.npos + pos) * ncols + c0 + 16 * m + 4 * kq) = v;
         }
     }
 }
 
 // dX: task = (column group, 16 input channels, input position)
-template <int MT>
+template <int MT, int ADD>
 __global__ __launch_bounds__(256) void k_cpad_mfma_dx(LayerDev L, const float* __restrict__ P, const float* __restrict__ dpre, int B, float* __restrict__ out,
-                                                      const float* __restrict__ ysrc, int ldy, int act_src, int ntasks) {
+                                                      const float* __restrict__ ysrc, int ldy, int act_src, int ntasks, const float* __restrict__ dY) {
     const int lane = threadIdx.x & 63, l15 = lane & 15, kq = lane >> 4;
     int task = __builtin_amdgcn_readfirstlane(xcd_remap(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6));
     if (task >= ntasks) return;
@@ -234,11 +258,17 @@ __global__ __launch_bounds__(256) void k_cpad_mfma_dx(LayerDev L, const float* _
             }
         }
     }
+    f32x4 add[MT];
+    if (ADD) {      // every load of the addend before the first use
+#pragma unroll
+        for (int m = 0; m < MT; m++) add[m] = *reinterpret_cast<const f32x4*>(dY + feat * B + b0 + 16 * m + 4 * kq);
+    }
 #pragma unroll
     for (int m = 0; m < MT; m++) {
         f32x4 v = acc[m];
         if (have) { v.x = tot[m].x + v.x; v.y = tot[m].y + v.y; v.z = tot[m].z + v.z; v.w = tot[m].w + v.w; }
         const int bcol = b0 + 16 * m + 4 * kq;
+        if (ADD) { v.x = v.x + add[m].x; v.y = v.y + add[m].y; v.z = v.z + add[m].z; v.w = v.w + add[m].w; }
         if (ysrc) { const f32x4 y = *reinterpret_cast<const f32x4*>(ysrc + feat * ldy + bcol); dact_v4(v, y, act_src); }
         *reinterpret_cast<f32x4*>(out + feat * B + bcol) = v;
     }
@@ -310,19 +340,32 @@ static bool cpad_mfma_fwd_ok(const LayerDev& L, int ncols, const float* Y) {
     const int S = dqn_nchunks(L.K, L.fwd_kc), kc = dqn_chunk_len(L.K, L.fwd_kc);
     return !(L.N % 16 || ncols % 16 || L.K % 4 || (S > 1 && kc % 4) || L.K > 16384 || L.kh > 255 || L.kw > 255 || L.cin > 32767) && al16(Y);
 }
-void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y, int mf, int xu8) {
+void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y, int mf, int xu8, const float* R, int ldr, int rcol0) {
+    if (R) {      // the fused join of a map block (an inner layer never reads the observation: no byte arena); the addend tile is read 16 bytes per lane where its rows allow it
+        if (mf && cpad_mfma_fwd_ok(L, ncols, Y) && !(ldr % 4 || rcol0 % 4) && al16(R)) {
+            const int MT = (ncols % 32 == 0 && (long)(ncols / 32) * (L.N / 16) * L.npos >= 1024) ? 2 : 1, NT = L.N % 32 == 0 ? 2 : 1;
+            const int ntasks = (L.N / (16 * NT)) * (ncols / (16 * MT)) * L.npos; const size_t lds = (size_t)L.K * sizeof(int); const dim3 g((ntasks + 3) / 4), b(256);
+#define CPR(m, n) hipLaunchKernelGGL((k_cpad_mfma_fwd<m, n, 0, 1>), g, b, lds, st, L, P, X, ldx, col0, ncols, Y, ntasks, R, ldr, rcol0)
+            if (MT == 2 && NT == 2) CPR(2, 2); else if (MT == 2) CPR(2, 1); else if (NT == 2) CPR(1, 2); else CPR(1, 1);
+#undef CPR
+            return;
+        }
+        const size_t tot = (size_t)L.N * L.npos * ncols; const dim3 g((unsigned)((tot + 255) / 256)), b(256);
+        hipLaunchKernelGGL((k_cpad_fwd<0, 1>), g, b, 0, st, L, P, X, ldx, col0, ncols, Y, R, ldr, rcol0);
+        return;
+    }
     if (mf && cpad_mfma_fwd_ok(L, ncols, Y)) {
         const int MT = (ncols % 32 == 0 && (long)(ncols / 32) * (L.N / 16) * L.npos >= 1024) ? 2 : 1, NT = L.N % 32 == 0 ? 2 : 1;
         const int ntasks = (L.N / (16 * NT)) * (ncols / (16 * MT)) * L.npos; const size_t lds = (size_t)L.K * sizeof(int); const dim3 g((ntasks + 3) / 4), b(256);
-#define CPF(m, n, u) hipLaunchKernelGGL((k_cpad_mfma_fwd<m, n, u>), g, b, lds, st, L, P, X, ldx, col0, ncols, Y, ntasks)
+#define CPF(m, n, u) hipLaunchKernelGGL((k_cpad_mfma_fwd<m, n, u, 0>), g, b, lds, st, L, P, X, ldx, col0, ncols, Y, ntasks, (const float*)nullptr, 0, 0)
         if (xu8) { if (MT == 2 && NT == 2) CPF(2, 2, 1); else if (MT == 2) CPF(2, 1, 1); else if (NT == 2) CPF(1, 2, 1); else CPF(1, 1, 1); }
         else     { if (MT == 2 && NT == 2) CPF(2, 2, 0); else if (MT == 2) CPF(2, 1, 0); else if (NT == 2) CPF(1, 2, 0); else CPF(1, 1, 0); }
 #undef CPF
         return;
     }
     const size_t tot = (size_t)L.N * L.npos * ncols; const dim3 g((unsigned)((tot + 255) / 256)), b(256);
-    if (xu8) hipLaunchKernelGGL(k_cpad_fwd<1>, g, b, 0, st, L, P, X, ldx, col0, ncols, Y);
-    else hipLaunchKernelGGL(k_cpad_fwd<0>, g, b, 0, st, L, P, X, ldx, col0, ncols, Y);
+    if (xu8) hipLaunchKernelGGL((k_cpad_fwd<1, 0>), g, b, 0, st, L, P, X, ldx, col0, ncols, Y, (const float*)nullptr, 0, 0);
+    else hipLaunchKernelGGL((k_cpad_fwd<0, 0>), g, b, 0, st, L, P, X, ldx, col0, ncols, Y, (const float*)nullptr, 0, 0);
 }
 // dst: the layer's (K+1) x N gradient block, or S = dqn_nchunks(npos*B, dw_kc) slabs of it
 void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8) {
@@ -337,14 +380,17 @@ void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, c
     if (xu8) hipLaunchKernelGGL(k_cpad_dw<1>, g, b, 0, st, L, X, ldx, dpre, B, S, kc, dst);
     else hipLaunchKernelGGL(k_cpad_dw<0>, g, b, 0, st, L, X, ldx, dpre, B, S, kc, dst);
 }
-void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out, const float* ysrc, int ldy, int act_src, int mf) {
-    if (mf && !(B % 16 || L.N % 4 || L.cin % 16 || ldy % 4) && al16(out) && al16(ysrc)) {
+void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out, const float* ysrc, int ldy, int act_src, int mf, const float* dY) {
+    if (mf && !(B % 16 || L.N % 4 || L.cin % 16 || ldy % 4) && al16(out) && al16(ysrc) && al16(dY)) {
         const int MT = (B % 32 == 0 && (long)(B / 32) * (L.cin / 16) * L.ih * L.iw >= 1024) ? 2 : 1;
         const int ntasks = (B / (16 * MT)) * (L.cin / 16) * L.ih * L.iw; const dim3 g((ntasks + 3) / 4), b(256);
-        if (MT == 2) hipLaunchKernelGGL((k_cpad_mfma_dx<2>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks);
-        else hipLaunchKernelGGL((k_cpad_mfma_dx<1>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks);
+        if (dY) { if (MT == 2) hipLaunchKernelGGL((k_cpad_mfma_dx<2, 1>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks, dY);
+                  else hipLaunchKernelGGL((k_cpad_mfma_dx<1, 1>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks, dY); }
+        else if (MT == 2) hipLaunchKernelGGL((k_cpad_mfma_dx<2, 0>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks, dY);
+        else hipLaunchKernelGGL((k_cpad_mfma_dx<1, 0>), g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, ntasks, dY);
         return;
     }
     const size_t tot = (size_t)L.in_feat * B; const dim3 g((unsigned)((tot + 255) / 256)), b(256);
-    hipLaunchKernelGGL(k_cpad_dx, g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src);
+    if (dY) hipLaunchKernelGGL(k_cpad_dx<1>, g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, dY);
+    else hipLaunchKernelGGL(k_cpad_dx<0>, g, b, 0, st, L, P, dpre, B, out, ysrc, ldy, act_src, dY);
 }

@@ -137,6 +137,30 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
               if (!(p >= 0.0) || !(p < 1.0)) return fail("layer %d: Dropout p = %g (bit pattern 0x%08x%08x) must be finite with 0 <= p < 1%s", i, p, (unsigned)d[i].cout, (unsigned)d[i].cin,
                                                          p == 1.0 ? " (p = 1 drops every feature: Q would be constant)" : ""); }
             l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (is_skip_map(l.kind)) {      // the join of a CONVOLUTIONAL SkipConnection(layers, +) block: the same law on a (c, h, w) map; inner layers = padded Convs, entry = a Conv / pool / map join
+            const int m = d[i].cin;
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a convolutional skip block is supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: a convolutional skip block's join has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
+            if (m < 1) return fail("layer %d: a convolutional skip block holds at least one inner layer (cin = m = %d must be >= 1)", i, m);
+            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: a convolutional skip block's join uses n_in, n_out and cin (the number of inner layers) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
+            if (m > i) return fail("layer %d: the convolutional skip block's %d inner layers would start before the first layer (the block cannot be the first layer: its input is never the observation)", i, m);
+            for (int j = i - m; j < i; j++) {
+                if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the convolutional skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
+                if (is_skip(L[j].kind)) return fail("layer %d: the convolutional skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
+                if (is_pool(L[j].kind)) return fail("layer %d: the convolutional skip block holds a MaxPool / MeanPool layer (layer %d); its inner layers are Conv layers with pad != 0 only", i, j);
+                if (L[j].kind == DQN_LAYER_CONV && !is_padded(L[j])) return fail("layer %d: the convolutional skip block holds a Conv with pad 0 (layer %d, kernel (%d, %d)); its inner layers are Conv layers with pad != 0 only", i, j, L[j].kh, L[j].kw);
+                if (L[j].kind != DQN_LAYER_CONV) return fail("layer %d: the convolutional skip block holds %s (layer %d); its inner layers are Conv layers with pad != 0 only", i,
+                                                             is_recurrent(L[j].kind) ? "a recurrent layer" : is_ln(L[j].kind) ? "a LayerNorm layer" : is_do(L[j].kind) ? "a Dropout layer" : "a Dense layer", j);
+            }
+            const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
+            if (pp < 0) return fail("layer %d: the convolutional skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block)", i, i - m);
+            if (!has_map(L[pp].kind)) return fail("layer %d: the convolutional skip block's input is the feature vector of layer %d (%s); a convolutional skip block stands on the (c, h, w) map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block", i, pp,
+                                                  L[pp].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[pp].kind) ? "a recurrent layer" : is_ln(L[pp].kind) ? "a LayerNorm layer" : is_do(L[pp].kind) ? "a Dropout layer" : "a Dense layer");
+            if (L[prev].cout != L[pp].cout || L[prev].oh != L[pp].oh || L[prev].ow != L[pp].ow) return fail("layer %d: the convolutional skip block maps a (%d, %d, %d) map to a (%d, %d, %d) map; SkipConnection(layers, +) needs layers: (c, h, w) -> (c, h, w)", i, L[pp].cout, L[pp].oh, L[pp].ow, L[prev].cout, L[prev].oh, L[prev].ow);
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: convolutional skip block n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: convolutional skip block size n = %d != the block's features %d * %d * %d = %d", i, d[i].n_in, c, h, w, l.in_feat);
+            l.cin = m; l.src2 = pp; l.cout = c; l.ih = l.oh = h; l.iw = l.ow = w;      // (cin is m, NOT the channel count: the layer behind the join reads cout, oh, ow)
+            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat;
         } else if (is_skip(l.kind)) {      // the join of a Flux SkipConnection(layers, +) block (skip.hip): y = y_K + y_P; cin = m, the number of inner layers (the m descriptors in front)
             const int m = d[i].cin;
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a skip block is supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
@@ -204,7 +228,7 @@ void read_opts(EngineOpts& o, bool comm_only) {
     // switches that keep a SECOND SCHEDULE of the same arithmetic under parity tests (tests/ name each of them) or that a tool under tools/ drives
     o.no_tiny = F("DQN_NO_TINY"); o.fwd_m32 = I("DQN_FWD_M32", -1); o.no_fwd_wres = F("DQN_NO_FWD_WRES"); o.sim_world = I("DQN_SIM_WORLD", 0); o.no_pregather = F("DQN_NO_PREGATHER");
     o.no_red_head = F("DQN_NO_RED_HEAD"); o.no_head_cols4 = I("DQN_NO_HEAD_COLS4", 0); o.dw_split = I("DQN_DW_SPLIT", 128); o.no_rh_pm = F("DQN_NO_RH_PM"); o.no_act_head = F("DQN_NO_ACT_HEAD"); o.drqn_stamps = F("DQN_DRQN_STAMPS");
-    o.gru_stepwise = F("DQN_GRU_STEPWISE"); o.rnn_stepwise = F("DQN_RNN_STEPWISE");
+    o.gru_stepwise = F("DQN_GRU_STEPWISE"); o.rnn_stepwise = F("DQN_RNN_STEPWISE"); o.no_skip_fuse = F("DQN_NO_SKIP_FUSE");
     // r06 removed (the constants they set are now the only behaviour): DQN_ADAM_MODE, DQN_PRIO_LEVEL, DQN_PRIO_NOSPLIT, DQN_PRIO_FORK, DQN_HEAD_FUSE_MAXB,
     // DQN_NO_HEAD_FUSE, DQN_NO_U8_ARENA, DQN_LSTM_DW_MFMA, DQN_NO_GRAPH_UPLOAD, DQN_NO_ST_WT, DQN_NO_DX_WIDE, DQN_NO_ROLLOUT_CYCLE, DQN_MID_GROUP, DQN_MID_BIG
     // (docs/history/r06.md lists each with the number that decided it)

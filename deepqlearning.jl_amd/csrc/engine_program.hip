@@ -80,7 +80,12 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
             //   a Dropout layer (dropout.hip): ACTIVE in the first pass of the train step only, on its leading E.do_cols columns (online network, s): it writes a buffer of its own -- the producer's output
             //     must survive for the producer's backward -- and copies the s' columns behind them.  Every other pass emits NOTHING: the layer's activation pointer there is its producer's (engine.hip)
+            //   a convolutional skip block whose last inner layer K has no activation (skip_fused_fwd): K's launch takes the entry's stored output of the pass as its residual
+            //     operand and writes act(tot + bias) + y_P straight into the JOIN's activation (conv_pad.hip), named "<pass>_conv<K>+skip<join>"; the join's level emits nothing.
+            //     K's own activation buffer is then never written, and never read: its one consumer is the join, and the join's backward is the alias (skip_dact_alias)
             const int l = lv[0]; const LayerDev L = view(l); const bool dropout = is_do(L.kind), join = is_skip(L.kind);
+            const int jn = is_padded(L) ? skip_join_of_last(e, l) : -1; const bool fuse_res = jn >= 0 && skip_fused_fwd(e, jn);
+            const bool fused_join = join && skip_fused_fwd(e, l);
             float* stat0 = (is_ln(L.kind) && E.ln_stat) ? (E.ln_stat[l] = palloc(e, (size_t)2 * passes[0].ncols)) : nullptr;
             for (int pi = 0; pi < np; pi++) {
                 const Prob q = prob(l, pi);
@@ -88,6 +93,13 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
                 if (dropout) {
                     const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
                     if (pi == 0 && C > 0) prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
+                    continue;
+                }
+                if (fused_join) continue;      // written by the last inner layer's launch
+                if (fuse_res) {
+                    char nm[64]; snprintf(nm, sizeof nm, "%s_%s%d+skip%d", passes[pi].tag, kind_traits(L).tag, l, jn); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
+                    const float* R = passes[pi].in[e->L[jn].src2]; float* Yj = passes[pi].out[jn];
+                    prog.push_back({name, [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, Yj, mf ? 1 : 0, 0, R, q.ncols, 0); }});
                     continue;
                 }
                 float* stat = pi == 0 ? stat0 : nullptr; const float* X2 = join ? passes[pi].in[L.src2] : nullptr;
@@ -497,7 +509,8 @@ int build_program(dqn_engine* e) {
     // kind, l may also be the FIRST inner layer of a skip block: the block's entry launch is queued behind its level (post_level)
     auto emit_own_level_bwd = [&](int l, std::vector<dqn_engine::Step>& post_level) {
         const LayerDev L = e->L[l]; const float* X = L.src < 0 ? e->x0 : e->act_on[L.src]; const int ldx = L.src < 0 ? ld0 : ncon; float* dpre = e->dact[l];
-        for (int j = l + 1; j < e->nl; j++) if (is_skip(e->L[j].kind) && j - e->L[j].cin == l) {
+        const int jf = skip_join_of_first(e, l); const bool fuse_entry = jf >= 0 && skip_fused_dx(e, jf);      // a map block: the entry's sum and derivative run in THIS layer's dX epilogue (below)
+        for (int j = l + 1; j < e->nl; j++) if (is_skip(e->L[j].kind) && j - e->L[j].cin == l && !fuse_entry && wants_dx(l)) {
             // this layer is the FIRST inner layer of the skip block that joins at j: its input-gradient launch, whatever its kind, runs with the IDENTITY epilogue
             // (src_act) and leaves the raw dF in dact[P].  Behind every launch of this level the block's entry launch (skip.hip) adds the join's dY and takes P's
             // derivative once, after the sum, in place:  dact[P] = (dF + dY) .* act_P'(y_P)
@@ -531,7 +544,15 @@ int build_program(dqn_engine* e) {
             // reads the observation -- dX with the producing layer's activation derivative
             float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8; const float* P = e->p_on;
             e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
-            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
+            // the FIRST inner layer of a convolutional skip block (fuse_entry): the launch adds the join's dY = dact[join] to its own sum and takes the entry's REAL activation
+            // derivative after it -- dact[P] = (dF + dY) .* act_P'(y_P), what the bwd_entry launch (skip.hip) computes behind a raw dF; named "bwd_conv<F>+skip<join>".  With
+            // one inner layer dpre IS dY (skip_dact_alias): read twice, written by nobody here
+            if (wants_dx(l) && fuse_entry) {
+                char nm[64]; snprintf(nm, sizeof nm, "bwd_%s%d+skip%d", kind_traits(L).tag, l, jf); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
+                const float* dYj = e->dact[jf]; const int act_p = e->L[L.src].act;
+                e->prog.push_back({name, [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_p, mf ? 1 : 0, dYj); }});
+            }
+            else if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
         }
         return true;
     };

@@ -112,9 +112,31 @@ is_glue(l) = l === identity || l === flattenbatch || l isa Function
 # layers' in order, which flatparams below follows) and no activation.  Lowered as the inner layers' descriptors, then ONE join descriptor of kind 9 directly behind them:
 # cin = m, the number of inner descriptors; n_in = n_out = 0: the engine takes the feature count.  The engine checks the placement (base chain, on a feature vector, never
 # first or last, n -> n); what it cannot see is refused here by name: another connection (vcat, *, a closure), a nested block, an inner layer that is not Dense / LayerNorm / Dropout
+#
+# The CONVOLUTIONAL block, x + Conv(Conv(x)): where the descriptor in front is a Conv, a pool or the join of another such block (kinds 1, 5, 6, 10) and every inner layer
+# is a Conv or a pool, the join is of kind 10 -- the same descriptor shape.  Its inner layers are Convs with pad != 0 that keep the channel count; a pool, a pad-0 Conv and
+# a channel change are refused here by name, that the block keeps (h, w) is the engine's check
+is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10
+is_map_layer(x) = x isa Conv || x isa Flux.MaxPool || x isa Flux.MeanPool
+function lower_skip_map!(descs, l, stream, inner)
+    m = 0; c_in = 0; c_out = 0
+    for x in inner
+        is_glue(x) && continue
+        x isa Conv || throw("DeepQLearningError: a MaxPool / MeanPool layer inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only)")
+        all(==(0), x.pad) && throw("DeepQLearningError: a Conv with pad 0 inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only; 1x1 and unpadded inner convolutions are not supported)")
+        m == 0 && (c_in = size(x.weight, 3)); c_out = size(x.weight, 4)
+        push!(descs, lower_layer(x, stream)); m += 1
+    end
+    c_in == c_out || throw("DeepQLearningError: the convolutional SkipConnection maps $(c_in) channels to $(c_out); SkipConnection(layers, +) needs layers: (c, h, w) -> (c, h, w)")
+    push!(descs, LayerDesc(10, 0, stream, 0, 0, m, 0, 0, 0, 0, 0))
+end
 function lower_skip!(descs, l, stream)
     l.connection === (+) || throw("DeepQLearningError: SkipConnection(layers, $(l.connection)) is not supported; the MI355X engine runs SkipConnection with the connection + only (vcat, *, closures and Parallel are not supported)")
     inner = l.layers isa Flux.Chain ? collect(l.layers.layers) : Any[l.layers]
+    real = filter(!is_glue, inner)
+    if !isempty(descs) && is_map_desc(descs[end]) && !isempty(real) && all(is_map_layer, real)
+        return lower_skip_map!(descs, l, stream, inner)
+    end
     m = 0
     for x in inner
         is_glue(x) && continue

@@ -256,7 +256,10 @@ class SkipConnection:
     """Flux 0.14 SkipConnection(layers, +) on a feature vector (recalled, not executed here): y = layers(x) .+ x.  No parameters and no activation of its own: Flux.params
     yields the inner layers' parameters in order.  `layers` is a Chain (or one layer) of Dense, LayerNorm and Dropout layers that maps n -> n; the connection is `+` only
     ("+" or operator.add).  The block stands in the base chain behind a Dense, recurrent, LayerNorm or Dropout layer or another block: never first, never behind a
-    Conv / pool, never the output layer (DESIGN.md section 4 "Skip connections").  create_dueling_network treats it as a non-Dense layer."""
+    Conv / pool, never the output layer (DESIGN.md section 4 "Skip connections").  create_dueling_network treats it as a non-Dense layer.
+
+    On a (c, h, w) map -- behind a Conv, a MaxPool / MeanPool or another such block -- `layers` is a Chain (or one layer) of Conv layers with pad != 0 that maps
+    (c, h, w) -> (c, h, w): the residual convolutional block x + Conv(Conv(x)) (DESIGN.md section 4 "Convolutional skip blocks")."""
     kind = "skip"
 
     def __init__(self, layers, connection):
@@ -321,6 +324,7 @@ def lower(net):
     """Chain | DuelingNetwork -> (list[LayerDesc], dueling flag)."""
     out = []
     chan = [0]      # channels of the map the next layer reads (0 in front of the first Conv: the engine takes the observation's)
+    map_join = [False]      # the last block lowered was a convolutional one: what follows it stands on a map
     top = None if isinstance(net, DuelingNetwork) else net      # the chain whose last layer is the network's output layer (a dueling base chain's is not)
 
     def add_skip(blk, stream, first, prev_kind, is_last):
@@ -330,7 +334,10 @@ def lower(net):
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} is supported in the base chain only (not in a value / advantage stream)")
         if first:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the first layer: a skip block's input is never the observation (it must follow a Dense, recurrent, LayerNorm or Dropout layer or another skip block)")
-        if prev_kind in ("conv", "maxpool", "meanpool"):
+        on_map = prev_kind in ("conv", "maxpool", "meanpool") or (prev_kind == "skip" and map_join[0])
+        if on_map and not first and all(getattr(l, "kind", None) in ("conv", "maxpool", "meanpool") for l in blk.layers):
+            return add_skip_map(blk, stream, is_last)
+        if on_map:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot follow a Conv / MaxPool / MeanPool layer: a skip block stands on a feature vector (convolutional residual blocks are not supported)")
         if is_last:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the network's output layer")
@@ -354,6 +361,26 @@ def lower(net):
         d = _abi.LayerDesc()
         d.kind, d.act, d.stream, d.cin = _abi.LAYER_SKIPADD, _abi.ACT_IDENTITY, stream, len(blk.layers)
         out.append(d)
+        map_join[0] = False
+
+    def add_skip_map(blk, stream, is_last):
+        # the block stands on a (c, h, w) map and holds Conv / pool layers only: the convolutional block, kind SKIPADD_MAP -- the same descriptor shape.  Its inner layers are
+        # Convs with pad != 0 and keep the channel count; that they keep (h, w) is the engine's check (it knows the map)
+        if is_last:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the network's output layer")
+        for l in blk.layers:
+            if l.kind in ("maxpool", "meanpool"):
+                raise _abi.DQNError(f"DeepQLearningError: a MaxPool / MeanPool layer inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only): {blk!r}")
+            if l.ph == 0 and l.pw == 0:
+                raise _abi.DQNError(f"DeepQLearningError: a Conv with pad 0 inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only; 1x1 and unpadded inner convolutions are not supported): {blk!r}")
+        cin, cout = blk.layers.layers[0].cin, blk.layers.layers[-1].cout
+        if cin != cout:
+            raise _abi.DQNError(f"DeepQLearningError: {blk!r} maps {cin} channels to {cout}; SkipConnection(layers, +) needs layers: (c, h, w) -> (c, h, w)")
+        add(blk.layers, stream)
+        d = _abi.LayerDesc()
+        d.kind, d.act, d.stream, d.cin = _abi.LAYER_SKIPADD_MAP, _abi.ACT_IDENTITY, stream, len(blk.layers)
+        out.append(d)
+        map_join[0] = True
 
     def add(chain, stream):
         layers = list(chain)

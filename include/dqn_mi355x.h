@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -109,8 +109,17 @@ typedef struct {
                                           Backward: dact[K] = dY .* act_K'(y_K); F's input gradient dF is taken raw and dact[P] = (dF + dY) .* act_P'(y_P) -- P's derivative once,
                                           after the sum.  The inner layers are Dense, LayerNorm and Dropout layers (no recurrent layer, Conv, pool or nested block) and map n -> n;
                                           P is a Dense, recurrent, LayerNorm or Dropout layer or the join of a preceding block: never the observation (the block is never the first
-                                          layer), never a Conv / pool map (convolutional residual blocks are not supported); the block is never the output layer.  LayerNorm and
-                                          Dropout may be the first inner layer and may directly follow a join.  Base chain only, single GPU only */
+                                          layer), never a Conv / pool map (a convolutional residual block is the next kind, SKIPADD_MAP; under this kind it is refused); the block is never the output layer.  LayerNorm and
+                                          Dropout may be the first inner layer and may directly follow a join.  Base chain only, single GPU only;
+                                          SKIPADD_MAP, the join of a CONVOLUTIONAL SkipConnection(layers, +) block, x + Conv(Conv(x)) on a (c, h, w) map: the descriptor has the shape
+                                          of SKIPADD's -- ONE descriptor directly after the m inner descriptors, cin = m >= 1, n_in == n_out == c * h * w (or both 0), act = IDENTITY,
+                                          stream = BASE, every other slot 0, an all-zero plan entry -- and the law is SKIPADD's, element for element of the map X[(ci, iy, ix)][column].
+                                          The inner layers are Convs with pad != 0 on at least one axis (no pad-0 Conv, pool, Dense, LayerNorm, Dropout, recurrent layer or nested
+                                          block) and map (c, h, w) -> (c, h, w); P is a Conv (padded or not, any activation), a MaxPool / MeanPool or the join of a preceding
+                                          SKIPADD_MAP block: never the observation, never a feature vector, never a SKIPADD join.  The join's output is a (c, h, w) map for whatever
+                                          follows (a Conv, a pool, another block, or a Dense / recurrent layer on c * h * w features).  Where K has no activation the add runs in the
+                                          epilogue of K's forward launch, and the + dY of the entry in the epilogue of F's input-gradient launch (conv_pad.hip): the same bits as the
+                                          separate launches.  Base chain only, never the output layer, single GPU only */
 } dqn_layer_desc;
 
 /* Summation-order plan of one layer: the K dimension of each contraction is cut
