@@ -879,6 +879,10 @@ static inline int drqn_fused_cg(const LayerDev* L, int nl, int E, int B, int T, 
     }
     return 0;
 }
+// the largest column group a plan may ask for: one thread per (sequence set, gate, column, unit), nset * 4 * H * cg <= 1024 with nset >= 2 and H >= 8.  The kernel's per-column
+// tables are sized by it (they held 4 entries, the largest group the default plan picks, while build_program admitted a caller's groups up to this bound)
+#define DRQN_COLS_MAX_CG 16
+size_t drqn_cols_lds_floats(const DrqnColsArgs& a);      // dynamic LDS of the launch for a.cg (B, T, H, E, nA, dueling, nset, Pint set)
 int launch_drqn_cols(hipStream_t st, const DrqnColsArgs& a, int slot);      // 0 = launched; -1 = the LDS attribute could not be raised
 int adam_blocks(size_t P);
 static inline int gmax_slots(size_t) { return 65536; }   // per-block max |g| of every Adam job of a step (each job owns a slot range)

@@ -45,7 +45,7 @@ __device__ __forceinline__ void ldsb() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts
 template <int TT, int HH, int WK>
 __global__ __launch_bounds__(1024) void k_drqn_cols(const DrqnColsArgs A, const int slot_i) {
     extern __shared__ __align__(16) float sm[];
-    __shared__ int np_s[4]; __shared__ long long ep_s4[4];
+    __shared__ int np_s[DRQN_COLS_MAX_CG]; __shared__ long long ep_s4[DRQN_COLS_MAX_CG];      // per column of the group (a caller's plan may ask for any group size the thread-count rule admits: common.h)
     const int tid = threadIdx.x, NT = blockDim.x;
     const int B = A.B, T = A.T, H = A.H, E = A.E, nA = A.nA, cg = A.cg, nset = A.nset, N = 4 * H, per = H * cg, Ep = (E + 3) & ~3;
     const int duel = A.dueling ? 1 : 0, no = nA + duel, Pint = (int)A.Pint;
@@ -373,7 +373,7 @@ __global__ __launch_bounds__(1024) void k_drqn_cols(const DrqnColsArgs A, const 
     stamp();
 }
 
-static size_t drqn_cols_lds_floats(const DrqnColsArgs& a) {
+size_t drqn_cols_lds_floats(const DrqnColsArgs& a) {
     const size_t T = a.T, cg = a.cg, H = a.H, N = 4 * H, per = H * cg, Ep = (a.E + 3) & ~3, no = a.nA + (a.dueling ? 1 : 0), ns = a.nset;
     return 2 * (size_t)a.Pint + 2 * T * cg * Ep + 4 * T * cg + ns * T * per + ns * per + ns * 4 * per + T * cg * N + 2 * T * per + ((ns * T * cg * no + 3) & ~(size_t)3) + ((T * cg * no + 3) & ~(size_t)3) + T * per + 2 * per + H * (N + 4) + ns * ((T * cg + 15) / 16 * 16) * N;
 }

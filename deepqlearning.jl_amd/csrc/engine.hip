@@ -339,6 +339,20 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     for (int i = 0; i < e->nl; i++) {
         e->L[i].fwd_kc = plan[i].fwd_kc; e->L[i].dx_kc = plan[i].dx_kc; e->L[i].dw_kc = plan[i].dw_kc;
         if (!kind_traits(e->L[i]).contracts) e->L[i].fwd_kc = e->L[i].dx_kc = e->L[i].dw_kc = 0;      // nothing to contract: a pool / LayerNorm / Dropout layer's / skip join's plan entry is ignored
+        // a chunk length is 0 (unsplit) or positive.  A negative fwd_kc / dx_kc ran unsplit but stayed in the plan (dqn_engine_get_plan, checkpoints) and made two layers of
+        // one geometry differ (same_geo): refused, with the layer and the rule.  dw_kc < 0 is the column-group form, a group of at most batch_size columns (this also keeps
+        // -dw_kc representable: INT_MIN has no negative)
+        if (e->L[i].fwd_kc < 0 || e->L[i].dx_kc < 0) return fail("plan: layer %d: fwd_kc = %d, dx_kc = %d: a chunk length must be >= 0 (0 = unsplit)", i, e->L[i].fwd_kc, e->L[i].dx_kc);
+        if (e->L[i].dw_kc < -e->B) return fail("plan: layer %d: dw_kc = %d: a column group (dw_kc < 0) holds at most batch_size = %d columns", i, e->L[i].dw_kc, e->B);
+        {   // every plan chunk beyond the first is one more slab -- a copy of the layer's output (forward), gradient block (dW) or input gradient (dense dX) -- in workspaces the
+            // program builder allocates per launch: a plan whose slabs of one layer pass 2^28 floats (1 GiB; the default plans stay below 2^22) is refused here, by name,
+            // instead of running into a failed allocation there
+            const LayerDev& l = e->L[i]; const size_t cap = (size_t)1 << 28;
+            const size_t Bc_ = (size_t)e->B * (hp->recurrence ? std::max(1, hp->trace_length) : 1), ncon_ = hp->double_q ? 2 * Bc_ : Bc_;
+            const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = l.dw_kc > 0 ? dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc_, INT_MAX), l.dw_kc) : 1, sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1;
+            if ((sf > 1 && sf * l.out_feat * ncon_ > cap) || (sw > 1 && sw * ((size_t)l.K + 1) * l.N > cap) || (sx > 1 && sx * l.in_feat * Bc_ > cap))
+                return fail("plan: layer %d: (fwd_kc, dx_kc, dw_kc) = (%d, %d, %d) cuts its sums into %zu / %zu / %zu chunks: the slabs of one layer may hold at most 2^28 floats", i, l.fwd_kc, l.dx_kc, l.dw_kc, sf, sx, sw);
+        }
         if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }

@@ -204,6 +204,11 @@ int build_program(dqn_engine* e) {
                                  "H a multiple of 8 up to 64, unsplit input projection and head dX, ONE device without a communicator -- use dw_kc >= 0 (plan = NULL picks a plan that fits; with a communicator dqn_comm_init re-derives it)", -cgm);
             DrqnColsArgs a; memset(&a, 0, sizeof a);
             a.B = Bb; a.T = T; a.H = L0.H; a.E = e->E; a.nA = e->nA; a.dueling = e->hp.dueling; a.double_q = e->hp.double_q; a.cg = cgm; a.nset = nset; a.gamma = e->hp.gamma; a.Pint = (unsigned)e->Pint;
+            // a CALLER's group size: the default plan picks one whose workgroup fits (drqn_fused_cg); any other is held to the same two bounds here, by name, instead of at the
+            // launch -- the per-column tables of the kernel (DRQN_COLS_MAX_CG) and one workgroup's 160 KB of LDS for both networks' parameters and the group's activations
+            if (cgm > DRQN_COLS_MAX_CG || (drqn_cols_lds_floats(a) + 64) * sizeof(float) > (size_t)160 * 1024)
+                return fail("plan: column-group dW chunks (dw_kc = %d): a group of %d batch columns needs %zu bytes of LDS in the fused recurrent step (at most %d columns and 160 KB) -- use a smaller group (plan = NULL picks one that fits)",
+                            -cgm, cgm, drqn_cols_lds_floats(a) * sizeof(float), DRQN_COLS_MAX_CG);
             a.wi_off = (unsigned)L0.w_off; a.b_off = (unsigned)L0.b_off; a.wh_off = (unsigned)L0.wh_off; a.h0_off = (unsigned)L0.h0_off; a.c0_off = (unsigned)L0.c0_off;
             const int ha = e->hp.dueling ? e->last_adv : e->last_base, hv = e->hp.dueling ? e->last_val : -1;
             for (int hd = 0; hd < 2; hd++) { const int l = hd == 0 ? ha : hv; if (l < 0) continue; const LayerDev& L = e->L[l];

@@ -207,6 +207,12 @@ int ref_create(const dqn_layer_desc* d, int n, const dqn_hparams* hp, const dqn_
     e->last_base = e->last_val = e->last_adv = -1;
     dqn_layer_plan defp[MAXL];
     if (!plan) { ref_plan_default(d, n, hp, defp); plan = defp; }
+    /* a chunk length is 0 (unsplit) or positive; a column group (dw_kc < 0) holds at most batch_size columns (engine.hip engine_init: the same two refusals; the entry of a
+       layer that contracts nothing -- pool, LayerNorm, Dropout, skip join -- is ignored there and here) */
+    for (int i = 0; i < n; i++) if (d[i].kind <= DQN_LAYER_RNN) {
+        if (plan[i].fwd_kc < 0 || plan[i].dx_kc < 0) { free(e); FAIL("plan: layer %d: fwd_kc = %d, dx_kc = %d: a chunk length must be >= 0 (0 = unsplit)", i, plan[i].fwd_kc, plan[i].dx_kc); }
+        if (plan[i].dw_kc < -hp->batch_size) { free(e); FAIL("plan: layer %d: dw_kc = %d: a column group (dw_kc < 0) holds at most batch_size = %d columns", i, plan[i].dw_kc, hp->batch_size); }
+    }
     /* column-group dW chunks (dw_kc = -cg): recurrent engines only, every layer alike, cg divides the batch */
     for (int i = 0; i < n; i++) if (plan[i].dw_kc < 0) {
         if (!hp->recurrence) { free(e); FAIL("plan: dw_kc < 0 (column-group chunks) needs recurrence = true"); }

@@ -3,9 +3,10 @@ tests/feedforward_reference.py and the bit-for-bit companions, for every case ta
 tests/test_feedforward_edges_gpu.py on the HIP engine), tests/pool_reference.py and tests/conv_pad_reference.py.
 
 The edge table: feed-forward train steps at the edges of the kernel-selection rules and on rectangular convolutions.  The selection rules of nn_gemm.hip /
-nn_mfma.hip / engine_program.hip / engine.hip / red_head.hip are RESTATED here (facts()), evaluated on the default plan, and every case states in `want` the side
-of each rule it was written for: a case on the wrong side fails instead of silently testing something else.  launches() turns the same facts into the launch
-names profile_step must (and must not) show.
+nn_mfma.hip / engine_program.hip / engine.hip / red_head.hip are RESTATED here (facts()), evaluated on the plan the case runs under -- the default plan for the
+tables of this file, an edited one for tests/plan_edges_common.py (case_plan) -- and every case states in `want` the side of each rule it was written for: a
+case on the wrong side fails instead of silently testing something else.  launches() turns the same facts into the launch names profile_step must (and must
+not) show.
 
 Tolerances are those of tests/test_twin_vs_oracle.py::run_case (Q, td, loss, grad_norm, priorities), recurrent_reference.GRAD_C / GRAD_RTOL
 (gradients per block) and recurrent_reference.check_params (parameters); none is widened here."""
@@ -229,6 +230,10 @@ def facts(net, plan, B, hp):
             S = 1 if (mf and not addend and mode == 3) else Sp
             f[f"dx{i}"] = "lds" if (mf and not addend and mode >= 0) else ("mfma" if mf and g.N >= 16 and mfma_dx_ok(g, B, ncon) else "valu")
             f[f"dxred{i}"] = S > 1
+    # the dW slabs of plan chunks (engine_program.hip, final_segs): summed inside the Adam launch when every split block is a whole number of 16-byte sets and there
+    # are at most eight of them, else by a launch of their own ("dw_reduce_all")
+    split = [g for g in G if nchunks(g.npos * B, g.dw_kc) > 1]
+    f["dwsum"] = "none" if not split else ("adam" if len(split) <= 8 and all(g.w_off % 4 == 0 and ((g.K + 1) * g.N) % 4 == 0 for g in split) else "launch")
     return f
 
 
@@ -238,6 +243,7 @@ def launches(f):
     if f["tiny"]:
         return {"tiny_step"}, {"head_td", "red_head", "head_cols4", "td_huber", "adam"}
     must, never = {f["head"], "adam"}, {"tiny_step"} | ({"head_td", "red_head", "head_cols4", "td_huber"} - {f["head"]})
+    (must if f["dwsum"] == "launch" else never).add("dw_reduce_all")
     G = f["G"]
     for lvl in f["levels"]:
         for i in lvl:
@@ -303,9 +309,16 @@ def hparams(c, net, graph=None, mfma=None):
                            use_mfma=c.mfma if mfma is None else mfma, use_graph=c.graph if graph is None else graph, seed=5)
 
 
+def case_plan(c, layers, hp):
+    """the plan the case runs under: the default plan, through the case's `edit` where it has one (tests/plan_edges_common.py)"""
+    plan = ref.default_plan(layers, hp)
+    edit = getattr(c, "edit", None)
+    return [tuple(p) for p in edit(plan)] if edit else plan
+
+
 def case_facts(c):
     net = network(c); hp = hparams(c, net)
-    return facts(net, ref.default_plan(FR.layer_descs(net), hp), c.B, hp)
+    return facts(net, case_plan(c, FR.layer_descs(net), hp), c.B, hp)
 
 
 def check_want(c):

@@ -117,7 +117,7 @@ def test_rollout_with_fused_acting_head_bit_exact(pkg, envs, monkeypatch, n_envs
     np.testing.assert_array_equal(outs[0][0], outs[1][0]); np.testing.assert_array_equal(outs[0][1], outs[1][1])
 
 
-@pytest.mark.parametrize("case", ["wide_fc_dueling", "wide_fc_dueling_u8", "wide_fc_dueling_s13", "wide_fc_plain", "wide_fc_dueling_uniform", "gridworld", "gridworld_1024", "small_fc_dueling", "gridworld_unequal_streams", "gridworld_unequal_streams_16",
+@pytest.mark.parametrize("case", ["wide_fc_dueling", "wide_fc_dueling_u8", "wide_fc_dueling_s13", "wide_fc_dueling_s16", "wide_fc_dueling_s17", "wide_fc_plain", "wide_fc_dueling_uniform", "gridworld", "gridworld_1024", "small_fc_dueling", "gridworld_unequal_streams", "gridworld_unequal_streams_16",
                                   "wide_fc_dueling_u8_b32"])
 def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
     """r06: the acting step's tail as ONE launch -- k_act_head (act_head.hip): split-K reduce of the heads' producers + heads + Q / argmax + eps-greedy +
@@ -130,14 +130,17 @@ def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
     programs read float columns -- also the evaluation set's, built after the train program, at 16 copies (a multiple of the LDS-tiled launch's column tile)."""
     grid = case.startswith("gridworld")      # (gridworld_1024: the largest copy count, 256 groups = every RolloutDev record in use)
     unequal, b32 = case.startswith("gridworld_unequal_streams"), case.endswith("b32")
-    net = {"wide_fc_dueling": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8_b32": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s13": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_uniform": EC.testmdp_wide_fc_dueling, "wide_fc_plain": EC.testmdp_wide_fc_plain,
+    net = {"wide_fc_dueling": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_u8_b32": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s13": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s16": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_s17": EC.testmdp_wide_fc_dueling, "wide_fc_dueling_uniform": EC.testmdp_wide_fc_dueling, "wide_fc_plain": EC.testmdp_wide_fc_plain,
            "gridworld": EC.gridworld_mlp_dueling, "gridworld_1024": EC.gridworld_mlp_dueling, "small_fc_dueling": EC.testmdp_conv_dueling,
            "gridworld_unequal_streams": EC.gridworld_mlp_unequal_streams, "gridworld_unequal_streams_16": EC.gridworld_mlp_unequal_streams}[case]()
-    n_envs = {"wide_fc_dueling": 8, "wide_fc_dueling_u8": 12, "wide_fc_dueling_s13": 8, "wide_fc_dueling_uniform": 8, "wide_fc_plain": 4, "gridworld": 64, "gridworld_1024": 1024, "small_fc_dueling": 8, "gridworld_unequal_streams": 4, "gridworld_unequal_streams_16": 16,
+    n_envs = {"wide_fc_dueling": 8, "wide_fc_dueling_u8": 12, "wide_fc_dueling_s13": 8, "wide_fc_dueling_s16": 8, "wide_fc_dueling_s17": 8, "wide_fc_dueling_uniform": 8, "wide_fc_plain": 4, "gridworld": 64, "gridworld_1024": 1024, "small_fc_dueling": 8, "gridworld_unequal_streams": 4, "gridworld_unequal_streams_16": 16,
               "wide_fc_dueling_u8_b32": 16}[case]
     # plan edits (the twin takes the same plan): 13 slabs per hidden layer (the 16-slab instantiation of the launch); 32-row chunks for the plain net's 64-input head (the default
     # plan leaves it unsplit, which the launch does not cover)
-    plan_edit = {"wide_fc_dueling_s13": lambda pl: [(128, dx, dw) if fk == 392 else (fk, dx, dw) for fk, dx, dw in pl],
+    # ... and the launch's slab cap (act_head_ok, red_head_ok: S <= 16) from both sides: 16 slabs (15 x 100 + 68 of the 1568 inputs) keep the fused tail, 17 (16 x 96 + 32) take the
+    # four-launch tail -- and, in the train step, the head launch without the fused reduce -- under either setting
+    resplit = lambda kc: (lambda pl: [(kc, dx, dw) if fk == 392 else (fk, dx, dw) for fk, dx, dw in pl])
+    plan_edit = {"wide_fc_dueling_s13": resplit(128), "wide_fc_dueling_s16": resplit(100), "wide_fc_dueling_s17": resplit(96),
                  "wide_fc_plain": lambda pl: pl[:-1] + [(32, pl[-1][1], pl[-1][2])]}.get(case)
     outs = []
     for fused in (True, False):
@@ -151,7 +154,11 @@ def test_rollout_fused_acting_tail_both_schedules(pkg, envs, monkeypatch, case):
         for h in (g, t):
             h.envs_create(spec, max_episode_length=20 if grid else 100, seed=17)
         compare_state(g, t)
-        assert g.envs_info() == (n_envs, fused and not unequal), "the schedule under test is not the one this case names"
+        if plan_edit:
+            assert g.plan() == t.plan() == plan_edit(pkg.default_plan(ref.layers_from_network(net), hp)) != pkg.default_plan(ref.layers_from_network(net), hp)
+        if case[-4:] in ("_s16", "_s17"):
+            assert [-(-1568 // fk) for fk, _, _ in g.plan() if fk not in (0, 32)] == [int(case[-2:])] * 2, g.plan()
+        assert g.envs_info() == (n_envs, fused and not unequal and not case.endswith("_s17")), "the schedule under test is not the one this case names"
         t0 = 1
         for chunk, cad in ((1, False), (4, False), (3, True), (9, False), (5, True), (6, False)):      # the 80-slot ring wraps; episodes end every 5 steps (TestMDP) / within 20 (GridWorld)
             kw = dict(t0=t0, train_freq=2 if cad else 3, target_update_freq=7, eps=(0.6, 0.05, 15.0), env_step_cadence=cad)      # cad: n / 2 train steps per vector step, the whole vector step as one graph

@@ -733,7 +733,25 @@ def test_checkpoint_resume_is_bit_exact(pkg, u8, tmp_path):
         c = pkg.Engine(ref.layers_from_network(net), hp, plan=other)
         with pytest.raises(pkg.DQNError, match="different summation plan"):
             c.restore(ck)
-        c.close()
+        # ... and a checkpoint written under that EDITED plan: an engine created with the same plan continues the run bit for bit, the default plan's engine refuses it
+        fill((c,), net, 137, u8=u8); set_same_params((c,), net)
+        for _ in range(3):
+            c.train_step()
+        ck2 = c.checkpoint()
+        assert [tuple(r) for r in ck2["plan"]] == other
+        run2 = [c.train_step() for _ in range(3)]
+        d = pkg.Engine(ref.layers_from_network(net), hp, plan=other)
+        d.restore(ck2)
+        for want in run2:
+            got = d.train_step()
+            assert got[0] == want[0] and got[1] == want[1]
+            np.testing.assert_array_equal(got[2], want[2])
+        np.testing.assert_array_equal(c.get_params(0), d.get_params(0)); np.testing.assert_array_equal(c.replay_priorities(), d.replay_priorities())
+        with pytest.raises(pkg.DQNError, match="different summation plan"):
+            b.restore(ck2)
+        c.close(); d.close()
+    else:
+        raise AssertionError("the edited plan of this test is the default plan: it tests nothing")
 
 
 def test_sampler_distinct_gpu_equals_twin(pkg):

@@ -382,3 +382,94 @@ def test_stack_policy_state(mods, name):
             np.testing.assert_array_equal(x, np.repeat(s0.numpy().astype(np.float32)[:, None], S, axis=1))
     np.testing.assert_allclose(h.forward(xs[0]), want[0], atol=1e-5, rtol=1e-5)
     h.close()
+
+
+# ------------------------------------------------------------------ e. caller-supplied summation plans (the feed-forward table: tests/plan_edges_common.py)
+def _state(h):
+    return [h.get_grads(), h.get_params(0)]
+
+
+def plan_case_checked(mods, c, plan, default, launched=(), twin=True, steps=2):
+    """the case under `plan`: against the fp64 reference; plan() returns the plan; bit for bit the C twin (LSTM networks) and the other schedule (use_graph); at least one bit
+    of the gradient or the parameters differs from the run under `default`; `launched` names show in profile_step"""
+    assert plan != default, c.name
+    net, h, ring, out = run_checked(mods, c, steps=steps, plan=plan)
+    assert h.plan() == plan, (c.name, h.plan())
+    others = [make_engine(mods, c, plan=plan, graph=1 - c.graph)[1]] + ([make_engine(mods, c, plan=plan, twin=True)[1]] if twin else [])
+    for o in others:
+        assert replay(o, out) == [x[0] for x in out], c.name
+        same_state(h, o)
+        o.close()
+    d = make_engine(mods, c, plan=default)[1]
+    replay(d, out)
+    assert any(not np.array_equal(a, b) for a, b in zip(_state(h), _state(d))), f"{c.name}: the plan gives the default plan's bits: the case tests nothing"
+    d.close()
+    names = {n for n, _ in h.profile_step(max_entries=4096)}
+    assert set(launched) <= names, (c.name, sorted(names))
+    h.close()
+    return names
+
+
+def default_plan_of(mods, c):
+    net, h, *_ = make_engine(mods, c)
+    plan = h.plan(); h.close()
+    return plan
+
+
+@pytest.mark.parametrize("kc", [20, 32, 24, 7])
+def test_fused_column_step_with_a_chunked_head(mods, kc):
+    """Chain(LSTM(6, 40), Dense(40, 3)) on the fused column-parallel step (drqn_cols.hip reads the head's chunk count and length): head chunks 20 + 20, 32 + 8, 24 + 16 and
+    5 x 7 + 5.  (H = 40 is the widest LSTM whose double-Q step fits the fused launch's LDS rule, drqn_fused_cg, at these sizes; at H = 64 both networks' parameters alone pass it.)"""
+    c = _case(f"lstm_cols_head_kc{kc}", "lstm", 40, 4, 3, None)
+    default = default_plan_of(mods, c)
+    assert all(p[2] < 0 for p in default) and default[1][0] == 0, default      # the fused step (column-group dW chunks), head unsplit
+    plan = [default[0], (kc, default[1][1], default[1][2])]
+    plan_case_checked(mods, c, plan, default, launched=("drqn_cols", "adam"))
+
+
+@pytest.mark.parametrize("H, B, dq, groups", [(8, 12, 0, (1, 2, 3, 4, 6, 12)), (16, 8, 1, (1, 2, 4))], ids=["h8_b12", "h16_b8_doubleq"])
+def test_every_admissible_column_group_size(mods, H, B, dq, groups):
+    """dw_kc = -cg on every layer for each divisor cg of B with nset * 4 * H * cg <= 1024 (one thread per sequence set, gate, column and unit): group sizes the default plan
+    never picks (it stops at 4), sizes that are no power of two, and the whole batch as one group.  Found here, by reading before running: the kernel's per-column tables held
+    four entries while build_program admitted groups up to 16 columns; they are sized by that bound now (DRQN_COLS_MAX_CG)."""
+    nset = 3 if dq else 2
+    assert groups == tuple(g for g in range(1, B + 1) if B % g == 0 and nset * 4 * H * g <= 1024)
+    c = _case(f"lstm_cols_h{H}_b{B}", "lstm", H, B, 3, None, double_q=dq)
+    default = default_plan_of(mods, c)
+    assert default[0][2] < 0 and -default[0][2] in groups, default
+    for cg in groups:
+        plan = [(p[0], p[1], -cg) for p in default]
+        if plan == default:
+            continue
+        c.name = f"lstm_cols_h{H}_b{B}_cg{cg}"
+        plan_case_checked(mods, c, plan, default, launched=("drqn_cols", "adam"))
+
+
+def test_column_group_beyond_the_workgroups_lds_is_refused_by_name(mods):
+    """a divisor of B the thread-count rule admits (2 * 4 * 8 * 16 = 1024) whose group does not fit one workgroup's LDS (T = 64 rows of 64 features for 16 columns, twice):
+    refused when the program is built, before anything is launched, with the group and the bytes named -- not left to a launch that cannot be configured"""
+    pkg, nn = mods
+    c = Case(name="lstm_cols_lds", mk=_one("lstm", 8, E=64), E=64, nA=3, B=16, T=64, gamma=0.95, double_q=0, mfma=1, graph=1, want=None, seed=7)
+    default = default_plan_of(mods, c)
+    assert all(p[2] == -1 for p in default), default      # the default plan's group fits
+    net, h, ring, *_ = make_engine(mods, c, plan=[(p[0], p[1], -16) for p in default])
+    with pytest.raises(pkg.DQNError, match=r"column-group dW chunks \(dw_kc = -16\): a group of 16 batch columns needs \d+ bytes of LDS"):
+        h.train_step_drqn(*draws(ring, c.B, np.random.default_rng(1)))
+    h.close()
+
+
+MULTI_LAUNCH_DW = [      # (case, dw_kc on every layer, a launch that must show)
+    (_case("lstm_h64_dw32", "lstm", 64, 8, 8, None), 32, "dw_wh_dense0"),       # T * B = 64 columns in chunks of 32: Wh | junk (65 x 256 > 16384) on the LDS-tiled dW, Wi | b and the head as VALU tasks
+    (_case("lstm_h16_dw24", "lstm", 16, 8, 8, None, graph=0), 24, "bwd_valu_dense0"),      # ragged: 24 + 24 + 16
+    (_case("gru_h16_dw10", "gru", 16, 6, 4, None), 10, "bwd_valu_dense0"),      # 24 columns: 10 + 10 + 4; the GRU's junk row is cleared in every slab
+    (_case("rnn_h32_dw32", "rnn", 32, 8, 8, None, act="tanh", mfma=0), 32, "bwd_valu_dense0"),
+]
+
+
+@pytest.mark.parametrize("c, kc, launch", MULTI_LAUNCH_DW, ids=[x[0].name for x in MULTI_LAUNCH_DW])
+def test_multi_launch_program_with_dw_chunks(mods, c, kc, launch):
+    """one LSTM, one GRU and one RNN network on the multi-launch recurrent program with dw_kc > 0: the T * B sample columns of every dW / db (Wi | b, Wh | junk, the head) in chunks"""
+    pkg, nn = mods
+    default = [(p[0], p[1], max(p[2], 0)) for p in default_plan_of(mods, c)]      # never the fused column step
+    plan = [(p[0], p[1], kc) for p in default]
+    plan_case_checked(mods, c, plan, default, launched=(launch,), twin=c.name.startswith("lstm"))
