@@ -20,6 +20,7 @@ LAYER_DROPOUT = 8                         # Flux Dropout(p): n_in == n_out == th
 ACT_IDENTITY, ACT_RELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
 ACT_LEAKYRELU, ACT_ELU, ACT_SELU, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_RELU6, ACT_HARDTANH = 4, 5, 6, 7, 8, 9, 10      # NNlib's default parameters only (include/dqn_mi355x.h has the table)
 LAYER_SKIPADD = 9                         # the join of a Flux SkipConnection(layers, +) block, placed directly AFTER its inner layers' descriptors: cin = m, their number; n_in == n_out == the feature count (or both 0); act IDENTITY, stream BASE; no parameters
+LAYER_GROUPNORM = 11                      # Flux GroupNorm(chs, G, act; eps) on a (c, h, w) map: cin == cout == chs (or both 0), kh = G, kw = the fp32 bit pattern of eps, n_in == n_out == c * h * w (or both 0); Flux.params holds beta (c), THEN gamma (c)
 LAYER_SKIPADD_MAP = 10                    # the join of a CONVOLUTIONAL SkipConnection(layers, +) block on a (c, h, w) map: SKIPADD's descriptor shape (cin = m; n_in == n_out == c * h * w or both 0); inner layers = Convs with pad != 0, entry = a Conv / pool / another such join
 STREAM_BASE, STREAM_VAL, STREAM_ADV = 0, 1, 2
 OBS_F32, OBS_U8 = 0, 1

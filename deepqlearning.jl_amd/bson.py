@@ -50,6 +50,8 @@ def julia_param_shapes(net):
             out += [((h, l.n_in), h * l.n_in), ((h, h), h * h), ((h,), h), ((h, 1), h)]
         elif l.kind == "layernorm":   # Flux 0.14 LayerNorm(n): diag = Scale(n): scale (n), then bias (n)
             out += [((l.n,), l.n), ((l.n,), l.n)]
+        elif l.kind == "groupnorm":   # Flux 0.14 GroupNorm(chs, G): β (chs), then γ (chs) -- bias first
+            out += [((l.chs,), l.chs), ((l.chs,), l.chs)]
         elif l.kind in ("maxpool", "meanpool", "dropout"):   # Flux.params(MaxPool / MeanPool / Dropout) is empty: the file holds no array for the layer
             continue
         else:

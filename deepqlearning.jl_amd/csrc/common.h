@@ -41,12 +41,17 @@ static inline __host__ __device__ bool is_recurrent(int kind) { return kind == D
 
 // Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
 static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
-static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP; }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow)
+// Flux GroupNorm(chs, G, act; eps) (groupnorm.hip) on the incoming (c, h, w) map, which it keeps: cin = cout = c, (oh, ow) = (ih, iw) = (h, w), npos = h * w; kh = G, kw = the fp32 bit
+// pattern of eps (0 = 1f-5: gn_eps); K = N = c and a parameter block of 2c floats, gamma at w_off, beta at b_off = w_off + c (layer_wn) -- Flux.params has beta FIRST, so the
+// EXTERNAL offsets are eb_off, then ew_off = eb_off + c (engine.hip).  Launched alone on its level, as pools and LayerNorm are
+static inline __host__ __device__ bool is_gn(int kind) { return kind == DQN_LAYER_GROUPNORM; }
+static inline float gn_eps(const LayerDev& L) { if (L.kw == 0) return 1e-5f; float f; memcpy(&f, &L.kw, sizeof f); return f; }
+static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP || is_gn(kind); }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow; a GroupNorm keeps the incoming one)
 // Flux LayerNorm (layernorm.hip): K = N = n features in and out, a parameter block of 2n floats (scale at w_off, bias at b_off = w_off + n -- NOT K * N weights: layer_wn),
 // the fp32 bit pattern of eps in cin (0 = 1f-5); launched alone on its level, as pools are
 static inline __host__ __device__ bool is_ln(int kind) { return kind == DQN_LAYER_LAYERNORM; }
 static inline float ln_eps(const LayerDev& L) { if (L.cin == 0) return 1e-5f; float f; memcpy(&f, &L.cin, sizeof f); return f; }
-static inline __host__ __device__ size_t layer_wn(const LayerDev& L) { return is_ln(L.kind) ? (size_t)L.N : (size_t)L.K * L.N; }      // floats in front of the layer's bias
+static inline __host__ __device__ size_t layer_wn(const LayerDev& L) { return (is_ln(L.kind) || L.kind == DQN_LAYER_GROUPNORM) ? (size_t)L.N : (size_t)L.K * L.N; }      // floats in front of the layer's bias (a GroupNorm's gamma)
 // Flux Dropout(p) (dropout.hip): parameter-free (K = N = 0 as a pool's), out_feat = in_feat = n; the Float64 bit pattern of p in (cin = low word, cout = high word).  Launched
 // alone on its level in the ONE active pass (online network, s columns of the train step); in every other pass it is the identity and costs nothing: the layer's target /
 // policy activation pointer IS its producer's (engine.hip), so its consumer reads the producer's output
@@ -76,11 +81,11 @@ struct KindTraits {
     bool output_ok;            // may be the network's output layer
     const char *a_noun, *plural;      // what the refusals call it (plain text, printed through %s); plural != null: single GPU only (dqn_comm_init and DQN_SIM_WORLD refuse the network)
 };
-enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
+enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
 static inline int kind_row(const LayerDev& L) {
     switch (L.kind) {
     case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: return KT_POOL;
-    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;
+    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;
     case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
     }
 }
@@ -92,6 +97,7 @@ static inline const KindTraits& kind_traits(const LayerDev& L) {
         /* KT_LN        */ {"ln",      true,     false,    false,     true,           true,             false, "a LayerNorm layer", "LayerNorm layers"},
         /* KT_DO        */ {"do",      true,     false,    false,     true,           true,             false, "a Dropout layer", "Dropout layers"},
         /* KT_SKIP      */ {"skip",    true,     false,    false,     true,           true,             false, "a skip block", "skip blocks"},
+        /* KT_GN        */ {"gn",      true,     false,    false,     true,           true,             false, "a GroupNorm layer", "GroupNorm layers"},
         /* KT_CONV      */ {"conv",    false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_DENSE     */ {"dense",   false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_RECURRENT */ {"dense",   false,    true,     false,     false,          false,            true,  nullptr, nullptr},      // named after its batched part, the dense view Gx = Wi*x (gx_view)
@@ -1098,6 +1104,21 @@ void launch_ln_fwd(hipStream_t st, const LayerDev& L, const float* P, const floa
 // dpre[n][B] = dY .* act'(y) (written by the layer above); X[n][ld] the layer's input (online net, s columns 0 .. B); stat[2][ld_stat] from the forward.
 // dX[n][B] = (gradient of the law) .* act_src'(X); g_scale[n], g_bias[n] = the column sums.  Two launches
 void launch_ln_bwd(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, float* dX, int act_src, float* g_scale, float* g_bias);
+// groupnorm.hip: Flux GroupNorm over the (c, h, w) map Y[feature][column]; a group is n_g = (c / G) * h * w contiguous rows, cut into chunks of GN_R rows.
+// part: workspace of gn_part_floats(L, ncols) floats (the chunks' (mean, M2)); stat (optional): [2 * G][ncols] floats, mu then r = 1 / sqrt(var + eps) per (group, column),
+// kept by the online pass for the backward.  Two launches: the chunk statistics, then the normalise pass
+#define GN_R 64
+static inline int gn_nchunks(const LayerDev& L) { const int ng = (L.cout / L.kh) * L.npos; return (ng + GN_R - 1) / GN_R; }
+static inline size_t gn_part_floats(const LayerDev& L, int ncols) { return (size_t)2 * L.kh * gn_nchunks(L) * ncols; }
+void launch_gn_stat(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* part);
+void launch_gn_norm(hipStream_t st, const LayerDev& L, const float* P, const float* X, int ldx, int col0, int ncols, float* Y /*[c * h * w][ncols]*/, const float* part, float* stat);
+// dpre[n][B] = dY .* act'(y) (written by the layer above); X[n][ld] the layer's input (online net, s columns 0 .. B); stat[2 * G][ld_stat] from the forward; part: gn_part_floats(L, B)
+// floats; rowp: 2 * n floats.  Four launches: the chunk sums of g and g * x_hat (g = dpre * gamma); dX[n][B] = (gradient of the law) .* act_src'(X); the row sums of dpre * x_hat
+// and dpre; their per-channel sums g_gamma[c], g_beta[c]
+void launch_gn_bwd_sums(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, float* part);
+void launch_gn_bwd_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, const float* part, float* dX, int act_src);
+void launch_gn_bwd_rows(hipStream_t st, const LayerDev& L, const float* dpre, const float* X, int ld, const float* stat, int ld_stat, int B, float* rowp);
+void launch_gn_bwd_par(hipStream_t st, const LayerDev& L, const float* rowp, float* g_gamma, float* g_beta);
 // dropout.hip: the ACTIVE pass of a Dropout layer.  X, Y: [n][ld], the first C columns get the mask of train step k = st->step (read on the device: graphs and
 // dqn_train_steps replay it; the step's TD launch has not bumped it yet), the columns C .. ncols are copied; layer: the layer's index (the counter's tag)
 void launch_do_fwd(hipStream_t stream, int n, double p, unsigned long long seed, int layer, const StepState* st, const float* X, float* Y, int ld, int ncols, int C);

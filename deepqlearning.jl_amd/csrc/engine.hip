@@ -62,7 +62,7 @@ extern "C" int dqn_hparams_default(dqn_hparams* hp) {
 }
 
 // THE single-GPU rule: the exchange paths (operand all-gather, all-reduce) have never run with an own-level kind's launches in the program -- refused instead of claimed.
-// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
+// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block, GroupNorm), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
 static int refuse_replicas(const char* who, const LayerDev* L, int nl) {
     for (int r = 0; r < KT_OWN_LEVEL; r++) for (int i = 0; i < nl; i++) {
         const KindTraits& t = kind_traits(L[i]); if (kind_row(L[i]) != r || !t.plural) continue;
@@ -113,6 +113,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_ln(l.kind)) {      // Flux LayerNorm(n, act; affine = true, eps) (layernorm.hip): per column over the n incoming features; K = N = n, parameters scale (n), bias (n)
             if (prev < 0) return fail("layer %d: LayerNorm cannot be the first layer (it must directly follow a Dense or recurrent layer)", i);
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: LayerNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (is_gn(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (has_map(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (is_ln(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a LayerNorm layer)", i, prev);
             if (d[i].n_in != d[i].n_out) return fail("layer %d: LayerNorm n_in %d != n_out %d (both carry the size n)", i, d[i].n_in, d[i].n_out);
@@ -123,9 +124,25 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             l.cin = d[i].cin;      // the fp32 bit pattern of eps, 0 = the default 1f-5 (ln_eps)
             { const float eps = ln_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: LayerNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].cin); }
             l.K = l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (is_gn(l.kind)) {      // Flux GroupNorm(chs, G, act; eps) (groupnorm.hip): per column and group of c / G contiguous channels of the incoming (c, h, w) map, which it keeps; K = N = c, parameters beta (c), gamma (c)
+            if (prev < 0) return fail("layer %d: GroupNorm cannot be the first layer (normalising the observation is not supported; it must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block)", i);
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: GroupNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (!has_map(L[prev].kind)) return fail("layer %d: GroupNorm must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block (layer %d is %s, whose output is no (c, h, w) map)", i, prev,
+                                                    L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer");
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: GroupNorm activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
+            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: GroupNorm chs (cin %d / cout %d) != incoming channels %d", i, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: GroupNorm n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: GroupNorm size n = %d != incoming features %d * %d * %d = %d", i, d[i].n_in, c, h, w, l.in_feat);
+            if (d[i].sh || d[i].sw) return fail("layer %d: GroupNorm uses cin, cout, kh (the group count G), kw (the bit pattern of eps), n_in, n_out and act only; sh / sw = %d / %d must be 0", i, d[i].sh, d[i].sw);
+            if (d[i].kh < 1 || c % d[i].kh) return fail("layer %d: GroupNorm G = %d must be >= 1 and divide the channel count %d", i, d[i].kh, c);
+            if ((long long)(c / d[i].kh) * h * w < 2) return fail("layer %d: GroupNorm(%d, %d) on a (%d, %d, %d) map normalises over n_g = %d element (n_g must be >= 2: over one element the variance is identically 0 and the output is constant)", i, c, d[i].kh, c, h, w, (c / d[i].kh) * h * w);
+            l.cin = l.cout = c; l.kh = d[i].kh; l.kw = d[i].kw;      // G, and the fp32 bit pattern of eps, 0 = the default 1f-5 (gn_eps)
+            { const float eps = gn_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: GroupNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].kw); }
+            l.ih = l.oh = h; l.iw = l.ow = w; l.K = l.N = c; l.npos = h * w; l.out_feat = l.in_feat;
         } else if (is_do(l.kind)) {      // Flux Dropout(p), dims = : (dropout.hip): per element of the n incoming features; no parameters (K = N = 0 as a pool's), p's Float64 bits in (cin, cout)
             if (prev < 0) return fail("layer %d: Dropout cannot be the first layer (it must directly follow a Dense, recurrent or LayerNorm layer; dropout on the observation is not supported)", i);
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Dropout layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (is_gn(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (has_map(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (is_do(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Dropout layer)", i, prev);
             if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: Dropout has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
@@ -150,7 +167,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                 if (is_pool(L[j].kind)) return fail("layer %d: the convolutional skip block holds a MaxPool / MeanPool layer (layer %d); its inner layers are Conv layers with pad != 0 only", i, j);
                 if (L[j].kind == DQN_LAYER_CONV && !is_padded(L[j])) return fail("layer %d: the convolutional skip block holds a Conv with pad 0 (layer %d, kernel (%d, %d)); its inner layers are Conv layers with pad != 0 only", i, j, L[j].kh, L[j].kw);
                 if (L[j].kind != DQN_LAYER_CONV) return fail("layer %d: the convolutional skip block holds %s (layer %d); its inner layers are Conv layers with pad != 0 only", i,
-                                                             is_recurrent(L[j].kind) ? "a recurrent layer" : is_ln(L[j].kind) ? "a LayerNorm layer" : is_do(L[j].kind) ? "a Dropout layer" : "a Dense layer", j);
+                                                             is_recurrent(L[j].kind) ? "a recurrent layer" : is_ln(L[j].kind) ? "a LayerNorm layer" : is_do(L[j].kind) ? "a Dropout layer" : is_gn(L[j].kind) ? "a GroupNorm layer" : "a Dense layer", j);
             }
             const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
             if (pp < 0) return fail("layer %d: the convolutional skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block)", i, i - m);
@@ -172,10 +189,12 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                 if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
                 if (is_skip(L[j].kind)) return fail("layer %d: the skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
                 if (is_recurrent(L[j].kind)) return fail("layer %d: the skip block holds a recurrent layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only", i, j);
+                if (is_gn(L[j].kind)) return fail("layer %d: the skip block holds a GroupNorm layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (GroupNorm inside a skip block is not supported)", i, j);
                 if (has_map(L[j].kind)) return fail("layer %d: the skip block holds a Conv / MaxPool / MeanPool layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (convolutional residual blocks are not supported)", i, j);
             }
             const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
             if (pp < 0) return fail("layer %d: the skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the output of a Dense, recurrent, LayerNorm or Dropout layer or of another skip block)", i, i - m);
+            if (is_gn(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a GroupNorm layer); a skip block stands on a feature vector", i, pp);
             if (has_map(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a Conv / MaxPool / MeanPool layer); a skip block stands on a feature vector (convolutional residual blocks are not supported)", i, pp);
             if (L[prev].out_feat != L[pp].out_feat) return fail("layer %d: the skip block maps %d features to %d; SkipConnection(layers, +) needs layers: n -> n", i, L[pp].out_feat, L[prev].out_feat);
             if (d[i].n_in != d[i].n_out) return fail("layer %d: skip block n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
@@ -203,7 +222,8 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             l.h0_off = off; off += l.H; if (has_c) { l.c0_off = off; off += l.H; } off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
         } else {
             const size_t wn = layer_wn(l);      // K * N weights; a LayerNorm's scale vector (N)
-            l.ew_off = eoff; eoff += wn; l.eb_off = eoff; eoff += l.N;
+            if (is_gn(l.kind)) { l.eb_off = eoff; eoff += l.N; l.ew_off = eoff; eoff += wn; }      // Flux.params of a GroupNorm: beta, THEN gamma
+            else { l.ew_off = eoff; eoff += wn; l.eb_off = eoff; eoff += l.N; }
             off = (off + 3) / 4 * 4; l.w_off = off; off += wn; l.b_off = off; off += l.N;
         }
         if (l.stream == DQN_STREAM_BASE) *lb = i; else if (l.stream == DQN_STREAM_VAL) *lv = i; else *la = i;
@@ -412,6 +432,7 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
         const size_t sw = dqn_nchunks(l.npos * Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
         const size_t sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
         jmax = std::max(jmax, (size_t)l.in_feat * Bc);
+        if (is_gn(l.kind)) pmax = std::max(pmax, gn_part_floats(l, e->ncon));      // the chunk statistics of the launches outside the train program (launch_layer_fwd)
         if (is_recurrent(l.kind)) {
             // gates, tcb (CellSeq::aux) and dcn (CellBwdArgs::dh2) belong to the cells with a gate stash: the RNN's BPTT reads h_t back from act_on and has one gate gradient
             const CellOps* C = cell_ops(l.kind);
@@ -701,6 +722,7 @@ void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const f
     if (is_do(l.kind)) return;      // inactive everywhere but the train step's online pass on s (emit_forward): the identity, and Y IS X (the layer's activation aliases its producer's)
     if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
+    else if (is_gn(l.kind)) { launch_gn_stat(st, l, X, ldx, col0, ncols, partials); launch_gn_norm(st, l, P, X, ldx, col0, ncols, Y, partials, ln_stat); }      // partials: >= gn_part_floats(l, ncols) floats
     else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
     else if (!(use_mfma && launch_mfma_fwd(st, l, P, X, ldx, col0, ncols, Y, partials))) launch_valu_fwd(st, l, P, X, ldx, col0, ncols, Y, partials);
 }
@@ -1134,7 +1156,7 @@ int policy_ws(dqn_engine* e, int n) {
     if (n <= e->pol_n) return 0;
     HIPCHK(hipStreamSynchronize(e->stream)); free_policy_ws(e); drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
     size_t need = 1;   // split-K partials of the widest forward at n columns
-    for (int i = 0; i < e->nl; i++) { const size_t sf = dqn_nchunks(e->L[i].K, e->L[i].fwd_kc); if (sf > 1) need = std::max(need, sf * (size_t)e->L[i].out_feat * n); }
+    for (int i = 0; i < e->nl; i++) { const size_t sf = dqn_nchunks(e->L[i].K, e->L[i].fwd_kc); if (sf > 1) need = std::max(need, sf * (size_t)e->L[i].out_feat * n); if (is_gn(e->L[i].kind)) need = std::max(need, gn_part_floats(e->L[i], n)); }
     if (need > e->partials_elems) { drop_graphs(e); hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * need); e->partials_elems = need; }
     DM(e->pol_obs, (size_t)n * e->E); DM(e->pol_x, (size_t)n * e->E); DM(e->pol_q, (size_t)n * e->nA); DM(e->pol_a, n);
     for (int i = 0; i < e->nl; i++) { if (is_do(e->L[i].kind)) e->pol_act[i] = e->pol_act[e->L[i].src]; else DM(e->pol_act[i], (size_t)e->L[i].out_feat * n); }      // Dropout: inactive when acting, the producer's output

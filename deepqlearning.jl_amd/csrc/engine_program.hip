@@ -76,6 +76,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
         if (kind_traits(e->L[lv[0]]).own_level) {
             // a layer launched alone on its level (base chain only): one launch per pass it is active in, never grouped with a GEMM layer.  Per kind:
             //   a pool (pool.hip), a padded conv (conv_pad.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
+            //   a GroupNorm layer (groupnorm.hip): every pass, TWO launches, "<pass>_gn<l>_stat" and "<pass>_gn<l>"; the first pass keeps (mu, r) per (group, column) for the backward
             //   the join of a skip block (skip.hip): every pass, y = (the last inner layer's stored output) + (the stored output of the block's entry, LayerDev::src2) on that pass's
             //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
             //   a Dropout layer (dropout.hip): ACTIVE in the first pass of the train step only, on its leading E.do_cols columns (online network, s): it writes a buffer of its own -- the producer's output
@@ -87,6 +88,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             const int jn = is_padded(L) ? skip_join_of_last(e, l) : -1; const bool fuse_res = jn >= 0 && skip_fused_fwd(e, jn);
             const bool fused_join = join && skip_fused_fwd(e, l);
             float* stat0 = (is_ln(L.kind) && E.ln_stat) ? (E.ln_stat[l] = palloc(e, (size_t)2 * passes[0].ncols)) : nullptr;
+            if (is_gn(L.kind) && E.ln_stat) stat0 = E.ln_stat[l] = palloc(e, (size_t)2 * L.kh * passes[0].ncols);      // (mu, r) per (group, column)
             for (int pi = 0; pi < np; pi++) {
                 const Prob q = prob(l, pi);
                 HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = (dropout || join) ? nullptr : q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;      // (a Dropout layer, a join: no parameters, IDENTITY)
@@ -103,6 +105,13 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
                     continue;
                 }
                 float* stat = pi == 0 ? stat0 : nullptr; const float* X2 = join ? passes[pi].in[L.src2] : nullptr;
+                if (is_gn(L.kind)) {      // two launches (groupnorm.hip): the chunk statistics into a workspace of the pass's own, then the normalise pass, which combines them per workgroup
+                    float* part = palloc(e, gn_part_floats(L, q.ncols));
+                    char nm[64]; snprintf(nm, sizeof nm, "%s_%s%d_stat", passes[pi].tag, kind_traits(L).tag, l); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
+                    prog.push_back({name, [=](dqn_engine* en) { launch_gn_stat(en->stream, L, q.X, q.ldx, q.col0, q.ncols, part); }});
+                    prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_gn_norm(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, part, stat); }});
+                    continue;
+                }
                 prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_layer_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, q.Y, mf, L.xu8, stat, nullptr, X2, q.ncols); }});
             }
             continue;
@@ -539,6 +548,23 @@ int build_program(dqn_engine* e) {
             // that layer's own, unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation
             const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state;
             e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_do_bwd(en->stream, L.out_feat, p, seed, l, stt, dpre, Ysrc, ncon, B, out, act_src); }});
+        } else if (is_gn(L.kind)) {
+            // four launches (groupnorm.hip): the chunk sums of g and g * x_hat, dX with the producing layer's activation derivative (neither where the input reaches the observation
+            // through pool layers only: nobody reads it), the row sums of dpre * x_hat and dpre, and their per-channel sums dgamma / dbeta straight into the flat gradient, which
+            // the Adam launch reads like any bias range
+            const float* P = e->p_on; const float* stat = ln_stat[l]; float *gg = e->grad + L.w_off, *gb = e->grad + L.b_off;
+            if (wants_dx(l)) {
+                float* part = palloc(e, gn_part_floats(L, B));
+                char nm[64]; snprintf(nm, sizeof nm, "bwd_%s%d_sums", kind_traits(L).tag, l); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
+                e->prog.push_back({name, [=](dqn_engine* en) { launch_gn_bwd_sums(en->stream, L, P, dpre, X, ncon, stat, ncon, B, part); }});
+                e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_gn_bwd_dx(en->stream, L, P, dpre, X, ncon, stat, ncon, B, part, out, act_src); }});
+            }
+            float* rowp = palloc(e, (size_t)2 * L.out_feat);
+            for (const char* piece : {"rows", "par"}) {
+                char nm[64]; snprintf(nm, sizeof nm, "bwd_%s%d_%s", kind_traits(L).tag, l, piece); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
+                if (piece[0] == 'r') e->prog.push_back({name, [=](dqn_engine* en) { launch_gn_bwd_rows(en->stream, L, dpre, X, ncon, stat, ncon, B, rowp); }});
+                else e->prog.push_back({name, [=](dqn_engine* en) { launch_gn_bwd_par(en->stream, L, rowp, gg, gb); }});
+            }
         } else if (is_ln(L.kind)) {
             // two launches (layernorm.hip): dX with the producing layer's activation derivative -- a recurrent producer's `act` is IDENTITY, so its dact is the cell's dH -- and the
             // column sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation

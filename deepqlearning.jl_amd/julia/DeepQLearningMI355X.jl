@@ -55,8 +55,8 @@ check(rc) = rc == 0 ? nothing : throw(unsafe_string(ccall((:dqn_last_error, LIB)
 const ACT = Dict(identity => 0, relu => 1, tanh => 2, sigmoid => 3, leakyrelu => 4, elu => 5, selu => 6, softplus => 7, softsign => 8, relu6 => 9, hardtanh => 10)
 const ACT_SUPPORTED = "identity / relu / tanh / sigmoid / leakyrelu / elu / selu / softplus / softsign / relu6 / hardtanh"
 const ACT_NEEDS_X = (gelu, swish, mish, hardswish)      # not monotone: the derivative is no function of the output
-# the activation a layer carries: σ of a Dense / Conv / RNN cell, λ of a LayerNorm; nothing for the layers without one
-layer_act(l) = (l isa Dense || l isa Conv) ? l.σ : l isa Flux.LayerNorm ? l.λ : (l isa Flux.Recur && l.cell isa Flux.RNNCell) ? l.cell.σ : nothing
+# the activation a layer carries: σ of a Dense / Conv / RNN cell, λ of a LayerNorm / GroupNorm; nothing for the layers without one
+layer_act(l) = (l isa Dense || l isa Conv) ? l.σ : (l isa Flux.LayerNorm || l isa Flux.GroupNorm) ? l.λ : (l isa Flux.Recur && l.cell isa Flux.RNNCell) ? l.cell.σ : nothing
 # the one check of a layer's activation: lower_layer calls it first, so that every ACT[...] lookup below it is a hit (a bare lookup died on a KeyError with no explanation).
 # Throws the DeepQLearningError that names what is supported, and why the rest is not
 function check_act(l)
@@ -89,6 +89,12 @@ function lower_layer(l, stream)::LayerDesc
         length(l.size) == 1 || throw("DeepQLearningError: the MI355X engine supports LayerNorm(n) with an integer n only, got size=$(l.size)")
         (l.affine && l.diag isa Flux.Scale) || throw("DeepQLearningError: the MI355X engine supports LayerNorm with affine=true only")
         return LayerDesc(7, ACT[l.λ], stream, l.size[1], l.size[1], reinterpret(Int32, Float32(l.ϵ)), 0, 0, 0, 0, 0)
+    elseif l isa Flux.GroupNorm      # Flux 0.14 fields G, λ, β, γ, μ, σ², ϵ, momentum, chs, affine, track_stats, active; Flux.params order β, γ (bias FIRST) == the ABI's GroupNorm block
+        # _norm_layer_forward: (x .- μ) ./ sqrt.(σ² .+ ϵ) with the uncorrected σ² per sample and group of chs / G contiguous channels: ϵ INSIDE the root (not LayerNorm's σ + ϵ).
+        # cin = cout = chs, kh = G, the Float32 bit pattern of ϵ in kw; n_in = n_out = 0: the engine takes the feature count of the incoming map
+        l.affine || throw("DeepQLearningError: the MI355X engine supports GroupNorm with affine=true only")
+        l.track_stats && throw("DeepQLearningError: the MI355X engine supports GroupNorm with track_stats=false only (it keeps no running statistics: every pass normalises with the statistics of its own input)")
+        return LayerDesc(11, ACT[l.λ], stream, 0, 0, l.chs, l.chs, l.G, reinterpret(Int32, Float32(l.ϵ)), 0, 0)
     elseif l isa Flux.Dropout      # Flux 0.14 fields p, dims, active, rng; no parameters (Flux.params skips the layer)
         # automatic mode (active === nothing): the layer is active only under Flux.gradient -- the engine masks the online forward on s and nothing else.  A forced mode
         # (trainmode! / testmode!) is not the reference's behaviour.  p crosses as its Float64 bit pattern, low word in cin, high word in cout (Float32(0.1) would move
@@ -104,8 +110,10 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ (the engine accepts the first four codes there)
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
+    l isa Flux.BatchNorm && throw("DeepQLearningError: BatchNorm is not supported: it keeps running statistics, so the online pass on s, the pass on s', the target pass and the acting pass would compute different functions; of Flux's normalisation layers the MI355X engine runs LayerNorm(n) and GroupNorm(chs, G)")
+    l isa Flux.InstanceNorm && throw("DeepQLearningError: InstanceNorm is not supported: its default is affine = false, which the MI355X engine does not run; GroupNorm(chs, chs) is instance normalisation with a per-channel affine")
     l isa Flux.Parallel && throw("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (SkipConnection(+) / Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 # Flux 0.14 SkipConnection(layers, connection), fields layers, connection: layers(x) .+ x for connection === +.  No parameters of its own (Flux.params yields the inner
@@ -116,7 +124,7 @@ is_glue(l) = l === identity || l === flattenbatch || l isa Function
 # The CONVOLUTIONAL block, x + Conv(Conv(x)): where the descriptor in front is a Conv, a pool or the join of another such block (kinds 1, 5, 6, 10) and every inner layer
 # is a Conv or a pool, the join is of kind 10 -- the same descriptor shape.  Its inner layers are Convs with pad != 0 that keep the channel count; a pool, a pad-0 Conv and
 # a channel change are refused here by name, that the block keeps (h, w) is the engine's check
-is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10
+is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10 || d.kind == 11      # (11: a GroupNorm keeps the incoming map)
 is_map_layer(x) = x isa Conv || x isa Flux.MaxPool || x isa Flux.MeanPool
 function lower_skip_map!(descs, l, stream, inner)
     m = 0; c_in = 0; c_out = 0
@@ -134,6 +142,7 @@ function lower_skip!(descs, l, stream)
     l.connection === (+) || throw("DeepQLearningError: SkipConnection(layers, $(l.connection)) is not supported; the MI355X engine runs SkipConnection with the connection + only (vcat, *, closures and Parallel are not supported)")
     inner = l.layers isa Flux.Chain ? collect(l.layers.layers) : Any[l.layers]
     real = filter(!is_glue, inner)
+    any(x -> x isa Flux.GroupNorm, real) && throw("DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block)")
     if !isempty(descs) && is_map_desc(descs[end]) && !isempty(real) && all(is_map_layer, real)
         return lower_skip_map!(descs, l, stream, inner)
     end

@@ -176,6 +176,53 @@ class LayerNorm:
         return [(self.n,), (self.n,)]
 
 
+class GroupNorm:
+    """Flux 0.14 GroupNorm(chs, G, λ = identity; affine = true, track_stats = false, eps = 1f-5) on a (w, h, chs, batch) map (Flux's `_norm_layer_forward`; recalled, not
+    executed here): the channels form G contiguous groups of chs / G; per sample and group μ = mean(x), σ² = mean((x - μ)²) (uncorrected),
+    y = λ.(γ_ch .* (x - μ) / sqrt(σ² + eps) .+ β_ch) -- eps INSIDE the root (torch's law, not LayerNorm's σ + eps).  Flux.params: β (chs, zeros), THEN γ (chs, ones).
+    Directly behind a Conv, a MaxPool / MeanPool, a convolutional SkipConnection or another GroupNorm; base chain only, never the first or the output layer."""
+    kind = "groupnorm"
+
+    def __init__(self, chs, G, act=identity, eps=1e-5, affine=True, track_stats=False):
+        if not affine:
+            raise _abi.DQNError(f"DeepQLearningError: GroupNorm({chs}, {G}; affine=false) is not supported; the MI355X engine runs the layer with its γ and β (affine=true)")
+        if track_stats:
+            raise _abi.DQNError(f"DeepQLearningError: GroupNorm({chs}, {G}; track_stats=true) is not supported; the MI355X engine keeps no running statistics "
+                                "(every pass normalises with the statistics of its own input: track_stats=false, Flux 0.14's default)")
+        self.chs, self.G, self.act, self.eps = int(chs), int(G), act, float(eps)
+        if self.G < 1 or self.chs < 1 or self.chs % self.G:
+            raise _abi.DQNError(f"DeepQLearningError: GroupNorm({self.chs}, {self.G}): the number of groups G must be >= 1 and divide the channel count")
+        with np.errstate(over="ignore"):
+            e32 = np.float32(self.eps)
+        if not (np.isfinite(e32) and e32 > 0):
+            raise _abi.DQNError(f"DeepQLearningError: GroupNorm({self.chs}, {self.G}; eps={eps!r}): eps must be finite and > 0 in Float32")
+
+    def __repr__(self):
+        return f"GroupNorm({self.chs}, {self.G}, act={self.act}, eps={self.eps!r})"
+
+    def shapes(self):   # Flux.params order: β, γ
+        return [(self.chs,), (self.chs,)]
+
+
+class BatchNorm:
+    """Flux BatchNorm: named so that the refusal can name it; the MI355X engine does not run it."""
+    kind = "batchnorm"
+
+    def __init__(self, *args, **kwargs):
+        raise _abi.DQNError("DeepQLearningError: BatchNorm is not supported: it keeps running statistics, so the online pass on s, the pass on s', the target pass and the acting "
+                            "pass would compute different functions; of Flux's normalisation layers the MI355X engine runs LayerNorm(n) and GroupNorm(chs, G) (GroupNorm(chs, 1) "
+                            "normalises the whole map)")
+
+
+class InstanceNorm:
+    """Flux InstanceNorm: named so that the refusal can name it; the MI355X engine does not run it."""
+    kind = "instancenorm"
+
+    def __init__(self, *args, **kwargs):
+        raise _abi.DQNError("DeepQLearningError: InstanceNorm is not supported: its default is affine = false (no γ, β), which the MI355X engine does not run; "
+                            "GroupNorm(chs, chs) is instance normalisation with a per-channel affine")
+
+
 class Dropout:
     """Flux 0.14 Dropout(p; dims = :) on a feature vector, per batch column, in Flux's automatic mode (recalled, not executed here): active only under Flux.gradient --
     in the train step's online forward on s, y = keep ? x * Float32(1 / (1 - p)) : 0 -- and the identity in every other pass (online on s', target, acting, evaluation,
@@ -334,7 +381,9 @@ def lower(net):
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} is supported in the base chain only (not in a value / advantage stream)")
         if first:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the first layer: a skip block's input is never the observation (it must follow a Dense, recurrent, LayerNorm or Dropout layer or another skip block)")
-        on_map = prev_kind in ("conv", "maxpool", "meanpool") or (prev_kind == "skip" and map_join[0])
+        if any(getattr(l, "kind", None) == "groupnorm" for l in blk.layers):
+            raise _abi.DQNError(f"DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block): {blk!r}")
+        on_map = prev_kind in ("conv", "maxpool", "meanpool", "groupnorm") or (prev_kind == "skip" and map_join[0])
         if on_map and not first and all(getattr(l, "kind", None) in ("conv", "maxpool", "meanpool") for l in blk.layers):
             return add_skip_map(blk, stream, is_last)
         if on_map:
@@ -391,8 +440,8 @@ def lower(net):
             if getattr(l, "kind", None) == "skip":
                 add_skip(l, stream, not out, getattr(layers[i - 1], "kind", None) if i > 0 else None, i + 1 == len(layers) and chain is top)
                 continue
-            if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "layernorm"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (SkipConnection(+) / Conv / MaxPool / MeanPool / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "groupnorm", "layernorm"):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
             d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -405,6 +454,15 @@ def lower(net):
             elif l.kind == "layernorm":      # n in both size slots; the fp32 bit pattern of eps rides in cin (as a Conv's pad rides in n_in / n_out)
                 d.kind, d.n_in, d.n_out = _abi.LAYER_LAYERNORM, l.n, l.n
                 d.cin = int(np.float32(l.eps).view(np.int32))
+            elif l.kind == "groupnorm":      # cin == cout == chs, kh = G, the fp32 bit pattern of eps in kw; n_in == n_out == 0: the engine fills in c * h * w
+                if not out:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the first layer: normalising the observation is not supported (it must follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional SkipConnection)")
+                if stream != _abi.STREAM_BASE:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+                if i + 1 == len(layers) and chain is top:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                d.kind, d.cin, d.cout, d.kh = _abi.LAYER_GROUPNORM, l.chs, l.chs, l.G
+                d.kw = int(np.float32(l.eps).view(np.int32))
             elif l.kind == "dropout":      # n_in == n_out == 0: the engine fills in the incoming feature count; p crosses as its Float64 bit pattern, low word in cin, high in cout
                 bits = int(np.float64(l.p).view(np.uint64))
                 d.kind = _abi.LAYER_DROPOUT
@@ -451,6 +509,9 @@ def glorot_params(net, seed=1):
     parts = []
     for l in all_layers(net):
         if l.kind in ("maxpool", "meanpool", "dropout"):      # no parameters
+            continue
+        if l.kind == "groupnorm":      # β = zeros, then γ = ones
+            parts += [np.zeros(l.chs, np.float32), np.ones(l.chs, np.float32)]
             continue
         if l.kind == "layernorm":      # Flux Scale(n): scale = ones, bias = zeros
             parts += [np.ones(l.n, np.float32), np.zeros(l.n, np.float32)]

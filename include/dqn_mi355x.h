@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -90,6 +90,13 @@ typedef struct {
                                           mu = mean(x), sigma = sqrt(mean((x - mu)^2)), y = act(scale * (x - mu) / (sigma + eps) + bias): eps is added to sigma OUTSIDE the root (not torch's
                                           sqrt(var + eps)).  Parameters in Flux.params order: scale (n), bias (n).  Directly behind a Dense or recurrent layer (or the Dropout layer that follows one), base chain only, never the
                                           output layer, single GPU only; its plan entry is ignored.  A column with sigma = 0 has a finite forward (x_hat = 0); its backward is undefined;
+                                          GroupNorm(chs, G, act; affine = true, track_stats = false, eps) (Flux 0.14 `_norm_layer_forward`, recalled, not executed) on the incoming
+                                          (c, h, w) map: cin == cout == chs == c (or both 0: the engine fills them in), kh = G >= 1 with c % G == 0 and (c / G) * h * w >= 2, kw = the fp32
+                                          BIT PATTERN of eps (0 = the default 1f-5; finite and > 0), n_in == n_out == c * h * w (or both 0), act = the layer's activation (any of the eleven),
+                                          stream = BASE, sh = sw = 0.  Per batch column and group of c / G contiguous channels: mu = mean(x), var = mean((x - mu)^2),
+                                          y = act(gamma_ch * (x - mu) / sqrt(var + eps) + beta_ch): eps INSIDE the root (torch's law, not LayerNorm's).  Parameters in Flux.params order:
+                                          beta (c, zeros), gamma (c, ones) -- bias FIRST.  Directly behind a Conv, a MaxPool / MeanPool, a convolutional skip block or another GroupNorm; base
+                                          chain only, never the first or the output layer, not inside a skip block, single GPU only; its plan entry is all zeros and ignored;
                                           Dropout(p), dims = : (Flux 0.14 automatic mode, recalled, not executed): n_in == n_out == the incoming feature count (or both 0: the engine fills them
                                           in), act = IDENTITY, stream = BASE, p as its Float64 BIT PATTERN, low word in cin, high word in cout (finite, 0 <= p < 1), every other slot 0.
                                           No parameters (Flux.params skips the layer); its plan entry is all zeros and ignored.  ACTIVE only in the online network's pass on the s columns
