@@ -40,7 +40,13 @@ struct LayerDev {
 static inline __host__ __device__ bool is_recurrent(int kind) { return kind == DQN_LAYER_LSTM || kind == DQN_LAYER_GRU || kind == DQN_LAYER_RNN; }
 
 // Flux MaxPool / MeanPool (pool.hip): parameter-free (K = N = 0: no weights, no plan), cin = cout = channels, a (cout, oh, ow) map out like a convolution's
-static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL; }
+// Flux AdaptiveMaxPool / AdaptiveMeanPool and GlobalMaxPool / GlobalMeanPool (kinds 12 / 13): the descriptor carries the OUTPUT size; build_layers resolves (kh, kw, sh, sw) from the
+// incoming map (stride = in / out, k = in - (out - 1) * stride), and from there on the layer IS a pool with that geometry.  Where the resolved window is the whole map (oh = ow = 1) the
+// launches are pool_global.hip's (is_global_pool), otherwise pool.hip's; kinds 5 / 6 keep pool.hip for every geometry
+static inline __host__ __device__ bool is_adaptive_pool(int kind) { return kind == DQN_LAYER_ADAPTIVEMAXPOOL || kind == DQN_LAYER_ADAPTIVEMEANPOOL; }
+static inline __host__ __device__ bool is_pool(int kind) { return kind == DQN_LAYER_MAXPOOL || kind == DQN_LAYER_MEANPOOL || is_adaptive_pool(kind); }
+static inline __host__ __device__ bool is_mean_pool(int kind) { return kind == DQN_LAYER_MEANPOOL || kind == DQN_LAYER_ADAPTIVEMEANPOOL; }
+static inline bool is_global_pool(const LayerDev& L) { return is_adaptive_pool(L.kind) && L.oh == 1 && L.ow == 1; }
 // Flux GroupNorm(chs, G, act; eps) (groupnorm.hip) on the incoming (c, h, w) map, which it keeps: cin = cout = c, (oh, ow) = (ih, iw) = (h, w), npos = h * w; kh = G, kw = the fp32 bit
 // pattern of eps (0 = 1f-5: gn_eps); K = N = c and a parameter block of 2c floats, gamma at w_off, beta at b_off = w_off + c (layer_wn) -- Flux.params has beta FIRST, so the
 // EXTERNAL offsets are eb_off, then ew_off = eb_off + c (engine.hip).  Launched alone on its level, as pools and LayerNorm are
@@ -84,7 +90,7 @@ struct KindTraits {
 enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
 static inline int kind_row(const LayerDev& L) {
     switch (L.kind) {
-    case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: return KT_POOL;
+    case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: case DQN_LAYER_ADAPTIVEMAXPOOL: case DQN_LAYER_ADAPTIVEMEANPOOL: return KT_POOL;
     case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;
     case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
     }
@@ -1133,6 +1139,10 @@ void launch_skip_bwd_join(hipStream_t stream, int n, const float* dY, const floa
 void launch_skip_bwd_entry(hipStream_t stream, int n, const float* dF, const float* dY, const float* Yp, int ld, int B, float* dP, int act_p);
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_feat][B]*/, const float* X /* the pool's input */, const float* Y /* its output */, int ld /* of X and Y */, int B,
                      float* dX /*[in_feat][B]*/, int act_src);
+// pool_global.hip: a pool whose window is the whole (h, w) map (is_global_pool): one workgroup per (channel, column tile) reduces the channel's n = h * w rows.  Y[c][ncols];
+// the backward recomputes the MaxPool's first maximal row from X (nothing is stashed) and applies the producing layer's activation derivative
+void launch_gpool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[c][ncols]*/);
+void launch_gpool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[c][B]*/, const float* X /* the pool's input */, int ld /* of X */, int B, float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');
 // mf = hp.use_mfma (MFMA tiles where the shape allows, the same bits either way); xu8: X is the byte arena of a u8 replay
 // R (or null): the residual operand of a map block's fused join, [out_feat][ldr] read on the columns rcol0 .. rcol0 + ncols: Y = act(tot + bias) + R

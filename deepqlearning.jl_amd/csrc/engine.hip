@@ -99,6 +99,19 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
             l.ih = h; l.iw = w; l.oh = (h + 2 * l.ph - l.kh) / l.sh + 1; l.ow = (w + 2 * l.pw - l.kw) / l.sw + 1;      // trailing rows / columns of the extended map no window covers are dropped
             l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
+        } else if (is_adaptive_pool(l.kind)) {      // Flux AdaptiveMaxPool / AdaptiveMeanPool((ow, oh)), GlobalMaxPool / GlobalMeanPool (output (1, 1)): kh, kw carry the OUTPUT size; resolved here into a pool's geometry
+            const char* nm = l.kind == DQN_LAYER_ADAPTIVEMAXPOOL ? "AdaptiveMaxPool" : "AdaptiveMeanPool";
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, nm, l.stream);
+            if (prev >= 0 && !has_map(L[prev].kind)) return fail("layer %d: %s must be the first layer or follow a layer whose output is a (c, h, w) map (layer %d is %s, whose output is a feature vector of %d)", i, nm, prev,
+                                                                 L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer", L[prev].out_feat);
+            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
+            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
+            if (d[i].sh || d[i].sw || d[i].n_in || d[i].n_out) return fail("layer %d: %s uses cin, cout, kh and kw (the OUTPUT size (oh, ow)) only; sh / sw / n_in / n_out = %d / %d / %d / %d must be 0", i, nm, d[i].sh, d[i].sw, d[i].n_in, d[i].n_out);
+            if (d[i].kh < 1 || d[i].kw < 1) return fail("layer %d: %s output size (%d, %d) must be at least (1, 1)", i, nm, d[i].kh, d[i].kw);
+            if (d[i].kh > h || d[i].kw > w) return fail("layer %d: %s output size (%d, %d) is larger than the %dx%d input map (the adaptive rule needs 1 <= out <= in per axis)", i, nm, d[i].kh, d[i].kw, h, w);
+            // Flux's rule per axis (NOT torch's adaptive windows): stride = in / out, k = in - (out - 1) * stride, pad 0; then (in - k) / stride + 1 == out
+            l.cin = l.cout = c; l.oh = d[i].kh; l.ow = d[i].kw; l.sh = h / l.oh; l.sw = w / l.ow; l.kh = h - (l.oh - 1) * l.sh; l.kw = w - (l.ow - 1) * l.sw;
+            l.ih = h; l.iw = w; l.K = 0; l.N = 0; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
         } else if (is_pool(l.kind)) {      // Flux MaxPool / MeanPool, pad 0 (pool.hip): per channel on the incoming (c, h, w) map; no parameters (K = N = 0), no activation
             const char* nm = l.kind == DQN_LAYER_MAXPOOL ? "MaxPool" : "MeanPool";
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream)", i, nm);
@@ -720,7 +733,8 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials, const float* X2, int ldx2) {
     if (is_skip(l.kind)) { launch_skip_fwd(st, l.out_feat, X, ldx, X2, ldx2, col0, ncols, Y); return; }      // X: the last inner layer's output, X2: the block's entry's
     if (is_do(l.kind)) return;      // inactive everywhere but the train step's online pass on s (emit_forward): the identity, and Y IS X (the layer's activation aliases its producer's)
-    if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
+    if (is_global_pool(l)) launch_gpool_fwd(st, l, X, ldx, col0, ncols, Y);      // an adaptive / global pool whose window is the whole map (pool_global.hip); structural, never a function of the batch
+    else if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
     else if (is_gn(l.kind)) { launch_gn_stat(st, l, X, ldx, col0, ncols, partials); launch_gn_norm(st, l, P, X, ldx, col0, ncols, Y, partials, ln_stat); }      // partials: >= gn_part_floats(l, ncols) floats
     else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);

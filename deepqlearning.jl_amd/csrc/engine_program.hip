@@ -75,7 +75,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
         if (E.skip_last && last) continue;
         if (kind_traits(e->L[lv[0]]).own_level) {
             // a layer launched alone on its level (base chain only): one launch per pass it is active in, never grouped with a GEMM layer.  Per kind:
-            //   a pool (pool.hip), a padded conv (conv_pad.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
+            //   a pool (pool.hip; an adaptive / global pool whose resolved window is the whole map: pool_global.hip -- launch_layer_fwd decides), a padded conv (conv_pad.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
             //   a GroupNorm layer (groupnorm.hip): every pass, TWO launches, "<pass>_gn<l>_stat" and "<pass>_gn<l>"; the first pass keeps (mu, r) per (group, column) for the backward
             //   the join of a skip block (skip.hip): every pass, y = (the last inner layer's stored output) + (the stored output of the block's entry, LayerDev::src2) on that pass's
             //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
@@ -542,7 +542,8 @@ int build_program(dqn_engine* e) {
         } else if (is_pool(L.kind)) {
             // gathers dY per input element and applies the producing layer's activation derivative.  No parameters, so no dW; a pool on the observation has no input gradient to compute
             const float* Yp = e->act_on[l];
-            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
+            if (wants_dx(l) && is_global_pool(L)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_gpool_bwd(en->stream, L, dpre, X, ncon, B, out, act_src); }});      // whole-map window of an adaptive / global pool (pool_global.hip)
+            else if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
         } else if (is_do(L.kind)) {
             // regenerates the forward's mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on
             // that layer's own, unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation

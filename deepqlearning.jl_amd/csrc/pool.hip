@@ -1,4 +1,4 @@
-// pool.hip -- Flux MaxPool / MeanPool (pad 0) over the batch-innermost Y[feature][column] layout: parameter-free layers between the
+// pool.hip -- Flux MaxPool / MeanPool (pad 0; and the adaptive kinds on their resolved geometry, unless the window is the whole map: pool_global.hip) over the batch-innermost Y[feature][column] layout: parameter-free layers between the
 // convolutions of a Q-network.  No contraction, no MFMA: every launch here is bandwidth- and launch-bound.
 //
 // Canonical order:
@@ -118,13 +118,13 @@ void launch_pool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx,
     const PoolGeo G = pool_geo(L);
     const int vec = (ldx % 4 == 0 && col0 % 4 == 0 && ncols % 4 == 0 && al16(X) && al16(Y)) ? 1 : 0;
     const size_t threads = (size_t)L.out_feat * ((ncols + 3) / 4); const unsigned blocks = (unsigned)((threads + 255) / 256);
-    if (L.kind == DQN_LAYER_MEANPOOL) hipLaunchKernelGGL(k_pool_fwd<1>, dim3(blocks), dim3(256), 0, st, G, X, ldx, col0, ncols, Y, vec);
+    if (is_mean_pool(L.kind)) hipLaunchKernelGGL(k_pool_fwd<1>, dim3(blocks), dim3(256), 0, st, G, X, ldx, col0, ncols, Y, vec);
     else hipLaunchKernelGGL(k_pool_fwd<0>, dim3(blocks), dim3(256), 0, st, G, X, ldx, col0, ncols, Y, vec);
 }
 void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY, const float* X, const float* Y, int ld, int B, float* dX, int act_src) {
     const PoolGeo G = pool_geo(L);
     const int vec = (ld % 4 == 0 && B % 4 == 0 && al16(dY) && al16(X) && al16(Y) && al16(dX)) ? 1 : 0;
     const size_t threads = (size_t)L.in_feat * ((B + 3) / 4); const unsigned blocks = (unsigned)((threads + 255) / 256);
-    if (L.kind == DQN_LAYER_MEANPOOL) hipLaunchKernelGGL(k_pool_bwd<1>, dim3(blocks), dim3(256), 0, st, G, dY, X, Y, ld, B, dX, act_src, vec);
+    if (is_mean_pool(L.kind)) hipLaunchKernelGGL(k_pool_bwd<1>, dim3(blocks), dim3(256), 0, st, G, dY, X, Y, ld, B, dX, act_src, vec);
     else hipLaunchKernelGGL(k_pool_bwd<0>, dim3(blocks), dim3(256), 0, st, G, dY, X, Y, ld, B, dX, act_src, vec);
 }

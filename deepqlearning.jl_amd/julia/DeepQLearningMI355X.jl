@@ -83,6 +83,11 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.MeanPool
         any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MeanPool with pad=0 only")
         return LayerDesc(6, 0, stream, 0, 0, 0, 0, l.k[2], l.k[1], l.stride[2], l.stride[1])
+    elseif l isa Flux.GlobalMaxPool || l isa Flux.GlobalMeanPool      # no fields; maxpool / meanpool with window = the whole (w, h) map, output (1, 1, c, batch): the adaptive kinds with output (1, 1)
+        return LayerDesc(l isa Flux.GlobalMaxPool ? 12 : 13, 0, stream, 0, 0, 0, 0, 1, 1, 0, 0)
+    elseif l isa Flux.AdaptiveMaxPool || l isa Flux.AdaptiveMeanPool      # field out, in Julia's (W, H) order; no parameters.  Flux's PoolDims rule per axis -- stride = in ÷ out,
+        # k = in - (out - 1) * stride, pad 0 -- needs the map size, which the engine knows: kh, kw carry the OUTPUT size (oh, ow), sh = sw = 0, and the engine resolves the window
+        return LayerDesc(l isa Flux.AdaptiveMaxPool ? 12 : 13, 0, stream, 0, 0, 0, 0, l.out[2], l.out[1], 0, 0)
     elseif l isa Flux.LayerNorm      # Flux 0.14 fields λ, diag, ϵ, size, affine; Flux.params order diag.scale, diag.bias == the ABI's LayerNorm block
         # normalise(x; dims, ϵ) = (x .- μ) ./ (σ .+ ϵ) with the uncorrected σ: ϵ is added OUTSIDE the root -- the engine runs this law, not torch's sqrt(var + eps).
         # n in both size slots, the Float32 bit pattern of ϵ in cin (as a Conv's pad rides in n_in / n_out)
@@ -113,7 +118,7 @@ function lower_layer(l, stream)::LayerDesc
     l isa Flux.BatchNorm && throw("DeepQLearningError: BatchNorm is not supported: it keeps running statistics, so the online pass on s, the pass on s', the target pass and the acting pass would compute different functions; of Flux's normalisation layers the MI355X engine runs LayerNorm(n) and GroupNorm(chs, G)")
     l isa Flux.InstanceNorm && throw("DeepQLearningError: InstanceNorm is not supported: its default is affine = false, which the MI355X engine does not run; GroupNorm(chs, chs) is instance normalisation with a per-channel affine")
     l isa Flux.Parallel && throw("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only))")
 end
 is_glue(l) = l === identity || l === flattenbatch || l isa Function
 # Flux 0.14 SkipConnection(layers, connection), fields layers, connection: layers(x) .+ x for connection === +.  No parameters of its own (Flux.params yields the inner
@@ -124,8 +129,8 @@ is_glue(l) = l === identity || l === flattenbatch || l isa Function
 # The CONVOLUTIONAL block, x + Conv(Conv(x)): where the descriptor in front is a Conv, a pool or the join of another such block (kinds 1, 5, 6, 10) and every inner layer
 # is a Conv or a pool, the join is of kind 10 -- the same descriptor shape.  Its inner layers are Convs with pad != 0 that keep the channel count; a pool, a pad-0 Conv and
 # a channel change are refused here by name, that the block keeps (h, w) is the engine's check
-is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10 || d.kind == 11      # (11: a GroupNorm keeps the incoming map)
-is_map_layer(x) = x isa Conv || x isa Flux.MaxPool || x isa Flux.MeanPool
+is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10 || d.kind == 11 || d.kind == 12 || d.kind == 13      # (11: a GroupNorm keeps the incoming map; 12, 13: the adaptive / global pools)
+is_map_layer(x) = x isa Conv || x isa Flux.MaxPool || x isa Flux.MeanPool || x isa Flux.AdaptiveMaxPool || x isa Flux.AdaptiveMeanPool || x isa Flux.GlobalMaxPool || x isa Flux.GlobalMeanPool
 function lower_skip_map!(descs, l, stream, inner)
     m = 0; c_in = 0; c_out = 0
     for x in inner

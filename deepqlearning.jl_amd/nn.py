@@ -148,6 +148,64 @@ class MeanPool(_Pool):
     kind = "meanpool"
 
 
+class _AdaptivePool:
+    """Flux 0.14 AdaptiveMaxPool / AdaptiveMeanPool(out) over NNlib (recalled, not executed here): per channel on a (C, H, W) map, output (C, oh, ow) with 1 <= out <= in per
+    axis.  Flux's rule per axis: stride = in ÷ out, k = in - (out - 1) * stride, pad = 0, then maxpool / meanpool with that geometry -- NOT torch's adaptive windows (5 -> 3:
+    Flux takes [0..2] [1..3] [2..4], torch [0,2) [1,4) [3,5)).  The map size is the engine's to know: it resolves the window (build_layers).  `out` is an integer or (oh, ow)
+    in this mirror's (H, W) order; Flux writes (ow, oh).  No parameters, no activation.  Placement is a pool's."""
+
+    def __init__(self, out):
+        if np.isscalar(out):
+            self.oh = self.ow = int(out)
+        else:
+            t = tuple(int(v) for v in out)
+            if len(t) != 2:
+                raise _abi.DQNError(f"DeepQLearningError: {type(self).__name__}({out!r}): the output size must be an integer or a pair (oh, ow)")
+            self.oh, self.ow = t
+        if self.oh < 1 or self.ow < 1:
+            raise _abi.DQNError(f"DeepQLearningError: {type(self).__name__}(({self.oh}, {self.ow})): the output size must be at least (1, 1)")
+        self.act = identity
+
+    def shapes(self):   # Flux.params holds nothing for a pool layer
+        return []
+
+    def __repr__(self):
+        return f"{type(self).__name__}(({self.ow}, {self.oh}))"      # Flux's order: (W, H)
+
+
+class AdaptiveMaxPool(_AdaptivePool):
+    kind = "adaptivemaxpool"
+
+
+class AdaptiveMeanPool(_AdaptivePool):
+    kind = "adaptivemeanpool"
+
+
+class GlobalMaxPool(_AdaptivePool):
+    """Flux 0.14 GlobalMaxPool(): maxpool with window = the whole (h, w) map, output (1, 1, c, batch) -- AdaptiveMaxPool((1, 1)) exactly, and lowered as it"""
+    kind = "adaptivemaxpool"
+
+    def __init__(self):
+        super().__init__(1)
+
+    def __repr__(self):
+        return "GlobalMaxPool()"
+
+
+class GlobalMeanPool(_AdaptivePool):
+    """Flux 0.14 GlobalMeanPool(): meanpool with window = the whole (h, w) map, output (1, 1, c, batch) -- AdaptiveMeanPool((1, 1)) exactly, and lowered as it"""
+    kind = "adaptivemeanpool"
+
+    def __init__(self):
+        super().__init__(1)
+
+    def __repr__(self):
+        return "GlobalMeanPool()"
+
+
+POOL_KINDS = ("maxpool", "meanpool", "adaptivemaxpool", "adaptivemeanpool")      # parameter-free layers on a (c, h, w) map whose output is a map
+
+
 class LayerNorm:
     """Flux 0.14 LayerNorm(n, λ = identity; affine = true, eps = 1f-5) on a feature vector of length n, per batch column (Flux's `normalise`; recalled, not executed here):
     μ = mean(x), σ = sqrt(mean((x - μ)²)) (uncorrected), y = λ.(scale .* (x - μ) / (σ + eps) .+ bias) -- eps is added to σ OUTSIDE the root, which is not torch's
@@ -383,8 +441,8 @@ def lower(net):
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the first layer: a skip block's input is never the observation (it must follow a Dense, recurrent, LayerNorm or Dropout layer or another skip block)")
         if any(getattr(l, "kind", None) == "groupnorm" for l in blk.layers):
             raise _abi.DQNError(f"DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block): {blk!r}")
-        on_map = prev_kind in ("conv", "maxpool", "meanpool", "groupnorm") or (prev_kind == "skip" and map_join[0])
-        if on_map and not first and all(getattr(l, "kind", None) in ("conv", "maxpool", "meanpool") for l in blk.layers):
+        on_map = prev_kind in ("conv", "groupnorm") + POOL_KINDS or (prev_kind == "skip" and map_join[0])
+        if on_map and not first and all(getattr(l, "kind", None) in ("conv",) + POOL_KINDS for l in blk.layers):
             return add_skip_map(blk, stream, is_last)
         if on_map:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot follow a Conv / MaxPool / MeanPool layer: a skip block stands on a feature vector (convolutional residual blocks are not supported)")
@@ -397,7 +455,7 @@ def lower(net):
                 raise _abi.DQNError(f"DeepQLearningError: a SkipConnection inside a SkipConnection is not supported (nested skip blocks): {blk!r}")
             if k in ("lstm", "gru", "rnn"):
                 raise _abi.DQNError(f"DeepQLearningError: a recurrent layer inside a SkipConnection is not supported (its inner layers are Dense, LayerNorm and Dropout layers only): {blk!r}")
-            if k in ("conv", "maxpool", "meanpool"):
+            if k in ("conv",) + POOL_KINDS:
                 raise _abi.DQNError(f"DeepQLearningError: a Conv / MaxPool / MeanPool layer inside a SkipConnection is not supported (its inner layers are Dense, LayerNorm and Dropout layers only; convolutional residual blocks are not supported): {blk!r}")
             if k not in ("dense", "layernorm", "dropout"):
                 raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} inside a SkipConnection (Dense / LayerNorm / Dropout only)")
@@ -418,7 +476,7 @@ def lower(net):
         if is_last:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the network's output layer")
         for l in blk.layers:
-            if l.kind in ("maxpool", "meanpool"):
+            if l.kind in POOL_KINDS:
                 raise _abi.DQNError(f"DeepQLearningError: a MaxPool / MeanPool layer inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only): {blk!r}")
             if l.ph == 0 and l.pw == 0:
                 raise _abi.DQNError(f"DeepQLearningError: a Conv with pad 0 inside a convolutional SkipConnection is not supported (its inner layers are Conv layers with pad != 0 only; 1x1 and unpadded inner convolutions are not supported): {blk!r}")
@@ -440,8 +498,8 @@ def lower(net):
             if getattr(l, "kind", None) == "skip":
                 add_skip(l, stream, not out, getattr(layers[i - 1], "kind", None) if i > 0 else None, i + 1 == len(layers) and chain is top)
                 continue
-            if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "maxpool", "meanpool", "groupnorm", "layernorm"):
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only)")
+            if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "groupnorm", "layernorm") + POOL_KINDS:
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only))")
             d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -467,6 +525,14 @@ def lower(net):
                 bits = int(np.float64(l.p).view(np.uint64))
                 d.kind = _abi.LAYER_DROPOUT
                 d.cin, d.cout = int(np.uint32(bits & 0xFFFFFFFF).view(np.int32)), int(np.uint32(bits >> 32).view(np.int32))
+            elif l.kind in ("adaptivemaxpool", "adaptivemeanpool"):      # kh, kw = the OUTPUT size (oh, ow); sh = sw = n_in = n_out = 0: the engine resolves the window from the map
+                if stream != _abi.STREAM_BASE:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+                if i + 1 == len(layers) and chain is top:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                d.kind = _abi.LAYER_ADAPTIVEMAXPOOL if l.kind == "adaptivemaxpool" else _abi.LAYER_ADAPTIVEMEANPOOL
+                d.cin = d.cout = chan[0]
+                d.kh, d.kw = l.oh, l.ow
             elif l.kind in ("maxpool", "meanpool"):      # cin == cout == channels of the incoming map
                 d.kind = _abi.LAYER_MAXPOOL if l.kind == "maxpool" else _abi.LAYER_MEANPOOL
                 d.cin = d.cout = chan[0]
@@ -508,7 +574,7 @@ def glorot_params(net, seed=1):
     rng = np.random.default_rng(seed)
     parts = []
     for l in all_layers(net):
-        if l.kind in ("maxpool", "meanpool", "dropout"):      # no parameters
+        if l.kind in POOL_KINDS + ("dropout",):      # no parameters
             continue
         if l.kind == "groupnorm":      # β = zeros, then γ = ones
             parts += [np.zeros(l.chs, np.float32), np.ones(l.chs, np.float32)]

@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11, DQN_LAYER_ADAPTIVEMAXPOOL = 12, DQN_LAYER_ADAPTIVEMEANPOOL = 13 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -85,6 +85,13 @@ typedef struct {
                                           (H + 2 pad_h - kh) / sh + 1 by (W + 2 pad_w - kw) / sw + 1; a padded Conv is base chain only and single GPU only;
                                           MaxPool((kh,kw); stride=(sh,sw)) / MeanPool(...), pad 0: cin == cout == channels of the incoming map (or both 0: the engine fills them in), act = IDENTITY,
                                           no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored;
+                                          AdaptiveMaxPool((ow, oh)) / AdaptiveMeanPool(...) (kinds 12 / 13; Flux 0.14 over NNlib, recalled, not executed) and GlobalMaxPool() / GlobalMeanPool()
+                                          (the same kinds with output (1, 1)): kh, kw = the OUTPUT size (oh, ow), 1 <= oh <= h, 1 <= ow <= w of the incoming (c, h, w) map; sh = sw = 0,
+                                          n_in = n_out = 0, cin == cout == channels (or both 0), act = IDENTITY, stream = BASE; its plan entry is all zeros and ignored.  The engine
+                                          resolves the window per axis by FLUX's rule, stride = in / out (integer division), k = in - (out - 1) * stride, pad 0 -- NOT torch's adaptive
+                                          windows (5 -> 3: Flux [0..2] [1..3] [2..4], torch [0,2) [1,4) [3,5)) -- and the layer is then MaxPool / MeanPool with that geometry in every
+                                          respect (placement, tie rule, divisor f32(kh * kw), backward, single GPU only).  Output (1, 1) -- the window is the whole map, the
+                                          (1, 1, c, batch) output of the Global layers -- runs the whole-map reduction kernels (pool_global.hip); every other output runs the pool kernels;
                                           LayerNorm(n, act; affine = true, eps) (Flux 0.14 `normalise`, recalled, not executed): n_in == n_out == n >= 2 == the incoming feature count, act = the
                                           layer's activation, stream = BASE, cin = the fp32 BIT PATTERN of eps (0 = the default 1f-5; finite and > 0), every other slot 0.  Per batch column
                                           mu = mean(x), sigma = sqrt(mean((x - mu)^2)), y = act(scale * (x - mu) / (sigma + eps) + bias): eps is added to sigma OUTSIDE the root (not torch's
