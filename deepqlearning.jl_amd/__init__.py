@@ -12,7 +12,7 @@ import ctypes as _C
 import os as _os
 
 from . import _abi
-from ._abi import (ACT_ELU, ACT_HARDTANH, ACT_IDENTITY, ACT_LEAKYRELU, ACT_RELU, ACT_RELU6, ACT_SELU, ACT_SIGMOID, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_TANH, NET_ONLINE, NET_TARGET, OBS_F32, OBS_U8, DQNError, HParams,  # noqa: F401
+from ._abi import (ACT_ELU, ACT_GELU, ACT_HARDSWISH, ACT_HARDTANH, ACT_MISH, ACT_SWISH, ACT_IDENTITY, ACT_LEAKYRELU, ACT_RELU, ACT_RELU6, ACT_SELU, ACT_SIGMOID, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_TANH, NET_ONLINE, NET_TARGET, OBS_F32, OBS_U8, DQNError, HParams,  # noqa: F401
                    LayerDesc, LayerPlan, default_hparams)
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))

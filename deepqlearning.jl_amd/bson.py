@@ -52,7 +52,7 @@ def julia_param_shapes(net):
             out += [((l.n,), l.n), ((l.n,), l.n)]
         elif l.kind == "groupnorm":   # Flux 0.14 GroupNorm(chs, G): β (chs), then γ (chs) -- bias first
             out += [((l.chs,), l.chs), ((l.chs,), l.chs)]
-        elif l.kind in ("maxpool", "meanpool", "adaptivemaxpool", "adaptivemeanpool", "dropout"):   # Flux.params(MaxPool / MeanPool / Global... / Adaptive...Pool / Dropout) is empty: the file holds no array for the layer
+        elif l.kind in ("maxpool", "meanpool", "adaptivemaxpool", "adaptivemeanpool", "dropout", "activation"):   # Flux.params(MaxPool / MeanPool / Global... / Adaptive...Pool / Dropout / BroadcastFunction) is empty: the file holds no array for the layer
             continue
         else:
             raise ValueError(f"unsupported layer kind {l.kind}")

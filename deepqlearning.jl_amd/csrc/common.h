@@ -53,6 +53,13 @@ static inline bool is_global_pool(const LayerDev& L) { return is_adaptive_pool(L
 static inline __host__ __device__ bool is_gn(int kind) { return kind == DQN_LAYER_GROUPNORM; }
 static inline float gn_eps(const LayerDev& L) { if (L.kw == 0) return 1e-5f; float f; memcpy(&f, &L.kw, sizeof f); return f; }
 static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP || is_gn(kind); }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow; a GroupNorm keeps the incoming one)
+// the standalone activation layer (act_layer.hip; Julia's Base.Broadcast.BroadcastFunction(σ) in a Chain): y = σ(x) per element, parameter-free (K = N = 0 as a pool's).  The code σ
+// -- any of 0 .. DQN_ACT_LAYER_LAST -- lives in `cell_act`; `act` stays IDENTITY, as a recurrent layer's does: the generic forward / dX epilogues read `act`, so the layer above
+// writes its RAW input gradient into this layer's dY and the head kernels read its output as finished.  It keeps its input's shape AND its kind of shape: behind a map it
+// carries the map in cout, oh, ow (out_is_map looks through it), behind a feature vector it is one
+static inline __host__ __device__ bool is_actl(int kind) { return kind == DQN_LAYER_ACTIVATION; }
+// layer i's output is a (cout, oh, ow) map: has_map of its kind, looking through standalone activations (which keep what they are given)
+static inline bool out_is_map(const LayerDev* L, int i) { while (i >= 0 && is_actl(L[i].kind)) i = L[i].src; return i >= 0 && has_map(L[i].kind); }
 // Flux LayerNorm (layernorm.hip): K = N = n features in and out, a parameter block of 2n floats (scale at w_off, bias at b_off = w_off + n -- NOT K * N weights: layer_wn),
 // the fp32 bit pattern of eps in cin (0 = 1f-5); launched alone on its level, as pools are
 static inline __host__ __device__ bool is_ln(int kind) { return kind == DQN_LAYER_LAYERNORM; }
@@ -87,11 +94,11 @@ struct KindTraits {
     bool output_ok;            // may be the network's output layer
     const char *a_noun, *plural;      // what the refusals call it (plain text, printed through %s); plural != null: single GPU only (dqn_comm_init and DQN_SIM_WORLD refuse the network)
 };
-enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
+enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_ACT, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
 static inline int kind_row(const LayerDev& L) {
     switch (L.kind) {
     case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: case DQN_LAYER_ADAPTIVEMAXPOOL: case DQN_LAYER_ADAPTIVEMEANPOOL: return KT_POOL;
-    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;
+    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;      case DQN_LAYER_ACTIVATION: return KT_ACT;
     case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
     }
 }
@@ -104,6 +111,7 @@ static inline const KindTraits& kind_traits(const LayerDev& L) {
         /* KT_DO        */ {"do",      true,     false,    false,     true,           true,             false, "a Dropout layer", "Dropout layers"},
         /* KT_SKIP      */ {"skip",    true,     false,    false,     true,           true,             false, "a skip block", "skip blocks"},
         /* KT_GN        */ {"gn",      true,     false,    false,     true,           true,             false, "a GroupNorm layer", "GroupNorm layers"},
+        /* KT_ACT       */ {"act",     true,     false,    false,     true,           true,             false, "an Activation layer", "Activation layers"},
         /* KT_CONV      */ {"conv",    false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_DENSE     */ {"dense",   false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_RECURRENT */ {"dense",   false,    true,     false,     false,          false,            true,  nullptr, nullptr},      // named after its batched part, the dense view Gx = Wi*x (gx_view)
@@ -160,6 +168,8 @@ static inline __host__ __device__ int dqn_chunk_len(int K, int kc) { return (kc 
 // transcendental or a division go through Float64 and round once, as tanh / sigmoid do; the three select-only ones (leakyrelu, relu6, hardtanh) are plain fp32.
 // NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu α = 1; selu's λ, α below.  Codes >= DQN_ACT_TANH take the out-of-line path: identity / relu layers pay one range
 // compare inline, nothing else (docs/history/activations.md has the instruction counts).
+// gelu / swish / mish / hardswish (DQN_ACT_GELU .. DQN_ACT_HARDSWISH) are NOT here: their derivative needs x, so only the standalone activation layer runs them, and their bodies
+// live in act_layer.hip alone -- added to act_slow / dact_new they would be four more branch targets nobody takes in every kernel that includes this header.
 #define DQN_SELU_LAMBDA 1.0507009873554805
 #define DQN_SELU_ALPHA 1.6732632423543772
 #define DQN_SELU_LAMBDA_ALPHA 1.7580993408473766
@@ -1141,6 +1151,10 @@ void launch_pool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[out_f
                      float* dX /*[in_feat][B]*/, int act_src);
 // pool_global.hip: a pool whose window is the whole (h, w) map (is_global_pool): one workgroup per (channel, column tile) reduces the channel's n = h * w rows.  Y[c][ncols];
 // the backward recomputes the MaxPool's first maximal row from X (nothing is stashed) and applies the producing layer's activation derivative
+// act_layer.hip: the standalone activation layer.  n features; act = the layer's σ (0 .. DQN_ACT_LAYER_LAST); X[n][ldx] at columns col0 .. col0 + ncols -> Y[n][ncols]
+void launch_actl_fwd(hipStream_t st, int n, int act, const float* X, int ldx, int col0, int ncols, float* Y);
+// dY[n][B]; X = the layer's input = the producing layer's output, Y = the layer's output, both [n][ld], columns 0 .. B; dX[n][B] = dY σ′ times the producer's derivative (act_src) on X
+void launch_actl_bwd(hipStream_t st, int n, int act, const float* dY, const float* X, const float* Y, int ld, int B, float* dX, int act_src);
 void launch_gpool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[c][ncols]*/);
 void launch_gpool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[c][B]*/, const float* X /* the pool's input */, int ld /* of X */, int B, float* dX /*[in_feat][B]*/, int act_src);
 // conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');

@@ -62,7 +62,7 @@ extern "C" int dqn_hparams_default(dqn_hparams* hp) {
 }
 
 // THE single-GPU rule: the exchange paths (operand all-gather, all-reduce) have never run with an own-level kind's launches in the program -- refused instead of claimed.
-// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block, GroupNorm), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
+// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block, GroupNorm, Activation), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
 static int refuse_replicas(const char* who, const LayerDev* L, int nl) {
     for (int r = 0; r < KT_OWN_LEVEL; r++) for (int i = 0; i < nl; i++) {
         const KindTraits& t = kind_traits(L[i]); if (kind_row(L[i]) != r || !t.plural) continue;
@@ -83,7 +83,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         l.src = prev;
         int c, h, w;
         if (prev < 0) { c = hp->obs_c; h = hp->obs_h; w = hp->obs_w; }
-        else if (has_map(L[prev].kind)) { c = L[prev].cout; h = L[prev].oh; w = L[prev].ow; }
+        else if (out_is_map(L, prev)) { c = L[prev].cout; h = L[prev].oh; w = L[prev].ow; }
         else { c = L[prev].out_feat; h = 1; w = 1; }
         l.in_feat = c * h * w;
         if (l.kind == DQN_LAYER_CONV) {
@@ -102,8 +102,8 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_adaptive_pool(l.kind)) {      // Flux AdaptiveMaxPool / AdaptiveMeanPool((ow, oh)), GlobalMaxPool / GlobalMeanPool (output (1, 1)): kh, kw carry the OUTPUT size; resolved here into a pool's geometry
             const char* nm = l.kind == DQN_LAYER_ADAPTIVEMAXPOOL ? "AdaptiveMaxPool" : "AdaptiveMeanPool";
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, nm, l.stream);
-            if (prev >= 0 && !has_map(L[prev].kind)) return fail("layer %d: %s must be the first layer or follow a layer whose output is a (c, h, w) map (layer %d is %s, whose output is a feature vector of %d)", i, nm, prev,
-                                                                 L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer", L[prev].out_feat);
+            if (prev >= 0 && !out_is_map(L, prev)) return fail("layer %d: %s must be the first layer or follow a layer whose output is a (c, h, w) map (layer %d is %s, whose output is a feature vector of %d)", i, nm, prev,
+                                                                 is_actl(L[prev].kind) ? "an Activation layer on a feature vector" : L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer", L[prev].out_feat);
             if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
             if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
             if (d[i].sh || d[i].sw || d[i].n_in || d[i].n_out) return fail("layer %d: %s uses cin, cout, kh and kw (the OUTPUT size (oh, ow)) only; sh / sw / n_in / n_out = %d / %d / %d / %d must be 0", i, nm, d[i].sh, d[i].sw, d[i].n_in, d[i].n_out);
@@ -115,7 +115,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_pool(l.kind)) {      // Flux MaxPool / MeanPool, pad 0 (pool.hip): per channel on the incoming (c, h, w) map; no parameters (K = N = 0), no activation
             const char* nm = l.kind == DQN_LAYER_MAXPOOL ? "MaxPool" : "MeanPool";
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream)", i, nm);
-            if (prev >= 0 && !has_map(L[prev].kind)) return fail("layer %d: %s must be the first layer or follow a Conv / MaxPool / MeanPool layer (it follows a Dense or recurrent layer, whose output is no (c, h, w) map)", i, nm);
+            if (prev >= 0 && !out_is_map(L, prev)) return fail("layer %d: %s must be the first layer or follow a Conv / MaxPool / MeanPool layer (it follows a Dense or recurrent layer, whose output is no (c, h, w) map)", i, nm);
             if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
             if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
             if (d[i].sh < 1 || d[i].sw < 1) return fail("layer %d: %s stride (%d, %d) must be positive", i, nm, d[i].sh, d[i].sw);
@@ -126,6 +126,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_ln(l.kind)) {      // Flux LayerNorm(n, act; affine = true, eps) (layernorm.hip): per column over the n incoming features; K = N = n, parameters scale (n), bias (n)
             if (prev < 0) return fail("layer %d: LayerNorm cannot be the first layer (it must directly follow a Dense or recurrent layer)", i);
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: LayerNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (is_actl(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is an Activation layer; a LayerNorm directly behind a standalone activation is not supported)", i, prev);
             if (is_gn(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (has_map(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (is_ln(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a LayerNorm layer)", i, prev);
@@ -140,8 +141,8 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_gn(l.kind)) {      // Flux GroupNorm(chs, G, act; eps) (groupnorm.hip): per column and group of c / G contiguous channels of the incoming (c, h, w) map, which it keeps; K = N = c, parameters beta (c), gamma (c)
             if (prev < 0) return fail("layer %d: GroupNorm cannot be the first layer (normalising the observation is not supported; it must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block)", i);
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: GroupNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (!has_map(L[prev].kind)) return fail("layer %d: GroupNorm must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block (layer %d is %s, whose output is no (c, h, w) map)", i, prev,
-                                                    L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer");
+            if (!out_is_map(L, prev)) return fail("layer %d: GroupNorm must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block (layer %d is %s, whose output is no (c, h, w) map)", i, prev,
+                                                    is_actl(L[prev].kind) ? "an Activation layer on a feature vector" : L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer");
             if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: GroupNorm activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: GroupNorm chs (cin %d / cout %d) != incoming channels %d", i, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
             if (d[i].n_in != d[i].n_out) return fail("layer %d: GroupNorm n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
@@ -155,6 +156,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
         } else if (is_do(l.kind)) {      // Flux Dropout(p), dims = : (dropout.hip): per element of the n incoming features; no parameters (K = N = 0 as a pool's), p's Float64 bits in (cin, cout)
             if (prev < 0) return fail("layer %d: Dropout cannot be the first layer (it must directly follow a Dense, recurrent or LayerNorm layer; dropout on the observation is not supported)", i);
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Dropout layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (is_actl(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is an Activation layer; a Dropout directly behind a standalone activation is not supported)", i, prev);
             if (is_gn(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (has_map(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
             if (is_do(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Dropout layer)", i, prev);
@@ -177,6 +179,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             for (int j = i - m; j < i; j++) {
                 if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the convolutional skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
                 if (is_skip(L[j].kind)) return fail("layer %d: the convolutional skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
+                if (is_actl(L[j].kind)) return fail("layer %d: the convolutional skip block holds an Activation layer (layer %d); its inner layers are Conv layers with pad != 0 only (a standalone activation inside a skip block is not supported)", i, j);
                 if (is_pool(L[j].kind)) return fail("layer %d: the convolutional skip block holds a MaxPool / MeanPool layer (layer %d); its inner layers are Conv layers with pad != 0 only", i, j);
                 if (L[j].kind == DQN_LAYER_CONV && !is_padded(L[j])) return fail("layer %d: the convolutional skip block holds a Conv with pad 0 (layer %d, kernel (%d, %d)); its inner layers are Conv layers with pad != 0 only", i, j, L[j].kh, L[j].kw);
                 if (L[j].kind != DQN_LAYER_CONV) return fail("layer %d: the convolutional skip block holds %s (layer %d); its inner layers are Conv layers with pad != 0 only", i,
@@ -184,8 +187,8 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             }
             const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
             if (pp < 0) return fail("layer %d: the convolutional skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block)", i, i - m);
-            if (!has_map(L[pp].kind)) return fail("layer %d: the convolutional skip block's input is the feature vector of layer %d (%s); a convolutional skip block stands on the (c, h, w) map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block", i, pp,
-                                                  L[pp].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[pp].kind) ? "a recurrent layer" : is_ln(L[pp].kind) ? "a LayerNorm layer" : is_do(L[pp].kind) ? "a Dropout layer" : "a Dense layer");
+            if (!out_is_map(L, pp)) return fail("layer %d: the convolutional skip block's input is the feature vector of layer %d (%s); a convolutional skip block stands on the (c, h, w) map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block", i, pp,
+                                                  is_actl(L[pp].kind) ? "an Activation layer on a feature vector" : L[pp].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[pp].kind) ? "a recurrent layer" : is_ln(L[pp].kind) ? "a LayerNorm layer" : is_do(L[pp].kind) ? "a Dropout layer" : "a Dense layer");
             if (L[prev].cout != L[pp].cout || L[prev].oh != L[pp].oh || L[prev].ow != L[pp].ow) return fail("layer %d: the convolutional skip block maps a (%d, %d, %d) map to a (%d, %d, %d) map; SkipConnection(layers, +) needs layers: (c, h, w) -> (c, h, w)", i, L[pp].cout, L[pp].oh, L[pp].ow, L[prev].cout, L[prev].oh, L[prev].ow);
             if (d[i].n_in != d[i].n_out) return fail("layer %d: convolutional skip block n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
             if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: convolutional skip block size n = %d != the block's features %d * %d * %d = %d", i, d[i].n_in, c, h, w, l.in_feat);
@@ -202,18 +205,29 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                 if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
                 if (is_skip(L[j].kind)) return fail("layer %d: the skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
                 if (is_recurrent(L[j].kind)) return fail("layer %d: the skip block holds a recurrent layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only", i, j);
+                if (is_actl(L[j].kind)) return fail("layer %d: the skip block holds an Activation layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (a standalone activation inside a skip block is not supported)", i, j);
                 if (is_gn(L[j].kind)) return fail("layer %d: the skip block holds a GroupNorm layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (GroupNorm inside a skip block is not supported)", i, j);
                 if (has_map(L[j].kind)) return fail("layer %d: the skip block holds a Conv / MaxPool / MeanPool layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (convolutional residual blocks are not supported)", i, j);
             }
             const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
             if (pp < 0) return fail("layer %d: the skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the output of a Dense, recurrent, LayerNorm or Dropout layer or of another skip block)", i, i - m);
             if (is_gn(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a GroupNorm layer); a skip block stands on a feature vector", i, pp);
-            if (has_map(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a Conv / MaxPool / MeanPool layer); a skip block stands on a feature vector (convolutional residual blocks are not supported)", i, pp);
+            if (out_is_map(L, pp)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a Conv / MaxPool / MeanPool layer); a skip block stands on a feature vector (convolutional residual blocks are not supported)", i, pp);
             if (L[prev].out_feat != L[pp].out_feat) return fail("layer %d: the skip block maps %d features to %d; SkipConnection(layers, +) needs layers: n -> n", i, L[pp].out_feat, L[prev].out_feat);
             if (d[i].n_in != d[i].n_out) return fail("layer %d: skip block n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
             if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: skip block size n = %d != the block's features %d", i, d[i].n_in, l.in_feat);
             l.cin = m; l.src2 = pp;
             l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
+        } else if (is_actl(l.kind)) {      // the standalone activation layer (act_layer.hip): y = σ(x) per element on whatever the layer in front yields -- a feature vector or a (c, h, w) map, kept; no parameters (K = N = 0 as a pool's)
+            if (prev < 0) return fail("layer %d: an Activation layer cannot be the first layer (its input is the stored output of the layer in front; an activation on the observation is not supported)", i);
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Activation layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAYER_LAST) return fail("layer %d: Activation code %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAYER_LAST);
+            if (d[i].n_in != d[i].n_out) return fail("layer %d: Activation n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
+            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: Activation size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
+            if (d[i].cin || d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: Activation uses act, n_in and n_out only; cin / cout / kh / kw / sh / sw = %d / %d / %d / %d / %d / %d must be 0", i, d[i].cin, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
+            l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY;      // σ, and what the generic epilogues read (common.h)
+            l.cin = l.cout = c; l.ih = l.oh = h; l.iw = l.ow = w;      // behind a map: the map, for the layer behind it (out_is_map); behind a feature vector: (n, 1, 1)
+            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat;
         } else if (l.kind == DQN_LAYER_DENSE) {
             if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Dense activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
@@ -732,6 +746,7 @@ extern "C" int dqn_update_priorities(dqn_engine_t* e, const int64_t* idx, const 
 // ---------------------------------------------------------------- the train step
 void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, bool use_mfma, int xu8, float* ln_stat, float* partials, const float* X2, int ldx2) {
     if (is_skip(l.kind)) { launch_skip_fwd(st, l.out_feat, X, ldx, X2, ldx2, col0, ncols, Y); return; }      // X: the last inner layer's output, X2: the block's entry's
+    if (is_actl(l.kind)) { launch_actl_fwd(st, l.out_feat, l.cell_act, X, ldx, col0, ncols, Y); return; }      // the standalone activation layer (act_layer.hip)
     if (is_do(l.kind)) return;      // inactive everywhere but the train step's online pass on s (emit_forward): the identity, and Y IS X (the layer's activation aliases its producer's)
     if (is_global_pool(l)) launch_gpool_fwd(st, l, X, ldx, col0, ncols, Y);      // an adaptive / global pool whose window is the whole map (pool_global.hip); structural, never a function of the batch
     else if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);

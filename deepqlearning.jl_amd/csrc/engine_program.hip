@@ -81,6 +81,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
             //   a Dropout layer (dropout.hip): ACTIVE in the first pass of the train step only, on its leading E.do_cols columns (online network, s): it writes a buffer of its own -- the producer's output
             //     must survive for the producer's backward -- and copies the s' columns behind them.  Every other pass emits NOTHING: the layer's activation pointer there is its producer's (engine.hip)
+            //   a standalone activation layer (act_layer.hip): every pass, one element-wise launch on the producer's stored output of that pass
             //   a convolutional skip block whose last inner layer K has no activation (skip_fused_fwd): K's launch takes the entry's stored output of the pass as its residual
             //     operand and writes act(tot + bias) + y_P straight into the JOIN's activation (conv_pad.hip), named "<pass>_conv<K>+skip<join>"; the join's level emits nothing.
             //     K's own activation buffer is then never written, and never read: its one consumer is the join, and the join's backward is the alias (skip_dact_alias)
@@ -91,7 +92,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             if (is_gn(L.kind) && E.ln_stat) stat0 = E.ln_stat[l] = palloc(e, (size_t)2 * L.kh * passes[0].ncols);      // (mu, r) per (group, column)
             for (int pi = 0; pi < np; pi++) {
                 const Prob q = prob(l, pi);
-                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = (dropout || join) ? nullptr : q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;      // (a Dropout layer, a join: no parameters, IDENTITY)
+                HeadSrc h; h.p = q.Y; h.ld = q.ncols; h.S = 1; h.per_s = 0; h.bias = (dropout || join || is_actl(L.kind)) ? nullptr : q.P + L.b_off; h.act = L.act; E.head[l][pi] = h;      // (a Dropout layer, a join, an Activation layer: no parameters, IDENTITY -- the Activation's σ is in cell_act and already applied)
                 if (dropout) {
                     const double p = do_p(L); const unsigned long long seed = e->hp.seed; const StepState* stt = e->state; const int C = E.do_cols;
                     if (pi == 0 && C > 0) prog.push_back({pname(e, passes[pi].tag, L, l), [=](dqn_engine* en) { launch_do_fwd(en->stream, L.out_feat, p, seed, l, stt, q.X, q.Y, q.ncols, q.ncols, C); }});
@@ -517,8 +518,8 @@ int build_program(dqn_engine* e) {
     const bool pg_want = e->hp.prioritized_replay && !rec && (prio_in_adam ? (fuse_heads || e->prio_in_bwd) : e->prio_forked) && !e->sim_world &&
                          (e->hp.obs_dtype != DQN_OBS_U8 || e->arena_u8) && !e->opt.no_pregather && (!e->hp.sample_distinct || Bb <= 64 || e->prio_in_bwd);      // u8 rows: only onto the byte arena; distinct mode at B > 64 without a carrying backward launch: sample launch + gather launch every step
     bool joined = false;
-    // a layer's input gradient has a reader unless the layer reads the observation -- directly, or through pool layers only (a pool has no parameters: its dY would feed nothing)
-    auto wants_dx = [&](int l) { int s = e->L[l].src; while (s >= 0 && is_pool(e->L[s].kind)) s = e->L[s].src; return s >= 0; };
+    // a layer's input gradient has a reader unless the layer reads the observation -- directly, or through pool and Activation layers only (neither has parameters: its dY would feed nothing)
+    auto wants_dx = [&](int l) { int s = e->L[l].src; while (s >= 0 && (is_pool(e->L[s].kind) || is_actl(e->L[s].kind))) s = e->L[s].src; return s >= 0; };
     // the backward of the own-level kinds: launches of the layer's own, never grouped.  Returns true where layer l is one (the GEMM path has nothing to add).  Whatever its
     // kind, l may also be the FIRST inner layer of a skip block: the block's entry launch is queued behind its level (post_level)
     auto emit_own_level_bwd = [&](int l, std::vector<dqn_engine::Step>& post_level) {
@@ -544,6 +545,12 @@ int build_program(dqn_engine* e) {
             const float* Yp = e->act_on[l];
             if (wants_dx(l) && is_global_pool(L)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_gpool_bwd(en->stream, L, dpre, X, ncon, B, out, act_src); }});      // whole-map window of an adaptive / global pool (pool_global.hip)
             else if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_pool_bwd(en->stream, L, dpre, X, Yp, ncon, B, out, act_src); }});
+        } else if (is_actl(L.kind)) {
+            // dY σ′ -- σ′ from the layer's own output for the eleven codes of the fused epilogues, from its input for gelu / swish / mish / hardswish -- then the producing layer's
+            // activation derivative on that layer's output, which IS the input (act_layer.hip).  No parameters, so no dW; nothing where the input reaches the observation through
+            // pool / Activation layers only: nobody reads it
+            const float* Yl = e->act_on[l]; const int sigma = L.cell_act;
+            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_actl_bwd(en->stream, L.out_feat, sigma, dpre, X, Yl, ncon, B, out, act_src); }});
         } else if (is_do(L.kind)) {
             // regenerates the forward's mask (the TD launch bumped the step counter in between: dropout.hip subtracts) and applies the producing layer's activation derivative on
             // that layer's own, unmasked output.  No parameters, so no dW; always a dX: the layer never reads the observation

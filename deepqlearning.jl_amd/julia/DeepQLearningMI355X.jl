@@ -115,12 +115,45 @@ function lower_layer(l, stream)::LayerDesc
     elseif l isa Flux.Recur && l.cell isa Flux.RNNCell      # Flux.params order Wi, Wh, b, state0 (h0) == the ABI's RNN block; act = the cell's σ (the engine accepts the first four codes there)
         return LayerDesc(4, ACT[l.cell.σ], stream, size(l.cell.Wi, 2), size(l.cell.Wh, 2), 0, 0, 0, 0, 0, 0)
     end
+    if l isa Base.Broadcast.BroadcastFunction      # Julia's own callable struct (>= 1.6; field f, recalled): BroadcastFunction(σ)(x) == σ.(x) -- the standalone activation layer, kind 14.
+        # No parameters (Flux.params finds nothing in it).  act = σ's code: the eleven of ACT, then ACT_NEEDS_X in order = 11..14 (gelu, swish, mish, hardswish: the layer reads the
+        # stored output of the layer in front, so the pre-activation their derivative needs is there).  n_in = n_out = 0: the engine takes the incoming feature count and shape
+        i = findfirst(g -> l.f === g, ACT_NEEDS_X)
+        code = haskey(ACT, l.f) ? ACT[l.f] : i === nothing ? -1 : 10 + i
+        code >= 0 || throw("DeepQLearningError: unsupported activation $(l.f) in Base.BroadcastFunction (supported: $(ACT_SUPPORTED) / gelu / swish / mish / hardswish); default parameters only: a closure such as x -> leakyrelu(x, 0.2f0) has no code")
+        return LayerDesc(14, code, stream, 0, 0, 0, 0, 0, 0, 0, 0)
+    end
     l isa Flux.BatchNorm && throw("DeepQLearningError: BatchNorm is not supported: it keeps running statistics, so the online pass on s, the pass on s', the target pass and the acting pass would compute different functions; of Flux's normalisation layers the MI355X engine runs LayerNorm(n) and GroupNorm(chs, G)")
     l isa Flux.InstanceNorm && throw("DeepQLearningError: InstanceNorm is not supported: its default is affine = false, which the MI355X engine does not run; GroupNorm(chs, chs) is instance normalisation with a per-channel affine")
     l isa Flux.Parallel && throw("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
-    throw("DeepQLearningError: unsupported layer $(typeof(l)) (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only))")
+    throw("DeepQLearningError: unsupported layer $(typeof(l)) (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only); a standalone activation is written Base.BroadcastFunction(relu): an anonymous closure such as x -> relu.(x) cannot be inspected and is skipped as glue, like x -> flattenbatch(x))")
 end
-is_glue(l) = l === identity || l === flattenbatch || l isa Function
+# What a Chain may hold beside layers.  ORDER MATTERS: Julia declares `struct BroadcastFunction{F} <: Function` (recalled), so the standalone activation layer IS a Function and
+# must be recognised BEFORE anything is taken for glue -- asked second, Base.BroadcastFunction(gelu) would be dropped and the network would train without its activations.
+#   is_act_layer   Base.BroadcastFunction(σ): a layer (kind 14), never glue
+#   glue           identity, flattenbatch and EVERY other function, named or anonymous, as before: no descriptor, the engine flattens between a map and a Dense by itself.
+#                  The reference's own models write the flatten as a closure -- Chain(x -> flattenbatch(x), Dense(...), ...) in its tests and benchmarks -- and a closure
+#                  cannot be inspected, so it cannot be told from x -> relu.(x).  THE LIMITATION: an activation written as a closure is skipped like any glue and the
+#                  network trains without it; a standalone activation must be written Base.BroadcastFunction(relu) (README, DESIGN section 4 "Activation layers")
+is_act_layer(l) = l isa Base.Broadcast.BroadcastFunction
+is_glue(l) = !is_act_layer(l) && (l === identity || l === flattenbatch || l isa Function)
+# the placement of the standalone activation layers, by name (the engine's build_layers holds the same rules by layer index for C callers): never the first layer, never the
+# network's output layer (the last base layer of a dueling network is fine), base chain only, no LayerNorm / Dropout directly behind it -- the NEXT DESCRIPTOR, whatever it
+# belongs to: a LayerNorm / Dropout that is the first inner layer of a SkipConnection directly behind the Activation reads the Activation's output and is refused too, as the engine refuses it
+const ACT_LAYER_NAMES = ("identity", "relu", "tanh", "sigmoid", "leakyrelu", "elu", "selu", "softplus", "softsign", "relu6", "hardtanh", "gelu", "swish", "mish", "hardswish")
+function check_act_layers(descs, dueling)
+    for (i, d) in enumerate(descs)
+        d.kind == 14 || continue
+        nm = "Base.BroadcastFunction($(ACT_LAYER_NAMES[d.act + 1]))"
+        i == 1 && throw("DeepQLearningError: $(nm) cannot be the first layer: its input is the stored output of the layer in front (an activation on the observation is not supported)")
+        d.stream == 0 || throw("DeepQLearningError: $(nm) is supported in the base chain only (not in a value / advantage stream)")
+        (!dueling && i == length(descs)) && throw("DeepQLearningError: $(nm) cannot be the network's output layer")
+        if i < length(descs) && descs[i + 1].stream == 0 && (descs[i + 1].kind == 7 || descs[i + 1].kind == 8)
+            throw("DeepQLearningError: $(descs[i + 1].kind == 7 ? "LayerNorm" : "Dropout") cannot directly follow $(nm): a LayerNorm / Dropout directly behind a standalone activation layer is not supported")
+        end
+    end
+    descs
+end
 # Flux 0.14 SkipConnection(layers, connection), fields layers, connection: layers(x) .+ x for connection === +.  No parameters of its own (Flux.params yields the inner
 # layers' in order, which flatparams below follows) and no activation.  Lowered as the inner layers' descriptors, then ONE join descriptor of kind 9 directly behind them:
 # cin = m, the number of inner descriptors; n_in = n_out = 0: the engine takes the feature count.  The engine checks the placement (base chain, on a feature vector, never
@@ -146,9 +179,14 @@ end
 function lower_skip!(descs, l, stream)
     l.connection === (+) || throw("DeepQLearningError: SkipConnection(layers, $(l.connection)) is not supported; the MI355X engine runs SkipConnection with the connection + only (vcat, *, closures and Parallel are not supported)")
     inner = l.layers isa Flux.Chain ? collect(l.layers.layers) : Any[l.layers]
+    any(is_act_layer, inner) && throw("DeepQLearningError: an Activation layer (Base.BroadcastFunction) inside a SkipConnection is not supported (a standalone activation stands in the base chain, in front of or behind the block; inside, use the fused activation of Dense / Conv)")      # asked BEFORE the glue filter: the layer is a Function
     real = filter(!is_glue, inner)
     any(x -> x isa Flux.GroupNorm, real) && throw("DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block)")
     if !isempty(descs) && is_map_desc(descs[end]) && !isempty(real) && all(is_map_layer, real)
+        return lower_skip_map!(descs, l, stream, inner)
+    end
+    k = length(descs); while k >= 1 && descs[k].kind == 14; k -= 1; end      # a standalone activation keeps its input's shape AND kind of shape: look through it
+    if 1 <= k < length(descs) && is_map_desc(descs[k]) && !isempty(real) && all(is_map_layer, real)
         return lower_skip_map!(descs, l, stream, inner)
     end
     m = 0
@@ -171,7 +209,7 @@ function lower(q)
     else
         for l in q.layers; lower_into!(descs, l, Int32(0)); end
     end
-    descs
+    check_act_layers(descs, q isa DeepQLearning.DuelingNetwork)
 end
 flatparams(q) = reduce(vcat, [vec(Float32.(w)) for w in Flux.params(q)])   # Flux.params order, Julia memory order: exactly the ABI layout
 

@@ -30,7 +30,10 @@ class _UnsupportedActivation:
 
 
 # not monotone: the derivative is no function of the output y, and the engine keeps only y (every backward epilogue differentiates from it)
+# ... as the fused activation of a Dense / Conv / LayerNorm / GroupNorm, that is.  A standalone Activation(σ) layer reads the stored output of the layer in front, so x is there:
+# the four are its codes 11..14 (LAYER_ACT_NAMES), taken by their .name
 gelu, swish, mish, hardswish = (_UnsupportedActivation(n) for n in ("gelu", "swish", "mish", "hardswish"))
+LAYER_ACT_NAMES = ACT_NAMES + ("gelu", "swish", "mish", "hardswish")      # index = the DQN_ACT_* code on an Activation layer (kind 14), the only kind that takes 11..14
 
 
 def _act_code(l):
@@ -302,6 +305,31 @@ class Dropout:
         return []
 
 
+class Activation:
+    """A standalone activation layer: Julia's Base.Broadcast.BroadcastFunction(σ) in a Chain (BroadcastFunction(σ)(x) == σ.(x); recalled, not executed here).  y = σ.(x) on
+    whatever the layer in front yields -- a feature vector or a (c, h, w) map, kept.  σ is any of the eleven codes or of nn.gelu / nn.swish / nn.mish / nn.hardswish (NNlib's
+    tanh-form gelu).  No parameters: Flux.params skips the layer.  Base chain only, never the first or the output layer (the last base layer of a dueling network is fine), not
+    inside a SkipConnection; a LayerNorm or Dropout may not directly follow it.  What it is for: the post-add relu of a ResNet-v1 block, and the four activations a fused layer
+    cannot run (DESIGN.md section 4 "Activation layers")."""
+    kind = "activation"
+
+    def __init__(self, sigma):
+        if isinstance(sigma, _UnsupportedActivation) and sigma.name in LAYER_ACT_NAMES:
+            self.code = LAYER_ACT_NAMES.index(sigma.name)
+        elif isinstance(sigma, (int, np.integer)) and not isinstance(sigma, bool) and 0 <= int(sigma) < len(LAYER_ACT_NAMES):
+            self.code = int(sigma)
+        else:
+            raise _abi.DQNError(f"DeepQLearningError: unsupported activation {sigma!r} on Activation (supported: {' / '.join(LAYER_ACT_NAMES)}, with NNlib's default parameters only; "
+                                "a closure cannot be inspected)")
+        self.act = identity      # the layer has no fused activation: σ is the layer (lowered into dqn_layer_desc.act from .code)
+
+    def __repr__(self):
+        return f"Activation({LAYER_ACT_NAMES[self.code]})"
+
+    def shapes(self):   # Flux.params holds nothing for the layer
+        return []
+
+
 class LSTM:
     """Flux LSTM(in, out) = Recur(LSTMCell): params Wi (4out,in), Wh (4out,out), b (4out, forget gate bias 1), state0 (h0, c0)."""
     kind = "lstm"
@@ -439,6 +467,8 @@ def lower(net):
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} is supported in the base chain only (not in a value / advantage stream)")
         if first:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} cannot be the first layer: a skip block's input is never the observation (it must follow a Dense, recurrent, LayerNorm or Dropout layer or another skip block)")
+        if any(getattr(l, "kind", None) == "activation" for l in blk.layers):
+            raise _abi.DQNError(f"DeepQLearningError: an Activation layer inside a SkipConnection is not supported (a standalone activation stands in the base chain, in front of or behind the block; inside, use the fused activation of Dense / Conv): {blk!r}")
         if any(getattr(l, "kind", None) == "groupnorm" for l in blk.layers):
             raise _abi.DQNError(f"DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block): {blk!r}")
         on_map = prev_kind in ("conv", "groupnorm") + POOL_KINDS or (prev_kind == "skip" and map_join[0])
@@ -489,6 +519,13 @@ def lower(net):
         out.append(d)
         map_join[0] = True
 
+    def shape_kind(layers, i):
+        # the kind of the layer whose output shape layer i reads: the layer in front, looking through Activation layers (they keep the shape AND the kind of shape)
+        j = i - 1
+        while j >= 0 and getattr(layers[j], "kind", None) == "activation":
+            j -= 1
+        return getattr(layers[j], "kind", None) if j >= 0 else None
+
     def add(chain, stream):
         layers = list(chain)
         for i, l in enumerate(layers):
@@ -496,10 +533,26 @@ def lower(net):
             if getattr(l, "kind", None) == "parallel":
                 raise _abi.DQNError("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
             if getattr(l, "kind", None) == "skip":
-                add_skip(l, stream, not out, getattr(layers[i - 1], "kind", None) if i > 0 else None, i + 1 == len(layers) and chain is top)
+                add_skip(l, stream, not out, shape_kind(layers, i), i + 1 == len(layers) and chain is top)
                 continue
+            if getattr(l, "kind", None) == "activation":      # act = σ (0..14); n_in == n_out == 0: the engine fills in the incoming feature count and keeps the incoming shape
+                if not out:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the first layer: its input is the stored output of the layer in front (an activation on the observation is not supported)")
+                if stream != _abi.STREAM_BASE:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+                if i + 1 == len(layers) and chain is top:
+                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                d.kind, d.act, d.stream = _abi.LAYER_ACTIVATION, l.code, stream
+                out.append(d)
+                continue
+            if callable(l) and getattr(l, "kind", None) is None and not isinstance(l, type):
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r}: a closure cannot be inspected; write a standalone activation as Activation(relu) "
+                                    "(Julia: Base.BroadcastFunction(relu)), not as x -> relu.(x)")
             if getattr(l, "kind", None) not in ("dense", "dropout", "lstm", "gru", "rnn", "conv", "groupnorm", "layernorm") + POOL_KINDS:
-                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only))")
+                raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only); a standalone activation is Activation(σ))")
+            if l.kind in ("layernorm", "dropout") and i > 0 and getattr(layers[i - 1], "kind", None) == "activation":
+                raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot directly follow {layers[i - 1]!r}: a {type(l).__name__} directly behind a standalone Activation layer is not supported "
+                                    "(it must directly follow a Dense, recurrent" + (" or LayerNorm" if l.kind == "dropout" else "") + " layer)")
             d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":
                 d.kind, d.n_in, d.n_out = _abi.LAYER_DENSE, l.n_in, l.n_out
@@ -574,7 +627,7 @@ def glorot_params(net, seed=1):
     rng = np.random.default_rng(seed)
     parts = []
     for l in all_layers(net):
-        if l.kind in POOL_KINDS + ("dropout",):      # no parameters
+        if l.kind in POOL_KINDS + ("dropout", "activation"):      # no parameters
             continue
         if l.kind == "groupnorm":      # β = zeros, then γ = ones
             parts += [np.zeros(l.chs, np.float32), np.ones(l.chs, np.float32)]

@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11, DQN_LAYER_ADAPTIVEMAXPOOL = 12, DQN_LAYER_ADAPTIVEMEANPOOL = 13 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11, DQN_LAYER_ADAPTIVEMAXPOOL = 12, DQN_LAYER_ADAPTIVEMEANPOOL = 13, DQN_LAYER_ACTIVATION = 14 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -64,6 +64,17 @@ enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GR
 enum { DQN_ACT_IDENTITY = 0, DQN_ACT_RELU = 1, DQN_ACT_TANH = 2, DQN_ACT_SIGMOID = 3, DQN_ACT_LEAKYRELU = 4, DQN_ACT_ELU = 5, DQN_ACT_SELU = 6, DQN_ACT_SOFTPLUS = 7,
        DQN_ACT_SOFTSIGN = 8, DQN_ACT_RELU6 = 9, DQN_ACT_HARDTANH = 10 };
 #define DQN_ACT_LAST DQN_ACT_HARDTANH
+/* Four more codes, valid on DQN_LAYER_ACTIVATION ONLY (every other kind keeps refusing codes above DQN_ACT_LAST): the standalone activation layer's input is the stored
+ * output of the layer in front, so x is there and the derivative is taken from it.  Float64, rounded once; the backward is ONE fp32 multiply dy * (float)sigma'(x).
+ *   code          forward                                                                    sigma'(x), Float64
+ *   GELU      11  0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3)))   (NNlib's tanh form)         0.5 (1 + t) + 0.5 x (1 - t^2) sqrt(2/pi) (1 + 3 * 0.044715 x^2)
+ *   SWISH     12  x s,  s = 1 / (1 + exp(-x))                                                  s (1 + x (1 - s))
+ *   MISH      13  x t,  t = tanh(softplus(x))  (softplus as code 7)                             t + x (1 - t^2) s
+ *   HARDSWISH 14  x clamp((x + 3) / 6, 0, 1)                                                   x < -3 ? 0 : x > 3 ? 1 : (2x + 3) / 6
+ * On that layer the eleven codes above run the table's forward on the stored input and the table's derivative from the layer's own output: Dense(n, m) -> Activation(sigma)
+ * trains with the bits of Dense(n, m, sigma).  Which value the kinks take is NNlib's rule and unpinned. */
+enum { DQN_ACT_GELU = 11, DQN_ACT_SWISH = 12, DQN_ACT_MISH = 13, DQN_ACT_HARDSWISH = 14 };
+#define DQN_ACT_LAYER_LAST DQN_ACT_HARDSWISH
 enum { DQN_STREAM_BASE = 0, DQN_STREAM_VAL = 1, DQN_STREAM_ADV = 2 };
 enum { DQN_OBS_F32 = 0, DQN_OBS_U8 = 1 }; /* u8: stored byte, consumed as (float)byte/255f0 (test/test_env.jl:59) */
 enum { DQN_NET_ONLINE = 0, DQN_NET_TARGET = 1 };
@@ -104,6 +115,11 @@ typedef struct {
                                           y = act(gamma_ch * (x - mu) / sqrt(var + eps) + beta_ch): eps INSIDE the root (torch's law, not LayerNorm's).  Parameters in Flux.params order:
                                           beta (c, zeros), gamma (c, ones) -- bias FIRST.  Directly behind a Conv, a MaxPool / MeanPool, a convolutional skip block or another GroupNorm; base
                                           chain only, never the first or the output layer, not inside a skip block, single GPU only; its plan entry is all zeros and ignored;
+                                          Activation (kind 14; Julia's Base.Broadcast.BroadcastFunction(sigma) in a Chain, recalled, not executed): y = sigma(x) per element on the incoming
+                                          feature vector or (c, h, w) map, whose shape and kind of shape it keeps.  act = any of the fifteen codes 0..14, stream = BASE, n_in == n_out == the
+                                          incoming feature count (or both 0: the engine fills them in), every other slot 0.  No parameters (Flux.params skips the layer); its plan entry is
+                                          all zeros and ignored.  Base chain only, never the first or the output layer (the last base layer of a dueling network is fine), not inside a skip
+                                          block, single GPU only; a LayerNorm or Dropout may not directly follow it;
                                           Dropout(p), dims = : (Flux 0.14 automatic mode, recalled, not executed): n_in == n_out == the incoming feature count (or both 0: the engine fills them
                                           in), act = IDENTITY, stream = BASE, p as its Float64 BIT PATTERN, low word in cin, high word in cout (finite, 0 <= p < 1), every other slot 0.
                                           No parameters (Flux.params skips the layer); its plan entry is all zeros and ignored.  ACTIVE only in the online network's pass on the s columns
