@@ -23,6 +23,7 @@ LAYER_SKIPADD = 9                         # the join of a Flux SkipConnection(la
 LAYER_GROUPNORM = 11                      # Flux GroupNorm(chs, G, act; eps) on a (c, h, w) map: cin == cout == chs (or both 0), kh = G, kw = the fp32 bit pattern of eps, n_in == n_out == c * h * w (or both 0); Flux.params holds beta (c), THEN gamma (c)
 LAYER_SKIPADD_MAP = 10                    # the join of a CONVOLUTIONAL SkipConnection(layers, +) block on a (c, h, w) map: SKIPADD's descriptor shape (cin = m; n_in == n_out == c * h * w or both 0); inner layers = Convs with pad != 0, entry = a Conv / pool / another such join
 LAYER_ACTIVATION = 14                     # the standalone activation layer (Julia: Base.Broadcast.BroadcastFunction(σ) in a Chain): act = σ, any of 0..14; n_in == n_out == the incoming feature count (or both 0); stream BASE; every other slot 0; no parameters; keeps the incoming shape (vector or map)
+LAYER_CONV_DG = 15                        # Conv(...; dilation = (dh, dw), groups = g) / DepthwiseConv: cin, cout FULL channel counts, kh, kw, sh, sw as Conv; n_in = pad_h | pad_w << 16, n_out = dh | dw << 8 | g << 16; weight (cout, cin/g, kh, kw); base chain only
 ACT_GELU, ACT_SWISH, ACT_MISH, ACT_HARDSWISH = 11, 12, 13, 14      # valid on LAYER_ACTIVATION only: their derivative needs the input, which only that layer has (include/dqn_mi355x.h has the table)
 LAYER_ADAPTIVEMAXPOOL, LAYER_ADAPTIVEMEANPOOL = 12, 13     # Flux AdaptiveMaxPool / AdaptiveMeanPool((ow, oh)) and GlobalMaxPool / GlobalMeanPool (output (1, 1)): kh, kw = the OUTPUT size (oh, ow), sh = sw = n_in = n_out = 0; the engine resolves the window from the incoming map (stride = in ÷ out, k = in - (out - 1) * stride); parameter-free
 STREAM_BASE, STREAM_VAL, STREAM_ADV = 0, 1, 2

@@ -38,7 +38,8 @@ def julia_param_shapes(net):
         if l.kind == "dense":
             out += [((l.n_out, l.n_in), l.n_out * l.n_in), ((l.n_out,), l.n_out)]
         elif l.kind == "conv":
-            out += [((l.kw, l.kh, l.cin, l.cout), l.kw * l.kh * l.cin * l.cout), ((l.cout,), l.cout)]
+            cg = l.cin // getattr(l, "groups", 1)      # Flux: the weight of a grouped Conv is (kw, kh, cin ÷ groups, cout)
+            out += [((l.kw, l.kh, cg, l.cout), l.kw * l.kh * cg * l.cout), ((l.cout,), l.cout)]
         elif l.kind == "lstm":   # Flux 0.14 Recur(LSTMCell): Wi, Wh, b, state0 = (h0, c0) as (out, 1) matrices
             h = l.n_out
             out += [((4 * h, l.n_in), 4 * h * l.n_in), ((4 * h, h), 4 * h * h), ((4 * h,), 4 * h), ((h, 1), h), ((h, 1), h)]

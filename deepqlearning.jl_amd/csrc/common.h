@@ -34,6 +34,7 @@ struct LayerDev {
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
     int ph, pw;                        // Conv: symmetric zero padding per axis (dqn_layer_desc n_in / n_out slots); ih, iw stay the UNPADDED map, oh = (ih + 2 ph - kh) / sh + 1
     int src2;                          // DQN_LAYER_SKIPADD / _MAP: the block's entry P, the producer the block's first inner layer reads (src = the last inner layer K); -1 on every other layer
+    int dh, dw, groups;                // DQN_LAYER_CONV_DG: dilation per axis and the group count (conv_dg.hip); cin, cout stay the FULL channel counts, K = (cin / groups) * kh * kw.  0 on every other layer
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
@@ -52,7 +53,11 @@ static inline bool is_global_pool(const LayerDev& L) { return is_adaptive_pool(L
 // EXTERNAL offsets are eb_off, then ew_off = eb_off + c (engine.hip).  Launched alone on its level, as pools and LayerNorm are
 static inline __host__ __device__ bool is_gn(int kind) { return kind == DQN_LAYER_GROUPNORM; }
 static inline float gn_eps(const LayerDev& L) { if (L.kw == 0) return 1e-5f; float f; memcpy(&f, &L.kw, sizeof f); return f; }
-static inline __host__ __device__ bool has_map(int kind) { return kind == DQN_LAYER_CONV || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP || is_gn(kind); }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow; a GroupNorm keeps the incoming one)
+// Flux Conv(...; dilation, groups) / DepthwiseConv (conv_dg.hip): a kind of its own, launched alone on its level as the padded Conv is; the pad-0 GEMM bodies never see it.
+// is_conv_kind: what the plan rules say of "a conv" (dx_kc counts RAW taps, dw_kc counts positions * samples) holds for both kinds
+static inline __host__ __device__ bool is_cdg(int kind) { return kind == DQN_LAYER_CONV_DG; }
+static inline __host__ __device__ bool is_conv_kind(int kind) { return kind == DQN_LAYER_CONV || kind == DQN_LAYER_CONV_DG; }
+static inline __host__ __device__ bool has_map(int kind) { return is_conv_kind(kind) || is_pool(kind) || kind == DQN_LAYER_SKIPADD_MAP || is_gn(kind); }      // the layer's output is a (cout, oh, ow) map (a map block's join carries its block's map in cout, oh, ow; a GroupNorm keeps the incoming one)
 // the standalone activation layer (act_layer.hip; Julia's Base.Broadcast.BroadcastFunction(σ) in a Chain): y = σ(x) per element, parameter-free (K = N = 0 as a pool's).  The code σ
 // -- any of 0 .. DQN_ACT_LAYER_LAST -- lives in `cell_act`; `act` stays IDENTITY, as a recurrent layer's does: the generic forward / dX epilogues read `act`, so the layer above
 // writes its RAW input gradient into this layer's dY and the head kernels read its output as finished.  It keeps its input's shape AND its kind of shape: behind a map it
@@ -94,11 +99,11 @@ struct KindTraits {
     bool output_ok;            // may be the network's output layer
     const char *a_noun, *plural;      // what the refusals call it (plain text, printed through %s); plural != null: single GPU only (dqn_comm_init and DQN_SIM_WORLD refuse the network)
 };
-enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_ACT, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
+enum { KT_CPAD, KT_POOL, KT_LN, KT_DO, KT_SKIP, KT_GN, KT_ACT, KT_CDG, KT_OWN_LEVEL /* rows below: the GEMM kinds */, KT_CONV = KT_OWN_LEVEL, KT_DENSE, KT_RECURRENT };
 static inline int kind_row(const LayerDev& L) {
     switch (L.kind) {
     case DQN_LAYER_CONV: return (L.ph || L.pw) ? KT_CPAD : KT_CONV;      case DQN_LAYER_MAXPOOL: case DQN_LAYER_MEANPOOL: case DQN_LAYER_ADAPTIVEMAXPOOL: case DQN_LAYER_ADAPTIVEMEANPOOL: return KT_POOL;
-    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;      case DQN_LAYER_ACTIVATION: return KT_ACT;
+    case DQN_LAYER_LAYERNORM: return KT_LN;      case DQN_LAYER_DROPOUT: return KT_DO;      case DQN_LAYER_SKIPADD: case DQN_LAYER_SKIPADD_MAP: return KT_SKIP;      case DQN_LAYER_GROUPNORM: return KT_GN;      case DQN_LAYER_ACTIVATION: return KT_ACT;      case DQN_LAYER_CONV_DG: return KT_CDG;
     case DQN_LAYER_LSTM: case DQN_LAYER_GRU: case DQN_LAYER_RNN: return KT_RECURRENT;      default: return KT_DENSE;
     }
 }
@@ -112,6 +117,7 @@ static inline const KindTraits& kind_traits(const LayerDev& L) {
         /* KT_SKIP      */ {"skip",    true,     false,    false,     true,           true,             false, "a skip block", "skip blocks"},
         /* KT_GN        */ {"gn",      true,     false,    false,     true,           true,             false, "a GroupNorm layer", "GroupNorm layers"},
         /* KT_ACT       */ {"act",     true,     false,    false,     true,           true,             false, "an Activation layer", "Activation layers"},
+        /* KT_CDG       */ {"cdg",     true,     true,     false,     false,          true,             true,  "a Conv with dilation / groups", "dilated / grouped convolutions"},
         /* KT_CONV      */ {"conv",    false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_DENSE     */ {"dense",   false,    true,     true,      false,          false,            true,  nullptr, nullptr},
         /* KT_RECURRENT */ {"dense",   false,    true,     false,     false,          false,            true,  nullptr, nullptr},      // named after its batched part, the dense view Gx = Wi*x (gx_view)
@@ -1164,6 +1170,10 @@ void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const vo
 void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
 // dY (or null): the addend of a map block's fused entry, [in_feat][B]: out = dact(acc + dY, ysrc, act_src).  May be the buffer dpre points at (single inner layer): both are read only
 void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf, const float* dY = nullptr);
+// conv_dg.hip: DQN_LAYER_CONV_DG (dilation, groups, depthwise); the arguments of the padded conv's launchers, without the residual operands
+void launch_cdg_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8);
+void launch_cdg_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
+void launch_cdg_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf);
 bool mfma_fwd_ok(const LayerDev& L, int ncols);
 bool mfma_dw_ok(const LayerDev& L, int B);
 bool mfma_dx_ok(const LayerDev& L, int B, int ldy);

@@ -62,7 +62,7 @@ extern "C" int dqn_hparams_default(dqn_hparams* hp) {
 }
 
 // THE single-GPU rule: the exchange paths (operand all-gather, all-reduce) have never run with an own-level kind's launches in the program -- refused instead of claimed.
-// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block, GroupNorm, Activation), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
+// Kinds in the table's order (padded conv, pool, LayerNorm, Dropout, skip block, GroupNorm, Activation, dilated / grouped conv), then layers: Dense -> LayerNorm -> Conv(1x1) -> MaxPool(1x1) -> Dense, a LayerNorm at layer 1 and a pool at layer 3, names the pool
 static int refuse_replicas(const char* who, const LayerDev* L, int nl) {
     for (int r = 0; r < KT_OWN_LEVEL; r++) for (int i = 0; i < nl; i++) {
         const KindTraits& t = kind_traits(L[i]); if (kind_row(L[i]) != r || !t.plural) continue;
@@ -99,6 +99,22 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
             l.ih = h; l.iw = w; l.oh = (h + 2 * l.ph - l.kh) / l.sh + 1; l.ow = (w + 2 * l.pw - l.kw) / l.sw + 1;      // trailing rows / columns of the extended map no window covers are dropped
             l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
+        } else if (is_cdg(l.kind)) {      // Flux Conv(...; dilation, groups) / DepthwiseConv (conv_dg.hip): a block of its own, so that no message of the Conv block above changes
+            l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
+            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: dilated / grouped Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
+            // pad_h | pad_w << 16 rides in n_in, dh | dw << 8 | g << 16 in n_out (include/dqn_mi355x.h)
+            if (d[i].n_in < 0 || d[i].n_out < 0) return fail("layer %d: dilated / grouped Conv: the packed slots n_in = %d (pad_h | pad_w << 16) and n_out = %d (dh | dw << 8 | groups << 16) must not be negative", i, d[i].n_in, d[i].n_out);
+            l.ph = d[i].n_in & 0xffff; l.pw = d[i].n_in >> 16; l.dh = d[i].n_out & 0xff; l.dw = (d[i].n_out >> 8) & 0xff; l.groups = d[i].n_out >> 16;
+            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a Conv with dilation (%d, %d) / groups %d is supported in the base chain only (not in a value / advantage stream)", i, l.dh, l.dw, l.groups);
+            if (l.dh < 1 || l.dw < 1) return fail("layer %d: Conv dilation (%d, %d) must be at least 1 per axis", i, l.dh, l.dw);
+            if (l.kh < 1 || l.kw < 1 || l.sh < 1 || l.sw < 1) return fail("layer %d: dilated / grouped Conv kernel (%d, %d) / stride (%d, %d) must be positive", i, l.kh, l.kw, l.sh, l.sw);
+            if (l.cin < 1 || l.cout < 1 || l.groups < 1 || l.cin % l.groups || l.cout % l.groups) return fail("layer %d: Conv groups = %d must be >= 1 and divide cin = %d and cout = %d", i, l.groups, l.cin, l.cout);
+            if (l.cin != c) return fail("layer %d: dilated / grouped Conv cin %d != incoming channels %d", i, l.cin, c);
+            { const long long eh = (long long)(l.kh - 1) * l.dh, ew = (long long)(l.kw - 1) * l.dw;      // the dilated extent minus one, per axis
+              if (l.ph > eh || l.pw > ew) return fail("layer %d: Conv pad (%d, %d) is larger than the dilated kernel extent - 1 = (%lld, %lld): a window would lie in the padding alone", i, l.ph, l.pw, eh, ew);
+              if (eh + 1 > h + 2 * l.ph || ew + 1 > w + 2 * l.pw) return fail("layer %d: Conv kernel (%d, %d) with dilation (%d, %d) spans (%lld, %lld) and does not fit the %dx%d input map extended by pad (%d, %d)", i, l.kh, l.kw, l.dh, l.dw, eh + 1, ew + 1, h, w, l.ph, l.pw);
+              l.ih = h; l.iw = w; l.oh = (int)((h + 2 * l.ph - eh - 1) / l.sh) + 1; l.ow = (int)((w + 2 * l.pw - ew - 1) / l.sw) + 1; }
+            l.K = (l.cin / l.groups) * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
         } else if (is_adaptive_pool(l.kind)) {      // Flux AdaptiveMaxPool / AdaptiveMeanPool((ow, oh)), GlobalMaxPool / GlobalMeanPool (output (1, 1)): kh, kw carry the OUTPUT size; resolved here into a pool's geometry
             const char* nm = l.kind == DQN_LAYER_ADAPTIVEMAXPOOL ? "AdaptiveMaxPool" : "AdaptiveMeanPool";
             if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, nm, l.stream);
@@ -181,6 +197,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                 if (is_skip(L[j].kind)) return fail("layer %d: the convolutional skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
                 if (is_actl(L[j].kind)) return fail("layer %d: the convolutional skip block holds an Activation layer (layer %d); its inner layers are Conv layers with pad != 0 only (a standalone activation inside a skip block is not supported)", i, j);
                 if (is_pool(L[j].kind)) return fail("layer %d: the convolutional skip block holds a MaxPool / MeanPool layer (layer %d); its inner layers are Conv layers with pad != 0 only", i, j);
+                if (is_cdg(L[j].kind)) return fail("layer %d: the convolutional skip block holds a Conv with dilation (%d, %d) / groups %d (layer %d); its inner layers are Conv layers with pad != 0, dilation 1 and groups 1 only (dilated and grouped residual blocks are not supported)", i, L[j].dh, L[j].dw, L[j].groups, j);
                 if (L[j].kind == DQN_LAYER_CONV && !is_padded(L[j])) return fail("layer %d: the convolutional skip block holds a Conv with pad 0 (layer %d, kernel (%d, %d)); its inner layers are Conv layers with pad != 0 only", i, j, L[j].kh, L[j].kw);
                 if (L[j].kind != DQN_LAYER_CONV) return fail("layer %d: the convolutional skip block holds %s (layer %d); its inner layers are Conv layers with pad != 0 only", i,
                                                              is_recurrent(L[j].kind) ? "a recurrent layer" : is_ln(L[j].kind) ? "a LayerNorm layer" : is_do(L[j].kind) ? "a Dropout layer" : is_gn(L[j].kind) ? "a GroupNorm layer" : "a Dense layer", j);
@@ -207,6 +224,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
                 if (is_recurrent(L[j].kind)) return fail("layer %d: the skip block holds a recurrent layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only", i, j);
                 if (is_actl(L[j].kind)) return fail("layer %d: the skip block holds an Activation layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (a standalone activation inside a skip block is not supported)", i, j);
                 if (is_gn(L[j].kind)) return fail("layer %d: the skip block holds a GroupNorm layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (GroupNorm inside a skip block is not supported)", i, j);
+                if (is_cdg(L[j].kind)) return fail("layer %d: the skip block holds a Conv with dilation (%d, %d) / groups %d (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (dilated and grouped residual blocks are not supported)", i, L[j].dh, L[j].dw, L[j].groups, j);
                 if (has_map(L[j].kind)) return fail("layer %d: the skip block holds a Conv / MaxPool / MeanPool layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (convolutional residual blocks are not supported)", i, j);
             }
             const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
@@ -296,14 +314,14 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
         //  picker's workgroup threshold, which then chose 16-channel tiles; with those tiles chosen for dense layers outright (fwd_pick_nt, nn_gemm.hip) seven slabs of 448 win:
         //  forward launch 14.9 (448, 32-channel tiles) -> 14.0 (544, 16) -> 13.2 us (448, 16); profiles/r06_zl_plan_probe_fwd.txt, r06_zo_fwd_nt_probe.txt)
         else if (L[i].kind == DQN_LAYER_DENSE && L[i].N < 16 && L[i].K >= 128) out[i].fwd_kc = 32;   // heads: 16+ short chains instead of one long one (at any batch: unsplit, the B = 512 head launch took 25 us instead of 7 + 6)
-        out[i].dx_kc = (L[i].kind != DQN_LAYER_CONV && L[i].N > 512) ? 256 : 0;
+        out[i].dx_kc = (!is_conv_kind(L[i].kind) && L[i].N > 512) ? 256 : 0;
         // small batches (the 32 x 32 output tiles of k_dx_units, nn_gemm.hip): cut the dX contraction so that an output tile has up to four
         // independent chains, one per wave -- dense: N/4 (N/2 per stream at the dueling join, where two sources meet); conv: RAW taps per chunk
         // such that an interior input position has <= 4 chunks with a valid tap.  Only the rounding order changes.
         const bool join = L[i].stream != DQN_STREAM_BASE && L[i].src >= 0 && L[L[i].src].stream == DQN_STREAM_BASE;
         if (L[i].kind == DQN_LAYER_DENSE && L[i].N <= 512 && B <= 64 && L[i].N >= 128) {
             const int S = join ? 2 : 4; const int kc = ((L[i].N + S - 1) / S + 31) / 32 * 32; if (kc < L[i].N) out[i].dx_kc = kc;
-        } else if (L[i].kind == DQN_LAYER_CONV && B <= 64) {
+        } else if (is_conv_kind(L[i].kind) && B <= 64) {
             const int valid = ((L[i].kh + L[i].sh - 1) / L[i].sh) * ((L[i].kw + L[i].sw - 1) / L[i].sw), raw = ((valid + 3) / 4) * L[i].sw;
             // r06: ... but only where the chain of an output element is longer than eight K tiles (valid taps x channels > 256): the 4x4 / stride-2 layer of the Nature net has four
             // valid taps x 64 channels and runs faster as ONE chain per element than as four (its launch 12.6 -> 11.8 us with the dW workgroups of the rule below beside it;
@@ -315,7 +333,7 @@ static void default_plan(const LayerDev* L, int n, int B, dqn_layer_plan* out, c
         // B-long chain per output.  Feed-forward networks compute the heads' dW as tail tasks of the widest backward launch, where a 512-deep chain
         // hides, and unsplit gradients keep the slab sums foldable into the Adam launch (r03: the separate reduce launch cost 12-19 us at config 5)
         if (L[i].kind == DQN_LAYER_DENSE && L[i].N < 16 && B >= 128 && rec) out[i].dw_kc = 64;
-        if (L[i].kind == DQN_LAYER_CONV) {   // positions per chunk so that (K/64 row tiles) x chunks >= ~512 workgroups
+        if (is_conv_kind(L[i].kind)) {   // positions per chunk so that (K/64 row tiles) x chunks >= ~512 workgroups
             const int tgt = 512;      // (r03: 256 / 128 workgroups measured no faster)
             const int mrows_ = (L[i].K + 63) / 64, st = (tgt + mrows_ - 1) / mrows_; int ppc = L[i].npos / st; if (ppc < 1) ppc = 1;
             // r06: an EVEN number of 32-sample K tiles per chunk where a chunk is 3+ of them -- the dW loop is software-pipelined two tiles per round and an odd count pays a
@@ -396,11 +414,11 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
             // instead of running into a failed allocation there
             const LayerDev& l = e->L[i]; const size_t cap = (size_t)1 << 28;
             const size_t Bc_ = (size_t)e->B * (hp->recurrence ? std::max(1, hp->trace_length) : 1), ncon_ = hp->double_q ? 2 * Bc_ : Bc_;
-            const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = l.dw_kc > 0 ? dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc_, INT_MAX), l.dw_kc) : 1, sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1;
+            const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = l.dw_kc > 0 ? dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc_, INT_MAX), l.dw_kc) : 1, sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1;
             if ((sf > 1 && sf * l.out_feat * ncon_ > cap) || (sw > 1 && sw * ((size_t)l.K + 1) * l.N > cap) || (sx > 1 && sx * l.in_feat * Bc_ > cap))
                 return fail("plan: layer %d: (fwd_kc, dx_kc, dw_kc) = (%d, %d, %d) cuts its sums into %zu / %zu / %zu chunks: the slabs of one layer may hold at most 2^28 floats", i, l.fwd_kc, l.dx_kc, l.dw_kc, sf, sx, sw);
         }
-        if (e->L[i].kind == DQN_LAYER_CONV && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
+        if (is_conv_kind(e->L[i].kind) && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
         if (e->L[i].dw_kc < 0 && (!hp->recurrence || e->B % (-e->L[i].dw_kc))) return fail("plan: dw_kc < 0 (column-group chunks of %d batch columns) needs recurrence = true and a group size that divides batch_size", -e->L[i].dw_kc);
     }
     HIPCHK(hipSetDevice(device));
@@ -457,7 +475,7 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
         else DM(e->act_tg[i], (size_t)l.out_feat * Bc);
         const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
         const size_t sw = dqn_nchunks(l.npos * Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
-        const size_t sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
+        const size_t sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
         jmax = std::max(jmax, (size_t)l.in_feat * Bc);
         if (is_gn(l.kind)) pmax = std::max(pmax, gn_part_floats(l, e->ncon));      // the chunk statistics of the launches outside the train program (launch_layer_fwd)
         if (is_recurrent(l.kind)) {
@@ -753,6 +771,7 @@ void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const f
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
     else if (is_gn(l.kind)) { launch_gn_stat(st, l, X, ldx, col0, ncols, partials); launch_gn_norm(st, l, P, X, ldx, col0, ncols, Y, partials, ln_stat); }      // partials: >= gn_part_floats(l, ncols) floats
     else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
+    else if (is_cdg(l.kind)) launch_cdg_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);      // a dilated / grouped conv (conv_dg.hip)
     else if (!(use_mfma && launch_mfma_fwd(st, l, P, X, ldx, col0, ncols, Y, partials))) launch_valu_fwd(st, l, P, X, ldx, col0, ncols, Y, partials);
 }
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name, const float* X2, int ldx2) {
@@ -1285,7 +1304,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
             LayerDev& l = e->L[i]; l.fwd_kc = defp[i].fwd_kc; l.dx_kc = defp[i].dx_kc; l.dw_kc = defp[i].dw_kc;
             const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
             const size_t sw = dqn_nchunks(l.npos * e->Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
-            const size_t sx = l.kind != DQN_LAYER_CONV ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * e->Bc);
+            const size_t sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * e->Bc);
         }
         HIPCHK(hipMemcpy(e->L_dev, e->L, sizeof(LayerDev) * e->nl, hipMemcpyHostToDevice));
         if (pmax > e->partials_elems) { hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * pmax); e->partials_elems = pmax; }

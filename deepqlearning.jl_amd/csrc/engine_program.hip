@@ -9,7 +9,7 @@
 float* palloc(dqn_engine* e, size_t n) { float* d = nullptr; hipMalloc((void**)&d, n * 4); (e->alloc_sink ? *e->alloc_sink : e->prog_allocs).push_back(d); return d; }
 bool same_geo(const LayerDev& a, const LayerDev& b) {
     return a.kind == b.kind && a.act == b.act && a.K == b.K && a.N == b.N && a.npos == b.npos && a.cin == b.cin && a.kh == b.kh && a.kw == b.kw &&
-           a.sh == b.sh && a.sw == b.sw && a.ph == b.ph && a.pw == b.pw && a.ih == b.ih && a.iw == b.iw && a.fwd_kc == b.fwd_kc && a.src == b.src;
+           a.sh == b.sh && a.sw == b.sw && a.ph == b.ph && a.pw == b.pw && a.dh == b.dh && a.dw == b.dw && a.groups == b.groups && a.ih == b.ih && a.iw == b.iw && a.fwd_kc == b.fwd_kc && a.src == b.src;
 }
 void add_valu(dqn_engine* e, std::vector<VTask>& pend, const VTask& t) { pend.push_back(t); }
 // prio: the step's priority block (update_priorities! + the next step's index draw) rides as workgroup 0 of this launch
@@ -300,7 +300,7 @@ int build_program(dqn_engine* e) {
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
         if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && !is_pool(e->L[l0].kind) /* pool.hip reads floats: a pool as the first layer keeps the fp32 arena */ && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
-            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || (gemm_fwd_eligible(e->L[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; }
+            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || is_cdg(e->L[l0].kind) /* and so does conv_dg.hip */ || (gemm_fwd_eligible(e->L[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; }
     }
     // ---------------- small batches: the head level (forwards of both nets), the TD kernel and the head layers' dX run as ONE launch with a
     // workgroup per batch column (k_head_td); the heads' dW/db and the loss fold ride as tail tasks of the next backward launch
@@ -578,6 +578,11 @@ int build_program(dqn_engine* e) {
             // column sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
             const float* P = e->p_on; const float* stat = ln_stat[l]; float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
             e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
+        } else if (is_cdg(L.kind)) {
+            // a dilated / grouped conv (conv_dg.hip): the padded conv's two launches with its own kernels; never inside a skip block, so no fused entry
+            float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8; const float* P = e->p_on;
+            e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_cdg_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
+            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cdg_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
         } else {
             // a padded conv (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then -- unless the layer
             // reads the observation -- dX with the producing layer's activation derivative

@@ -572,6 +572,12 @@ __global__ void k_convert_params(const LayerDev* __restrict__ layers, int nl, co
                 const int ky = L.kh - 1 - yy, kx = L.kw - 1 - xx;
                 e = ((size_t)(ci * L.kh + ky) * L.kw + kx) * L.cout + co;
             }
+            if (L.kind == DQN_LAYER_CONV_DG) {   // external ((co*(cin/g) + ci)*kh + yy)*kw + xx with ci inside co's group; internal row k = (ci, ky, kx) of the layer's own K
+                const int cg = L.cin / L.groups;
+                const int xx = (int)(e % L.kw); e /= L.kw; const int yy = (int)(e % L.kh); e /= L.kh; const int ci = (int)(e % cg); const int co = (int)(e / cg);
+                const int ky = L.kh - 1 - yy, kx = L.kw - 1 - xx;
+                e = ((size_t)(ci * L.kh + ky) * L.kw + kx) * L.cout + co;
+            }
             j = L.w_off + e; break;
         }
         if (i >= L.eb_off && i < L.eb_off + (size_t)L.N) { j = L.b_off + (i - L.eb_off); break; }

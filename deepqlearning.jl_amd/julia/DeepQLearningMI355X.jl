@@ -76,6 +76,18 @@ function lower_layer(l, stream)::LayerDesc
         # (SamePad() on an even kernel yields lo != hi); the engine checks 0 <= pad <= kernel - 1.  (pad_h, pad_w) ride in the n_in, n_out slots a Conv leaves unused
         p = length(l.pad) == 4 ? l.pad : (l.pad[1], l.pad[1], l.pad[2], l.pad[2])
         (p[1] == p[2] && p[3] == p[4]) || throw("DeepQLearningError: the MI355X engine supports Conv with symmetric pad only (lo == hi on each axis), got asymmetric pad=$(l.pad)")
+        # l.dilation is NTuple{2} in (W, H) order, like l.stride; l.groups an Int; with groups the weight is (kw, kh, cin ÷ groups, cout), so size(l.weight, 3) is the channels PER GROUP.
+        # dilation = 1 and groups = 1 stays kind 1, the descriptor it always was; anything else (DepthwiseConv included: Flux builds it as Conv(...; groups = cin)) is kind 15 with
+        # the FULL channel counts and the five small integers packed: pad_h | pad_w << 16 in n_in, dh | dw << 8 | groups << 16 in n_out (include/dqn_mi355x.h)
+        dil = l.dilation; g = l.groups
+        if any(!=(1), dil) || g != 1
+            all(>=(1), dil) || throw("DeepQLearningError: Conv with dilation=$(dil): the dilation must be at least 1 per axis")
+            (all(<=(255), dil) && g <= 32767) || throw("DeepQLearningError: Conv with dilation=$(dil), groups=$(g): the MI355X engine takes dilation <= 255 and groups <= 32767")
+            (g >= 1 && cout % g == 0) || throw("DeepQLearningError: Conv with groups=$(g): groups must be >= 1 and divide cin = $(cin * g) and cout = $(cout)")
+            (p[3] <= (kh - 1) * dil[2] && p[1] <= (kw - 1) * dil[1]) || throw("DeepQLearningError: Conv pad ($(p[3]), $(p[1])) is larger than the dilated kernel extent - 1 = ($((kh - 1) * dil[2]), $((kw - 1) * dil[1]))")
+            stream == 0 || throw("DeepQLearningError: a Conv with dilation=$(dil) / groups=$(g) is supported in the base chain only (not in a value / advantage stream)")
+            return LayerDesc(15, ACT[l.σ], stream, p[3] | (p[1] << 16), dil[2] | (dil[1] << 8) | (g << 16), cin * g, cout, kh, kw, l.stride[2], l.stride[1])
+        end
         return LayerDesc(1, ACT[l.σ], stream, p[3], p[1], cin, cout, kh, kw, l.stride[2], l.stride[1])
     elseif l isa Flux.MaxPool      # fields k, pad, stride; no parameters; cin = cout = 0: the engine takes the channels of the incoming map
         any(!=(0), l.pad) && throw("DeepQLearningError: the MI355X engine supports MaxPool with pad=0 only")
@@ -162,7 +174,8 @@ end
 # The CONVOLUTIONAL block, x + Conv(Conv(x)): where the descriptor in front is a Conv, a pool or the join of another such block (kinds 1, 5, 6, 10) and every inner layer
 # is a Conv or a pool, the join is of kind 10 -- the same descriptor shape.  Its inner layers are Convs with pad != 0 that keep the channel count; a pool, a pad-0 Conv and
 # a channel change are refused here by name, that the block keeps (h, w) is the engine's check
-is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10 || d.kind == 11 || d.kind == 12 || d.kind == 13      # (11: a GroupNorm keeps the incoming map; 12, 13: the adaptive / global pools)
+is_map_desc(d) = d.kind == 1 || d.kind == 5 || d.kind == 6 || d.kind == 10 || d.kind == 11 || d.kind == 12 || d.kind == 13 || d.kind == 15      # (11: a GroupNorm keeps the incoming map; 12, 13: the adaptive / global pools; 15: a dilated / grouped Conv)
+is_general_conv(x) = x isa Conv && (any(!=(1), x.dilation) || x.groups != 1)      # kind 15: never inside a SkipConnection, so lower_skip_map! must not take it for a padded Conv
 is_map_layer(x) = x isa Conv || x isa Flux.MaxPool || x isa Flux.MeanPool || x isa Flux.AdaptiveMaxPool || x isa Flux.AdaptiveMeanPool || x isa Flux.GlobalMaxPool || x isa Flux.GlobalMeanPool
 function lower_skip_map!(descs, l, stream, inner)
     m = 0; c_in = 0; c_out = 0
@@ -181,6 +194,7 @@ function lower_skip!(descs, l, stream)
     inner = l.layers isa Flux.Chain ? collect(l.layers.layers) : Any[l.layers]
     any(is_act_layer, inner) && throw("DeepQLearningError: an Activation layer (Base.BroadcastFunction) inside a SkipConnection is not supported (a standalone activation stands in the base chain, in front of or behind the block; inside, use the fused activation of Dense / Conv)")      # asked BEFORE the glue filter: the layer is a Function
     real = filter(!is_glue, inner)
+    any(is_general_conv, real) && throw("DeepQLearningError: a Conv with dilation != 1 or groups != 1 (DepthwiseConv included) inside a SkipConnection is not supported (dilated and grouped residual blocks are not supported; the layer stands in the base chain, in front of or behind the block)")
     any(x -> x isa Flux.GroupNorm, real) && throw("DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block)")
     if !isempty(descs) && is_map_desc(descs[end]) && !isempty(real) && all(is_map_layer, real)
         return lower_skip_map!(descs, l, stream, inner)

@@ -77,13 +77,26 @@ class SamePad:
         return "SamePad()"
 
 
-def _resolve_pad(pad, kh, kw):
-    """Flux's pad argument -> symmetric (ph, pw): an int, a 2-tuple (per axis), a 4-tuple (lo, hi per axis: W axis first, as Flux stores it) or SamePad()."""
-    name = f"Conv(({kh}, {kw}), ...; pad={pad!r})"
+def _pair(v, name, what):
+    """an int or a 2-tuple in this mirror's (H, W) order -> (h, w)"""
+    if np.isscalar(v):
+        return int(v), int(v)
+    t = tuple(int(x) for x in v)
+    if len(t) != 2:
+        raise _abi.DQNError(f"DeepQLearningError: {name}: {what} must be an int or a pair")
+    return t
+
+
+def _resolve_pad(pad, kh, kw, dh=1, dw=1):
+    """Flux's pad argument -> symmetric (ph, pw): an int, a 2-tuple (per axis), a 4-tuple (lo, hi per axis: W axis first, as Flux stores it) or SamePad().  With a dilation
+    the kernel's extent per axis is (k - 1) * d + 1: SamePad() resolves to (k - 1) * d / 2, and the pad may reach the extent minus one."""
+    dil = "" if dh == dw == 1 else f", dilation=({dh}, {dw})"
+    name = f"Conv(({kh}, {kw}), ...; pad={pad!r}{dil})"
+    eh, ew = (kh - 1) * dh, (kw - 1) * dw      # the (dilated) extent minus one
     if isinstance(pad, SamePad) or pad is SamePad:
-        if kh % 2 == 0 or kw % 2 == 0:
+        if eh % 2 or ew % 2:
             raise _abi.DQNError(f"DeepQLearningError: {name}: SamePad() on an even kernel is an asymmetric pad (lo != hi); the MI355X engine supports symmetric zero padding only")
-        return (kh - 1) // 2, (kw - 1) // 2
+        return eh // 2, ew // 2
     if np.isscalar(pad):
         ph = pw = int(pad)
     else:
@@ -98,30 +111,57 @@ def _resolve_pad(pad, kh, kw):
             raise _abi.DQNError(f"DeepQLearningError: {name}: pad must be an int, a 2-tuple, a symmetric 4-tuple or SamePad()")
     if ph < 0 or pw < 0:
         raise _abi.DQNError(f"DeepQLearningError: {name}: pad ({ph}, {pw}) must not be negative")
-    if ph > kh - 1 or pw > kw - 1:
-        raise _abi.DQNError(f"DeepQLearningError: {name}: pad ({ph}, {pw}) is larger than kernel - 1 = ({kh - 1}, {kw - 1})")
+    if ph > eh or pw > ew:
+        raise _abi.DQNError(f"DeepQLearningError: {name}: pad ({ph}, {pw}) is larger than " + ("kernel - 1" if dh == dw == 1 else "the dilated kernel extent - 1") + f" = ({eh}, {ew})")
     return ph, pw
 
 
 class Conv:
-    """Flux Conv((kh,kw), cin=>cout, act; stride, pad) -- true convolution; pad = symmetric zero padding per axis (an int, (ph, pw), a symmetric Flux 4-tuple or
-    SamePad() on an odd kernel), 0 <= pad <= kernel - 1.  Output map (H + 2 ph - kh) ÷ sh + 1 by (W + 2 pw - kw) ÷ sw + 1."""
+    """Flux Conv((kh,kw), cin=>cout, act; stride, pad, dilation, groups) -- true convolution; pad = symmetric zero padding per axis (an int, (ph, pw), a symmetric Flux 4-tuple
+    or SamePad()), 0 <= pad <= (kernel - 1) * dilation.  Output map (H + 2 ph - (kh - 1) dh - 1) ÷ sh + 1 by (W + 2 pw - (kw - 1) dw - 1) ÷ sw + 1.  dilation: an int or
+    (dh, dw) in this mirror's (H, W) order (Flux writes (W, H), as for stride).  groups = g divides cin and cout: output channels [j cout/g, (j+1) cout/g) read input channels
+    [j cin/g, (j+1) cin/g); the weight is (kw, kh, cin ÷ g, cout) and the glorot fans are nfan of that size.  dilation = 1 and groups = 1 is the Conv it always was (layer
+    kind 1); anything else is layer kind 15 (csrc/conv_dg.hip): base chain only, not inside a SkipConnection."""
     kind = "conv"
 
-    def __init__(self, k, cin, cout, act=identity, stride=1, pad=0):
+    def __init__(self, k, cin, cout, act=identity, stride=1, pad=0, dilation=1, groups=1):
         self.kh, self.kw = (k, k) if np.isscalar(k) else (int(k[0]), int(k[1]))
         self.sh, self.sw = (stride, stride) if np.isscalar(stride) else (int(stride[0]), int(stride[1]))
         self.cin, self.cout, self.act = int(cin), int(cout), act
-        self.ph, self.pw = _resolve_pad(pad, self.kh, self.kw)
+        name = f"{type(self).__name__}(({self.kh}, {self.kw}), {self.cin} => {self.cout}; dilation={dilation!r}, groups={groups!r})"
+        self.dh, self.dw = _pair(dilation, name, "dilation")
+        self.groups = int(groups)
+        if self.dh < 1 or self.dw < 1:
+            raise _abi.DQNError(f"DeepQLearningError: {name}: dilation must be at least 1 per axis")
+        if self.dh > 255 or self.dw > 255 or self.groups > 32767:
+            raise _abi.DQNError(f"DeepQLearningError: {name}: the MI355X engine takes dilation <= 255 and groups <= 32767")
+        if self.groups < 1 or self.cin % self.groups or self.cout % self.groups:
+            raise _abi.DQNError(f"DeepQLearningError: {name}: groups must be >= 1 and divide cin = {self.cin} and cout = {self.cout}")
+        self.ph, self.pw = _resolve_pad(pad, self.kh, self.kw, self.dh, self.dw)
+
+    @property
+    def general(self):
+        """dilation != 1 or groups != 1: the layer lowers to kind 15 (LAYER_CONV_DG)"""
+        return (self.dh, self.dw, self.groups) != (1, 1, 1)
 
     def __repr__(self):
-        return f"Conv(({self.kh}, {self.kw}), {self.cin} => {self.cout}, act={self.act}, stride=({self.sh}, {self.sw}), pad=({self.ph}, {self.pw}))"
+        dg = f", dilation=({self.dh}, {self.dw}), groups={self.groups}" if self.general else ""
+        return f"Conv(({self.kh}, {self.kw}), {self.cin} => {self.cout}, act={self.act}, stride=({self.sh}, {self.sw}), pad=({self.ph}, {self.pw}){dg})"
 
-    def shapes(self):  # weight (kw,kh,cin,cout) == C (cout,cin,kh,kw)
-        return [(self.cout, self.cin, self.kh, self.kw), (self.cout,)]
+    def shapes(self):  # weight (kw,kh,cin÷g,cout) == C (cout,cin÷g,kh,kw)
+        return [(self.cout, self.cin // self.groups, self.kh, self.kw), (self.cout,)]
 
-    def fans(self):
-        return self.kh * self.kw * self.cin, self.kh * self.kw * self.cout
+    def fans(self):    # Flux nfan(kw, kh, cin ÷ g, cout)
+        return self.kh * self.kw * (self.cin // self.groups), self.kh * self.kw * self.cout
+
+
+class DepthwiseConv(Conv):
+    """Flux DepthwiseConv((kh,kw), cin=>cout, act; stride, pad, dilation) = Conv(...; groups = cin), cout a multiple of cin"""
+
+    def __init__(self, k, cin, cout, act=identity, stride=1, pad=0, dilation=1):
+        if int(cin) < 1 or int(cout) % int(cin):
+            raise _abi.DQNError(f"DeepQLearningError: DepthwiseConv({k!r}, {cin} => {cout}): groups = cin must divide cout (cout is a multiple of cin)")
+        super().__init__(k, cin, cout, act, stride, pad, dilation, groups=int(cin))
 
 
 class _Pool:
@@ -471,6 +511,8 @@ def lower(net):
             raise _abi.DQNError(f"DeepQLearningError: an Activation layer inside a SkipConnection is not supported (a standalone activation stands in the base chain, in front of or behind the block; inside, use the fused activation of Dense / Conv): {blk!r}")
         if any(getattr(l, "kind", None) == "groupnorm" for l in blk.layers):
             raise _abi.DQNError(f"DeepQLearningError: a GroupNorm layer inside a SkipConnection is not supported (GroupNorm stands in the base chain, in front of or behind the block): {blk!r}")
+        if any(getattr(l, "kind", None) == "conv" and l.general for l in blk.layers):
+            raise _abi.DQNError(f"DeepQLearningError: a Conv with dilation != 1 or groups != 1 (DepthwiseConv included) inside a SkipConnection is not supported (dilated and grouped residual blocks are not supported; the layer stands in the base chain, in front of or behind the block): {blk!r}")
         on_map = prev_kind in ("conv", "groupnorm") + POOL_KINDS or (prev_kind == "skip" and map_join[0])
         if on_map and not first and all(getattr(l, "kind", None) in ("conv",) + POOL_KINDS for l in blk.layers):
             return add_skip_map(blk, stream, is_last)
@@ -591,9 +633,15 @@ def lower(net):
                 d.cin = d.cout = chan[0]
                 d.kh, d.kw, d.sh, d.sw = l.kh, l.kw, l.sh, l.sw
             else:
-                d.kind = _abi.LAYER_CONV
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
-                d.n_in, d.n_out = l.ph, l.pw      # the pad rides in the slots a Conv leaves unused (0, 0 for every unpadded layer)
+                if l.general:      # dilation != 1 or groups != 1: kind 15; the five small integers ride packed, pad_h | pad_w << 16 in n_in, dh | dw << 8 | g << 16 in n_out
+                    if stream != _abi.STREAM_BASE:
+                        raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+                    d.kind = _abi.LAYER_CONV_DG
+                    d.n_in, d.n_out = l.ph | (l.pw << 16), l.dh | (l.dw << 8) | (l.groups << 16)
+                else:
+                    d.kind = _abi.LAYER_CONV
+                    d.n_in, d.n_out = l.ph, l.pw      # the pad rides in the slots a Conv leaves unused (0, 0 for every unpadded layer)
                 chan[0] = l.cout
             out.append(d)
 

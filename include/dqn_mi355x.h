@@ -41,7 +41,7 @@ extern "C" {
 
 typedef struct dqn_engine dqn_engine_t;
 
-enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11, DQN_LAYER_ADAPTIVEMAXPOOL = 12, DQN_LAYER_ADAPTIVEMEANPOOL = 13, DQN_LAYER_ACTIVATION = 14 };
+enum { DQN_LAYER_DENSE = 0, DQN_LAYER_CONV = 1, DQN_LAYER_LSTM = 2, DQN_LAYER_GRU = 3, DQN_LAYER_RNN = 4, DQN_LAYER_MAXPOOL = 5, DQN_LAYER_MEANPOOL = 6, DQN_LAYER_LAYERNORM = 7, DQN_LAYER_DROPOUT = 8, DQN_LAYER_SKIPADD = 9, DQN_LAYER_SKIPADD_MAP = 10, DQN_LAYER_GROUPNORM = 11, DQN_LAYER_ADAPTIVEMAXPOOL = 12, DQN_LAYER_ADAPTIVEMEANPOOL = 13, DQN_LAYER_ACTIVATION = 14, DQN_LAYER_CONV_DG = 15 };
 /* Activations of Dense, Conv and LayerNorm layers (NNlib's DEFAULT parameters only: leakyrelu a = 0.01, elu alpha = 1).  x: the fp32 pre-activation, y: the stored fp32
  * output.  The engine keeps only y and differentiates from it, as NNlib's own rules do (deriv_elu(y), deriv_selu(y), (1 - abs(y))^2, ...).  The forwards with a
  * transcendental or a division go through Float64 and round once.  L = 1.0507009873554805, A = 1.6732632423543772, LA = L * A = 1.7580993408473766.
@@ -94,6 +94,14 @@ typedef struct {
     int32_t cin, cout, kh, kw, sh, sw; /* Conv((kh,kw), cin=>cout; stride=(sh,sw), pad=(pad_h,pad_w)): for DQN_LAYER_CONV the slots n_in / n_out carry pad_h / pad_w,
                                           symmetric zero padding per axis, 0 <= pad_h <= kh - 1, 0 <= pad_w <= kw - 1 (0, 0 = no padding); output map
                                           (H + 2 pad_h - kh) / sh + 1 by (W + 2 pad_w - kw) / sw + 1; a padded Conv is base chain only and single GPU only;
+                                          CONV_DG (kind 15): Conv((kh,kw), cin=>cout, act; stride, pad, dilation=(dh,dw), groups=g) and DepthwiseConv (g = cin) -- Flux 0.14, recalled, not
+                                          executed.  cin, cout = the FULL channel counts, kh, kw, sh, sw as for Conv.  The five small integers ride packed: n_in = pad_h | pad_w << 16
+                                          (each 0..65535), n_out = dh | dw << 8 | g << 16 (dh, dw 1..255, g 1..32767); a negative slot or a field outside its range is refused.  g divides
+                                          cin and cout; output channels [j cout/g, (j+1) cout/g) read input channels [j cin/g, (j+1) cin/g).  Tap (ky, kx) of output (oy, ox) reads
+                                          iy = oy sh + ky dh - pad_h, ix = ox sw + kx dw - pad_w; 0 <= pad_h <= (kh-1) dh, likewise w; output map (H + 2 pad_h - (kh-1) dh - 1) / sh + 1 by
+                                          (W + 2 pad_w - (kw-1) dw - 1) / sw + 1.  Parameters: weight (cout, cin/g, kh, kw) (Julia (kw, kh, cin/g, cout)), bias (cout).  The plan entry
+                                          means what a Conv's means, on K = (cin/g) kh kw and N = cout.  Base chain only (first layer included), never inside a skip block, single GPU
+                                          only.  dh = dw = g = 1 is valid here and gives the bits of DQN_LAYER_CONV; the shim and the Python mirror lower such a Conv to DQN_LAYER_CONV;
                                           MaxPool((kh,kw); stride=(sh,sw)) / MeanPool(...), pad 0: cin == cout == channels of the incoming map (or both 0: the engine fills them in), act = IDENTITY,
                                           no parameters (Flux.params skips the layer); base chain only, first or behind a Conv / pool; its plan entry is ignored;
                                           AdaptiveMaxPool((ow, oh)) / AdaptiveMeanPool(...) (kinds 12 / 13; Flux 0.14 over NNlib, recalled, not executed) and GlobalMaxPool() / GlobalMeanPool()
