@@ -30,14 +30,13 @@ import torch
 import torch.nn.functional as F
 
 import activation_reference as AR
-import dqn_oracle as O
 import groupnorm_reference as GR
 import layernorm_reference as LR
 import recurrent_reference as R
-from drqn_common import draws, make_episodes      # noqa: F401
+import step_reference as S
 from feedforward_edges_common import GAP, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD      # noqa: F401  (one set of constants)
 from feedforward_reference import GRAD_C, GRAD_RTOL, RELU_MARGIN, Adam, check_params      # noqa: F401
-from gru_reference import gru_cell, param_arrays
+from step_reference import blocks, check_grads, ff_batch, ff_data, legs_agree, rec_data      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
@@ -114,154 +113,36 @@ class _ActNumpy(torch.autograd.Function):
         return torch.tensor(dactl_np(dy.numpy(), xn, y, a)), None
 
 
-LEGS = {"torch": actl_torch, "numpy": _ActNumpy.apply}
+LEGS = {"torch": {}, "numpy": {"activation": S.activation_law(_ActNumpy.apply)}}
 
 
-# ------------------------------------------------------------------ chains of nn descriptors
-def new_probe():
-    return dict(kink=np.inf, pool=np.inf)
-
-
-def _kink(probe, x, a):
+# ------------------------------------------------------------------ the observers, and the step (step_reference's, bound to the legs)
+def _kink(probe, x, a, cx):
     for k in KINKS.get(a, ()):
-        probe["kink"] = min(probe["kink"], GR._min((x.detach()[GR._rows(probe, x)] - k).abs()))
+        probe["kink"] = min(probe["kink"], GR._min((S.kept(cx, x.detach()) - k).abs()))
 
 
-def _run(layers, it, x, hs, leg, probe, st):
-    """one (time) step through a chain; `it` yields (flat layer index, parameter arrays) in nn.all_layers order; st['relu']: x holds the exact zeros of a relu"""
-    for l in layers:
-        if l.kind == "skip":
-            x = _run(l.layers.layers, it, x, hs, leg, probe, st) + x
-            st["relu"] = False
-            continue
-        k, a = next(it)
-        if l.kind == "activation":
-            if probe is not None:
-                _kink(probe, x, l.code)
-            x = LEGS[leg](x, l.code); st["relu"] = l.code == AR.RELU
-            continue
-        if l.kind == "lstm":
-            hs[k] = R.lstm_cell(x.reshape(x.shape[0], -1), hs[k][0], hs[k][1], a[0], a[1], a[2]); x = hs[k][0]; st["relu"] = False
-            continue
-        if l.kind == "gru":
-            hs[k] = gru_cell(x.reshape(x.shape[0], -1), hs[k], a[0], a[1], a[2]); x = hs[k]; st["relu"] = False
-            continue
-        if l.kind in ("maxpool", "meanpool"):
-            if l.kind == "maxpool" and probe is not None:
-                probe["pool"] = min(probe["pool"], GR._pool_gap(l, x.detach()[GR._rows(probe, x)], st["relu"]))
-            x = (F.max_pool2d if l.kind == "maxpool" else F.avg_pool2d)(x, (l.kh, l.kw), stride=(l.sh, l.sw))
-            st["relu"] = st["relu"] and l.kind == "maxpool"
-            continue
-        if l.kind == "adaptivemeanpool":      # GlobalMeanPool() only: the mean over the whole map (kinds 12 / 13 have their own table: adaptive_pool_reference)
-            assert (l.oh, l.ow) == (1, 1)
-            x = x.mean(dim=(2, 3), keepdim=True); st["relu"] = False
-            continue
-        if l.kind == "conv":      # a true convolution is the cross-correlation with the flipped kernel (feedforward_reference._layer_t)
-            pre = F.conv2d(x, a[0].flip(2, 3), a[1], stride=(l.sh, l.sw), padding=(l.ph, l.pw))
-        elif l.kind == "groupnorm":
-            pre = GR.gn_torch(x, a[0], a[1], l.G, float(np.float32(l.eps)))      # Flux.params order: beta, gamma
-        else:
-            assert l.kind == "dense", l.kind
-            pre = x.reshape(x.shape[0], -1) @ a[0] + a[1]
-        if probe is not None:
-            _kink(probe, pre, l.act)
-        x = AR.act_torch(pre, l.act); st["relu"] = l.act == AR.RELU
-    return x
+def _see_input(probe, l, x, cx):
+    if l.kind == "activation":
+        _kink(probe, x, l.code, cx)
+    elif l.kind == "maxpool":
+        probe["pool"] = min(probe["pool"], GR._pool_gap(l, S.kept(cx, x.detach()), cx.relu))
 
 
-def q_step(net, arrs, x, hs, leg="torch", probe=None):
-    it = iter(enumerate(arrs)); st = dict(relu=False)
-    if isinstance(net, nn.DuelingNetwork):
-        y = _run(net.base.layers, it, x, hs, leg, probe, st)
-        v = _run(net.val.layers, it, y, hs, leg, probe, dict(st))
-        a = _run(net.adv.layers, it, y, hs, leg, probe, dict(st))
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _run(net.layers, it, x, hs, leg, probe, st)
+# "kink": the smallest distance of an Activation layer's input, or of a fused layer's pre-activation, from a kink of its σ; "pool": the MaxPool margin
+OBSERVERS = {"in": _see_input, "pre": lambda probe, l, pre, cx: _kink(probe, pre, l.act, cx)}
 
 
-def is_recurrent(net):
-    return any(l.kind in ("lstm", "gru") for l in nn.all_layers(net))
+def new_probe():
+    return S.Probe(OBSERVERS, kink=np.inf, pool=np.inf)
 
 
-def q_values(net, p, x, leg="torch", probe=None, mask=None):
-    """Q (B, nA) as fp64 NumPy of a feed-forward network on x (B, ...); a recurrent network: x (T, B, ...) from the reset state -> [T] of (B, nA)"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not is_recurrent(net):
-            return q_step(net, arrs, LR._t64(x), {}, leg, probe).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1]); out = []
-        for t, xt in enumerate(x):
-            if probe is not None and mask is not None:
-                probe["rows"] = torch.tensor(np.asarray(mask[t]) > 0)
-            out.append(q_step(net, arrs, LR._t64(xt), hs, leg, probe).numpy())
-        return out
+q_values = S.bound(S.q_values, LEGS, "leg", "probe", "mask")
+ff_step, rec_step = S.bound(S.ff_step, LEGS, "leg"), S.bound(S.rec_step, LEGS, "leg")
 
 
 def probe_of(net, p, s, mask=None):
-    pr = new_probe(); q_values(net, p, s, probe=pr, mask=mask)
-    return pr
-
-
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, leg="torch"):
-    """layernorm_reference.ff_step over this module's chain.  batch = (s, a, r, sp, done, w) as get_batch returns it"""
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = (LR._t64(v) for v in (s, sp, r, done, w))
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():       # the targets are constants of the loss (src/solver.jl:209-217)
-        q_tg_sp = q_step(net, atg, sp, {}, leg)
-        q_on_sp = q_step(net, aon, sp, {}, leg) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)      # Julia's argmax: the smallest index among the maxima
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {}, leg)
-    td = q[torch.arange(B), a] - y
-    loss = LR._huber(w * td).sum() / B        # src/solver.jl:223-224
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, leg="torch"):
-    """layernorm_reference.rec_step over this module's chain.  batch = (s, a, r, sp, done, mask), each (T, B, ...)"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, leg)
-    q_on = q_values(net, p_on, sp, leg) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, LR._t64(s[t]), hs, leg)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - LR._t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + LR._huber(LR._t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, td=np.stack(tds))
-
-
-legs_agree = LR.legs_agree
-BLOCK_NAMES = {"lstm": ("Wi", "Wh", "b", "h0", "c0"), "gru": ("Wi", "Wh", "b", "h0"), "dense": ("W", "b"), "conv": ("W", "b"), "groupnorm": ("beta", "gamma"), "maxpool": (), "meanpool": (),
-               "adaptivemeanpool": (), "activation": ()}
-
-
-def blocks(net):
-    """[(name, slice into the flat Flux.params vector)]; an Activation layer holds nothing"""
-    out, off = [], 0
-    for li, l in enumerate(nn.all_layers(net)):
-        for nm, shp in zip(BLOCK_NAMES[l.kind], l.shapes()):
-            k = int(np.prod(shp)); out.append((f"{'gn' if l.kind == 'groupnorm' else l.kind}{li}.{nm}", slice(off, off + k))); off += k
-    return out
-
-
-def check_grads(net, got, want, live=True):
-    """recurrent_reference.check_grads per block (GRAD_C, GRAD_RTOL unchanged); live: no block's fp64 gradient is negligible"""
-    R.check_grads(net, nn, got, want, live=live, blks=blocks(net))
+    return S.probed(new_probe(), q_values, net, p, s, mask=mask)
 
 
 # ------------------------------------------------------------------ the case table: the smallest shapes at which each path of act_layer.hip and each placement can go wrong
@@ -356,7 +237,6 @@ def _build():
 
 _build()
 STEPS = 2      # train steps the GPU test runs per feed-forward case (the draws of layernorm_reference.ff_data)
-ff_data, ff_batch, rec_data = LR.ff_data, LR.ff_batch, LR.rec_data
 
 
 def trajectory(c, D=None, steps=STEPS, seed=None, leg="torch"):
@@ -392,26 +272,21 @@ def margins_ok(c, seed=None, k=2.0):
     return True
 
 
-def find_seed(c, cap=64):
-    """the smallest seed that keeps twice the margins along the case's fp64 trajectory (how the table's seeds were chosen, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if margins_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the margins")
+find_seed = lambda c, cap=64: S.find_seed(c, margins_ok, cap)
 
 
 _PREPARED = {}
 
 
-def prepare(c):
+def prepare(c, cache=_PREPARED):
     """the case's data, computed once and shared: asserts the margins on the first step (the GPU test asserts them again on every step it runs, on the engine's own parameters)"""
-    if c.name not in _PREPARED:
+    if c.name not in cache:
         D = rec_data(c) if c.T else ff_data(c)
         _, p, batch, _ = next(trajectory(c, D))
         km, pm, gap = margins(c, D.net, p, D.p_tg, batch)
         assert km > RELU_MARGIN and pm > RELU_MARGIN and gap > GAP, (c.name, km, pm, gap)
-        _PREPARED[c.name] = D
-    return _PREPARED[c.name]
+        cache[c.name] = D
+    return cache[c.name]
 
 
 def activations(net):

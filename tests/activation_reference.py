@@ -10,9 +10,9 @@ Two legs that share no activation code:
   * "torch"  torch float64 autograd over torch.nn.functional's own functions (F.leaky_relu, F.elu, F.selu, F.softplus, F.softsign, F.relu6, F.hardtanh);
   * "numpy"  the closed forms above in NumPy and, for the backward, the derivative written as a function of the OUTPUT y alone -- the column the engine runs, which keeps
              only y (dact_np) -- entered into the graph as a torch.autograd.Function.
-`wrong` names one of five WRONG engines (WRONG), each the numpy leg with one law replaced: tests/test_activations_cpu.py shows every one of them apart from the law.
-Everything that is no activation is imported: the LayerNorm law, the Dropout mask law, the LSTM cell, the Huber loss, Adam, the gradient and parameter checks and their
-constants.  feedforward_reference._act is neither edited nor patched.
+Five WRONG engines (WRONG) are legs of their own name, each the numpy leg with one law replaced: tests/test_activations_cpu.py shows every one of them apart from the law.
+A leg overrides the entry "act" (the fused activation) of step_reference's table of laws; everything that is no activation is step_reference's: the walker, the step, every
+other layer's law, the gradient blocks and their check; Adam, the parameter check and the constants are imported as before.  feedforward_reference._act is neither edited nor patched.
 
 Data rules, beside the argmax gap (GAP) of the feed-forward tables:
   * MARGIN: every fp64 pre-activation on s stays RELU_MARGIN away from each kink of its activation (KINKS: relu, leakyrelu, selu 0; relu6 0 and 6; hardtanh -1 and 1;
@@ -26,6 +26,7 @@ layer's middle one), and a saturating activation on the output layer needs per-a
 always sees pre-activations of standard deviation 4 around 3, so the absolute Q errors of those cases are larger than the other tables' (docs/history/activations.md).
 Seeds are fixed in the table and were found on the CPU with this module alone (find_seed); no case is skipped at run time."""
 
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -34,9 +35,10 @@ import dqn_oracle as O
 import dropout_reference as DR
 import layernorm_reference as LR
 import recurrent_reference as R
+import step_reference as S
 from feedforward_edges_common import GAP, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD      # noqa: F401  (one set of constants, with the meaning they have there)
-from feedforward_reference import GRAD_C, GRAD_RTOL, RELU_MARGIN, Adam, _huber_t, check_params      # noqa: F401
-from gru_reference import param_arrays
+from feedforward_reference import GRAD_C, GRAD_RTOL, RELU_MARGIN, Adam, check_params      # noqa: F401
+from step_reference import blocks, check_grads, legs_agree      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
@@ -126,69 +128,27 @@ class _ActNumpy(torch.autograd.Function):
         return torch.tensor(dact_np(dy.numpy(), ctx.y, ctx.a, ctx.wrong)), None, None
 
 
-def _act(x, a, leg, wrong):
-    return act_torch(x, a) if leg == "torch" else _ActNumpy.apply(x, a, wrong)
+def _numpy(wrong=None):
+    return {"act": S.act_law(lambda x, a: _ActNumpy.apply(x, a, wrong))}
 
 
-# ------------------------------------------------------------------ chains of nn descriptors
-def _chain(layers, arrs, x, hs, li0, masks, leg, wrong, probe):
-    """one (time) step through a chain.  masks: {layer index: keep (B, n)} of the Dropout layers, or None = inactive.  probe (or None): {"pre": {layer index: [fp64
-    pre-activations seen]}, "sigma": the smallest LayerNorm sigma}"""
-    for i, l in enumerate(layers):
-        a, k, B = arrs[li0 + i], li0 + i, x.shape[0]
-        if l.kind == "lstm":
-            hs[k] = R.lstm_cell(x.reshape(B, -1), hs[k][0], hs[k][1], a[0], a[1], a[2]); x = hs[k][0]
-            continue
-        if l.kind == "dropout":
-            x = x.reshape(B, -1)
-            if masks is not None:
-                x = DR.do_law(x, torch.tensor(masks[k]), DR.do_scale(l.p))
-            continue
-        if l.kind in ("maxpool", "meanpool"):
-            x = (F.max_pool2d if l.kind == "maxpool" else F.avg_pool2d)(x, (l.kh, l.kw), stride=(l.sh, l.sw))
-            continue
-        if l.kind == "conv":      # a true convolution is the cross-correlation with the flipped kernel
-            pre = F.conv2d(x, a[0].flip(2, 3), a[1], stride=(l.sh, l.sw), padding=(l.ph, l.pw))
-        elif l.kind == "layernorm":
-            pre, sigma = LR.ln_law(x.reshape(B, -1), a[0], a[1], float(np.float32(l.eps)))
-            if probe is not None:
-                probe["sigma"] = min(probe["sigma"], float(sigma.min()))
-        else:
-            assert l.kind == "dense", l.kind
-            pre = x.reshape(B, -1) @ a[0] + a[1]
-        if probe is not None:
-            probe["pre"].setdefault(k, []).append(pre.detach().numpy().copy())
-        x = _act(pre, l.act, leg, wrong)
-    return x
+LEGS = {"torch": {}, "numpy": _numpy()} | {w: _numpy(w) for w in WRONG}      # a wrong engine is a leg of its own name
 
 
-def q_step(net, arrs, x, hs, masks=None, leg="torch", wrong=None, probe=None):
-    if isinstance(net, nn.DuelingNetwork):
-        nb, nv = len(net.base.layers), len(net.val.layers)
-        y = _chain(net.base.layers, arrs, x, hs, 0, masks, leg, wrong, probe)
-        v = _chain(net.val.layers, arrs, y, hs, nb, masks, leg, wrong, probe)
-        a = _chain(net.adv.layers, arrs, y, hs, nb + nv, masks, leg, wrong, probe)
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _chain(net.layers, arrs, x, hs, 0, masks, leg, wrong, probe)
+def _see_pre(probe, l, pre, cx):
+    probe["pre"].setdefault(cx.k, []).append(pre.detach().numpy().copy())
 
 
-def is_recurrent(net):
-    return any(l.kind == "lstm" for l in nn.all_layers(net))
+OBSERVERS = {"pre": _see_pre, "sigma": LR.OBSERVERS["sigma"]}      # {"pre": {layer index: [fp64 pre-activations seen]}, "sigma": the smallest LayerNorm sigma}
 
 
 def new_probe():
-    return dict(pre={}, sigma=np.inf)
+    return S.Probe(OBSERVERS, pre={}, sigma=np.inf)
 
 
-def q_values(net, p, x, masks=None, leg="torch", wrong=None, probe=None):
-    """Q (B, nA) fp64 of a feed-forward network on x (B, ...); recurrent: x (T, B, ...) from the reset state -> [T] of (B, nA).  masks None: Dropout inactive (every pass
-    but the online one on s)"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not is_recurrent(net):
-            return q_step(net, arrs, LR._t64(x), {}, masks, leg, wrong, probe).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1])
-        return [q_step(net, arrs, LR._t64(xt), hs, DR._at(masks, t), leg, wrong, probe).numpy() for t, xt in enumerate(x)]
+# masks None: Dropout inactive (every pass but the online one on s)
+q_values = S.bound(S.q_values, LEGS, "masks")
+ff_step, rec_step = S.bound(S.ff_step, LEGS, "masks"), S.bound(S.rec_step, LEGS, "masks")
 
 
 def has_dropout(net):
@@ -200,78 +160,12 @@ def masks_of(net, k, B, T=0):
     return DR.masks_for(net, k, B, T) if has_dropout(net) else None
 
 
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, masks=None, leg="torch", wrong=None):
-    """batch = (s, a, r, sp, done, w) as get_batch returns it; everything the engine reports of one feed-forward batch_train!"""
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = LR._t64(s), LR._t64(sp), LR._t64(r), LR._t64(done), LR._t64(w)
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():       # the targets are constants of the loss (src/solver.jl:209-217)
-        q_tg_sp = q_step(net, atg, sp, {}, None, leg, wrong)
-        q_on_sp = q_step(net, aon, sp, {}, None, leg, wrong) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)      # Julia's argmax: the smallest index among the maxima
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {}, masks, leg, wrong)
-    td = q[torch.arange(B), a] - y
-    loss = _huber_t(w * td).sum() / B        # src/solver.jl:223-224
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, masks=None, leg="torch", wrong=None):
-    """batch = (s, a, r, sp, done, mask), each (T, B, ...): the target loop over s' (both networks), the BPTT loop over s (mask inside the Huber, /B per step, /T)"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, None, leg, wrong)
-    q_on = q_values(net, p_on, sp, None, leg, wrong) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, LR._t64(s[t]), hs, DR._at(masks, t), leg, wrong)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - LR._t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + _huber_t(LR._t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, y=np.stack(ys), td=np.stack(tds))
-
-
-legs_agree = LR.legs_agree
-
-
-def blocks(net):
-    """[(name, slice into the flat Flux.params vector)]; pools and Dropout layers hold nothing"""
-    names = {"lstm": ("Wi", "Wh", "b", "h0", "c0"), "dense": ("W", "b"), "conv": ("W", "b"), "layernorm": ("scale", "bias"), "dropout": (), "maxpool": (), "meanpool": ()}
-    out, off = [], 0
-    for li, l in enumerate(nn.all_layers(net)):
-        for nm, shp in zip(names[l.kind], l.shapes()):
-            k = int(np.prod(shp)); out.append((f"{'ln' if l.kind == 'layernorm' else l.kind}{li}.{nm}", slice(off, off + k))); off += k
-    return out
-
-
-def check_grads(net, got, want, live=True):
-    R.check_grads(net, nn, got, want, live=live, blks=blocks(net))
-
-
 def distance(a, b):
-    """{quantity: the largest |a - b| / tolerance} over what the GPU tests compare, with the project's constants (1.0 = at the bound); gradients per block as check_grads
-    weighs them"""
-    out = {}
-    for k, tol in (("q_on_s", TOL_Q), ("q_on_sp", TOL_Q), ("q_tg_sp", TOL_Q), ("y", TOL_TD), ("td", TOL_TD)):
-        if k in a and k in b:
-            x, y = np.asarray(a[k], np.float64), np.asarray(b[k], np.float64)
-            out[k] = float((np.abs(x - y) / (tol["atol"] + tol["rtol"] * np.abs(y))).max())
-    out["loss"] = abs(a["loss"] - b["loss"]) / (TOL_LOSS["atol"] + TOL_LOSS["rtol"] * abs(b["loss"]))
+    """step_reference.distance, plus grad_norm and the gradients as ONE block: a lower bound of check_grads' own measure (block scale <= max |g|)"""
+    out = S.distance(a, b)
     out["grad_norm"] = abs(a["grad_norm"] - b["grad_norm"]) / (TOL_GN["rtol"] * abs(b["grad_norm"]))
     ga, gb = a["grads"], b["grads"]; gmax = np.abs(gb).max()
-    out["grads"] = float((np.abs(ga - gb) / (GRAD_C * max(gmax, 1e-300) + GRAD_RTOL * np.abs(gb))).max())      # a lower bound of check_grads' own measure (block scale <= max |g|)
+    out["grads"] = float((np.abs(ga - gb) / (GRAD_C * max(gmax, 1e-300) + GRAD_RTOL * np.abs(gb))).max())
     return out
 
 
@@ -456,12 +350,7 @@ def rules_ok(c, seed=None, k=2.0):
     return m > k * RELU_MARGIN and occ >= OCCUPANCY and sg >= k * LR.SIGMA_MIN and gap > k * GAP
 
 
-def find_seed(c, cap=200):
-    """the smallest seed that keeps twice the margins and the occupancy along the case's three steps (how SEEDS was filled, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if rules_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the rules")
+find_seed = lambda c, cap=200: S.find_seed(c, rules_ok, cap)
 
 
 TELL = 100.0      # a wrong engine must move some compared quantity by this many of its tolerances
@@ -471,4 +360,4 @@ def tell_distance(c, wrong, seed=None):
     """what the wrong engine is off by on the case's first step, in tolerances: the largest over the compared quantities"""
     D = data(c, seed)
     for k, p, batch, o in trajectory(c, D, 1, leg="numpy"):
-        return max(distance(step(c, D, p, batch, k, leg="numpy", wrong=wrong), o).values())
+        return max(distance(step(c, D, p, batch, k, leg=wrong), o).values())

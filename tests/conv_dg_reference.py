@@ -9,13 +9,14 @@ Two legs of the layer that share no conv code:
   * "numpy"  a hand-written NumPy forward (one strided slice of the np.pad-ed map per tap, one matrix product per group) and backward (dW per tap, dX scattered into the padded
              map and cropped), entered into the graph as a torch.autograd.Function.
 Everything that is no such convolution -- Dense, the plain and padded Conv, pools, GroupNorm, Activation, SkipConnection, LSTM, the dueling join, the Huber loss, the batches,
-Adam, the margins, the gradient and parameter checks and their constants -- is activation_layer_reference's, which this module re-runs over its own chain walker: its step
-functions are instantiated a second time in a namespace whose `_run` is the walker below, so no law is restated and no tolerance is introduced here.
+Adam, the margins, the gradient and parameter checks and their constants -- is step_reference's and activation_layer_reference's: a leg of this module overrides the "conv"
+entry of step_reference's table of laws and nothing else, so no law is restated and no tolerance is introduced here.
 
 WRONG ENGINES (tests/test_conv_dg_cpu.py, "the tests can tell"): legs that make one plausible mistake each -- the dilation ignored, the groups ignored (a dense conv whose
 off-block weights are not zero), the group-to-channel map interleaved, the dX validity test without the dilation.
 
 expand() / expand_params(): the exact companion -- the groups = 1, dilation = 1 network whose conv holds the zero-stuffed, block-diagonal kernel."""
+import functools
 import types
 
 import numpy as np
@@ -23,7 +24,7 @@ import torch
 import torch.nn.functional as F
 
 import activation_layer_reference as AL
-import activation_reference as AR
+import step_reference as S
 from activation_layer_reference import (GAP, GRAD_C, GRAD_RTOL, LRATE, RELU_MARGIN, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD, Adam, blocks, check_grads, check_params, ff_batch, ff_data,      # noqa: F401
                                         legs_agree, rec_data)
 
@@ -102,36 +103,29 @@ class _ConvNumpy(torch.autograd.Function):
         return torch.tensor(dx), torch.tensor(dW), torch.tensor(db), None, None
 
 
-def conv_leg(x, W, b, l, leg):
-    if leg == "numpy":
-        return _ConvNumpy.apply(x, W, b, l, True)
-    if leg == "dx_no_dilation":
-        return _ConvNumpy.apply(x, W, b, l, False)
-    return conv_torch(x, W, b, l, leg)
+def _general_only(mode):
+    """a wrong engine is wrong at the general layer only"""
+    return lambda x, W, b, l: _ConvNumpy.apply(x, W, b, l, False) if (mode == "dx_no_dilation" and l.general) else conv_torch(x, W, b, l, mode if l.general else "torch")
 
 
-# ------------------------------------------------------------------ the chain walker: this module's Conv, activation_layer_reference's everything else
-def _run(layers, it, x, hs, leg, probe, st):
-    for l in layers:
-        if l.kind == "conv":
-            _, a = next(it)
-            pre = conv_leg(x, a[0], a[1], l, leg if l.general else ("numpy" if leg == "numpy" else "torch"))      # a wrong engine is wrong at the general layer only
-            if probe is not None:
-                AL._kink(probe, pre, l.act)
-            x = AR.act_torch(pre, l.act); st["relu"] = l.act == AR.RELU
-        else:      # one layer (a SkipConnection: its whole block, which holds no general conv) of activation_layer_reference's walker
-            x = AL._run([l], it, x, hs, "torch", probe, st)
-    return x
+def _numpy(l, x, a, cx):
+    """the hand-written forward and backward for every Conv of the chain, general or not; a SkipConnection block (which holds no general conv) stays with conv_torch"""
+    return conv_torch(x, a[0], a[1], l) if cx.inner else _ConvNumpy.apply(x, a[0], a[1], l, True)
 
 
-# activation_layer_reference's step functions, instantiated over the walker above: the same code objects in a namespace of their own (they call each other there)
-_G = dict(vars(AL)); _G.update(_run=_run, _PREPARED={})
-for _n in ("q_step", "q_values", "probe_of", "ff_step", "rec_step", "trajectory", "margins", "margins_ok", "find_seed", "prepare"):
-    _f = getattr(AL, _n)
-    _G[_n] = types.FunctionType(_f.__code__, _G, _f.__name__, _f.__defaults__, _f.__closure__)
-q_step, q_values, probe_of, ff_step, rec_step, trajectory, margins, margins_ok, find_seed, prepare = (_G[_n] for _n in ("q_step", "q_values", "probe_of", "ff_step", "rec_step",
-                                                                                                                       "trajectory", "margins", "margins_ok", "find_seed", "prepare"))
-STEPS = AL.STEPS
+# the legs: overrides of step_reference's "conv" entry (which is conv_torch)
+LEGS = {"torch": {}, "numpy": {"conv": _numpy}} | {w: {"conv": S.conv_law(_general_only(w))} for w in WRONG}
+
+
+def trajectory(c, D=None, steps=AL.STEPS, seed=None, leg="torch"):
+    """activation_layer_reference.trajectory under this module's legs"""
+    return AL.trajectory(c, D, steps, seed, LEGS[leg])
+
+
+# everything else is activation_layer_reference's as it stands: the default leg of both modules is step_reference's table
+q_values, probe_of, margins, margins_ok, find_seed, STEPS = AL.q_values, AL.probe_of, AL.margins, AL.margins_ok, AL.find_seed, AL.STEPS
+ff_step, rec_step = S.bound(S.ff_step, LEGS, "leg"), S.bound(S.rec_step, LEGS, "leg")
+prepare = functools.partial(AL.prepare, cache={})
 
 
 # ------------------------------------------------------------------ the exact companion: the kind-1 network on the zero-stuffed, block-diagonal kernel

@@ -12,7 +12,7 @@ Two legs that share no join code:
   * "numpy"  feed-forward steps: feedforward_reference's conv forward / backward BY IMPORT (the oracle's pad-0 conv on the np.pad-ed input, the input gradient cropped; the
              pools' stacked taps) under a HAND-WRITTEN backward of the whole step in the engine's order (np_step: one dact per program entry, the join and the entry as
              stated above); recurrent steps: the torch graph with the join entered as skip_reference's NumPy autograd Function, which hands dY to both operands.
-np_step also runs the WRONG engines test_conv_skip_cpu.test_the_tests_can_tell shows apart (WRONG).
+np_step also runs the WRONG engines test_conv_skip_cpu.test_the_tests_can_tell shows apart (WRONG).  The step and the walker are step_reference's.
 
 Tolerances, the gradient check and Adam are the project's one set (re-exported below).  Data rule: every relu pre-activation of the online network on s at least
 RELU_MARGIN off the kink, every MaxPool window's top two taps at least RELU_MARGIN apart (feedforward_reference.margins' rule: a window whose maximum is a relu's exact 0
@@ -20,16 +20,17 @@ is exempt), the argmax gap of the selecting network at least GAP, no dead gradie
 the table's seeds, which were found with this module alone (find_seed).  No case is skipped and no element is masked out."""
 import numpy as np
 import torch
-import torch.nn.functional as F
 
 import dqn_oracle as O
 import feedforward_reference as FR
 import layernorm_reference as LR
 import recurrent_reference as R
 import skip_reference as SR
+import step_reference as STEP
 from feedforward_reference import GRAD_C, GRAD_RTOL, RELU_MARGIN, Adam, check_params      # noqa: F401  (re-exported: one set of constants)
 from gru_reference import param_arrays
 from layernorm_reference import GAP, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD      # noqa: F401
+from step_reference import blocks, check_grads, ff_batch, ff_data, grad_distance, legs_agree, rec_data      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
@@ -37,93 +38,7 @@ ENGINE_SEED = SR.ENGINE_SEED
 TELL = SR.TELL
 # the wrong engines: (name, changes the forward)
 WRONG = (("entry_without_dY", False), ("p_derivative_before_the_sum", False), ("p_derivative_twice", False), ("k_derivative_omitted", False), ("skip_read_from_f", True))
-ACT = SR.ACT
 program, _first_inner = SR.program, SR._first_inner
-
-
-# ------------------------------------------------------------------ the "law" leg (and the recurrent "numpy" leg): torch
-def _chain_t(chain, arrs, x, hs, fi, leg):
-    """one (time) step through a chain that may hold blocks; x keeps its (B, c, h, w) shape until a Dense or recurrent layer flattens it; returns (output, next flat index)"""
-    for l in chain:
-        if l.kind == "skip":
-            a, fi = _chain_t(l.layers, arrs, x, hs, fi, leg)
-            x = SR.JOIN[leg](a, x)
-            continue
-        a = arrs[fi]
-        if l.kind == "conv":      # a true convolution is the cross-correlation with the flipped kernel
-            x = ACT[l.act](F.conv2d(x, a[0].flip(2, 3), a[1], stride=(l.sh, l.sw), padding=(l.ph, l.pw)))
-        elif l.kind in ("maxpool", "meanpool"):
-            x = (F.max_pool2d if l.kind == "maxpool" else F.avg_pool2d)(x, (l.kh, l.kw), stride=(l.sh, l.sw))
-        elif l.kind == "dense":
-            x = ACT[l.act](x.reshape(x.shape[0], -1) @ a[0] + a[1])
-        else:
-            assert l.kind == "lstm", l.kind
-            hs[fi] = R.lstm_cell(x.reshape(x.shape[0], -1), hs[fi][0], hs[fi][1], a[0], a[1], a[2]); x = hs[fi][0]
-        fi += 1
-    return x, fi
-
-
-def q_step(net, arrs, x, hs, leg="law"):
-    if isinstance(net, nn.DuelingNetwork):
-        y, fi = _chain_t(net.base, arrs, x, hs, 0, leg)
-        v, fi = _chain_t(net.val, arrs, y, hs, fi, leg)
-        a, fi = _chain_t(net.adv, arrs, y, hs, fi, leg)
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _chain_t(net, arrs, x, hs, 0, leg)[0]
-
-
-def q_values(net, p, x, leg="law"):
-    """Q (B, nA) fp64 on x (B, c, h, w); recurrent: x (T, B, c, h, w) from the reset state -> [T] of (B, nA)"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not LR.is_recurrent(net):
-            return q_step(net, arrs, LR._t64(x), {}, leg).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1])
-        return [q_step(net, arrs, LR._t64(xt), hs, leg).numpy() for xt in x]
-
-
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, leg="law"):
-    if leg == "numpy":
-        return np_step(net, p_on, p_tg, batch, gamma, double_q)
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = LR._t64(s), LR._t64(sp), LR._t64(r), LR._t64(done), LR._t64(w)
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():      # the targets are constants of the loss (src/solver.jl:209-217)
-        q_tg_sp = q_step(net, atg, sp, {})
-        q_on_sp = q_step(net, aon, sp, {}) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)      # Julia's argmax: the smallest index among the maxima
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {})
-    td = q[torch.arange(B), a] - y
-    loss = LR._huber(w * td).sum() / B      # src/solver.jl:223-224
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, leg="law"):
-    """batch = (s, a, r, sp, done, mask), each (T, B, ...): the mask inside the Huber, / B per step, / T (recurrent_reference.train_grads)"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, leg)
-    q_on = q_values(net, p_on, sp, leg) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, LR._t64(s[t]), hs, leg)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - LR._t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + LR._huber(LR._t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, y=np.stack(ys), td=np.stack(tds))
 
 
 # ------------------------------------------------------------------ the "numpy" leg: the engine's order, by hand (feed-forward)
@@ -225,30 +140,11 @@ def np_step(net, p_on, p_tg, batch, gamma, double_q, wrong=None):
     return dict(q_on_s=q, q_on_sp=q_on_sp, q_tg_sp=q_tg_sp, best_a=best, y=y, td=td, loss=loss, grads=gv, grad_norm=float(np.abs(gv).max()))
 
 
-legs_agree = LR.legs_agree
-
-
-def blocks(net):
-    return FR.rec_blocks(net, nn)      # Flux.params order: W, b of every Conv / Dense, the LSTM's five arrays; nothing for a pool or a join
-
-
-def check_grads(net, got, want, live=True):
-    R.check_grads(net, nn, got, want, live=live, blks=blocks(net))
-
-
-def grad_distance(net, got, want):
-    """the largest gradient error in units of recurrent_reference.check_grads's bound (1.0 = at the bound)"""
-    gmax = np.abs(want).max(); worst = 0.0
-    for nm, sl in blocks(net):
-        wv = want[sl]; scale = max(np.abs(wv).max(), 1e-2 * gmax)
-        worst = max(worst, float((np.abs(got[sl] - wv) / (GRAD_C * scale + GRAD_RTOL * np.abs(wv))).max()))
-    return worst
-
-
-def distance(net, a, b):
-    out = SR.DR.distance(a, b)
-    out["grads"] = grad_distance(net, a["grads"], b["grads"])
-    return out
+# the legs: "law" is step_reference's walker as it stands; "numpy" is np_step for a feed-forward step and skip_reference's NumPy join for a recurrent one
+q_values = STEP.bound(STEP.q_values, {"law": {}, "numpy": SR.JOIN_NUMPY}, "leg")
+ff_step = STEP.bound(STEP.ff_step, {"law": {}, "numpy": np_step}, "leg")
+rec_step = STEP.bound(STEP.rec_step, {"law": {}, "numpy": SR.JOIN_NUMPY}, "leg")
+distance = SR.distance
 
 
 # ------------------------------------------------------------------ the case table
@@ -300,16 +196,7 @@ def readout_net(c, hw, blocks=2, m=2):
     return net, np.concatenate(conv * (1 + blocks * m) + [np.eye(n, dtype=np.float32).ravel(), np.zeros(n, np.float32)]), n
 BY_NAME = {c.name: c for c in ALL}
 assert len(BY_NAME) == len(ALL)
-ff_data, ff_batch, rec_data = LR.ff_data, LR.ff_batch, LR.rec_data
-
-
-def first_step(c, seed=None):
-    """(network data, fp64 batch) of the case's first step"""
-    if c.T:
-        D = rec_data(c, seed); idx, start = D.draws[0]
-        return D, R.sample_batch(D.ring, idx, start, c.T, c.obs)
-    D = ff_data(c, seed)
-    return D, ff_batch(c, D, D.idx[0])
+first_step = STEP.first_step      # (network data, fp64 batch) of the case's first step
 
 
 def step(c, D, batch, p_on=None, leg="law"):
@@ -369,7 +256,7 @@ def margins_ok(c, seed=None, k=2.0):
         if not (rm > f * RELU_MARGIN and pm > f * RELU_MARGIN and gap > f * GAP):
             return False
     D, _ = first_step(c, seed)
-    return not R.dead_blocks(D.net, nn, tr[0][1]["grads"], blks=blocks(D.net))
+    return not STEP.dead_blocks(D.net, tr[0][1]["grads"])
 
 
 def applies(c, wrong):
@@ -403,9 +290,4 @@ def tells_ok(c, seed=None, k=2.0):
     return all(d >= k * TELL for d in tell_distances(c, seed).values())
 
 
-def find_seed(c, cap=200):
-    """the smallest seed that keeps twice the margins, live gradient blocks and twice the tell distances (how the table's seeds were chosen, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if margins_ok(c, seed) and tells_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the margins")
+find_seed = lambda c, cap=200: STEP.find_seed(c, lambda c, seed: margins_ok(c, seed) and tells_ok(c, seed), cap)

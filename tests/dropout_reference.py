@@ -10,27 +10,23 @@ the four words for columns 4 (col / 4) + 0..3, u = (word >> 8) * 2^-24, keep <=>
 Two legs:
   * "law"    torch float64 autograd through torch.where(keep, x * scale, 0);
   * "numpy"  the same step with every Dropout layer a hand-written NumPy forward and backward (do_forward_np / do_backward_np) entered as a torch.autograd.Function.
-Everything that is not a Dropout layer runs through layernorm_reference._chain (its "law" leg).  `where` says which passes are masked: ("s",) is the law; ("s", "sp") and
+The step, the walker and every other layer's law are step_reference's; a leg here overrides the Dropout law alone.  `where` says which passes are masked: ("s",) is the law; ("s", "sp") and
 ("s", "tg") are the two WRONG engines (the layer active in the online pass on s' / in the target pass) the CPU tests show apart from it.
 
 Data rule: the margins of layernorm_reference (SIGMA_MIN, RELU_MARGIN, GAP), taken on the masked s pass and the unmasked s' passes.  Seeds are fixed in the table and were
 found with this module alone (find_seed)."""
-import types
-
 import numpy as np
 import torch
 
-import dqn_oracle as O
 import layernorm_reference as LR
-import recurrent_reference as R
 import replay_reference as RR
-from gru_reference import param_arrays
+import step_reference as S
+from step_reference import blocks, check_grads, distance, ff_batch, ff_data, rec_data      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
 DO_TAG = 0x44520000
 ENGINE_SEED = 5      # hparams.seed of every engine the GPU tests build for these tables (the mask's key)
-LAW = ("s",)
 
 
 # ------------------------------------------------------------------ the mask law
@@ -98,119 +94,23 @@ class _DoNumpy(torch.autograd.Function):
         return torch.tensor(do_backward_np(ctx.keep, ctx.scale, dy.numpy())), None, None
 
 
-LEGS = {"law": do_law, "numpy": _DoNumpy.apply}
+LEGS = {"law": {}, "numpy": {"dropout": S.dropout_law(_DoNumpy.apply, do_scale)}}
 
 
-def _chain(layers, arrs, x, hs, li0, masks, leg, probe):
-    """layernorm_reference._chain over the runs between Dropout layers; masks: {layer index: keep (B, n)} or None = every Dropout layer inactive"""
-    i = 0
-    while i < len(layers):
-        j = i
-        while j < len(layers) and layers[j].kind != "dropout":
-            j += 1
-        if j > i:
-            x = LR._chain(layers[i:j], arrs, x, hs, li0 + i, "law", probe)
-        if j < len(layers):
-            x = x.reshape(x.shape[0], -1)
-            if probe is not None:
-                probe.setdefault("do_in", {})[li0 + j] = x.detach().numpy().copy()
-            if masks is not None:
-                x = LEGS[leg](x, torch.tensor(masks[li0 + j]), do_scale(layers[j].p))
-            j += 1
-        i = j
-    return x
+def _see_input(probe, l, x, cx):
+    if l.kind == "dropout":
+        probe.setdefault("do_in", {})[cx.k] = x.reshape(x.shape[0], -1).detach().numpy().copy()
 
 
-def q_step(net, arrs, x, hs, masks=None, leg="law", probe=None):
-    if isinstance(net, nn.DuelingNetwork):
-        nb, nv = len(net.base.layers), len(net.val.layers)
-        y = _chain(net.base.layers, arrs, x, hs, 0, masks, leg, probe)
-        v = _chain(net.val.layers, arrs, y, hs, nb, masks, leg, probe)
-        a = _chain(net.adv.layers, arrs, y, hs, nb + nv, masks, leg, probe)
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _chain(net.layers, arrs, x, hs, 0, masks, leg, probe)
+OBSERVERS = LR.OBSERVERS | {"in": _see_input}      # sigma, relu margin, and "do_in": {layer index: the layer's input}
 
 
-def _at(masks, t):
-    return None if masks is None else {k: v[t] for k, v in masks.items()}
+def new_probe():
+    return S.Probe(OBSERVERS, sigma=np.inf, relu=np.inf)
 
 
-def q_values(net, p, x, masks=None, leg="law", probe=None):
-    """Q (B, nA) fp64 of a feed-forward network on x (B, ...); recurrent: x (T, B, ...) from the reset state -> [T] of (B, nA).  masks None: the inactive layer"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not LR.is_recurrent(net):
-            return q_step(net, arrs, LR._t64(x), {}, masks, leg, probe).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1])
-        return [q_step(net, arrs, LR._t64(xt), hs, _at(masks, t), leg, probe).numpy() for t, xt in enumerate(x)]
-
-
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, masks, leg="law", where=LAW):
-    """layernorm_reference.ff_step with the Dropout layers active, under `masks`, in the passes `where` names ("s": the law)"""
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = LR._t64(s), LR._t64(sp), LR._t64(r), LR._t64(done), LR._t64(w)
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():
-        q_tg_sp = q_step(net, atg, sp, {}, masks if "tg" in where else None, leg)
-        q_on_sp = q_step(net, aon, sp, {}, masks if "sp" in where else None, leg) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {}, masks if "s" in where else None, leg)
-    td = q[torch.arange(B), a] - y
-    loss = LR._huber(w * td).sum() / B
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, masks, leg="law", where=LAW):
-    """layernorm_reference.rec_step: the target loop (both networks over s') unmasked, the BPTT loop over s with a fresh mask per time step (masks[layer][t])"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, masks if "tg" in where else None, leg)
-    q_on = q_values(net, p_on, sp, masks if "sp" in where else None, leg) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, LR._t64(s[t]), hs, _at(masks, t) if "s" in where else None, leg)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - LR._t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + LR._huber(LR._t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, y=np.stack(ys), td=np.stack(tds))
-
-
-def blocks(net):
-    """[(name, slice into the flat Flux.params vector)]: layernorm_reference.blocks; a Dropout layer holds nothing"""
-    names = {"lstm": ("Wi", "Wh", "b", "h0", "c0"), "gru": ("Wi", "Wh", "b", "h0"), "dense": ("W", "b"), "conv": ("W", "b"), "layernorm": ("scale", "bias"), "dropout": ()}
-    out, off = [], 0
-    for li, l in enumerate(nn.all_layers(net)):
-        for nm, shp in zip(names[l.kind], l.shapes()):
-            k = int(np.prod(shp)); out.append((f"{'ln' if l.kind == 'layernorm' else l.kind}{li}.{nm}", slice(off, off + k))); off += k
-    return out
-
-
-def check_grads(net, got, want, live=True):
-    R.check_grads(net, nn, got, want, live=live, blks=blocks(net))
-
-
-def distance(a, b):
-    """{quantity: the largest |a - b| / tolerance} over what the GPU tests compare with the project's constants (1.0 = at the bound)"""
-    out = {}
-    for k, tol in (("q_on_s", LR.TOL_Q), ("q_on_sp", LR.TOL_Q), ("q_tg_sp", LR.TOL_Q), ("y", LR.TOL_TD), ("td", LR.TOL_TD)):
-        if k in a and k in b:
-            x, y = np.asarray(a[k], np.float64), np.asarray(b[k], np.float64)
-            out[k] = float((np.abs(x - y) / (tol["atol"] + tol["rtol"] * np.abs(y))).max())
-    out["loss"] = abs(a["loss"] - b["loss"]) / (LR.TOL_LOSS["atol"] + LR.TOL_LOSS["rtol"] * abs(b["loss"]))
-    return out
+q_values = S.bound(S.q_values, LEGS, "masks")
+ff_step, rec_step = S.bound(S.ff_step, LEGS, "masks"), S.bound(S.rec_step, LEGS, "masks")
 
 
 # ------------------------------------------------------------------ the case table
@@ -247,16 +147,12 @@ REC_CASES = [
 ]
 BY_NAME = {c.name: c for c in CASES + REC_CASES}
 assert len(BY_NAME) == len(CASES) + len(REC_CASES)
-ff_data, ff_batch, rec_data = LR.ff_data, LR.ff_batch, LR.rec_data
 
 
 def first_step(c, seed=None):
     """(network data, fp64 batch, masks) of the case's first step"""
-    if c.T:
-        D = rec_data(c, seed); idx, start = D.draws[0]
-        return D, R.sample_batch(D.ring, idx, start, c.T, c.obs), masks_for(D.net, 0, c.B, c.T)
-    D = ff_data(c, seed)
-    return D, ff_batch(c, D, D.idx[0]), masks_for(D.net, 0, c.B)
+    D, batch = S.first_step(c, seed)
+    return D, batch, masks_for(D.net, 0, c.B, c.T)
 
 
 def step(c, D, batch, masks, **kw):
@@ -266,7 +162,7 @@ def step(c, D, batch, masks, **kw):
 def case_margins(c, seed=None):
     """(sigma_min, relu margin, argmax gap) of the first step in fp64: sigma and the relu margin over the MASKED s pass under the online parameters and the unmasked s'
     passes of both networks; the gap over the columns of the network that picks the action"""
-    D, batch, masks = first_step(c, seed); probe = dict(sigma=np.inf, relu=np.inf)
+    D, batch, masks = first_step(c, seed); probe = new_probe()
     q_values(D.net, D.p_on, batch[0], masks, probe=probe)
     qon = q_values(D.net, D.p_on, batch[3], probe=probe); qtg = q_values(D.net, D.p_tg, batch[3], probe=probe)
     qsel = qon if c.dq else qtg
@@ -296,18 +192,13 @@ def tells_ok(c, seed=None, k=2.0):
     return all(d is None or d >= k * TELL for d in tell_distances(c, seed))
 
 
-def find_seed(c, cap=200):
-    """the smallest seed that keeps twice the margins and twice the tell distances (how the table's seeds were chosen, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if margins_ok(c, seed) and tells_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the margins")
+find_seed = lambda c, cap=200: S.find_seed(c, lambda c, seed: margins_ok(c, seed) and tells_ok(c, seed), cap)
 
 
 def flip_one(c, D, batch, masks):
     """the masks with ONE element flipped: in the first Dropout layer, column 0 (recurrent: t = 0, b = 0), the feature where the layer's input is largest in magnitude
     (an element whose input is 0 -- a dead relu -- changes nothing under any mask)"""
-    probe = dict(sigma=np.inf, relu=np.inf); l = min(masks)
+    probe = new_probe(); l = min(masks)
     q_values(D.net, D.p_on, batch[0][:1] if c.T else batch[0], _at_first(masks) if c.T else masks, probe=probe)      # recurrent: the first time step alone
     x = probe["do_in"][l]
     f = int(np.abs(x[0]).argmax())

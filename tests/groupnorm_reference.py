@@ -13,8 +13,8 @@ Legs:
   * "ln_law"  the OTHER law, (x - mu) / (sigma + eps) as LayerNorm's `normalise` has it: only the tell-apart test of test_groupnorm_cpu calls it.
 tests/test_groupnorm_cpu.py holds the first two to 1e-10 of each other on every case and checks the hand-written gradient against central differences.
 
-Everything but the layer -- the constants, the cells, the batches, the gradient check per block, the fp64 Adam -- is that of layernorm_reference / recurrent_reference /
-feedforward_edges_common, imported, not restated.  No tolerance is introduced here.
+Everything but the layer -- the walker and the step, the constants, the cells, the batches, the gradient check per block, the fp64 Adam -- is that of step_reference /
+layernorm_reference / recurrent_reference / feedforward_edges_common, imported, not restated.  No tolerance is introduced here.
 
 Data rule: beside the relu margin and the argmax gap, every non-degenerate group keeps sqrt(var) >= SIGMA_MIN (the LayerNorm table's value; a group that is identically
 0 -- case dead_group -- is degenerate on purpose), and every MaxPool window keeps its top-two gap above RELU_MARGIN unless its maximum is an exact 0 out of a relu.
@@ -25,12 +25,12 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-import dqn_oracle as O
 import layernorm_reference as LR
 import recurrent_reference as R
-from drqn_common import draws, make_episodes      # noqa: F401
-from gru_reference import param_arrays
-from layernorm_reference import GAP, GRAD_C, GRAD_RTOL, RELU_MARGIN, SIGMA_MIN, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD, Adam, check_params, legs_agree, _gap, _huber, _t64      # noqa: F401  (one set of constants)
+import step_reference as S
+from gru_reference import param_arrays      # noqa: F401
+from layernorm_reference import GAP, GRAD_C, GRAD_RTOL, RELU_MARGIN, SIGMA_MIN, TOL_GN, TOL_LOSS, TOL_Q, TOL_TD, Adam, check_params      # noqa: F401  (one set of constants)
+from step_reference import _gap, _t64, blocks, check_grads, dead_blocks, ff_batch, legs_agree      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
@@ -92,18 +92,10 @@ class _GnNumpy(torch.autograd.Function):
         return torch.tensor(dx), torch.tensor(db), torch.tensor(dg), None, None
 
 
-LEGS = {"torch": gn_torch, "numpy": _GnNumpy.apply, "ln_law": gn_ln_law}
+LEGS = {"torch": {}, "numpy": {"groupnorm": S.groupnorm_law(_GnNumpy.apply)}, "ln_law": {"groupnorm": S.groupnorm_law(gn_ln_law)}}
 
 
-# ------------------------------------------------------------------ chains of nn descriptors
-def _act(y, act):
-    return {nn.identity: lambda v: v, nn.relu: torch.relu, nn.tanh: torch.tanh, nn.sigmoid: torch.sigmoid, nn.leakyrelu: lambda v: F.leaky_relu(v, 0.01)}[act](y)
-
-
-def new_probe():
-    return dict(sigma=np.inf, relu=np.inf, pool=np.inf, dead=0)
-
-
+# ------------------------------------------------------------------ the observers, and the step (step_reference's, bound to the legs)
 def _pool_gap(l, x, relu_out):
     """the smallest top-two gap over the MaxPool windows of x, except windows whose maximum is an exact 0 out of a relu (feedforward_reference.margins' rule)"""
     if l.kh * l.kw == 1:
@@ -115,148 +107,39 @@ def _pool_gap(l, x, relu_out):
     return float(gap.min())
 
 
-def _rows(probe, x):
-    """the columns a probe looks at: all, or those a recurrent batch's mask keeps (a padded column -- an all-zero observation -- carries mask 0 inside the Huber: no
-    gradient reaches it and nothing of it is compared, as feedforward_reference.rec_margins has it)"""
-    m = probe.get("rows")
-    return slice(None) if m is None else m
-
-
 def _min(t):
     return float(t.min()) if t.numel() else np.inf
 
 
-def _run(layers, it, x, hs, leg, probe, st):
-    """one (time) step through a chain; `it` yields (flat layer index, parameter arrays) in nn.all_layers order; st['relu']: x is the output of a relu (through pools)"""
-    for l in layers:
-        if l.kind == "skip":
-            x = _run(l.layers.layers, it, x, hs, leg, probe, st) + x
-            st["relu"] = False
-            continue
-        k, a = next(it)
-        if l.kind == "lstm":
-            hs[k] = R.lstm_cell(x.reshape(x.shape[0], -1), hs[k][0], hs[k][1], a[0], a[1], a[2]); x = hs[k][0]
-            st["relu"] = False
-            continue
-        if l.kind in ("maxpool", "meanpool"):
-            if l.kind == "maxpool" and probe is not None:
-                probe["pool"] = min(probe["pool"], _pool_gap(l, x.detach(), st["relu"]))
-            x = (F.max_pool2d if l.kind == "maxpool" else F.avg_pool2d)(x, (l.kh, l.kw), stride=(l.sh, l.sw))
-            st["relu"] = st["relu"] and l.kind == "maxpool"
-            continue
-        if l.kind == "conv":      # a true convolution is the cross-correlation with the flipped kernel (feedforward_reference._layer_t)
-            pre = F.conv2d(x, a[0].flip(2, 3), a[1], stride=(l.sh, l.sw), padding=(l.ph, l.pw))
-        elif l.kind == "groupnorm":
-            pre = LEGS[leg](x, a[0], a[1], l.G, float(np.float32(l.eps)))      # Flux.params order: beta, gamma
-            if probe is not None:
-                sg = _sigma(x.detach(), l.G)[_rows(probe, x)]; dead = sg == 0.0
-                probe["dead"] += int(dead.sum())
-                if (~dead).any():
-                    probe["sigma"] = min(probe["sigma"], _min(sg[~dead]))
-        else:
-            assert l.kind == "dense", l.kind
-            pre = x.reshape(x.shape[0], -1) @ a[0] + a[1]
-        if probe is not None and l.act == nn.relu:
-            probe["relu"] = min(probe["relu"], _min(pre.detach()[_rows(probe, x)].abs()))
-        x = _act(pre, l.act); st["relu"] = l.act == nn.relu
-    return x
+def _see_input(probe, l, x, cx):
+    if l.kind == "maxpool":
+        probe["pool"] = min(probe["pool"], _pool_gap(l, x.detach(), cx.relu))
+    elif l.kind == "groupnorm":
+        sg = S.kept(cx, _sigma(x.detach(), l.G)); dead = sg == 0.0
+        probe["dead"] += int(dead.sum())
+        if (~dead).any():
+            probe["sigma"] = min(probe["sigma"], _min(sg[~dead]))
 
 
-def q_step(net, arrs, x, hs, leg="torch", probe=None):
-    it = iter(enumerate(arrs)); st = dict(relu=False)
-    if isinstance(net, nn.DuelingNetwork):
-        y = _run(net.base.layers, it, x, hs, leg, probe, st)
-        v = _run(net.val.layers, it, y, hs, leg, probe, dict(st))
-        a = _run(net.adv.layers, it, y, hs, leg, probe, dict(st))
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _run(net.layers, it, x, hs, leg, probe, st)
+def _see_relu(probe, l, pre, cx):
+    if l.act == nn.relu:
+        probe["relu"] = min(probe["relu"], _min(S.kept(cx, pre.detach()).abs()))
 
 
-def is_recurrent(net):
-    return any(l.kind in LR.RECURRENT for l in nn.all_layers(net))
+# "sigma": the smallest sqrt(var) over the non-degenerate groups, "dead": the number of degenerate ones, "relu" / "pool": the relu and MaxPool margins
+OBSERVERS = {"in": _see_input, "pre": _see_relu}
 
 
-def q_values(net, p, x, leg="torch", probe=None, mask=None):
-    """Q (B, nA) as fp64 NumPy of a feed-forward network on observations x (B, C, H, W); a recurrent network: x (T, B, C, H, W) from the reset state -> [T] of (B, nA)"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not is_recurrent(net):
-            return q_step(net, arrs, _t64(x), {}, leg, probe).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1]); out = []
-        for t, xt in enumerate(x):
-            if probe is not None and mask is not None:
-                probe["rows"] = torch.tensor(np.asarray(mask[t]) > 0)
-            out.append(q_step(net, arrs, _t64(xt), hs, leg, probe).numpy())
-        return out
+def new_probe():
+    return S.Probe(OBSERVERS, sigma=np.inf, relu=np.inf, pool=np.inf, dead=0)
+
+
+q_values = S.bound(S.q_values, LEGS, "leg", "probe", "mask")
+ff_step, rec_step = S.bound(S.ff_step, LEGS, "leg"), S.bound(S.rec_step, LEGS, "leg")
 
 
 def probe_of(net, p, s, mask=None):
-    pr = new_probe(); q_values(net, p, s, probe=pr, mask=mask)
-    return pr
-
-
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, leg="torch", swap=None):
-    """layernorm_reference.ff_step over this module's chain.  batch = (s, a, r, sp, done, w) as get_batch returns it"""
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = _t64(s), _t64(sp), _t64(r), _t64(done), _t64(w)
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():       # the targets are constants of the loss (src/solver.jl:209-217)
-        q_tg_sp = q_step(net, atg, sp, {}, leg)
-        q_on_sp = q_step(net, aon, sp, {}, leg) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)      # Julia's argmax: the smallest index among the maxima
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {}, leg)
-    td = q[torch.arange(B), a] - y
-    loss = _huber(w * td).sum() / B        # src/solver.jl:223-224
-    loss.backward()
-    g = np.concatenate([(x.grad if x.grad is not None else torch.zeros_like(x)).numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, leg="torch"):
-    """layernorm_reference.rec_step over this module's chain.  batch = (s, a, r, sp, done, mask), each (T, B, ...)"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, leg)
-    q_on = q_values(net, p_on, sp, leg) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, _t64(s[t]), hs, leg)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - _t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + _huber(_t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, td=np.stack(tds))
-
-
-BLOCK_NAMES = {"lstm": ("Wi", "Wh", "b", "h0", "c0"), "dense": ("W", "b"), "conv": ("W", "b"), "groupnorm": ("beta", "gamma"), "maxpool": (), "meanpool": ()}
-
-
-def blocks(net):
-    """[(name, slice into the flat Flux.params vector)]; a GroupNorm layer i holds gn<i>.beta, THEN gn<i>.gamma"""
-    out, off = [], 0
-    for li, l in enumerate(nn.all_layers(net)):
-        for nm, shp in zip(BLOCK_NAMES[l.kind], l.shapes()):
-            k = int(np.prod(shp)); out.append((f"{'gn' if l.kind == 'groupnorm' else l.kind}{li}.{nm}", slice(off, off + k))); off += k
-    return out
-
-
-def dead_blocks(net, g):
-    return R.dead_blocks(net, nn, g, blks=blocks(net))
-
-
-def check_grads(net, got, want, live=True):
-    """recurrent_reference.check_grads per block (GRAD_C, GRAD_RTOL unchanged); live: no block's fp64 gradient is negligible"""
-    R.check_grads(net, nn, got, want, live=live, blks=blocks(net))
+    return S.probed(new_probe(), q_values, net, p, s, mask=mask)
 
 
 # ------------------------------------------------------------------ the case table
@@ -320,20 +203,16 @@ def _kill(c, net, p):
     return p
 
 
-def ff_data(c, seed=None):
-    """layernorm_reference.ff_data, plus the case's dead channels"""
-    D = LR.ff_data(c, seed)
-    _kill(c, D.net, D.p_on); _kill(c, D.net, D.p_tg)
-    return D
+def _data(data):
+    """layernorm_reference's data of a case, plus the case's c0scale and dead channels"""
+    def make(c, seed=None):
+        D = data(c, seed)
+        _kill(c, D.net, D.p_on); _kill(c, D.net, D.p_tg)
+        return D
+    return make
 
 
-ff_batch = LR.ff_batch
-
-
-def rec_data(c, seed=None):
-    D = LR.rec_data(c, seed)
-    _kill(c, D.net, D.p_on); _kill(c, D.net, D.p_tg)
-    return D
+ff_data, rec_data = _data(S.ff_data), _data(S.rec_data)
 
 
 def case_margins(c, seed=None):
@@ -356,9 +235,4 @@ def margins_ok(c, seed=None, k=2.0):
     return sg >= k * SIGMA_MIN and rm > k * RELU_MARGIN and pm > k * RELU_MARGIN and gap > k * GAP
 
 
-def find_seed(c, cap=200):
-    """the smallest seed that keeps twice the margins (how the table's seeds were chosen, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if margins_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the margins")
+find_seed = lambda c, cap=200: S.find_seed(c, margins_ok, cap)

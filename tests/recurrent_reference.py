@@ -137,16 +137,32 @@ def train_grads(net, nn, p_on, p_tg, batch, gamma, double_q):
     return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), ys=ys)
 
 
+def drqn_train_step(net, nn, p_on, p_tg, batch, gamma, double_q, lr=1e-3):
+    """train_grads plus the first fp64 Adam step from p_on.  batch = (s, a, r, sp, done, mask) as returned by Engine.episode_get_batch: s, sp [T][B][obs...], the rest [T][B]"""
+    o = train_grads(net, nn, p_on, p_tg, batch, gamma, double_q)
+    p64 = np.asarray(p_on, np.float64)
+    o["new_params"] = O.adam_update([p64], [o["grads"]], O.AdamState([p64], lr))[0]
+    return o
+
+
+def check_step(h, net, nn, batch, ep_idx, ep_start, gamma, double_q, p_on, p_tg):
+    """one engine train step on the given draws against the fp64 reference, at check_against_oracle's tolerances (tests/drqn_common.py)"""
+    o = drqn_train_step(net, nn, p_on, p_tg, batch, gamma, double_q)
+    loss, gn = h.train_step_drqn(ep_idx, ep_start)
+    np.testing.assert_allclose(loss, o["loss"], rtol=2e-5, atol=1e-7)
+    g = h.get_grads(); sc = np.abs(o["grads"]).max() + 1e-30
+    np.testing.assert_allclose(g, o["grads"], atol=3e-5 * sc, rtol=1e-4)
+    np.testing.assert_allclose(gn, o["grad_norm"], rtol=1e-4)
+    diff = np.abs(h.get_params(0) - o["new_params"])
+    assert diff.max() <= 2.1e-3 and (diff > 5e-6).mean() < 1e-3     # Adam at |g| ~ eps moves a parameter by up to lr (tests/drqn_common.py)
+    return loss, gn
+
+
 def blocks(net, nn):
-    """[(name, slice into the flat vector)]: the Wi, Wh, b, h0 (, c0) of each recurrent layer, the W and b of each Dense"""
-    names = {"lstm": ("Wi", "Wh", "b", "h0", "c0"), "gru": ("Wi", "Wh", "b", "h0"), "rnn": ("Wi", "Wh", "b", "h0"), "dense": ("W", "b")}
-    out, off = [], 0
-    for li, l in enumerate(nn.all_layers(net)):
-        for nm, s in zip(names[l.kind], l.shapes()):
-            k = int(np.prod(s))
-            out.append((f"{l.kind}{li}.{nm}", slice(off, off + k)))
-            off += k
-    return out
+    """[(name, slice into the flat vector)]: the Wi, Wh, b, h0 (, c0) of each recurrent layer, the W and b of each Dense: step_reference.blocks, the one table of block names
+    (imported here: that module imports this one)"""
+    from step_reference import blocks
+    return blocks(net)
 
 
 # gradient tolerance per block: atol = GRAD_C * max(max |g_block|, 1e-2 * max |g|) plus rtol GRAD_RTOL.  GRAD_C is 4x the largest

@@ -9,9 +9,10 @@ Two legs:
   * "law"    torch float64 autograd through `layers(x) + x` written out;
   * "numpy"  feed-forward steps: a NumPy forward and a HAND-WRITTEN backward of the whole step in the engine's order (np_step: one dact per layer, the join and entry
              rules above, ln_backward_np / do_backward_np for the two layer kinds that have one); recurrent steps: the torch graph with the join entered as a NumPy
-             torch.autograd.Function whose backward hands dY to both operands (and dropout_reference's NumPy Dropout).
-np_step also runs the WRONG engines test_skip_cpu.test_the_tests_can_tell shows apart (WRONG).  Dense layers are computed here (every activation the cases use, elu
-included); LayerNorm, Dropout and the recurrent cells are dropout_reference's / layernorm_reference's / recurrent_reference's, by import.
+             torch.autograd.Function whose backward hands dY to both operands (JOIN_NUMPY, the one override of the leg).
+The step and the walker are step_reference's.
+np_step also runs the WRONG engines test_skip_cpu.test_the_tests_can_tell shows apart (WRONG); its LayerNorm and Dropout are layernorm_reference's / dropout_reference's
+NumPy forward and backward, by import.
 
 A Dropout layer's mask is keyed by the layer's ENGINE index (its descriptor's position: every join in front of it counts), while the reference's arrays are indexed in
 Flux.params order (nn.all_layers: inner layers in place, no join); engine_index maps one to the other.
@@ -22,13 +23,12 @@ import types
 
 import numpy as np
 import torch
-import torch.nn.functional as F
 
-import dqn_oracle as O
 import dropout_reference as DR
 import layernorm_reference as LR
-import recurrent_reference as R
+import step_reference as STEP
 from gru_reference import param_arrays
+from step_reference import blocks, check_grads, ff_batch, ff_data, grad_distance, legs_agree, rec_data      # noqa: F401
 
 nn = LR.nn
 F64 = torch.float64
@@ -36,7 +36,6 @@ ENGINE_SEED = DR.ENGINE_SEED
 # the wrong engines: (name, changes the forward)
 WRONG = (("entry_without_dY", False), ("p_derivative_before_the_sum", False), ("p_derivative_twice", False), ("k_derivative_omitted", False),
          ("k_preactivation_added", True), ("skip_read_from_f", True))
-ACT = {nn.identity: lambda v: v, nn.relu: torch.relu, nn.tanh: torch.tanh, nn.sigmoid: torch.sigmoid, nn.elu: F.elu}
 
 
 # ------------------------------------------------------------------ structure
@@ -82,7 +81,7 @@ def masks_for(net, k, B, T=0, seed=ENGINE_SEED):
     return out
 
 
-# ------------------------------------------------------------------ the "law" leg (and the recurrent "numpy" leg): torch
+# ------------------------------------------------------------------ the join in NumPy (the recurrent "numpy" leg), and the step
 class _JoinNumpy(torch.autograd.Function):
     @staticmethod
     def forward(ctx, a, x):
@@ -94,89 +93,7 @@ class _JoinNumpy(torch.autograd.Function):
         return torch.tensor(g.copy()), torch.tensor(g.copy())      # the join hands dY to the inner chain AND to the entry
 
 
-JOIN = {"law": lambda a, x: a + x, "numpy": _JoinNumpy.apply}
-
-
-def _chain(chain, arrs, x, hs, fi, masks, leg, probe):
-    """one (time) step through a chain that may hold blocks; returns (output, next flat index)"""
-    for l in chain:
-        if l.kind == "skip":
-            x = x.reshape(x.shape[0], -1)
-            a, fi = _chain(l.layers, arrs, x, hs, fi, masks, leg, probe)
-            x = JOIN[leg](a, x)
-            continue
-        if l.kind == "dense":
-            pre = x.reshape(x.shape[0], -1) @ arrs[fi][0] + arrs[fi][1]
-            if probe is not None and l.act == nn.relu:
-                probe["relu"] = min(probe["relu"], float(pre.detach().abs().min()))
-            x = ACT[l.act](pre)
-        else:      # LayerNorm, Dropout, LSTM, GRU: the existing references' own
-            x = DR._chain([l], arrs, x, hs, fi, masks, leg, probe)
-        fi += 1
-    return x, fi
-
-
-def q_step(net, arrs, x, hs, masks=None, leg="law", probe=None):
-    if isinstance(net, nn.DuelingNetwork):
-        y, fi = _chain(net.base, arrs, x, hs, 0, masks, leg, probe)
-        v, fi = _chain(net.val, arrs, y, hs, fi, masks, leg, probe)
-        a, fi = _chain(net.adv, arrs, y, hs, fi, masks, leg, probe)
-        return v + a - a.mean(dim=1, keepdim=True)      # src/dueling.jl:10
-    return _chain(net, arrs, x, hs, 0, masks, leg, probe)[0]
-
-
-def q_values(net, p, x, masks=None, leg="law", probe=None):
-    """Q (B, nA) fp64 on x (B, ...); recurrent: x (T, B, ...) from the reset state -> [T] of (B, nA).  masks None: every Dropout layer inactive"""
-    arrs = param_arrays(net, nn, np.asarray(p, np.float64))
-    with torch.no_grad():
-        if not LR.is_recurrent(net):
-            return q_step(net, arrs, LR._t64(x), {}, masks, leg, probe).numpy()
-        hs = LR.init_state(net, arrs, np.asarray(x).shape[1])
-        return [q_step(net, arrs, LR._t64(xt), hs, DR._at(masks, t), leg, probe).numpy() for t, xt in enumerate(x)]
-
-
-def ff_step(net, p_on, p_tg, batch, gamma, double_q, masks, leg="law"):
-    if leg == "numpy":
-        return np_step(net, p_on, p_tg, batch, gamma, double_q, masks)
-    s, a, r, sp, done, w = batch
-    s, sp, r, done, w = LR._t64(s), LR._t64(sp), LR._t64(r), LR._t64(done), LR._t64(w)
-    a = torch.tensor(np.asarray(a, np.int64)); B = s.shape[0]
-    aon, atg = param_arrays(net, nn, np.asarray(p_on, np.float64)), param_arrays(net, nn, np.asarray(p_tg, np.float64))
-    with torch.no_grad():
-        q_tg_sp = q_step(net, atg, sp, {})
-        q_on_sp = q_step(net, aon, sp, {}) if double_q else q_tg_sp
-        best = (q_on_sp == q_on_sp.max(dim=1, keepdim=True).values).to(torch.int64).argmax(dim=1)
-        y = r + (1.0 - done) * float(gamma) * q_tg_sp[torch.arange(B), best]
-    leaves = [x for la in aon for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    q = q_step(net, aon, s, {}, masks)
-    td = q[torch.arange(B), a] - y
-    loss = LR._huber(w * td).sum() / B
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(q_on_s=q.detach().numpy(), q_on_sp=q_on_sp.numpy(), q_tg_sp=q_tg_sp.numpy(), best_a=best.numpy(), y=y.numpy(), td=td.detach().numpy(),
-                loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()))
-
-
-def rec_step(net, p_on, p_tg, batch, gamma, double_q, masks, leg="law"):
-    """dropout_reference.rec_step over this module's chains: the target loop unmasked, the BPTT loop over s with a fresh mask per time step"""
-    s, a, r, sp, d, m = batch; T, B = s.shape[0], s.shape[1]
-    q_tg = q_values(net, p_tg, sp, None, leg)
-    q_on = q_values(net, p_on, sp, None, leg) if double_q else q_tg
-    ys = [O.bellman_targets(q_on[t], q_tg[t], r[t].astype(np.float64), d[t].astype(np.float64), gamma, double_q)[0] for t in range(T)]
-    arrs = param_arrays(net, nn, np.asarray(p_on, np.float64)); leaves = [x for la in arrs for x in la]
-    for x in leaves:
-        x.requires_grad_(True)
-    hs = LR.init_state(net, arrs, B); loss = torch.zeros((), dtype=F64); tds = []
-    for t in range(T):
-        q = q_step(net, arrs, LR._t64(s[t]), hs, DR._at(masks, t), leg)
-        td = q[torch.arange(B), torch.tensor(a[t].astype(np.int64))] - LR._t64(ys[t]); tds.append(td.detach().numpy())
-        loss = loss + LR._huber(LR._t64(m[t]) * td).sum() / B
-    loss = loss / T
-    loss.backward()
-    g = np.concatenate([x.grad.numpy().reshape(-1) for x in leaves])
-    return dict(loss=float(loss.detach()), grads=g, grad_norm=float(np.abs(g).max()), q_on_sp=q_on, q_tg_sp=q_tg, y=np.stack(ys), td=np.stack(tds))
+JOIN_NUMPY = {"skip": lambda l, x, a, cx: _JoinNumpy.apply(a, x)}      # the override of step_reference's `layers(x) + x`; a: the inner chain's output
 
 
 # ------------------------------------------------------------------ the "numpy" leg: the engine's order, by hand (feed-forward)
@@ -297,36 +214,15 @@ def np_step(net, p_on, p_tg, batch, gamma, double_q, masks, wrong=None):
     return dict(q_on_s=q, q_on_sp=q_on_sp, q_tg_sp=q_tg_sp, best_a=best, y=y, td=td, loss=loss, grads=gv, grad_norm=float(np.abs(gv).max()))
 
 
-def legs_agree(a, b, rel=1e-10):
-    LR.legs_agree(a, b, rel)
-
-
-def blocks(net):
-    return DR.blocks(net)      # Flux.params order: the inner layers in place, nothing for a join
-
-
-def check_grads(net, got, want, live=True):
-    DR.check_grads(net, got, want, live=live)
-
-
-def grad_distance(net, got, want):
-    """the largest gradient error in units of recurrent_reference.check_grads's bound (1.0 = at the bound)"""
-    gmax = np.abs(want).max(); worst = 0.0
-    for nm, sl in blocks(net):
-        wv = want[sl]; scale = max(np.abs(wv).max(), 1e-2 * gmax)
-        worst = max(worst, float((np.abs(got[sl] - wv) / (R.GRAD_C * scale + R.GRAD_RTOL * np.abs(wv))).max()))
-    return worst
-
-
-def distance(net, a, b):
-    out = DR.distance(a, b)
-    out["grads"] = grad_distance(net, a["grads"], b["grads"])
-    return out
+# the legs: "law" is step_reference's walker as it stands; "numpy" is np_step for a feed-forward step and the NumPy join for a recurrent one
+q_values = STEP.bound(STEP.q_values, {"law": {}, "numpy": JOIN_NUMPY}, "masks")
+ff_step = STEP.bound(STEP.ff_step, {"law": {}, "numpy": np_step}, "masks")
+rec_step = STEP.bound(STEP.rec_step, {"law": {}, "numpy": JOIN_NUMPY}, "masks")
+distance = lambda net, a, b: STEP.distance(a, b, net)
 
 
 # ------------------------------------------------------------------ the case table
-def case(name, mk, B, **kw):
-    return LR.case(name, mk, B, **kw)
+case = LR.case
 
 
 def S(*inner):
@@ -372,16 +268,10 @@ REC_CASES = [
 ]
 BY_NAME = {c.name: c for c in CASES + REC_CASES}
 assert len(BY_NAME) == len(CASES) + len(REC_CASES)
-ff_data, ff_batch, rec_data = LR.ff_data, LR.ff_batch, LR.rec_data
-
-
 def first_step(c, seed=None):
     """(network data, fp64 batch, masks) of the case's first step"""
-    if c.T:
-        D = rec_data(c, seed); idx, start = D.draws[0]
-        return D, R.sample_batch(D.ring, idx, start, c.T, c.obs), masks_for(D.net, 0, c.B, c.T)
-    D = ff_data(c, seed)
-    return D, ff_batch(c, D, D.idx[0]), masks_for(D.net, 0, c.B)
+    D, batch = STEP.first_step(c, seed)
+    return D, batch, masks_for(D.net, 0, c.B, c.T)
 
 
 def step(c, D, batch, masks, p_on=None, leg="law"):
@@ -390,7 +280,7 @@ def step(c, D, batch, masks, p_on=None, leg="law"):
 
 def case_margins(c, seed=None):
     """(sigma_min, relu margin, argmax gap) of the first step in fp64, as dropout_reference.case_margins takes them"""
-    D, batch, masks = first_step(c, seed); probe = dict(sigma=np.inf, relu=np.inf)
+    D, batch, masks = first_step(c, seed); probe = DR.new_probe()
     q_values(D.net, D.p_on, batch[0], masks, probe=probe)
     qon = q_values(D.net, D.p_on, batch[3], probe=probe); qtg = q_values(D.net, D.p_tg, batch[3], probe=probe)
     qsel = qon if c.dq else qtg
@@ -402,7 +292,7 @@ def margins_ok(c, seed=None, k=2.0):
     if not (sg >= k * LR.SIGMA_MIN and rm > k * LR.RELU_MARGIN and gap > k * LR.GAP):
         return False
     D, batch, masks = first_step(c, seed)
-    return not R.dead_blocks(D.net, nn, step(c, D, batch, masks)["grads"], blks=blocks(D.net))
+    return not STEP.dead_blocks(D.net, step(c, D, batch, masks)["grads"])
 
 
 TELL = 100.0      # a wrong engine must move a compared quantity by this many of its tolerances
@@ -441,9 +331,4 @@ def tells_ok(c, seed=None, k=2.0):
     return all(d >= k * TELL for d in tell_distances(c, seed).values())
 
 
-def find_seed(c, cap=200):
-    """the smallest seed that keeps twice the margins, live gradient blocks and twice the tell distances (how the table's seeds were chosen, on the CPU, with this module alone)"""
-    for seed in range(1, cap):
-        if margins_ok(c, seed) and tells_ok(c, seed):
-            return seed
-    raise AssertionError(f"{c.name}: no seed below {cap} keeps the margins")
+find_seed = lambda c, cap=200: STEP.find_seed(c, lambda c, seed: margins_ok(c, seed) and tells_ok(c, seed), cap)
