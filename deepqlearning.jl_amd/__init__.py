@@ -13,7 +13,7 @@ import os as _os
 
 from . import _abi
 from ._abi import (ACT_ELU, ACT_GELU, ACT_HARDSWISH, ACT_HARDTANH, ACT_MISH, ACT_SWISH, ACT_IDENTITY, ACT_LEAKYRELU, ACT_RELU, ACT_RELU6, ACT_SELU, ACT_SIGMOID, ACT_SOFTPLUS, ACT_SOFTSIGN, ACT_TANH, NET_ONLINE, NET_TARGET, OBS_F32, OBS_U8, DQNError, HParams,  # noqa: F401
-                   LayerDesc, LayerPlan, default_hparams)
+                   EngineGroup, LayerDesc, LayerPlan, default_hparams)
 
 _HERE = _os.path.dirname(_os.path.abspath(__file__))
 LIB_PATH = _os.environ.get("DQN_MI355X_LIB") or _os.path.join(_HERE, "libdqn_mi355x.so")   # same variable the Julia shim reads

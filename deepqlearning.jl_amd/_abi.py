@@ -130,6 +130,11 @@ class CommInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("rccl_nranks", "rccl_rank", "rccl_device", "engine_world", "engine_rank", "sim_world", "exchange", "dp_overlap")]
 
 
+class GroupInfo(C.Structure):
+    """dqn_group_info_t (include/dqn_mi355x.h)"""
+    _fields_ = [("n_members", C.c_int32), ("max_lds_bytes", C.c_uint32), ("launches_per_step", C.c_int32), ("reserved", C.c_int32)]
+
+
 # name -> argtypes (without prefix).  All return int unless listed in _RESTYPE.
 PROTOS = {
     "plan_version": [],
@@ -156,6 +161,7 @@ PROTOS = {
     "step_scalars": [_vp, C.c_uint64, C.c_int, _f32p, _f32p, _P(C.c_uint64)],
     "get_last_q": [_vp, _f32p, _f32p, _f32p, _i32p, _f32p],
     "get_last_indices": [_vp, _i64p],
+    "get_last_td": [_vp, _f32p, _f32p],
     "get_grads": [_vp, _f32p, _sz],
     "forward": [_vp, C.c_int, _f32p, C.c_int, _f32p],
     "greedy_action": [_vp, _f32p, C.c_int, _i32p],
@@ -192,6 +198,10 @@ PROTOS = {
     "episode_import": [_vp, C.c_int64, _f32p, _f32p, _i32p, _f32p, _u8p, _i32p],
     "get_counters": [_vp, _P(Counters)],
     "set_counters": [_vp, _P(Counters)],
+    "group_create": [_P(_vp), C.c_int, _P(_vp)],
+    "group_train_steps": [_vp, C.c_int, _f32p, _f32p],
+    "group_info": [_vp, _P(GroupInfo)],
+    "group_destroy": [_vp],
 }
 
 class DQNError(RuntimeError):
@@ -263,7 +273,8 @@ class Handle:
     def close(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:
-            self.f["engine_destroy"](h)
+            if self.f["engine_destroy"](h) != 0:      # refused (a member of a live group): the engine lives on, the handle stays valid
+                raise DQNError(self.f["last_error"]().decode())
             self._handle = C.c_void_p()
 
     def __del__(self):
@@ -404,6 +415,12 @@ class Handle:
         best, y = np.empty(B, np.int32), np.empty(B, np.float32)
         self._check(self.f["get_last_q"](self._h, _ptr(qs, _f32p), _ptr(qsp, _f32p), _ptr(qt, _f32p), _ptr(best, _i32p), _ptr(y, _f32p)))
         return dict(q_on_s=qs, q_on_sp=qsp, q_tg_sp=qt, best_a=best, y=y)
+
+    def last_td(self):
+        """(td, IS weights) of the last train step: the unweighted TD errors Q(s, a) - y and the importance-sampling weights of its batch"""
+        td, w = np.empty(self.B, np.float32), np.empty(self.B, np.float32)
+        self._check(self.f["get_last_td"](self._h, _ptr(td, _f32p), _ptr(w, _f32p)))
+        return td, w
 
     def last_indices(self):
         idx = np.empty(self.B, np.int64)
@@ -655,3 +672,60 @@ class Handle:
     def comm_init(self, id128: bytes, rank: int, world: int):
         buf = C.create_string_buffer(id128, 128)
         self._check(self.f["comm_init"](self._h, C.cast(buf, _vp), rank, world))
+
+
+class EngineGroup:
+    """dqn_group_t over K engine handles: one launch of K workgroups steps all of them (include/dqn_mi355x.h, engine groups).  After train_steps(n) every member
+    is bit for bit what Handle.train_steps(n) would have left.  The group keeps its members alive; close() it before closing a member: dqn_engine_destroy refuses a
+    member of a live group, Handle.close() then raises and the engine lives on.  Handle.__del__ swallows that refusal and does not retry, so a member that is collected
+    before its group (interpreter teardown, a reference cycle) is never destroyed -- close the group, then the members, explicitly."""
+
+    def __init__(self, handles):
+        self.members = list(handles)
+        if not self.members:
+            raise DQNError("EngineGroup: at least one engine is needed")
+        self.f = self.members[0].f
+        if "group_create" not in self.f:
+            raise DQNError("this library does not export group_create")
+        arr = (C.c_void_p * len(self.members))(*[m._h.value for m in self.members])
+        g = C.c_void_p()
+        rc = self.f["group_create"](arr, len(self.members), C.byref(g))
+        self._group = g
+        self._check(rc)
+
+    def _check(self, rc):
+        if rc != 0:
+            raise DQNError(self.f["last_error"]().decode())
+
+    @property
+    def _g(self):
+        g = getattr(self, "_group", None)
+        if g is None or not g.value:
+            raise DQNError("the group has been closed (or was never created)")
+        return g
+
+    def __len__(self):
+        return len(self.members)
+
+    def train_steps(self, n):
+        """n sampled train steps of every member -> (loss[K], grad_norm[K]) of the last one"""
+        loss, gn = np.empty(len(self.members), np.float32), np.empty(len(self.members), np.float32)
+        self._check(self.f["group_train_steps"](self._g, int(n), _ptr(loss, _f32p), _ptr(gn, _f32p)))
+        return loss, gn
+
+    def info(self):
+        gi = GroupInfo()
+        self._check(self.f["group_info"](self._g, C.byref(gi)))
+        return dict(n_members=gi.n_members, max_lds_bytes=gi.max_lds_bytes, launches_per_step=gi.launches_per_step)
+
+    def close(self):
+        g = getattr(self, "_group", None)
+        if g is not None and g.value:
+            self.f["group_destroy"](g)
+            self._group = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -864,6 +864,7 @@ struct TinyArgs {
     int f64mode; float lr; double b1, b2, adam_eps;
 };
 int launch_tiny_step(hipStream_t st, const TinyArgs* a_dev, unsigned lds_bytes, int sample, int stop /* timing probe: return after phase n */);      // -1: the LDS attribute was refused
+int launch_tiny_group(hipStream_t st, const TinyArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int n_steps);      // n_steps launches of K workgroups, one per record; -1: the LDS attribute was refused
 
 // ---- the recurrent train step (batch_train!(..., ::EpisodeReplayBuffer), src/solver.jl:239-287) as a COLUMN-PARALLEL launch (drqn_cols.hip; BASELINE config 4):
 // batch columns never interact before the gradient sum, so workgroup g owns the batch columns [g*cg, (g+1)*cg) for the WHOLE step -- episode gather (prefix quirk),

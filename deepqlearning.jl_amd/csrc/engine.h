@@ -129,6 +129,8 @@ struct dqn_engine {
     unsigned long long mail_swept = 0; bool mail_plain = false;      // mail_swept: records [1, mail_swept] have been checked for device-side errors (mail_sweep); mail_plain: the ring is ordinary host memory (mapped allocation refused)
     bool pg_ok = false; PreGather pg; long adam_step = -1;      // pg_ok: the program supports the pre-gather (StepKey::take_pre / pregather)
     bool tiny = false;      // the whole step is ONE single-workgroup launch that samples and gathers itself (tiny_step.hip)
+    std::vector<TinyArgs> tiny_args;      // tiny: the host copy of the record that launch reads (one element) -- what a group copies into its device array (engine_group.hip)
+    int in_groups = 0;      // live dqn_group_t's this engine is a member of: dqn_engine_destroy is refused while any exists
     // fused recurrent step: episode draws travel through a mapped pinned host buffer of DQN_DRAW_SLOTS slots the kernel reads directly.  A slot is a LAUNCH PARAMETER, fixed per graph
     // node: two 8-step graphs (slots 0-7 / 8-15) and two single-step graphs (16 / 17) alternate, and before the host rewrites the slots of one it waits for the event recorded
     // behind that graph's previous launch
@@ -232,6 +234,7 @@ struct FwdEmit {
 // the forward launches of levels [li0, li1) into the current sink, for every pass: THE statement of the forward selection rules (train step and acting programs)
 void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, const std::vector<FwdPass>& passes, FwdEmit& E);
 int build_program(dqn_engine* e);
+std::string tiny_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup step (tiny_step.hip); empty: it does.  THE eligibility rule
 // engine_envs.hip
 void free_envs(dqn_engine* e);
 int ep_mirror_push(dqn_engine* e);      // recurrent env sets: host (ep_widx, ep_size) -> the device cursor, before a rollout

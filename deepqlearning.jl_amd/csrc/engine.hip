@@ -528,6 +528,7 @@ static void free_policy_ws(dqn_engine* e) {
 }
 extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     if (!e) return 0;
+    if (e->in_groups > 0) return fail("dqn_engine_destroy: this engine is a member of %d live group%s -- destroy the group first (dqn_group_destroy)", e->in_groups, e->in_groups > 1 ? "s" : "");
     hipSetDevice(e->device);
     if (e->stream) hipStreamSynchronize(e->stream);
     drop_graphs(e);
@@ -1194,6 +1195,13 @@ extern "C" int dqn_get_last_q(dqn_engine_t* e, float* qs, float* qsp, float* qt,
     if (y) HIPCHK(hipMemcpy(y, e->ytarget, (size_t)e->B * 4, hipMemcpyDeviceToHost));
     return 0;
 }
+extern "C" int dqn_get_last_td(dqn_engine_t* e, float* td, float* is_weights) { if (!e) return fail("null engine handle");
+    if (e->hp.recurrence) return fail("dqn_get_last_td: feed-forward engines only (the recurrent step has no IS weights)");
+    HIPCHK(hipSetDevice(e->device)); HIPCHK(hipStreamSynchronize(e->stream));
+    if (td) HIPCHK(hipMemcpy(td, e->td, (size_t)e->B * 4, hipMemcpyDeviceToHost));
+    if (is_weights) HIPCHK(hipMemcpy(is_weights, e->w_is, (size_t)e->B * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int dqn_get_last_indices(dqn_engine_t* e, int64_t* idx) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device)); HIPCHK(hipStreamSynchronize(e->stream));
     HIPCHK(hipMemcpy(idx, e->idx, (size_t)e->B * 8, hipMemcpyDeviceToHost)); return 0;
@@ -1274,6 +1282,7 @@ extern "C" int dqn_greedy_action(dqn_engine_t* e, const float* obs, int n, int32
 extern "C" int dqn_comm_unique_id(void* id128) { if (rccl_load()) return -1; const int rc = g_rccl.GetUniqueId(id128); return rc ? fail("ncclGetUniqueId failed (%d)", rc) : 0; }
 extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int world) { if (!e) return fail("null engine handle");
     if (refuse_replicas("dqn_comm_init", e->L, e->nl)) return -1;
+    if (e->in_groups > 0) return fail("dqn_comm_init: this engine is a member of %d live group%s: replicas take the multi-launch step program, and a group steps the program its members had when it was created -- destroy the group first (dqn_group_destroy)", e->in_groups, e->in_groups > 1 ? "s" : "");
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;

@@ -186,6 +186,42 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
         emit_reduce(e, segs, pname(e, E.reduce, e->L[lv[0]], lv[0]));
     }
 }
+// the LDS layout of the single-workgroup step (tiny_step.hip), in floats: parameters of both nets and the gradient, the observation arena, the Q columns, then per layer
+// the online / target activations and dL/dpre; at least the room the priority block's path state needs (it reuses the whole region).  a != null: the offsets are recorded
+static size_t tiny_layout(const dqn_engine* e, TinyArgs* a) {
+    const int B = e->Bc, ncon = e->ncon, ld0 = 2 * B;
+    size_t fl = 0; TinyArgs tmp; TinyArgs& A = a ? *a : tmp;
+    auto take = [&](size_t n) { const int o = (int)fl; fl += (n + 3) / 4 * 4; return o; };
+    A.pon_off = take(e->Pint); A.ptg_off = take(e->Pint); A.g_off = take(e->Pint); A.x0_off = take((size_t)e->E * ld0); A.misc_off = take((size_t)B * 3 * e->nA);
+    for (int i = 0; i < e->nl && i < TINY_MAX_LAYERS; i++) { A.on_off[i] = take((size_t)e->L[i].N * ncon); A.tg_off[i] = take((size_t)e->L[i].N * B); A.d_off[i] = take((size_t)e->L[i].N * B); }
+    if (fl * 4 < 7808 + 64 * 4 + 1024) fl = (7808 + 64 * 4 + 1024) / 4;
+    return fl;
+}
+// THE eligibility rule of the single-workgroup step, term by term: empty when the engine takes it, else the reason in words (build_program decides by it; dqn_group_create
+// reports it by member).  A pure function of the engine as created (layers, plan, hyper-parameters, switches, communicator): no program needs to exist
+std::string tiny_decline(const dqn_engine* e) {
+    char buf[200];
+    if (e->hp.recurrence) return "it is recurrent (recurrence = true)";
+    for (int i = 0; i < e->nl; i++) if (e->L[i].kind != DQN_LAYER_DENSE) { snprintf(buf, sizeof buf, "layer %d is not a Dense layer (kind %d)", i, e->L[i].kind); return buf; }
+    if (general_only(e->L, e->nl)) return "one of its layers takes the general train programs only";
+    if (e->sim_world || e->comm || e->world > 1) return "it runs as data-parallel replicas (a communicator, or created under DQN_SIM_WORLD)";
+    if (!e->hp.prioritized_replay) return "it has no prioritized replay (prioritized_replay = false)";
+    if (e->B > 64) { snprintf(buf, sizeof buf, "B > 64 (batch_size = %d)", e->B); return buf; }
+    if (e->opt.no_tiny) return "it was created under DQN_NO_TINY";
+    const int nlev = (int)net_levels(e).size();
+    if (e->nl > TINY_MAX_LAYERS || nlev > TINY_MAX_LAYERS) { snprintf(buf, sizeof buf, "it has too many layers (%d in %d levels, at most %d)", e->nl, nlev, TINY_MAX_LAYERS); return buf; }
+    // ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic
+    if (e->Pint > 16384 || (size_t)e->Pint * e->Bc > 262144) { snprintf(buf, sizeof buf, "it has too many parameters (%zu, at most 16384 and 262144 / batch_size)", e->Pint); return buf; }
+    for (int i = 0; i < e->nl; i++) {
+        const LayerDev& L = e->L[i];
+        if (dqn_nchunks(L.N, L.dx_kc) != 1) { snprintf(buf, sizeof buf, "the plan cuts layer %d's dX sum into %d chunks (dx_kc = %d); the single-workgroup step sums it in one (dx_kc = 0)", i, dqn_nchunks(L.N, L.dx_kc), L.dx_kc); return buf; }
+        if (L.src >= i) { snprintf(buf, sizeof buf, "layer %d reads a later layer (%d)", i, L.src); return buf; }
+    }
+    // one workgroup may hold up to 160 KB of LDS on gfx950 (beyond 64 KB the launcher raises the function's dynamic-LDS limit)
+    const size_t bytes = tiny_layout(e, nullptr) * 4;
+    if (bytes > 144 * 1024) { snprintf(buf, sizeof buf, "it needs %zu bytes of LDS (at most %d)", bytes, 144 * 1024); return buf; }
+    return std::string();
+}
 int build_program(dqn_engine* e) {
     if (e->prog_built) return 0;
     HIPCHK(hipSetDevice(e->device));
@@ -261,34 +297,27 @@ int build_program(dqn_engine* e) {
     }
     // ---------------- networks that fit in LDS: the WHOLE step is one single-workgroup launch (tiny_step.hip; BASELINE config 1)
     e->tiny = false;
-    if (!rec && !general && !e->comm && !e->sim_world && e->world <= 1 && e->hp.prioritized_replay && Bb <= 64 && e->nl <= TINY_MAX_LAYERS &&
-        (int)levels.size() <= TINY_MAX_LAYERS && e->Pint <= 16384 && (size_t)e->Pint * B <= 262144 /* ~5 MACs per parameter and column on ONE CU: <= ~9 us of arithmetic */ && !e->opt.no_tiny) {
-        bool ok = true; size_t fl = 0;
+    if (tiny_decline(e).empty()) {
         TinyArgs a; memset(&a, 0, sizeof a);
-        for (int i = 0; i < e->nl; i++) { const LayerDev& L = e->L[i]; ok = ok && L.kind == DQN_LAYER_DENSE && dqn_nchunks(L.N, L.dx_kc) == 1 && L.src < i; a.L[i] = L; }
-        auto take = [&](size_t n) { const int o = (int)fl; fl += (n + 3) / 4 * 4; return o; };
-        a.pon_off = take(e->Pint); a.ptg_off = take(e->Pint); a.g_off = take(e->Pint); a.x0_off = take((size_t)e->E * ld0); a.misc_off = take((size_t)B * 3 * e->nA);
-        for (int i = 0; i < e->nl; i++) { a.on_off[i] = take((size_t)e->L[i].N * ncon); a.tg_off[i] = take((size_t)e->L[i].N * B); a.d_off[i] = take((size_t)e->L[i].N * B); }
-        if (fl * 4 < 7808 + 64 * 4 + 1024) fl = (7808 + 64 * 4 + 1024) / 4;      // room for the priority block's path state (it reuses the whole region)
-        ok = ok && fl * 4 <= 144 * 1024;      // one workgroup may hold up to 160 KB of LDS on gfx950 (beyond 64 KB the launcher raises the function's dynamic-LDS limit)
-        if (ok) {
-            a.nl = e->nl; a.nlev = (int)levels.size(); a.B = B; a.nA = e->nA; a.E = e->E; a.ncon = ncon; a.dueling = e->hp.dueling; a.double_q = e->hp.double_q; a.obs_u8 = e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 0; a.distinct = e->hp.sample_distinct ? 1 : 0;
-            a.last_base = e->last_base; a.last_val = e->last_val; a.last_adv = e->last_adv;
-            a.gamma = e->hp.gamma; a.beta = e->hp.prio_beta; a.prio_eps = e->hp.prio_eps; a.prio_alpha = e->hp.prio_alpha; a.cap2 = e->cap2; a.seed = e->hp.seed; a.P = e->Pint;
-            for (size_t li = 0; li < levels.size(); li++) { a.lev_n[li] = (int)levels[li].size(); a.lev_l[li][0] = levels[li][0]; a.lev_l[li][1] = levels[li].size() > 1 ? levels[li][1] : levels[li][0]; }
-            a.lds_bytes = (unsigned)(fl * 4);
-            a.p_tg = e->p_tg; a.p_on = e->p_on; a.m = e->m; a.v = e->v; a.grad = e->grad; a.state = e->state; a.gmax_part = e->gmax_part; a.tree = e->tree;
-            a.idx = e->idx; a.idx_pre = e->idx_pre; a.s_rows = e->s_rows; a.sp_rows = e->sp_rows; a.ra = e->ra; a.rr = e->rr; a.rdone = e->rdone;
-            a.x0 = e->x0; a.w_is = e->w_is; a.td = e->td; a.q_on_s = e->q_on_s; a.q_on_sp = e->q_on_sp; a.q_tg_sp = e->q_tg_sp; a.ytarget = e->ytarget; a.best = e->best;
-            a.f64mode = e->hp.adam_f64_scalars; a.lr = e->hp.learning_rate; a.b1 = e->hp.adam_beta1; a.b2 = e->hp.adam_beta2; a.adam_eps = e->hp.adam_eps;
-            const TinyArgs* a_dev = upload(e, std::vector<TinyArgs>(1, a)); const unsigned lds = a.lds_bytes;
-            e->prog.push_back({"tiny_step", [=](dqn_engine* en) { if (launch_tiny_step(en->stream, a_dev, lds, en->cur.sampled ? 1 : 0, en->opt.tiny_stop)) en->launch_failed = true; }});
-            e->tiny = true; e->arena_u8 = false; e->prio_forked = false; e->prio_in_bwd = false; e->dp_gather = false; e->dp_overlap = false; e->prog_pre1_end = 0;
-            e->prog_post_begin = e->prog.size(); e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs); e->gmax_used = 1;
-            for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0;
-            e->prog_built = true;
-            return 0;
-        }
+        for (int i = 0; i < e->nl; i++) a.L[i] = e->L[i];
+        const size_t fl = tiny_layout(e, &a);
+        a.nl = e->nl; a.nlev = (int)levels.size(); a.B = B; a.nA = e->nA; a.E = e->E; a.ncon = ncon; a.dueling = e->hp.dueling; a.double_q = e->hp.double_q; a.obs_u8 = e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 0; a.distinct = e->hp.sample_distinct ? 1 : 0;
+        a.last_base = e->last_base; a.last_val = e->last_val; a.last_adv = e->last_adv;
+        a.gamma = e->hp.gamma; a.beta = e->hp.prio_beta; a.prio_eps = e->hp.prio_eps; a.prio_alpha = e->hp.prio_alpha; a.cap2 = e->cap2; a.seed = e->hp.seed; a.P = e->Pint;
+        for (size_t li = 0; li < levels.size(); li++) { a.lev_n[li] = (int)levels[li].size(); a.lev_l[li][0] = levels[li][0]; a.lev_l[li][1] = levels[li].size() > 1 ? levels[li][1] : levels[li][0]; }
+        a.lds_bytes = (unsigned)(fl * 4);
+        a.p_tg = e->p_tg; a.p_on = e->p_on; a.m = e->m; a.v = e->v; a.grad = e->grad; a.state = e->state; a.gmax_part = e->gmax_part; a.tree = e->tree;
+        a.idx = e->idx; a.idx_pre = e->idx_pre; a.s_rows = e->s_rows; a.sp_rows = e->sp_rows; a.ra = e->ra; a.rr = e->rr; a.rdone = e->rdone;
+        a.x0 = e->x0; a.w_is = e->w_is; a.td = e->td; a.q_on_s = e->q_on_s; a.q_on_sp = e->q_on_sp; a.q_tg_sp = e->q_tg_sp; a.ytarget = e->ytarget; a.best = e->best;
+        a.f64mode = e->hp.adam_f64_scalars; a.lr = e->hp.learning_rate; a.b1 = e->hp.adam_beta1; a.b2 = e->hp.adam_beta2; a.adam_eps = e->hp.adam_eps;
+        e->tiny_args.assign(1, a);
+        const TinyArgs* a_dev = upload(e, e->tiny_args); const unsigned lds = a.lds_bytes;
+        e->prog.push_back({"tiny_step", [=](dqn_engine* en) { if (launch_tiny_step(en->stream, a_dev, lds, en->cur.sampled ? 1 : 0, en->opt.tiny_stop)) en->launch_failed = true; }});
+        e->tiny = true; e->arena_u8 = false; e->prio_forked = false; e->prio_in_bwd = false; e->dp_gather = false; e->dp_overlap = false; e->prog_pre1_end = 0;
+        e->prog_post_begin = e->prog.size(); e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs); e->gmax_used = 1;
+        for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0;
+        e->prog_built = true;
+        return 0;
     }
     // ---------------- u8 replay: keep the observation arena in BYTES when its only consumers are the LDS-tiled forward and dW launches of ONE
     // first layer (they convert byte / 255 inside their tile loads): the gather writes 1 byte per element instead of 4 and the first layer reads

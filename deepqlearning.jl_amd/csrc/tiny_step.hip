@@ -29,7 +29,7 @@ __global__ __launch_bounds__(NTH) void k_tiny_step(const TinyArgs* __restrict__ 
     enum { F_K, F_N, F_ACT, F_SRC, F_W, F_B, F_FKC, F_DWKC, F_ON, F_TG, F_D, F_NF };
     __shared__ int LD[TINY_MAX_LAYERS][F_NF];
     __shared__ int LEV[TINY_MAX_LAYERS][3];
-    const TinyArgs& A = *Ap;
+    const TinyArgs& A = Ap[blockIdx.x];      // a standalone engine launches ONE workgroup; a group (engine_group.hip) one per member: members share nothing
     const int tid = threadIdx.x, B = A.B, nA = A.nA, E = A.E, ld0 = 2 * B, ncon = A.ncon;
     StepState* st = A.state;
     const int nlev = A.nlev, dueling = A.dueling, double_q = A.double_q, last_val = A.last_val, lq = A.dueling ? A.last_adv : A.last_base;
@@ -382,13 +382,29 @@ __global__ __launch_bounds__(NTH) void k_tiny_step(const TinyArgs* __restrict__ 
     pa.idx_pre = A.idx_pre; pa.seed = A.seed; pa.B = B; pa.phase = 0; pa.distinct = A.distinct;
     prio_block_run(pa, st, reinterpret_cast<long long*>(sm), A.lds_bytes, nullptr, sample ? ctr0 + 1 : ctr0);
 }
+// dynamic LDS beyond 64 KB has to be requested per function AND per device: asked for on every enqueue that needs it (an enqueue is a graph capture or an eager
+// launch, never the replay path), and a refusal is reported instead of leaving a launch that cannot run.  The limit belongs to the FUNCTION, which every
+// engine and group of the process shares, and a captured graph keeps relying on what it was granted: the request is the largest ever made on the device, never a lower one
+static int tiny_raise_lds(unsigned lds_bytes) {
+    if (lds_bytes <= 64 * 1024) return 0;
+    static unsigned asked[64] = {};      // per device
+    int dev = 0; if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) { (void)hipGetLastError(); dev = 0; }
+    const unsigned want = lds_bytes > asked[dev] ? lds_bytes : asked[dev];
+    const hipError_t le = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tiny_step<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)want);
+    if (le != hipSuccess) { (void)hipGetLastError(); return -1; }
+    asked[dev] = want;
+    return 0;
+}
 int launch_tiny_step(hipStream_t st, const TinyArgs* a_dev, unsigned lds_bytes, int sample, int stop) {
-    // dynamic LDS beyond 64 KB has to be requested per function AND per device: asked for on every enqueue that needs it (an enqueue is a graph capture or an eager
-    // launch, never the replay path), and a refusal is reported instead of leaving a launch that cannot run
-    if (lds_bytes > 64 * 1024) {
-        const hipError_t le = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_tiny_step<1024>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (le != hipSuccess) { (void)hipGetLastError(); return -1; }
-    }
+    if (tiny_raise_lds(lds_bytes)) return -1;
     hipLaunchKernelGGL((k_tiny_step<1024>), dim3(1), dim3(1024), lds_bytes, st, a_dev, sample, stop);
+    return 0;
+}
+// n_steps sampled steps of K independent engines: each step is ONE launch of K workgroups, workgroup k running member k's record a_dev[k] (engine_group.hip).
+// The dynamic-LDS size of the launch is the largest member's; every workgroup keeps laying out its own A.lds_bytes inside it.  Back-to-back launches on one
+// stream: step i + 1 of every member starts after step i of all of them
+int launch_tiny_group(hipStream_t st, const TinyArgs* a_dev, int K, unsigned max_lds_bytes, int n_steps) {
+    if (tiny_raise_lds(max_lds_bytes)) return -1;
+    for (int i = 0; i < n_steps; i++) hipLaunchKernelGGL((k_tiny_step<1024>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, 1 /* sample */, 0 /* stop */);
     return 0;
 }

@@ -21,7 +21,7 @@ import DeepQLearning: batch_train!, add_exp!, update_priorities!, get_batch, pop
 import CommonRLInterface: AbstractEnv, observe, actions, act!, reset!, terminated
 import TensorBoardLogger: TBLogger, log_value
 import StatsBase
-export MI355XSolver, HIPReplayBuffer, HIPEpisodeReplayBuffer, HIPNNPolicy, train_steps!
+export MI355XSolver, HIPReplayBuffer, HIPEpisodeReplayBuffer, HIPNNPolicy, train_steps!, EngineGroup, close!, group_info
 
 const LIB = get(ENV, "DQN_MI355X_LIB", "libdqn_mi355x.so")
 
@@ -344,6 +344,40 @@ function train_steps!(e::Engine, n::Integer)
     loss = Ref{Float32}(0); gn = Ref{Float32}(0)
     check(ccall((:dqn_train_steps, LIB), Cint, (Ptr{Cvoid}, Cint, Ref{Float32}, Ref{Float32}), e.h, n, loss, gn))
     return loss[], gn[]
+end
+
+# ---- engine groups (no reference equivalent): K small engines -- seeds, a learning-rate sweep, an ensemble -- stepped by ONE launch of K workgroups.  After
+# train_steps!(g, n) every member is bit for bit what train_steps!(e, n) would have left (include/dqn_mi355x.h, engine groups).  The group keeps its members
+# reachable; close!(g) before a member is finalized (dqn_engine_destroy refuses a member of a live group).
+mutable struct GroupInfo
+    n_members::Int32; max_lds_bytes::UInt32; launches_per_step::Int32; reserved::Int32
+    GroupInfo() = new(0, 0, 0, 0)
+end
+mutable struct EngineGroup
+    h::Ptr{Cvoid}
+    members::Vector{Engine}
+end
+function EngineGroup(members::Vector{Engine})
+    hs = Ptr{Cvoid}[e.h for e in members]; out = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:dqn_group_create, LIB), Cint, (Ptr{Ptr{Cvoid}}, Cint, Ref{Ptr{Cvoid}}), hs, length(hs), out))
+    g = EngineGroup(out[], members)
+    finalizer(close!, g)
+    g
+end
+function close!(g::EngineGroup)
+    g.h == C_NULL && return nothing
+    ccall((:dqn_group_destroy, LIB), Cint, (Ptr{Cvoid},), g.h); g.h = C_NULL
+    nothing
+end
+function train_steps!(g::EngineGroup, n::Integer)      # -> (loss[K], grad_norm[K]) of the last step
+    K = length(g.members); loss = zeros(Float32, K); gn = zeros(Float32, K)
+    check(ccall((:dqn_group_train_steps, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{Float32}, Ptr{Float32}), g.h, n, loss, gn))
+    return loss, gn
+end
+function group_info(g::EngineGroup)
+    gi = GroupInfo()
+    check(ccall((:dqn_group_info, LIB), Cint, (Ptr{Cvoid}, Ref{GroupInfo}), g.h, gi))
+    return (n_members = Int(gi.n_members), max_lds_bytes = Int(gi.max_lds_bytes), launches_per_step = Int(gi.launches_per_step))
 end
 
 # ---- DRQN: EpisodeReplayBuffer protocol (src/episode_replay.jl) and the recurrent batch_train! (src/solver.jl:239-287)

@@ -371,6 +371,12 @@ def make_engine(pkg_engine_cls, solver, env, net, discount):
 
 def solve(solver: DeepQLearningSolver, env, engine_cls=None, init_seed=1):
     """POMDPs.solve(solver, env) (src/solver.jl:40-57)."""
+    policy, replay = _prepare(solver, env, engine_cls, init_seed)
+    return dqn_train(solver, env, policy, replay)
+
+
+def _prepare(solver, env, engine_cls=None, init_seed=1):
+    """solve() up to the train loop (src/solver.jl:40-56): engine, initial parameters, prefilled replay, policy"""
     if engine_cls is None:
         from . import Engine as engine_cls
     if nn.isrecurrent(solver.qnetwork) and not solver.recurrence:
@@ -382,7 +388,7 @@ def solve(solver: DeepQLearningSolver, env, engine_cls=None, init_seed=1):
     engine.set_params(params, _abi.NET_ONLINE)
     replay = initialize_replay_buffer(solver, env, engine)
     policy = NNPolicy(env, engine, action_map, len(env.obs_shape), qnetwork=net)
-    return dqn_train(solver, env, policy, replay)
+    return policy, replay
 
 
 def batch_train(solver, env, policy, optimizer, target_q, replay, discount=None):
@@ -446,36 +452,131 @@ def dqn_train_device(solver, env, policy, replay):
     if solver.recurrence and not envs.is_tabular(env):           # (a tabular env was prefilled on the host, initialize_replay_buffer)
         populate_episode_replay_device(solver, env, e)      # then the env set is created again under the solver's seed; committed episodes stay
     e.envs_create(env, n_envs=env.n, max_episode_length=solver.max_episode_length, seed=solver.seed)
-    saved_mean_reward, scores_eval, model_saved = -np.inf, -np.inf, False
+    mk = _Marks()
     marks = sorted({solver.eval_freq, solver.log_freq, solver.save_freq})
     t, episodes, reward_sum = 1, 0, 0.0
-    save_next = False                                  # set at t % save_freq == 0, consumed at the next evaluation (src/solver.jl:109-113,150-152)
     while t <= solver.max_steps:
         nxt = min(min((t + m - 1) // m * m for m in marks), solver.max_steps)      # run up to the next eval/log/save boundary
         st = e.rollout(nxt - t + 1, t0=t, train_freq=solver.train_freq, target_update_freq=solver.target_update_freq, **exploration_table(solver.exploration_policy, t, nxt - t + 1))
         t = nxt + 1
         d_eps, d_rew = st["episodes"] - episodes, st["reward_sum"] - reward_sum
         episodes, reward_sum = st["episodes"], st["reward_sum"]
-        if nxt % solver.save_freq == 0:
-            save_next = True
-        if nxt % solver.eval_freq == 0:
-            if solver.evaluation_policy is basic_evaluation:        # the default rollout evaluation also runs on the device
-                scores_eval, steps_eval = e.evaluate(min(solver.num_ep_eval, 1024), solver.max_episode_length, seed=solver.seed + nxt)
-                if solver.verbose:
-                    print(f"Evaluation ... Avg Reward {scores_eval:2.2f} | Avg Step {steps_eval:2.2f}")
-            else:
-                scores_eval, _, _ = solver.evaluation_policy(policy, env, solver.num_ep_eval, solver.max_episode_length, solver.verbose)
-            if save_next and solver.logdir is not None:
-                model_saved, saved_mean_reward = save_model(solver, policy, scores_eval, saved_mean_reward, model_saved)
-                save_next = False
-        if nxt % solver.log_freq == 0 and solver.verbose:
-            avg = d_rew / d_eps if d_eps else float("nan")
-            name, val = next(iter(solver.exploration_policy.loginfo(nxt).items()))
-            print(f"{nxt:5d} / {solver.max_steps:5d} {name} {val:0.3f} |  avgR {avg:1.3f} | "
-                  f"Loss {st['loss']:2.3e} | Grad {st['grad_norm']:2.3e} | EvalR {scores_eval:1.3f}")
-    if model_saved and solver.verbose:
+        mk = _device_marks(solver, env, policy, nxt, mk, d_eps, d_rew, st["loss"], st["grad_norm"])
+    if mk.model_saved and solver.verbose:
         restore_best_model(solver, policy)
     return policy
+
+
+@dataclass
+class _Marks:
+    """what the device loops carry between the eval / log / save marks (src/solver.jl:101-122,150-167)"""
+    saved_mean_reward: float = -np.inf
+    scores_eval: float = -np.inf
+    model_saved: bool = False
+    save_next: bool = False                            # set at t % save_freq == 0, consumed at the next evaluation (src/solver.jl:109-113,150-152)
+
+
+def _device_marks(solver, env, policy, nxt, mk, d_eps, d_rew, loss, grad_norm):
+    """the eval / save / log marks of the device loop at vector step nxt (dqn_train_device and solve_many)"""
+    e = policy.engine
+    if nxt % solver.save_freq == 0:
+        mk.save_next = True
+    if nxt % solver.eval_freq == 0:
+        if solver.evaluation_policy is basic_evaluation:        # the default rollout evaluation also runs on the device
+            mk.scores_eval, steps_eval = e.evaluate(min(solver.num_ep_eval, 1024), solver.max_episode_length, seed=solver.seed + nxt)
+            if solver.verbose:
+                print(f"Evaluation ... Avg Reward {mk.scores_eval:2.2f} | Avg Step {steps_eval:2.2f}")
+        else:
+            mk.scores_eval, _, _ = solver.evaluation_policy(policy, env, solver.num_ep_eval, solver.max_episode_length, solver.verbose)
+        if mk.save_next and solver.logdir is not None:
+            mk.model_saved, mk.saved_mean_reward = save_model(solver, policy, mk.scores_eval, mk.saved_mean_reward, mk.model_saved)
+            mk.save_next = False
+    if nxt % solver.log_freq == 0 and solver.verbose:
+        avg = d_rew / d_eps if d_eps else float("nan")
+        name, val = next(iter(solver.exploration_policy.loginfo(nxt).items()))
+        print(f"{nxt:5d} / {solver.max_steps:5d} {name} {val:0.3f} |  avgR {avg:1.3f} | "
+              f"Loss {loss:2.3e} | Grad {grad_norm:2.3e} | EvalR {mk.scores_eval:1.3f}")
+    return mk
+
+
+_MANY_EQUAL = ("train_freq", "target_update_freq", "max_steps", "train_start", "buffer_size", "batch_size", "eval_freq", "log_freq", "save_freq", "device")
+
+
+def check_many(solvers, member_envs):
+    """solve_many's refusals, in pure Python, before any engine exists.  Each names the field and the two solver indices (one index where the field rules a
+    single solver out)."""
+    if len(solvers) < 1:
+        raise DQNError("solve_many: at least one solver is needed")
+    if len(member_envs) != len(solvers):
+        raise DQNError(f"solve_many: {len(member_envs)} environments were given for {len(solvers)} solvers (one for all, or one per solver)")
+    for k, s in enumerate(solvers):
+        if not s.device_envs:
+            raise DQNError(f"solve_many: device_envs of solver {k} is False -- the lock-stepped loop drives the device environments only (vector-step cadence)")
+        if s.recurrence or nn.isrecurrent(s.qnetwork):
+            raise DQNError(f"solve_many: recurrence of solver {k}: feed-forward networks only (a group steps the single-workgroup train step)")
+    for k in range(1, len(solvers)):
+        for f in _MANY_EQUAL:
+            if getattr(solvers[k], f) != getattr(solvers[0], f):
+                raise DQNError(f"solve_many: {f} differs between solvers 0 and {k} ({getattr(solvers[0], f)} vs {getattr(solvers[k], f)}): the members run in lock step")
+        if member_envs[k].n != member_envs[0].n:
+            raise DQNError(f"solve_many: env.n differs between solvers 0 and {k} ({member_envs[0].n} vs {member_envs[k].n}): the members run in lock step")
+    for j in range(len(solvers)):
+        for k in range(j + 1, len(solvers)):
+            if solvers[j].logdir is not None and solvers[k].logdir is not None and os.path.abspath(solvers[j].logdir) == os.path.abspath(solvers[k].logdir):
+                raise DQNError(f"solve_many: logdir is the same for solvers {j} and {k} ({solvers[j].logdir!r}): each member saves its own qnetwork.bson (or pass logdir=None)")
+
+
+def solve_many(solvers, env, engine_cls=None, init_seed=1):
+    """dqn_train! for K solvers at once on the device loop (device_envs=True), in lock step; returns the K policies.  Per block of vector steps up to the next
+    train / target-sync / eval / log / save boundary: every member's rollout (acting and add_exp! are each member's own launches, with its own exploration
+    table), then ONE group train step for all members (EngineGroup: one launch of K workgroups), then the target syncs and the marks, as in dqn_train_device.
+    The order inside a vector step is the standalone loop's (act, add, train, sync) and every device draw is keyed by (seed, t, copy, purpose), so member k ends
+    bit for bit where solve(solvers[k], env) ends.  `env` is one environment -- every member then works on its own deep copy of it, as given -- or a list of K."""
+    import copy
+    solvers = list(solvers)
+    member_envs = list(env) if isinstance(env, (list, tuple)) else [copy.deepcopy(env) for _ in solvers]
+    check_many(solvers, member_envs)
+    s0, K = solvers[0], len(solvers)
+    prepared = [_prepare(s, ev, engine_cls, init_seed) for s, ev in zip(solvers, member_envs)]
+    policies = [p for p, _ in prepared]
+    engines = [p.engine for p in policies]
+    group = _abi.EngineGroup(engines)
+    try:
+        for s, ev, e in zip(solvers, member_envs, engines):
+            e.sync_target()
+            e.envs_create(ev, n_envs=ev.n, max_episode_length=s.max_episode_length, seed=s.seed)
+        mks = [_Marks() for _ in solvers]
+        marks = sorted({s0.eval_freq, s0.log_freq, s0.save_freq})
+        bounds = sorted(set(marks) | {s0.train_freq, s0.target_update_freq})
+        episodes, reward_sum = [0] * K, [0.0] * K
+        loss, gn = np.full(K, np.nan, np.float32), np.full(K, np.nan, np.float32)
+        t, filled = 1, False
+        while t <= s0.max_steps:
+            nxt = min(min((t + m - 1) // m * m for m in bounds), s0.max_steps)
+            want_stats = nxt % s0.log_freq == 0 and any(s.verbose for s in solvers)
+            sts = [e.rollout(nxt - t + 1, t0=t, train_freq=0, target_update_freq=0, stats=want_stats, **exploration_table(s.exploration_policy, t, nxt - t + 1))
+                   for s, e in zip(solvers, engines)]
+            if nxt % s0.train_freq == 0:                                                                     # :134-139, for all members in one launch
+                filled = filled or min(e.replay_size()[0] for e in engines) >= s0.batch_size                 # (asked until it holds once: a replay never shrinks)
+                if filled:
+                    loss, gn = group.train_steps(1)
+            if nxt % s0.target_update_freq == 0:                                                             # :142-145
+                for e in engines:
+                    e.sync_target()
+            t = nxt + 1
+            for k, (s, ev, p) in enumerate(zip(solvers, member_envs, policies)):
+                d_eps = d_rew = 0
+                if want_stats:
+                    d_eps, d_rew = sts[k]["episodes"] - episodes[k], sts[k]["reward_sum"] - reward_sum[k]
+                    episodes[k], reward_sum[k] = sts[k]["episodes"], sts[k]["reward_sum"]
+                if any(nxt % m == 0 for m in marks):
+                    mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, float(loss[k]), float(gn[k]))
+    finally:
+        group.close()
+    for s, p, mk in zip(solvers, policies, mks):
+        if mk.model_saved and s.verbose:
+            restore_best_model(s, p)
+    return policies
 
 
 def dqn_train(solver, env, policy, replay):

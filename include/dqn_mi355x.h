@@ -282,6 +282,7 @@ int dqn_train_steps(dqn_engine_t* e, int n_steps, float* loss, float* grad_norm)
 int dqn_get_last_q(dqn_engine_t* e, float* q_on_s, float* q_on_sp, float* q_tg_sp /* each [B][nA] */,
                    int32_t* best_a /* B */, float* q_targets /* B */);
 int dqn_get_last_indices(dqn_engine_t* e, int64_t* idx /* B */);
+int dqn_get_last_td(dqn_engine_t* e, float* td /* B, unweighted: Q(s, a) - y */, float* is_weights /* B */); /* feed-forward engines; either may be NULL */
 int dqn_get_grads(dqn_engine_t* e, float* flat, size_t n); /* Flux.params order/layout */
 
 /* ---- DRQN (solver.recurrence = true): EpisodeReplayBuffer (src/episode_replay.jl) and batch_train!(..., ::EpisodeReplayBuffer)
@@ -486,6 +487,37 @@ int dqn_profile_step(dqn_engine_t* e, int max_entries, const char** names, float
  * launch (Adam) already gathers step i+1's batch, so a middle step has no gather launch of its own (where dqn_train_steps pipelines it;
  * otherwise both steps are plain ones).  Results of dqn_train_steps(n) are bit-identical to n dqn_train_step calls either way. */
 int dqn_profile_steady_step(dqn_engine_t* e, int max_entries, const char** names, float* ms, int* n_entries);
+
+/* ---- engine groups: many small Q-networks trained at once (seeds, learning-rate sweeps, bootstrapped ensembles; no reference equivalent).
+ * A network that fits in one workgroup's LDS trains as ONE launch of ONE workgroup per step (dqn_train_step on such an engine occupies one compute unit of the
+ * device).  A group steps K such engines with ONE launch of K workgroups per step: workgroup k runs member k's step on member k's own parameters, Adam state,
+ * sum-tree, replay rows and counters.  Members share nothing; there is no traffic between workgroups.
+ *
+ * THE LAW.  After dqn_group_train_steps(g, n, ...) every member is indistinguishable from an engine on which dqn_train_steps(e, n, ...) was called: parameters of
+ * both networks, gradients, Adam m / v / beta powers, the sum-tree and priorities, the counters, dqn_get_last_indices, dqn_get_last_q, the TD errors and IS weights,
+ * the returned loss and grad norm, and the bytes of a checkpoint are bit for bit the same.  Members may differ in everything an engine is created with: network
+ * (any network that takes the single-workgroup step), batch size, obs_dtype, seed, learning rate, gamma, Adam constants, double_q, dueling, sample_distinct, replay
+ * contents and replay size.
+ *
+ * STREAM ORDER.  The group owns a stream.  On entry that stream waits for everything enqueued so far on every member's stream; on exit every member's stream waits
+ * for the group's steps.  A member's own calls (dqn_replay_add, dqn_train_step, dqn_sync_target, dqn_rollout, the getters) can therefore be interleaved freely with
+ * group calls, with no host synchronise in between.  The n steps are n back-to-back launches.
+ *
+ * ERRORS.  A member's device-side assertion (AssertionError: all(new_priorities .> 0f0)) is reported by the group call in the standalone call's words, prefixed by
+ * "member <index>:"; the other members' steps stand and their entries of loss / grad_norm are written.
+ *
+ * REFUSED, each with a message naming the member index and the reason: a null or duplicate member; n_members outside 1..4096; a member on another device than
+ * member 0; a member that does not take the single-workgroup step -- recurrent, a layer that is not Dense, batch_size > 64, no prioritized replay, too many
+ * parameters, a plan that cuts a layer's dX sum into chunks (the default plan does for Dense layers 128 or more wide: create such an engine with dx_kc = 0), DQN_NO_TINY,
+ * data-parallel replicas (a communicator or DQN_SIM_WORLD),; at train time a member holding fewer than batch_size transitions (AssertionError: r._curr_size >=
+ * r.batch_size) and n < 1.  dqn_engine_destroy and dqn_comm_init of a member of a live group are refused (the latter would rebuild the member's step program under the group): destroy the group first.  dqn_group_create builds each member's step program.
+ * (Trace builds only: the timing probe DQN_TINY_STOP, which ends a standalone step early, is not honoured by a group: it always runs whole steps.) */
+typedef struct dqn_group dqn_group_t;
+typedef struct { int32_t n_members; uint32_t max_lds_bytes /* the launch's dynamic LDS: the largest member's */; int32_t launches_per_step /* 1 */; int32_t reserved; } dqn_group_info_t;
+int dqn_group_create(dqn_engine_t* const* members, int n_members, dqn_group_t** out);
+int dqn_group_train_steps(dqn_group_t* g, int n, float* loss_or_null /* [n_members] */, float* grad_norm_or_null /* [n_members] */);
+int dqn_group_info(dqn_group_t* g, dqn_group_info_t* out);
+int dqn_group_destroy(dqn_group_t* g);
 
 
 #if defined(__GNUC__) || defined(__clang__)
