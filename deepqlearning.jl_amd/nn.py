@@ -500,7 +500,7 @@ def lower(net):
     map_join = [False]      # the last block lowered was a convolutional one: what follows it stands on a map
     top = None if isinstance(net, DuelingNetwork) else net      # the chain whose last layer is the network's output layer (a dueling base chain's is not)
 
-    def add_skip(blk, stream, first, prev_kind, is_last):
+    def add_skip(blk, stream, first, prev_kind, is_last, front=None):
         # SkipConnection(Chain(inner...), +): the inner layers' descriptors, then ONE join descriptor (kind SKIPADD, cin = m the number of inner layers, n_in = n_out = 0: the
         # engine fills in the feature count).  The placement rules are stated here by name; the engine's build_layers holds them again for C callers
         if stream != _abi.STREAM_BASE:
@@ -536,6 +536,13 @@ def lower(net):
                 n_last = l.n_out
         if n_first is not None and n_first != n_last:
             raise _abi.DQNError(f"DeepQLearningError: {blk!r} maps {n_first} features to {n_last}; SkipConnection(layers, +) needs layers: n -> n")
+        inner0 = blk.layers.layers[0]      # the block's first inner layer reads the layer in front of the block: the rule of add() below holds across the block's edge (the engine refuses it by index)
+        if getattr(front, "kind", None) == "activation" and inner0.kind in ("layernorm", "dropout"):
+            raise _abi.DQNError(f"DeepQLearningError: {inner0!r} cannot directly follow {front!r}: a {type(inner0).__name__} directly behind a standalone Activation layer is not supported, "
+                                "as the first inner layer of a SkipConnection neither (it must directly follow a Dense, recurrent" + (" or LayerNorm" if inner0.kind == "dropout" else "") + " layer)")
+        if inner0.kind in ("layernorm", "dropout") and getattr(front, "kind", None) == inner0.kind:
+            raise _abi.DQNError(f"DeepQLearningError: {inner0!r} cannot directly follow {front!r}: two {type(inner0).__name__} layers in a row are not supported, "
+                                "as the first inner layer of a SkipConnection neither (it must directly follow a Dense, recurrent" + (" or LayerNorm" if inner0.kind == "dropout" else "") + " layer)")
         add(blk.layers, stream)
         d = _abi.LayerDesc()
         d.kind, d.act, d.stream, d.cin = _abi.LAYER_SKIPADD, _abi.ACT_IDENTITY, stream, len(blk.layers)
@@ -575,7 +582,7 @@ def lower(net):
             if getattr(l, "kind", None) == "parallel":
                 raise _abi.DQNError("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
             if getattr(l, "kind", None) == "skip":
-                add_skip(l, stream, not out, shape_kind(layers, i), i + 1 == len(layers) and chain is top)
+                add_skip(l, stream, not out, shape_kind(layers, i), i + 1 == len(layers) and chain is top, layers[i - 1] if i > 0 else None)
                 continue
             if getattr(l, "kind", None) == "activation":      # act = σ (0..14); n_in == n_out == 0: the engine fills in the incoming feature count and keeps the incoming shape
                 if not out:
@@ -594,6 +601,9 @@ def lower(net):
                 raise _abi.DQNError(f"DeepQLearningError: unsupported layer {l!r} (supported: GlobalMaxPool / GlobalMeanPool / AdaptiveMaxPool / AdaptiveMeanPool, and (SkipConnection(+) / Conv / MaxPool / MeanPool / GroupNorm / Dense / Dropout / LSTM / GRU / RNN / LayerNorm / flattenbatch only); a standalone activation is Activation(σ))")
             if l.kind in ("layernorm", "dropout") and i > 0 and getattr(layers[i - 1], "kind", None) == "activation":
                 raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot directly follow {layers[i - 1]!r}: a {type(l).__name__} directly behind a standalone Activation layer is not supported "
+                                    "(it must directly follow a Dense, recurrent" + (" or LayerNorm" if l.kind == "dropout" else "") + " layer)")
+            if l.kind in ("layernorm", "dropout") and i > 0 and getattr(layers[i - 1], "kind", None) == l.kind:      # (the engine refuses it by index: build_layers)
+                raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot directly follow {layers[i - 1]!r}: two {type(l).__name__} layers in a row are not supported "
                                     "(it must directly follow a Dense, recurrent" + (" or LayerNorm" if l.kind == "dropout" else "") + " layer)")
             d.act, d.stream = _act_code(l), stream
             if l.kind == "dense":

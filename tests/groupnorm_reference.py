@@ -98,7 +98,7 @@ LEGS = {"torch": {}, "numpy": {"groupnorm": S.groupnorm_law(_GnNumpy.apply)}, "l
 # ------------------------------------------------------------------ the observers, and the step (step_reference's, bound to the legs)
 def _pool_gap(l, x, relu_out):
     """the smallest top-two gap over the MaxPool windows of x, except windows whose maximum is an exact 0 out of a relu (feedforward_reference.margins' rule)"""
-    if l.kh * l.kw == 1:
+    if l.kh * l.kw == 1 or not x.numel():      # (no column: a time step of a recurrent batch whose every column is padding)
         return np.inf
     t = F.unfold(x.reshape(-1, 1, x.shape[2], x.shape[3]), (l.kh, l.kw), stride=(l.sh, l.sw)).sort(dim=1).values
     gap = t[:, -1] - t[:, -2]

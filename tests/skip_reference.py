@@ -68,15 +68,16 @@ def engine_index(net):
 
 
 def masks_for(net, k, B, T=0, seed=ENGINE_SEED):
-    """dropout_reference.masks_for, keyed by the FLAT index and drawn under the layer's ENGINE index"""
+    """dropout_reference.masks_for, keyed by the FLAT index and drawn under the layer's ENGINE index.  An Activation layer keeps the width of the layer in front; a layer
+    on a map (Conv, pools, GroupNorm) has none, and no Dropout layer stands behind one"""
     prog, out, width = program(net), {}, {}
     for i, e in enumerate(prog):
         w = width.get(e.src)
         if e.kind == "layer" and e.l.kind == "dropout":
             m = DR.keep_mask(seed, k, i, w, (T or 1) * B, e.l.p)
             out[e.fi] = m.reshape(T, B, w) if T else m
-        elif e.kind == "layer":
-            w = e.l.n if e.l.kind == "layernorm" else e.l.n_out
+        elif e.kind == "layer" and e.l.kind != "activation":
+            w = e.l.n if e.l.kind == "layernorm" else getattr(e.l, "n_out", None)
         width[i] = w
     return out
 

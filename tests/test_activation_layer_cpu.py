@@ -169,6 +169,14 @@ def test_the_mirror_refuses_by_name(mods):
         low(nn.Dense(6, 16), XR.A(1), nn.LayerNorm(16), nn.Dense(16, 4))
     with pytest.raises(abi.DQNError, match=r"Dropout\(0.1\) cannot directly follow Activation\(mish\)"):
         low(nn.Dense(6, 16), XR.A(13), nn.Dropout(0.1), nn.Dense(16, 4))
+    # ... across the edge of a skip block too: the block's first inner layer reads the Activation's output (the engine refuses it by index, the Julia shim by the next descriptor)
+    blk = lambda first: nn.SkipConnection(nn.Chain(first, nn.Dense(16, 16)), "+")
+    with pytest.raises(abi.DQNError, match=r"LayerNorm\(16.* cannot directly follow Activation\(tanh\): .* as the first inner layer of a SkipConnection neither"):
+        low(nn.Dense(6, 16), XR.A(2), blk(nn.LayerNorm(16)), nn.Dense(16, 4))
+    with pytest.raises(abi.DQNError, match=r"Dropout\(0.5\) cannot directly follow Activation\(gelu\): .* as the first inner layer of a SkipConnection neither"):
+        low(nn.Dense(6, 16), XR.A(11), blk(nn.Dropout(0.5)), nn.Dense(16, 4))
+    assert len(low(nn.Dense(6, 16), XR.A(2), blk(nn.Dense(16, 16, nn.relu)), nn.Dense(16, 4))[0]) == 6      # a Dense first: accepted, as before
+    assert len(low(nn.Dense(6, 16), blk(nn.LayerNorm(16)), nn.Dense(16, 4))[0]) == 5      # ... and a LayerNorm first behind a Dense
     with pytest.raises(abi.DQNError, match=r"a closure cannot be inspected; write a standalone activation as Activation\(relu\) \(Julia: Base.BroadcastFunction\(relu\)\)"):
         low(nn.Dense(6, 16), (lambda x: np.maximum(x, 0)), nn.Dense(16, 4))
 

@@ -90,6 +90,12 @@ def test_the_mirror_refuses_by_name(mods):
     nn.Dropout(0.5, dims=":")
     with pytest.raises(abi.DQNError, match=r"unsupported layer .*Dense / Dropout / LSTM.*RNN / LayerNorm / flattenbatch only"):
         nn.lower(nn.Chain(object()))
+    # two in a row: the engine refuses it by index (build_layers), the mirror by name -- across the edge of a skip block too
+    with pytest.raises(abi.DQNError, match=r"Dropout\(0.5\) cannot directly follow Dropout\(0.1\): two Dropout layers in a row are not supported"):
+        nn.lower(nn.Chain(nn.Dense(6, 16), nn.Dropout(0.1), nn.Dropout(0.5), nn.Dense(16, 4)))
+    with pytest.raises(abi.DQNError, match=r"two Dropout layers in a row are not supported, as the first inner layer of a SkipConnection neither"):
+        nn.lower(nn.Chain(nn.Dense(6, 16), nn.Dropout(0.1), nn.SkipConnection(nn.Chain(nn.Dropout(0.5), nn.Dense(16, 16)), "+"), nn.Dense(16, 4)))
+    assert len(nn.lower(nn.Chain(nn.Dense(6, 16), nn.Dropout(0.1), nn.LayerNorm(16), nn.Dropout(0.5), nn.Dense(16, 4)))[0]) == 5      # a LayerNorm between them: accepted, as before
 
 
 def _L(abi, kind, stream=0, act=0, n_in=0, n_out=0, cin=0, cout=0, k=0, s=0):

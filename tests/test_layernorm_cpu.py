@@ -90,6 +90,12 @@ def test_the_mirror_refuses_by_name(mods):
             nn.LayerNorm(8, eps=bad)
     with pytest.raises(abi.DQNError, match=r"unsupported layer .*MaxPool.*RNN / LayerNorm"):
         nn.lower(nn.Chain(object()))
+    # two in a row: the engine refuses it by index (build_layers), the mirror by name -- across the edge of a skip block too
+    with pytest.raises(abi.DQNError, match=r"LayerNorm\(16.* cannot directly follow LayerNorm\(16.*: two LayerNorm layers in a row are not supported"):
+        nn.lower(nn.Chain(nn.Dense(6, 16), nn.LayerNorm(16), nn.LayerNorm(16), nn.Dense(16, 4)))
+    with pytest.raises(abi.DQNError, match=r"two LayerNorm layers in a row are not supported, as the first inner layer of a SkipConnection neither"):
+        nn.lower(nn.Chain(nn.Dense(6, 16), nn.LayerNorm(16), nn.SkipConnection(nn.Chain(nn.LayerNorm(16), nn.Dense(16, 16)), "+"), nn.Dense(16, 4)))
+    assert len(nn.lower(nn.Chain(nn.Dense(6, 16), nn.LayerNorm(16), nn.Dropout(0.5), nn.LayerNorm(16), nn.Dense(16, 4)))[0]) == 5      # a Dropout between them: accepted, as before
 
 
 def _L(abi, kind, stream=0, act=0, n_in=0, n_out=0, cin=0, cout=0, k=0, s=0):
