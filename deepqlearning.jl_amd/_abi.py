@@ -202,6 +202,8 @@ PROTOS = {
     "group_train_steps": [_vp, C.c_int, _f32p, _f32p],
     "group_info": [_vp, _P(GroupInfo)],
     "group_destroy": [_vp],
+    "rollout_many": [_vp, C.c_int, _P(RolloutCfg), _P(_P(Exploration)), _P(RolloutStats)],
+    "rollout_many_info": [_vp, _P(C.c_int), _P(C.c_uint)],
 }
 
 class DQNError(RuntimeError):
@@ -712,6 +714,42 @@ class EngineGroup:
         loss, gn = np.empty(len(self.members), np.float32), np.empty(len(self.members), np.float32)
         self._check(self.f["group_train_steps"](self._g, int(n), _ptr(loss, _f32p), _ptr(gn, _f32p)))
         return loss, gn
+
+    def rollout(self, n_steps, t0=1, train_freq=4, target_update_freq=500, eps=(1.0, 0.01, 5000.0), explore=None, stats=True):
+        """dqn_rollout_many: n_steps vector steps of every member's device environment loop, ONE launch of K workgroups per vector step, the group train step at
+        t % train_freq == 0 and the target syncs at t % target_update_freq == 0 inside the call.  eps: one (start, stop, steps) for all members or a list of K;
+        explore: None, or a list of K entries, each None (that member's linear law) or ("eps" | "softmax", values) as in Handle.rollout.  Returns K dicts like
+        Handle.rollout's (None with stats=False); member k ends bit for bit where Handle.rollout would have left it."""
+        if "rollout_many" not in self.f:
+            raise DQNError("this library does not export rollout_many")
+        K = len(self.members)
+        eps_k = [eps] * K if len(eps) == 3 and not isinstance(eps[0], (tuple, list)) else list(eps)
+        if len(eps_k) != K:
+            raise DQNError(f"EngineGroup.rollout: {len(eps_k)} eps schedules were given for {K} members (one for all, or one per member)")
+        cfgs = (RolloutCfg * K)(*[RolloutCfg(int(train_freq), int(target_update_freq), float(e[0]), float(e[1]), float(e[2]), 0, int(t0)) for e in eps_k])
+        xs, keep = None, []
+        if explore is not None:
+            if len(explore) != K:
+                raise DQNError(f"EngineGroup.rollout: {len(explore)} exploration entries were given for {K} members (None, or one per member)")
+            xs = (_P(Exploration) * K)()
+            for k, ex in enumerate(explore):
+                if ex is None:
+                    continue
+                kind, values = ex
+                vals = None if values is None else np.ascontiguousarray(np.atleast_1d(values), np.float32)
+                x = Exploration(int(_EXPLORE_KINDS.get(kind, kind)), 0 if vals is None else int(vals.size), None if vals is None else vals.ctypes.data)
+                keep.append((vals, x)); xs[k] = C.pointer(x)
+        st = (RolloutStats * K)()
+        self._check(self.f["rollout_many"](self._g, int(n_steps), cfgs, xs, st if stats else None))
+        if not stats:
+            return None
+        return [dict(episodes=s.episodes, reward_sum=s.reward_sum, train_steps=s.train_steps, loss=s.last_loss, grad_norm=s.last_grad_norm) for s in st]
+
+    def rollout_info(self):
+        """(launches per vector step, dynamic LDS bytes of the acting launch); raises with the member and the reason where a member does not take the acting step"""
+        n, lds = C.c_int(), C.c_uint()
+        self._check(self.f["rollout_many_info"](self._g, C.byref(n), C.byref(lds)))
+        return n.value, lds.value
 
     def info(self):
         gi = GroupInfo()

@@ -994,6 +994,9 @@ void launch_td_drqn(hipStream_t st, const TdDrqnArgs& a);
 void launch_bcast_state(hipStream_t st, const float* src, int H, int n, float* dst);
 
 #ifdef __HIPCC__
+// barrier for phases that exchange LDS data only (tiny_step.hip, tiny_act.hip): __syncthreads() also drains vmcnt -- every parity store (Q columns, td, gradients, ...) of
+// the phase before would cost its round trip (1-2 us) at each of a step's ~8 barriers; here those stores stay in flight
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // head output (n, col): either the finished activation, or -- when the head's forward ran split-K and its reduction is
 // folded into this kernel -- act(sum_s partial + bias)
 // ascending sum of S split-K slabs p[0], p[stride], ..., p[(S-1)*stride]: loads go out in rounds of up to 32 (then 8) INDEPENDENT requests,
@@ -1073,6 +1076,25 @@ struct ActHeadArgs {
 bool act_head_ok(int n, int K, int S, int nA, int nstream, int N0, int N1);
 void launch_act_head(hipStream_t st, const ActHeadArgs& a);
 void launch_env_reset_pending(hipStream_t st, const EnvDev& V, const RolloutDev* rs, int force_all);
+// ---- one vector step of the device environment loop of a network that fits in LDS as ONE single-workgroup launch (tiny_act.hip): online forward on the n columns of
+// pol_x, then the tail of k_env_step (env_body.h env_step_body) on head outputs that never leave LDS, then what k_env_observe2 does.  One record per engine in device
+// memory; a group (engine_group.hip, dqn_rollout_many) launches a grid of K with the record taken from blockIdx.x
+#define TINY_ACT_TAIL_LDS (43 * 1024)      /* static LDS of the kernel: env_step_body's arrays (head staging, sum-tree levels and rims), the records and the layer table */
+struct TinyActArgs {
+    int nl, nlev, dueling, last_base, last_val, last_adv, rows_u8, pad; unsigned long long P;
+    LayerDev L[TINY_MAX_LAYERS];
+    int lev_n[TINY_MAX_LAYERS], lev_l[TINY_MAX_LAYERS][2];      // level -> its (one or two sibling) layers
+    int y_off[TINY_MAX_LAYERS];                                 // LDS float offsets of the layers' activations [N][n]
+    int p_off, x_off; unsigned lds_bytes;                       // the online parameters, the policy input x[E][n]; dynamic LDS of the record's workgroup
+    const float* p_on; float *pol_x, *pol_q; int* pol_a;
+    void *s_rows, *sp_rows;                                     // the replay ring's rows (rows_u8: bytes)
+    RolloutDev* rs;                                             // the member's record of the call (owned by the group)
+    EnvDev V; ReplayMeta R;
+};
+// one launch of K workgroups, workgroup k = record a_dev[k].  first: the policy input is observe(env) of the states as they stand (a call's first step; else pol_x, which
+// the step before left); last: the resets the step leaves pending are applied (a call's last step).  -1: the LDS attribute was refused
+int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int first, int last);
+int tiny_act_raise_lds(unsigned lds_bytes);      // what launch_tiny_act asks of the device, callable before anything is enqueued; -1: refused
 // ---- recurrent engines: the copies' open episodes (staging [n][T]) and the committed episode ring (envs.hip, engine_envs.hip)
 struct EpStage {
     int T; long long ep_cap;

@@ -235,7 +235,10 @@ struct FwdEmit {
 void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, const std::vector<FwdPass>& passes, FwdEmit& E);
 int build_program(dqn_engine* e);
 std::string tiny_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup step (tiny_step.hip); empty: it does.  THE eligibility rule
+// engine_group.hip
+std::string tiny_act_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup acting step (tiny_act.hip); empty: it does.  THE eligibility rule
 // engine_envs.hip
 void free_envs(dqn_engine* e);
+int explore_check(const dqn_exploration* x, int n_steps);      // dqn_rollout_explore's table: 0, or -1 with the refusal (nothing is enqueued)
 int ep_mirror_push(dqn_engine* e);      // recurrent env sets: host (ep_widx, ep_size) -> the device cursor, before a rollout
 int ep_mirror_pull(dqn_engine* e);      // ... and the device cursor and lengths -> the host mirror (ep_widx, ep_size, ep_len_host): one D2H + one synchronize

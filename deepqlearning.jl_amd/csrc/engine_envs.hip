@@ -291,7 +291,7 @@ static int envc_graph(dqn_engine* e, dqn_engine::ActProg& ap, int due) {
 }
 // dqn_rollout_explore's table.  explore_check refuses before anything is enqueued; explore_upload copies the values into the engine's buffer (grown on demand) and
 // names them in the record every RolloutDev of the call is copied from.  x == nullptr: the linear law (xtab stays null)
-static int explore_check(const dqn_exploration* x, int n_steps) {
+int explore_check(const dqn_exploration* x, int n_steps) {
     if (!x) return 0;
     if (x->kind != DQN_EXPLORE_EPS_GREEDY && x->kind != DQN_EXPLORE_SOFTMAX) return fail("exploration: unknown kind %d (0: eps-greedy, 1: softmax)", x->kind);
     if (x->n_values != 1 && x->n_values != n_steps) return fail("exploration: n_values = %d is neither 1 nor n_vector_steps = %d", x->n_values, n_steps);

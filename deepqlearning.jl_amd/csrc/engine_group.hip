@@ -5,6 +5,8 @@
 #include "engine.h"
 
 struct GroupScalars { float loss, gnorm; int err, pad; unsigned long long step; };      // what the standalone step's publish launch reports (StepMail), per member
+// ... and what dqn_rollout_explore fetches per engine at the end of a call: the episode statistics of the env set beside the step's scalars
+struct RolloutScalars { float loss, gnorm; int err, pad; unsigned long long step; long long episodes; double reward_sum; };
 
 struct dqn_group {
     int device = 0, K = 0; unsigned max_lds = 0;
@@ -13,6 +15,12 @@ struct dqn_group {
     hipStream_t stream = nullptr; std::vector<hipEvent_t> ev_in; hipEvent_t ev_done = nullptr;
     GroupScalars *out_dev = nullptr, *out_host = nullptr;      // out_host: pinned
     bool counted = false;      // the members' in_groups counts include this group
+    // dqn_rollout_many: the members' acting records (host copy = what the device array holds; rebuilt per call, uploaded when they changed), the call's RolloutDev
+    // records and exploration tables (ONE device array and ONE H2D copy each), the per-member results of a call
+    std::vector<TinyActArgs> act_host; TinyActArgs* act_dev = nullptr; unsigned act_lds = 0;
+    std::vector<RolloutDev> roll_host; RolloutDev* roll_dev = nullptr;
+    std::vector<float> xtab_host; float* xtab_dev = nullptr; size_t xtab_cap = 0;
+    struct RolloutScalars *ro_dev = nullptr, *ro_host = nullptr;      // ro_host: pinned
 };
 
 // per member, what k_publish_scalars does for a standalone engine after the last step of a call: globalnorm = the fold of the step's per-block maxima (ONE slot, the
@@ -75,6 +83,8 @@ extern "C" int dqn_group_destroy(dqn_group_t* g) {
     if (g->ev_done) hipEventDestroy(g->ev_done);
     if (g->stream) hipStreamDestroy(g->stream);
     if (g->out_host) hipHostFree(g->out_host);
+    if (g->ro_host) hipHostFree(g->ro_host);
+    hipFree(g->ro_dev); hipFree(g->xtab_dev); hipFree(g->roll_dev); hipFree(g->act_dev);
     hipFree(g->out_dev); hipFree(g->args_dev);
     delete g;
     return 0;
@@ -122,6 +132,208 @@ extern "C" int dqn_group_train_steps(dqn_group_t* g, int n, float* loss, float* 
     }
     if (bad >= 0) {
         const GroupScalars& o = g->out_host[bad];
+        const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
+        if (o.err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o.step, more);
+        return fail("member %d: device-side error %d at or before train step %llu%s", bad, o.err, o.step, more);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- grouped acting: dqn_rollout_many (tiny_act.hip)
+// the dynamic-LDS layout of the single-workgroup acting step, in floats: the online parameters, the policy input x[E][n], then per layer its activations [N][n]
+// (every part 16-byte aligned).  a != null: the offsets are recorded
+static size_t tiny_act_layout(const dqn_engine* e, TinyActArgs* a) {
+    const int n = e->env.n;
+    size_t fl = 0; TinyActArgs tmp; TinyActArgs& A = a ? *a : tmp;
+    auto take = [&](size_t m) { const int o = (int)fl; fl += (m + 3) / 4 * 4; return o; };
+    A.p_off = take(e->Pint); A.x_off = take((size_t)e->E * n);
+    for (int i = 0; i < e->nl && i < TINY_MAX_LAYERS; i++) A.y_off[i] = take((size_t)e->L[i].N * n);
+    return fl;
+}
+// THE eligibility rule of the single-workgroup acting step, term by term: empty when the engine takes it, else the reason in words.  A pure function of the engine as
+// it stands after dqn_envs_create / dqn_envs_create_tabular
+std::string tiny_act_decline(const dqn_engine* e) {
+    char buf[200];
+    if (!e->has_envs) return "it has no device environments (dqn_envs_create / dqn_envs_create_tabular)";
+    if (e->hp.recurrence) return "it is recurrent (recurrence = true)";
+    for (int i = 0; i < e->nl; i++) if (e->L[i].kind != DQN_LAYER_DENSE) { snprintf(buf, sizeof buf, "layer %d is not a Dense layer (kind %d)", i, e->L[i].kind); return buf; }
+    const int nlev = (int)net_levels(e).size();
+    if (e->nl > TINY_MAX_LAYERS || nlev > TINY_MAX_LAYERS) { snprintf(buf, sizeof buf, "it has too many layers (%d in %d levels, at most %d)", e->nl, nlev, TINY_MAX_LAYERS); return buf; }
+    // the one-CU arithmetic budget of the train step (tiny_decline), with the copies in the place of the batch columns; what the kernel costs at the bound: docs/history/group_rollout.md
+    if (e->Pint > 16384 || (size_t)e->Pint * e->env.n > 262144) { snprintf(buf, sizeof buf, "it has too many parameters for %d copies (%zu, at most 16384 and 262144 / n_envs)", e->env.n, e->Pint); return buf; }
+    const size_t bytes = tiny_act_layout(e, nullptr) * 4 + TINY_ACT_TAIL_LDS;
+    if (bytes > 144 * 1024) { snprintf(buf, sizeof buf, "it needs %zu bytes of LDS for its parameters, the policy input and the activations of %d copies (at most %d)", bytes, e->env.n, 144 * 1024); return buf; }
+    return std::string();
+}
+// the member's record, from the engine as it stands (the policy workspace is sized here: what build_act_program does for a standalone rollout)
+static int tiny_act_record(dqn_engine* e, RolloutDev* rs, TinyActArgs* out) {
+    if (policy_ws(e, std::max(e->env.n, std::max(e->pol_n, e->eval_n)))) return -1;
+    TinyActArgs a; memset(&a, 0, sizeof a);
+    const Levels levels = net_levels(e);
+    for (int i = 0; i < e->nl; i++) a.L[i] = e->L[i];
+    a.lds_bytes = (unsigned)(tiny_act_layout(e, &a) * 4);
+    a.nl = e->nl; a.nlev = (int)levels.size(); a.dueling = e->hp.dueling; a.last_base = e->last_base; a.last_val = e->last_val; a.last_adv = e->last_adv;
+    a.rows_u8 = e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 0; a.P = e->Pint;
+    for (size_t li = 0; li < levels.size(); li++) { a.lev_n[li] = (int)levels[li].size(); a.lev_l[li][0] = levels[li][0]; a.lev_l[li][1] = levels[li].size() > 1 ? levels[li][1] : levels[li][0]; }
+    a.p_on = e->p_on; a.pol_x = e->pol_x; a.pol_q = e->pol_q; a.pol_a = e->pol_a; a.s_rows = e->s_rows; a.sp_rows = e->sp_rows; a.rs = rs; a.V = e->env;
+    ReplayMeta& R = a.R; R.cap = e->cap; R.cap2 = e->cap2; R.a = e->ra; R.r = e->rr; R.done = e->rdone; R.tree = e->tree; R.state = e->state; R.eps = e->hp.prio_eps; R.alpha = e->hp.prio_alpha;
+    *out = a; return 0;
+}
+// Flux.loadparams!(target_q, params(active_q)) of every member: workgroup k copies member k's online parameters over its target parameters (dqn_sync_target keeps no host state)
+__global__ __launch_bounds__(256) void k_group_sync_target(const TinyArgs* __restrict__ A) {
+    const TinyArgs& a = A[blockIdx.x];
+    float* tg = const_cast<float*>(a.p_tg);
+    for (unsigned long long i = threadIdx.x; i < a.P; i += blockDim.x) tg[i] = a.p_on[i];
+}
+// per member, after the last step of a dqn_rollout_many call: the fold of the step's scalars (k_group_scalars; the grad norm only when the call trained), the consumed
+// assertion flag, and the env set's episode statistics summed in copy order in Float64 -- the host loop of dqn_rollout_explore
+__global__ __launch_bounds__(256) void k_group_rollout_scalars(const TinyArgs* __restrict__ A, const TinyActArgs* __restrict__ C, int K, int trained, RolloutScalars* __restrict__ out) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    StepState* st = A[k].state;
+    RolloutScalars o; o.loss = 0.0f; o.gnorm = 0.0f; o.pad = 0;
+    if (trained) { const float g = fmaxf(0.0f, A[k].gmax_part[0]); st->gnorm_bits = __float_as_uint(g); o.loss = st->loss; o.gnorm = g; }
+    o.err = atomicExch(&st->err, 0); o.step = st->step;
+    const EnvDev& V = C[k].V;
+    long long ep = 0; double rw = 0.0;
+    for (int i = 0; i < V.n; i++) { ep += V.fin_eps[i]; rw += V.fin_reward[i]; }
+    o.episodes = ep; o.reward_sum = rw;
+    out[k] = o;
+}
+
+// what every refusal below must be able to say of another member's refusal: the message of the last fail(), copied (fail() formats into the buffer it would read from)
+static std::string last_message() { return std::string(dqn_last_error()); }
+
+// the per-call validation of dqn_rollout_many: everything that can be refused, before anything is enqueued.  *train_at: per vector step of the call, 1 where the group train step runs
+static int rollout_many_check(dqn_group* g, int n_steps, const dqn_rollout_cfg* cfgs, const dqn_exploration* const* explore, std::vector<char>* train_at) {
+    if (n_steps < 1) return fail("dqn_rollout_many: n_steps = %d, at least one vector step is needed", n_steps);
+    if (!cfgs) return fail("dqn_rollout_many: cfgs is NULL (one dqn_rollout_cfg per member)");
+    const dqn_rollout_cfg& c0 = cfgs[0];
+    for (int k = 0; k < g->K; k++) {
+        const dqn_rollout_cfg& c = cfgs[k];
+        if (c.t0 < 1) return fail("dqn_rollout_many: member %d: t0 counts from 1 (src/solver.jl:82)", k);
+        if (c.cadence_env_steps != 0) return fail("dqn_rollout_many: member %d: cadence_env_steps = %d -- the group runs the vector-step cadence only (cadence_env_steps = 0)", k, c.cadence_env_steps);
+        if (c.train_freq != c0.train_freq) return fail("dqn_rollout_many: train_freq differs between members 0 and %d (%d vs %d): the members run in lock step", k, c0.train_freq, c.train_freq);
+        if (c.target_update_freq != c0.target_update_freq) return fail("dqn_rollout_many: target_update_freq differs between members 0 and %d (%d vs %d): the members run in lock step", k, c0.target_update_freq, c.target_update_freq);
+        if (c.t0 != c0.t0) return fail("dqn_rollout_many: t0 differs between members 0 and %d (%lld vs %lld): the members run in lock step", k, (long long)c0.t0, (long long)c.t0);
+    }
+    for (int k = 0; k < g->K; k++) if (explore && explore[k] && explore_check(explore[k], n_steps)) { const std::string why = last_message(); return fail("dqn_rollout_many: member %d: %s", k, why.c_str()); }
+    for (int k = 0; k < g->K; k++) {
+        const std::string why = tiny_act_decline(g->members[k]);
+        if (!why.empty()) return fail("dqn_rollout_many: member %d does not take the single-workgroup acting step: %s", k, why.c_str());
+    }
+    // the standalone loop trains a member only once its replay holds a batch, and a group launch cannot skip a member: size, n, cap and B are host-known, so every due
+    // step of the call is decided here, and members that disagree at one are refused
+    train_at->assign((size_t)n_steps, 0);
+    if (c0.train_freq > 0) {
+        std::vector<long long> size((size_t)g->K);
+        for (int k = 0; k < g->K; k++) size[k] = g->members[k]->size;
+        for (int j = 0; j < n_steps; j++) {
+            const long long t = c0.t0 + j;
+            for (int k = 0; k < g->K; k++) size[k] = std::min(g->members[k]->cap, size[k] + g->members[k]->env.n);
+            if (t % c0.train_freq != 0) continue;
+            const bool w0 = size[0] >= g->members[0]->B;
+            for (int k = 1; k < g->K; k++) if ((size[k] >= g->members[k]->B) != w0)
+                return fail("dqn_rollout_many: members 0 and %d disagree at vector step %lld on whether the train step runs (member 0 holds %lld of its batch of %d, member %d holds %lld of %d): "
+                            "one launch trains every member or none -- fill the replays so that every member holds a batch at the same due step", k, t, size[0], g->members[0]->B, k, size[k], g->members[k]->B);
+            (*train_at)[(size_t)j] = w0 ? 1 : 0;
+        }
+    }
+    return 0;
+}
+// the members' records, rebuilt from the engines as they stand (an env set may be created or replaced, a policy workspace may grow between two calls) and uploaded
+// when they differ from what the device array holds
+static int rollout_many_records(dqn_group* g) {
+    const size_t K = (size_t)g->K;
+    if (!g->roll_dev) { DM(g->roll_dev, K); DM(g->act_dev, K); DM(g->ro_dev, K); HIPCHK(hipHostMalloc((void**)&g->ro_host, sizeof(RolloutScalars) * K, hipHostMallocDefault)); g->roll_host.resize(K); }
+    std::vector<TinyActArgs> recs(K); unsigned lds = 0;
+    for (size_t k = 0; k < K; k++) { if (tiny_act_record(g->members[k], g->roll_dev + k, &recs[k])) return -1; lds = std::max(lds, recs[k].lds_bytes); }
+    if (g->act_host.size() != K || memcmp(g->act_host.data(), recs.data(), sizeof(TinyActArgs) * K) != 0) {
+        HIPCHK(hipStreamSynchronize(g->stream));
+        HIPCHK(hipMemcpy(g->act_dev, recs.data(), sizeof(TinyActArgs) * K, hipMemcpyHostToDevice));
+        g->act_host.swap(recs);
+    }
+    g->act_lds = lds;
+    return 0;
+}
+
+extern "C" int dqn_rollout_many_info(dqn_group_t* g, int* launches_per_vector_step, unsigned* max_lds_bytes) {
+    if (!g) return fail("null group handle");
+    unsigned lds = 0;
+    for (int k = 0; k < g->K; k++) {
+        const std::string why = tiny_act_decline(g->members[k]);
+        if (!why.empty()) return fail("dqn_rollout_many_info: member %d does not take the single-workgroup acting step: %s", k, why.c_str());
+        lds = std::max(lds, (unsigned)(tiny_act_layout(g->members[k], nullptr) * 4));
+    }
+    if (launches_per_vector_step) *launches_per_vector_step = 1;
+    if (max_lds_bytes) *max_lds_bytes = lds;
+    return 0;
+}
+
+extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_cfg* cfgs, const dqn_exploration* const* explore, dqn_rollout_stats* out) {
+    if (!g) return fail("null group handle");
+    std::vector<char> train_at;
+    if (rollout_many_check(g, n_steps, cfgs, explore, &train_at)) return -1;
+    HIPCHK(hipSetDevice(g->device));
+    if (rollout_many_records(g)) return -1;
+    if (tiny_act_raise_lds(g->act_lds)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds);
+    const int K = g->K; const dqn_rollout_cfg& c0 = cfgs[0];
+    // the call's records and tables: ONE contiguous array each, ONE H2D copy each
+    size_t nx = 0;
+    for (int k = 0; k < K; k++) if (explore && explore[k]) nx += (size_t)explore[k]->n_values;
+    if (nx > g->xtab_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream)); hipFree(g->xtab_dev); g->xtab_dev = nullptr; g->xtab_cap = 0;
+        const size_t cap = std::max<size_t>(1024, 2 * nx); DM(g->xtab_dev, cap); g->xtab_cap = cap;
+    }
+    g->xtab_host.clear();
+    for (int k = 0; k < K; k++) {
+        dqn_engine* e = g->members[k]; const dqn_rollout_cfg& c = cfgs[k]; const int n = e->env.n;
+        RolloutDev h; memset(&h, 0, sizeof h);
+        h.t = c.t0 - 1; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; h.eps_start = c.eps_start; h.eps_stop = c.eps_stop; h.eps_steps = c.eps_steps;
+        if (explore && explore[k]) {
+            const dqn_exploration* x = explore[k];
+            h.xkind = x->kind; h.xtab = g->xtab_dev + g->xtab_host.size(); h.xtab_t0 = c.t0; h.xtab_n = x->n_values;
+            g->xtab_host.insert(g->xtab_host.end(), x->values, x->values + x->n_values);      // the caller's arrays are not kept
+        }
+        g->roll_host[(size_t)k] = h;
+    }
+    // in: the group's stream behind everything the members have enqueued
+    for (int k = 0; k < K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
+    (void)hipGetLastError();
+    int rc = 0; hipError_t he = hipSuccess; long long trained = 0;
+    he = hipMemcpyAsync(g->roll_dev, g->roll_host.data(), sizeof(RolloutDev) * (size_t)K, hipMemcpyHostToDevice, g->stream);
+    if (he == hipSuccess && nx) he = hipMemcpyAsync(g->xtab_dev, g->xtab_host.data(), sizeof(float) * nx, hipMemcpyHostToDevice, g->stream);      // (both host arrays are the group's: they outlive the copies)
+    if (he != hipSuccess) rc = fail("dqn_rollout_many: HIP error %s uploading the call's records", hipGetErrorString(he));
+    for (int j = 0; j < n_steps && !rc; j++) {
+        const long long t = c0.t0 + j;
+        if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds); break; }
+        for (dqn_engine* e : g->members) { const int n = e->env.n; e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); }      // what dqn_rollout_explore keeps on the host
+        if (train_at[(size_t)j]) {      // :134-139, for all members in one launch
+            if (launch_tiny_group(g->stream, g->args_dev, K, g->max_lds, 1)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the group train launch (hipFuncSetAttribute)", g->max_lds); break; }
+            trained++;
+        }
+        if (c0.target_update_freq > 0 && t % c0.target_update_freq == 0) hipLaunchKernelGGL(k_group_sync_target, dim3(K), dim3(256), 0, g->stream, g->args_dev);      // :142-145
+    }
+    if (!rc) {
+        hipLaunchKernelGGL(k_group_rollout_scalars, dim3((K + 255) / 256), dim3(256), 0, g->stream, g->args_dev, g->act_dev, K, trained > 0 ? 1 : 0, g->ro_dev);
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipMemcpyAsync(g->ro_host, g->ro_dev, sizeof(RolloutScalars) * (size_t)K, hipMemcpyDeviceToHost, g->stream);
+        if (he != hipSuccess) rc = fail("dqn_rollout_many: HIP error %s behind the group's steps", hipGetErrorString(he));
+    }
+    // out: every member's stream behind whatever the group enqueued -- on the error paths too
+    he = hipEventRecord(g->ev_done, g->stream);
+    for (int k = 0; k < K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
+    const hipError_t hs = hipStreamSynchronize(g->stream);
+    if (rc) return rc;
+    if (he != hipSuccess || hs != hipSuccess) return fail("dqn_rollout_many: HIP error %s ordering the members' streams behind the group", hipGetErrorString(he != hipSuccess ? he : hs));
+    int bad = -1, nbad = 0;
+    for (int k = 0; k < K; k++) {
+        const RolloutScalars& o = g->ro_host[k];
+        if (out) { out[k].episodes = o.episodes; out[k].reward_sum = o.reward_sum; out[k].train_steps = trained; out[k].last_loss = o.loss; out[k].last_grad_norm = o.gnorm; }
+        if (o.err) { if (bad < 0) bad = k; nbad++; }
+    }
+    if (bad >= 0) {
+        const RolloutScalars& o = g->ro_host[bad];
         const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
         if (o.err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o.step, more);
         return fail("member %d: device-side error %d at or before train step %llu%s", bad, o.err, o.step, more);

@@ -15,10 +15,6 @@
 #include "common.h"
 #include "adam_body.h"
 
-// barrier for phases that exchange LDS data only: __syncthreads() also drains vmcnt -- every parity store (Q columns, td, gradients, ...) of the phase
-// before would cost its round trip (1-2 us) at each of the step's ~8 barriers; here those stores stay in flight
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
 template <int NTH>
 __global__ __launch_bounds__(NTH) void k_tiny_step(const TinyArgs* __restrict__ Ap, int sample, int stop) {
     extern __shared__ __align__(16) float sm[];

@@ -21,7 +21,7 @@ import DeepQLearning: batch_train!, add_exp!, update_priorities!, get_batch, pop
 import CommonRLInterface: AbstractEnv, observe, actions, act!, reset!, terminated
 import TensorBoardLogger: TBLogger, log_value
 import StatsBase
-export MI355XSolver, HIPReplayBuffer, HIPEpisodeReplayBuffer, HIPNNPolicy, train_steps!, EngineGroup, close!, group_info
+export MI355XSolver, HIPReplayBuffer, HIPEpisodeReplayBuffer, HIPNNPolicy, train_steps!, EngineGroup, close!, group_info, rollout_info
 
 const LIB = get(ENV, "DQN_MI355X_LIB", "libdqn_mi355x.so")
 
@@ -671,6 +671,41 @@ function rollout!(e::Engine, n_steps; t0 = 1, train_freq = 4, target_update_freq
         end
     end
     st
+end
+# ---- grouped acting (dqn_rollout_many): n_steps vector steps of EVERY member's device loop, one launch of K workgroups per vector step, the group train step and the
+# target syncs inside the call.  eps: one (start, stop, steps) for all members or a vector of K; explore: nothing, or a vector of K exploration policies (an entry
+# `nothing`: that member's linear law).  Returns K records; member k ends bit for bit where rollout!(g.members[k], ...) would have left it
+struct RolloutStatsRec      # the isbits form of RolloutStats: an array of K of them is what the call fills
+    episodes::Int64; reward_sum::Float64; train_steps::Int64; last_loss::Float32; last_grad_norm::Float32
+end
+function rollout!(g::EngineGroup, n_steps; t0 = 1, train_freq = 4, target_update_freq = 500, eps = (1f0, 0.01f0, 5000f0), explore = nothing)
+    K = length(g.members)
+    epsk = eps isa AbstractVector ? collect(eps) : fill(eps, K)
+    pols = explore === nothing ? fill(nothing, K) : collect(explore)
+    tabs = Any[p === nothing ? nothing : exploration_table(p, t0, n_steps) for p in pols]
+    cfgs = Vector{RolloutCfg}(undef, K); xs = Vector{Exploration}(undef, K); ptrs = fill(Ptr{Exploration}(C_NULL), K)
+    vals = Vector{Vector{Float32}}(undef, K)
+    for k in 1:K
+        e3 = (pols[k] === nothing || tabs[k] !== nothing) ? epsk[k] : linear_eps(pols[k])
+        cfgs[k] = RolloutCfg(train_freq, target_update_freq, e3[1], e3[2], e3[3], 0, t0)
+        vals[k] = tabs[k] === nothing ? Float32[] : tabs[k][2]
+    end
+    st = Vector{RolloutStatsRec}(undef, K)
+    GC.@preserve vals xs ptrs begin
+        for k in 1:K
+            tabs[k] === nothing && continue
+            xs[k] = Exploration(tabs[k][1], length(vals[k]), pointer(vals[k]))
+            ptrs[k] = pointer(xs, k)
+        end
+        check(ccall((:dqn_rollout_many, LIB), Cint, (Ptr{Cvoid}, Cint, Ptr{RolloutCfg}, Ptr{Ptr{Exploration}}, Ptr{RolloutStatsRec}),
+                    g.h, n_steps, cfgs, explore === nothing ? Ptr{Ptr{Exploration}}(C_NULL) : pointer(ptrs), st))
+    end
+    st
+end
+function rollout_info(g::EngineGroup)      # (launches per vector step, dynamic LDS bytes of the acting launch); throws with the member and the reason where one is declined
+    n = Ref{Cint}(0); lds = Ref{Cuint}(0)
+    check(ccall((:dqn_rollout_many_info, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cuint}), g.h, n, lds))
+    Int(n[]), Int(lds[])
 end
 
 end # module

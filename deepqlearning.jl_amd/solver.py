@@ -528,10 +528,12 @@ def check_many(solvers, member_envs):
 
 def solve_many(solvers, env, engine_cls=None, init_seed=1):
     """dqn_train! for K solvers at once on the device loop (device_envs=True), in lock step; returns the K policies.  Per block of vector steps up to the next
-    train / target-sync / eval / log / save boundary: every member's rollout (acting and add_exp! are each member's own launches, with its own exploration
-    table), then ONE group train step for all members (EngineGroup: one launch of K workgroups), then the target syncs and the marks, as in dqn_train_device.
-    The order inside a vector step is the standalone loop's (act, add, train, sync) and every device draw is keyed by (seed, t, copy, purpose), so member k ends
-    bit for bit where solve(solvers[k], env) ends.  `env` is one environment -- every member then works on its own deep copy of it, as given -- or a list of K."""
+    eval / log / save mark: ONE EngineGroup.rollout (dqn_rollout_many) -- per vector step one launch of K workgroups acts for every member under its own
+    exploration law or table, at t % train_freq == 0 one group train launch, at t % target_update_freq == 0 one target-sync launch -- then the marks, as in
+    dqn_train_device.  The order inside a vector step is the standalone loop's (act, add, train, sync) and every device draw is keyed by (seed, t, copy, purpose),
+    so member k ends bit for bit where solve(solvers[k], env) ends.  Where a member does not take the single-workgroup acting step (too many copies for its
+    network: EngineGroup.rollout_info says why) the whole run keeps the per-member loop: every member's own rollout per block up to the next train / target-sync
+    boundary, then one group train step.  `env` is one environment -- every member then works on its own deep copy of it, as given -- or a list of K."""
     import copy
     solvers = list(solvers)
     member_envs = list(env) if isinstance(env, (list, tuple)) else [copy.deepcopy(env) for _ in solvers]
@@ -551,6 +553,21 @@ def solve_many(solvers, env, engine_cls=None, init_seed=1):
         episodes, reward_sum = [0] * K, [0.0] * K
         loss, gn = np.full(K, np.nan, np.float32), np.full(K, np.nan, np.float32)
         t, filled = 1, False
+        try:
+            group.rollout_info()
+            grouped_acting = True
+        except DQNError:
+            grouped_acting = False
+        while grouped_acting and t <= s0.max_steps:
+            nxt = min(min((t + m - 1) // m * m for m in marks), s0.max_steps)
+            tabs = [exploration_table(s.exploration_policy, t, nxt - t + 1) for s in solvers]
+            sts = group.rollout(nxt - t + 1, t0=t, train_freq=s0.train_freq, target_update_freq=s0.target_update_freq,
+                                eps=[tb.get("eps", (1.0, 1.0, 1.0)) for tb in tabs], explore=[tb.get("explore") for tb in tabs])
+            t = nxt + 1
+            for k, (s, ev, p) in enumerate(zip(solvers, member_envs, policies)):
+                d_eps, d_rew = sts[k]["episodes"] - episodes[k], sts[k]["reward_sum"] - reward_sum[k]
+                episodes[k], reward_sum[k] = sts[k]["episodes"], sts[k]["reward_sum"]
+                mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, sts[k]["loss"], sts[k]["grad_norm"])
         while t <= s0.max_steps:
             nxt = min(min((t + m - 1) // m * m for m in bounds), s0.max_steps)
             want_stats = nxt % s0.log_freq == 0 and any(s.verbose for s in solvers)

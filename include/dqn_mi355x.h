@@ -519,6 +519,32 @@ int dqn_group_train_steps(dqn_group_t* g, int n, float* loss_or_null /* [n_membe
 int dqn_group_info(dqn_group_t* g, dqn_group_info_t* out);
 int dqn_group_destroy(dqn_group_t* g);
 
+/* ---- grouped acting: the device environment loop of all K members, ONE launch per vector step (tiny_act.hip).
+ * A member of a group is a Dense-only network whose parameters fit in LDS, so one vector step of its env loop -- policy forward on its n copies, Q, argmax,
+ * exploration, act!, add_exp! with its sum-tree ancestors, the ring rows and the next policy input -- runs as ONE workgroup.  dqn_rollout_many steps every member with
+ * one launch of K workgroups per vector step, one group train launch at t % train_freq == 0 and one target-sync launch at t % target_update_freq == 0.
+ *
+ * THE LAW.  After dqn_rollout_many(g, n, cfgs, xs, out) every member k is bit for bit what dqn_rollout_explore(member_k, n, &cfgs[k], xs ? xs[k] : NULL, &out[k])
+ * leaves: environment state and episode statistics, pol_x / pol_q / pol_a (what dqn_envs_peek returns), replay rows, metadata, priorities and tree, the counters,
+ * and -- after the interleaved train steps and target syncs -- parameters, Adam state, last loss / grad norm / indices / TD, and the bytes of a checkpoint.
+ *
+ * Vector-step cadence only.  Members may differ in everything an engine or an env set is created with (network, n_envs, env kind, obs_dtype, seed, eps schedule,
+ * table); train_freq, target_update_freq and t0 must be equal across cfgs and cadence_env_steps must be 0.  explore is NULL, or K pointers of which a NULL entry
+ * means that member's linear law.  The standalone loop trains a member only once its replay holds a batch and a group launch cannot skip a member: for every due
+ * step of the call the host decides beforehand whether each member would train, and members that disagree are refused.
+ *
+ * STREAM ORDER and ERRORS are the group's (above): events in from every member's stream, events out on the error paths too, one synchronise at the end; a member's
+ * device-side assertion is reported with its index, the other members' steps stand.  The flag is consumed by the call whether or not it trained.
+ *
+ * REFUSED before anything is enqueued, naming the member and the reason: a null handle, n_steps < 1, NULL cfgs, t0 < 1, unequal train_freq / target_update_freq /
+ * t0, cadence_env_steps != 0, an invalid table (dqn_rollout_explore's words), members that disagree on a due train step, and a member that does not take the
+ * single-workgroup acting step: no device environments, recurrent, a layer that is not Dense, parameters x n_envs > 262144, or more than 144 KB of LDS for its
+ * parameters, the policy input, the activations of its n copies and the step's tail.  The per-call work does not grow with K in launches or copies: one H2D copy of
+ * the K RolloutDev records, one of all tables, one launch that folds statistics, scalars and flags, one D2H copy -- and the 2 K event operations. */
+int dqn_rollout_many(dqn_group_t* g, int n_vector_steps, const dqn_rollout_cfg* cfgs /* [K] */, const dqn_exploration* const* explore /* NULL or [K] with NULL entries */,
+                     dqn_rollout_stats* out /* NULL or [K] */);
+int dqn_rollout_many_info(dqn_group_t* g, int* launches_per_vector_step /* 1 */, unsigned* max_lds_bytes /* the acting launch's dynamic LDS: the largest member's */);
+
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
