@@ -190,6 +190,7 @@ PROTOS = {
     "rollout": [_vp, C.c_int, _P(RolloutCfg), _P(RolloutStats)],
     "rollout_explore": [_vp, C.c_int, _P(RolloutCfg), _P(Exploration), _P(RolloutStats)],
     "envs_peek": [_vp, _f32p, _i32p, _f32p, _u8p],
+    "envs_peek_q": [_vp, _f32p, _i32p],
     "envs_info": [_vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32)],
     "evaluate": [_vp, C.c_int, C.c_int, C.c_uint64, _f64p, _f64p],
     "replay_export": [_vp, C.c_int64, C.c_int64, _vp, _vp, _i32p, _f32p, _u8p, _f32p],
@@ -578,6 +579,16 @@ class Handle:
         a, r, d = np.empty(n, np.int32), np.empty(n, np.float32), np.empty(n, np.uint8)
         self._check(self.f["envs_peek"](self._h, _ptr(obs, _f32p), _ptr(a, _i32p), _ptr(r, _f32p), _ptr(d, _u8p)))
         return obs, a, r, d
+
+    def envs_peek_q(self):
+        """(q[n_envs][n_actions], greedy[n_envs]) of the last vector step's acting forward, read-only: nothing is launched.  Raises before the set's first vector step
+        and after another forward used the policy workspace (forward, greedy_action, evaluate)."""
+        if "envs_peek_q" not in self.f:
+            raise DQNError("this library does not export envs_peek_q")
+        n = getattr(self, "n_envs", 0)      # (no env set yet: the library refuses)
+        q, a = np.empty((n, self.nA), np.float32), np.empty(n, np.int32)
+        self._check(self.f["envs_peek_q"](self._h, _ptr(q, _f32p), _ptr(a, _i32p)))
+        return q, a
 
     # ---- checkpoint / resume (product only)
     def replay_export(self, first=0, n=None):

@@ -82,6 +82,7 @@ struct dqn_engine {
     EnvDev env{}; bool has_envs = false; unsigned char* env_images = nullptr;
     float* env_tab = nullptr; unsigned char* env_term = nullptr;      // a tabular env set's tables (cumulative rows, rewards, feature rows) and terminal flags
     int pol_n = 0; float *pol_obs = nullptr, *pol_x = nullptr, *pol_act[DQN_MAX_LAYERS] = {}, *pol_q = nullptr; int* pol_a = nullptr;
+    bool env_q_valid = false;      // pol_q / pol_a hold the last vector step of the training env set (dqn_envs_peek_q): set by the rollouts, cleared by whatever else writes or frees them
     // the train-step graphs, one per StepKey in use (linear lookup: a handful of entries); with a communicator the step is cut in two around the exchange
     struct StepGraph { StepKey key; hipGraphExec_t g; }; std::vector<StepGraph> graphs;
     StepKey cur;      // the variant enqueue_step is enqueuing, for the program's closures (default outside enqueue_step)

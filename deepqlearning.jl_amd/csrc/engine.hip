@@ -524,7 +524,7 @@ void drop_act(dqn_engine* e, dqn_engine::ActProg& a) {
 static void free_policy_ws(dqn_engine* e) {
     hipFree(e->pol_obs); hipFree(e->pol_x); hipFree(e->pol_q); hipFree(e->pol_a);
     for (int i = 0; i < e->nl; i++) { if (!is_do(e->L[i].kind)) hipFree(e->pol_act[i]); e->pol_act[i] = nullptr; }      // (a Dropout layer's is its producer's)
-    e->pol_obs = e->pol_x = e->pol_q = nullptr; e->pol_a = nullptr; e->pol_n = 0;
+    e->pol_obs = e->pol_x = e->pol_q = nullptr; e->pol_a = nullptr; e->pol_n = 0; e->env_q_valid = false;
 }
 extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     if (!e) return 0;
@@ -1264,6 +1264,7 @@ static int policy_forward(dqn_engine* e, int which, const float* obs, int n) {
     }
     if (e->hp.recurrence) e->pol_flip ^= 1;
     const int lq = e->hp.dueling ? e->last_adv : e->last_base;
+    e->env_q_valid = false;      // pol_q / pol_a are this forward's now, not the env set's last vector step (dqn_envs_peek_q)
     launch_q_columns(e->stream, n, e->nA, e->hp.dueling, e->hp.dueling ? e->pol_act[e->last_val] : nullptr, e->pol_act[lq], e->pol_q, e->pol_a);
     return 0;
 }

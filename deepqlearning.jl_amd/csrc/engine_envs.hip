@@ -1,5 +1,5 @@
 // engine_envs.hip -- C ABI of the device-resident environments: dqn_envs_create / dqn_rollout / dqn_evaluate /
-// dqn_envs_peek; kernels in envs.hip.
+// dqn_envs_peek / dqn_envs_peek_q; kernels in envs.hip.
 #include <cmath>
 #include "engine.h"
 
@@ -17,7 +17,7 @@ void free_envs(dqn_engine* e) {
     hipFree(e->env_images); hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(e->roll);
     hipFree(e->env_tab); hipFree(e->env_term); hipFree(V.tb_s); hipFree(V.tb_o); hipFree(V.tb_oprev); e->env_tab = nullptr; e->env_term = nullptr;
     hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
-    e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false;
+    e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false; e->env_q_valid = false;
     free_env_arrays(e->eval_env); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
     drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
     hipFree(e->xtab); e->xtab = nullptr; e->xtab_cap = 0;
@@ -344,6 +344,7 @@ static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, c
         }
         if (tu > 0 && (envc ? (t * n) / tu != ((t - 1) * n) / tu : t % tu == 0)) { if (dqn_sync_target(e)) return -1; }
     }
+    if (n_steps > 0) e->env_q_valid = true;      // pol_q / pol_a: the last vector step's (dqn_envs_peek_q)
     launch_recur_reset(e->stream, V.pending, n, recur_state(e, false));      // resetstate!(policy) of the copies whose episode ended in the last step, then their env reset
     launch_env_reset_pending(e->stream, V, e->roll, 0);
     std::vector<long long> fe(n); std::vector<double> fr(n);
@@ -426,6 +427,7 @@ extern "C" int dqn_rollout_explore(dqn_engine_t* e, int n_steps, const dqn_rollo
         if (cfg->train_freq > 0 && t % cfg->train_freq == 0 && e->size >= e->B) { if (run_step(e, true)) return -1; trained++; }     // :134-139
         if (cfg->target_update_freq > 0 && t % cfg->target_update_freq == 0) { if (dqn_sync_target(e)) return -1; }                // :142-145
     }
+    if (n_steps > 0) e->env_q_valid = true;      // pol_q / pol_a: the last vector step's (dqn_envs_peek_q)
     launch_env_reset_pending(e->stream, V, e->roll, 0);      // episode bookkeeping of the last step (src/solver.jl:99-132)
     if (out) {
         std::vector<long long> fe(n); std::vector<double> fr(n);
@@ -468,6 +470,7 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
     }
     if (W.seed != seed || W.max_episode_length != max_episode_length) { W.seed = seed; W.max_episode_length = max_episode_length; drop_act(e, e->evalp); }   // baked into the program
     if (build_act_program(e, e->evalp, W, e->eval_roll)) return -1;
+    e->env_q_valid = false;      // the evaluation copies' forward writes pol_q / pol_a (dqn_envs_peek_q is refused until the training set steps again)
     RolloutDev h; memset(&h, 0, sizeof h);                                   // t = 0; eps schedule (0, 0, 1): always greedy
     h.eps_steps = 1.0f;
     { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
@@ -517,6 +520,18 @@ extern "C" int dqn_envs_peek(dqn_engine_t* e, float* obs, int32_t* actions, floa
     if (actions) HIPCHK(hipMemcpy(actions, V.actions, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (rewards) HIPCHK(hipMemcpy(rewards, V.rewards, (size_t)n * 4, hipMemcpyDeviceToHost));
     if (dones) HIPCHK(hipMemcpy(dones, V.dones, (size_t)n, hipMemcpyDeviceToHost));
+    return 0;
+}
+// read-only: what the acting forward of the training set's last vector step left in pol_q / pol_a.  Nothing is launched, nothing is rewritten
+extern "C" int dqn_envs_peek_q(dqn_engine_t* e, float* q, int32_t* greedy) { if (!e) return fail("null engine handle");
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
+    if (!e->env_q_valid) return fail("dqn_envs_peek_q: the env set has not taken a vector step since it was created, or the policy workspace was used since its last one "
+                                     "(dqn_forward, dqn_greedy_action, dqn_evaluate): call dqn_rollout first");
+    const int n = e->env.n;
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (q) HIPCHK(hipMemcpy(q, e->pol_q, (size_t)n * e->nA * 4, hipMemcpyDeviceToHost));
+    if (greedy) HIPCHK(hipMemcpy(greedy, e->pol_a, (size_t)n * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 

@@ -307,7 +307,7 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     for (int j = 0; j < n_steps && !rc; j++) {
         const long long t = c0.t0 + j;
         if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds); break; }
-        for (dqn_engine* e : g->members) { const int n = e->env.n; e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); }      // what dqn_rollout_explore keeps on the host
+        for (dqn_engine* e : g->members) { const int n = e->env.n; e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); e->env_q_valid = true; }      // what dqn_rollout_explore keeps on the host
         if (train_at[(size_t)j]) {      // :134-139, for all members in one launch
             if (launch_tiny_group(g->stream, g->args_dev, K, g->max_lds, 1)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the group train launch (hipFuncSetAttribute)", g->max_lds); break; }
             trained++;

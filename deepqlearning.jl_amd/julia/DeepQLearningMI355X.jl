@@ -638,6 +638,13 @@ function evaluate(e::Engine, n_eval, max_episode_length; seed = 0)              
     check(ccall((:dqn_evaluate, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, UInt64, Ref{Float64}, Ref{Float64}), e.h, n_eval, max_episode_length, seed, r, st))
     r[], st[]
 end
+# inspection: the Q columns (n_actions x n_envs) and the greedy actions (1-based) of the last vector step's acting forward; read-only, nothing is launched.  Throws before
+# the set's first vector step and after another forward used the policy workspace (a host-side action / value call, evaluate)
+function envs_peek_q(e::Engine, n_envs)
+    q = zeros(Float32, e.nA, n_envs); a = zeros(Int32, n_envs)
+    check(ccall((:dqn_envs_peek_q, LIB), Cint, (Ptr{Cvoid}, Ptr{Float32}, Ptr{Int32}), e.h, q, a))
+    q, a .+ Int32(1)
+end
 # ---- exploration on the device loop (dqn_exploration / dqn_rollout_explore): POMDPTools' EpsGreedyPolicy and SoftmaxPolicy with any schedule.  The schedule is
 # evaluated HERE, per vector step, and rounded to Float32; the device only reads the table.  A LinearDecaySchedule (or a constant eps) stays on dqn_rollout's own fp32
 # law, so existing trajectories do not move

@@ -435,6 +435,14 @@ int dqn_rollout_explore(dqn_engine_t* e, int n_vector_steps, const dqn_rollout_c
 int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length, uint64_t seed, double* avg_reward, double* avg_steps);
 /* inspection (parity tests): current observations float[n][C][H][W], last actions int32[n], last rewards float[n], last dones uint8[n] */
 int dqn_envs_peek(dqn_engine_t* e, float* obs, int32_t* actions, float* rewards, uint8_t* dones);
+/* inspection (parity tests): what the acting forward of the LAST vector step of the training env set computed, read-only -- the stream is synchronised and two buffers
+ * are copied; nothing is launched and nothing is rewritten (dqn_envs_peek re-observes the env states for its obs; this does not).  q[i] is the Q column of copy i's
+ * policy input at that step, after the dueling join ((v + a) - mean(a)); greedy[i] is its first-max argmax.  dqn_envs_peek's actions[i] is greedy[i] unless copy i
+ * explored.  Every schedule of the acting step writes them (the four-launch tail, the fused tail, the recurrent tail, the single-workgroup step of an engine group).
+ * Either pointer may be NULL.  Refused, with a message: no device environments; the set has not taken a vector step since it was created (dqn_rollout,
+ * dqn_rollout_explore or dqn_rollout_many with n_vector_steps >= 1); the policy workspace that holds the columns was used by another forward since that step
+ * (dqn_forward, dqn_greedy_action, dqn_evaluate, or a reallocation for more columns). */
+int dqn_envs_peek_q(dqn_engine_t* e, float* q /* [n_envs][n_actions] */, int32_t* greedy /* [n_envs] */);
 /* inspection (parity tests, which must know WHICH schedule they compared): n_envs of the training set; fused_tail = 1 when the acting step of that set runs its tail as one
  * launch (act_head.hip: reduce + heads + Q / argmax + eps-greedy + act! + add_exp!'s per-experience part), 0 for the general four-launch tail.  Builds the acting program
  * (as dqn_rollout would) if it does not exist yet. */
@@ -525,7 +533,8 @@ int dqn_group_destroy(dqn_group_t* g);
  * one launch of K workgroups per vector step, one group train launch at t % train_freq == 0 and one target-sync launch at t % target_update_freq == 0.
  *
  * THE LAW.  After dqn_rollout_many(g, n, cfgs, xs, out) every member k is bit for bit what dqn_rollout_explore(member_k, n, &cfgs[k], xs ? xs[k] : NULL, &out[k])
- * leaves: environment state and episode statistics, pol_x / pol_q / pol_a (what dqn_envs_peek returns), replay rows, metadata, priorities and tree, the counters,
+ * leaves: environment state and episode statistics (what dqn_envs_peek returns; its obs is re-observed from the env state, which the next policy input pol_x equals),
+ * the last step's Q columns and greedy actions pol_q / pol_a (what dqn_envs_peek_q returns), replay rows, metadata, priorities and tree, the counters,
  * and -- after the interleaved train steps and target syncs -- parameters, Adam state, last loss / grad norm / indices / TD, and the bytes of a checkpoint.
  *
  * Vector-step cadence only.  Members may differ in everything an engine or an env set is created with (network, n_envs, env kind, obs_dtype, seed, eps schedule,

@@ -1161,6 +1161,7 @@ typedef struct ref_envs {
     dqn_env_spec sp; int n, E, H, W; uint8_t* images;
     int8_t* tm_s; int32_t* tm_t; int32_t* gw_pos;
     int32_t* actions; float* rewards; uint8_t* dones; float* ep_reward; int32_t* ep_step; int64_t* fin_eps; double* fin_reward;
+    float* last_q; int32_t* last_greedy; int q_valid;      /* the acting step keeps its Q columns [n][nA] and greedy actions (ref_envs_peek_q) */
 } ref_envs;
 static uint32_t env_rand(uint64_t seed, uint64_t t, int env, uint32_t purpose) {
     uint32_t c[4] = {(uint32_t)t, (uint32_t)(t >> 32), (uint32_t)env, purpose};
@@ -1170,7 +1171,7 @@ static float u01(uint32_t r) { return (float)(r >> 8) * (1.0f / 16777216.0f); }
 static void envs_free(struct ref_envs* v) {
     if (!v) return;
     free(v->images); free(v->tm_s); free(v->tm_t); free(v->gw_pos); free(v->actions); free(v->rewards); free(v->dones); free(v->ep_reward); free(v->ep_step);
-    free(v->fin_eps); free(v->fin_reward); free(v);
+    free(v->fin_eps); free(v->fin_reward); free(v->last_q); free(v->last_greedy); free(v);
 }
 static void envs_reset_one(ref_envs* v, int i, uint64_t t) {
     v->ep_reward[i] = 0.0f; v->ep_step[i] = 0;      /* dones[] keeps the flags of the last act! (inspection) */
@@ -1207,6 +1208,7 @@ int ref_envs_create(ref_engine* e, const dqn_env_spec* sp) {
     } else { envs_free(v); FAIL("unknown environment kind"); }
     v->actions = (int32_t*)calloc(n, 4); v->rewards = (float*)calloc(n, 4); v->dones = (uint8_t*)calloc(n, 1); v->ep_reward = (float*)calloc(n, 4);
     v->ep_step = (int32_t*)calloc(n, 4); v->fin_eps = (int64_t*)calloc(n, 8); v->fin_reward = (double*)calloc(n, 8);
+    v->last_q = (float*)calloc((size_t)n * e->nA, 4); v->last_greedy = (int32_t*)calloc(n, 4); v->q_valid = 0;
     e->envs = v;
     return ref_envs_reset(e);
 }
@@ -1238,7 +1240,7 @@ int ref_rollout(ref_engine* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_roll
     ref_envs* v = e->envs; if (!v) FAIL("no environments");
     if (cfg->t0 < 1) FAIL("t0 counts from 1");
     int n = v->n, E = v->E, u8 = e->hp.obs_dtype == DQN_OBS_U8; int64_t trained = 0; float loss = 0.0f, gn = 0.0f;
-    float* obs = (float*)malloc((size_t)n * E * 4); int32_t* greedy = (int32_t*)malloc((size_t)n * 4); float* td0 = (float*)malloc((size_t)n * 4);
+    float* obs = (float*)malloc((size_t)n * E * 4); int32_t* greedy = v->last_greedy; float* td0 = (float*)malloc((size_t)n * 4);
     size_t rowb = (size_t)E * (u8 ? 1 : 4); uint8_t* srow = (uint8_t*)malloc(rowb * n); uint8_t* sprow = (uint8_t*)malloc(rowb * n);
     for (int k = 0; k < n_steps; k++) {
         int64_t t = cfg->t0 + k;
@@ -1246,7 +1248,9 @@ int ref_rollout(ref_engine* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_roll
         if (!(cfg->eps_steps > 0.0f) || eps < cfg->eps_stop) eps = cfg->eps_stop;
         for (int i = 0; i < n; i++) envs_observe(v, i, obs + (size_t)i * E, u8 ? srow + i * rowb : NULL);
         if (!u8) memcpy(srow, obs, rowb * n);
-        ref_greedy_action(e, obs, n, greedy);
+        ref_forward(e, DQN_NET_ONLINE, obs, n, v->last_q);      /* ref_greedy_action's two lines, with the Q columns kept */
+        for (int b = 0; b < n; b++) greedy[b] = argmax_first(v->last_q + (size_t)b * e->nA, e->nA);
+        v->q_valid = 1;
         for (int i = 0; i < n; i++) {
             int a = greedy[i];
             if (u01(env_rand(v->sp.seed, (uint64_t)t, i, 1u)) < eps) a = (int)(env_rand(v->sp.seed, (uint64_t)t, i, 2u) % (uint32_t)e->nA);
@@ -1269,7 +1273,7 @@ int ref_rollout(ref_engine* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_roll
     }
     if (out) { out->episodes = 0; out->reward_sum = 0.0; out->train_steps = trained; out->last_loss = loss; out->last_grad_norm = gn;
                for (int i = 0; i < n; i++) { out->episodes += v->fin_eps[i]; out->reward_sum += v->fin_reward[i]; } }
-    free(obs); free(greedy); free(td0); free(srow); free(sprow); return 0;
+    free(obs); free(td0); free(srow); free(sprow); return 0;
 }
 int ref_envs_peek(ref_engine* e, float* obs, int32_t* actions, float* rewards, uint8_t* dones) {
     ref_envs* v = e->envs; if (!v) FAIL("no environments");
@@ -1279,12 +1283,21 @@ int ref_envs_peek(ref_engine* e, float* obs, int32_t* actions, float* rewards, u
     if (dones) memcpy(dones, v->dones, (size_t)v->n);
     return 0;
 }
+/* the Q columns [n][nA] and greedy actions of the last vector step; refused where dqn_envs_peek_q is: before the set's first vector step and after an evaluation */
+int ref_envs_peek_q(ref_engine* e, float* q, int32_t* greedy) {
+    ref_envs* v = e->envs; if (!v) FAIL("no environments");
+    if (!v->q_valid) FAIL("ref_envs_peek_q: the env set has not taken a vector step since it was created (or an evaluation ran since its last one)");
+    if (q) memcpy(q, v->last_q, (size_t)v->n * e->nA * 4);
+    if (greedy) memcpy(greedy, v->last_greedy, (size_t)v->n * 4);
+    return 0;
+}
 
 /* basic_evaluation (src/evaluation_policy.jl:17-42): n_eval fresh copies of the MDP of ref_envs_create, one greedy episode each,
  * while !done && step <= max_episode_length; r_tot accumulates in Float64.  Same Philox draws as dqn_evaluate (seed, t from 1). */
 int ref_evaluate(ref_engine* e, int n_eval, int max_episode_length, uint64_t seed, double* avg_reward, double* avg_steps) {
     ref_envs* tr = e->envs; if (!tr) FAIL("no environments");
     ref_envs v = *tr; int n = n_eval, E = tr->E;
+    tr->q_valid = 0;      /* dqn_evaluate's forward takes the policy workspace: the product refuses dqn_envs_peek_q after it */
     v.n = n; v.sp.seed = seed;
     v.tm_s = (int8_t*)calloc((size_t)n * 4, 1); v.tm_t = (int32_t*)calloc(n, 4); v.gw_pos = (int32_t*)calloc((size_t)n * 2, 4);
     v.actions = (int32_t*)calloc(n, 4); v.rewards = (float*)calloc(n, 4); v.dones = (uint8_t*)calloc(n, 1); v.ep_reward = (float*)calloc(n, 4);

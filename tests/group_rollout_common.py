@@ -86,8 +86,8 @@ def build(spec, factory, default_plan, envs, env_seed=17, **factory_kw):
 
 
 def observables(h, stats=None, td=True, trained=True):
-    """everything THE LAW names, as a flat dict of arrays: the train step's observables and checkpoint() field by field (engine_group_common), what dqn_envs_peek returns,
-    the replay size, and the call's statistics"""
+    """everything THE LAW names, as a flat dict of arrays: the train step's observables and checkpoint() field by field (engine_group_common), what dqn_envs_peek and
+    dqn_envs_peek_q return, the replay size, and the call's statistics.  The engine has taken a vector step (dqn_envs_peek_q is refused before the first)"""
     if trained:
         out = step_observables(h, td=td)
     else:      # nothing trained yet: the last-step getters have nothing to show
@@ -96,6 +96,7 @@ def observables(h, stats=None, td=True, trained=True):
         out.update({"counters." + k: np.asarray(x) for k, x in h.get_counters().items()})
         out.update({"ck." + k: np.asarray(x) for k, x in h.checkpoint().items()})
     out.update({"peek." + k: x for k, x in zip(("obs", "actions", "rewards", "dones"), h.envs_peek())})
+    out.update({"peekq." + k: x for k, x in zip(("q", "greedy"), h.envs_peek_q())})      # the last vector step's Q columns and greedy actions: pol_q / pol_a
     out["replay_size"] = np.asarray(h.replay_size())
     if stats is not None:
         out.update({"stats." + k: np.asarray(x) for k, x in stats.items()})

@@ -281,6 +281,10 @@ class LockStep:
         if g is not None:
             st = g.rollout(1, t0=t, train_freq=self.tf, target_update_freq=self.tu, eps=self.eps, env_step_cadence=self.cadence)
             obs, a, r, d = g.envs_peek()
+            q, gr = g.envs_peek_q()      # what the recurrent tail left in pol_q / pol_a: the shadow's greedy actions, explored copies included, and the first-max argmax of q
+            np.testing.assert_array_equal(gr, np.argmax(q, axis=1), err_msg=f"greedy vs the argmax of q at step {t}")
+            if greedy is not None:
+                np.testing.assert_array_equal(gr, greedy, err_msg=f"greedy actions at step {t}")
         else:
             st, a = None, np.array([explore(self.seed, t, i, (1.0, 1.0, 1.0), 4) for i in range(n)], np.int32)
         want_a = np.array([explore(self.seed, t, i, self.eps, 4) for i in range(n)], object)

@@ -241,6 +241,10 @@ class TabLockStep:
         if g is not None:
             st = g.rollout(1, t0=t, train_freq=self.tf, target_update_freq=self.tu, eps=self.eps)
             obs, a, r, d = g.envs_peek()
+            q, gr = g.envs_peek_q()      # the step's own Q columns and greedy actions: the shadow's, explored copies included
+            np.testing.assert_array_equal(gr, np.argmax(q, axis=1), err_msg=f"greedy vs the argmax of q at step {t}")
+            if greedy is not None:
+                np.testing.assert_array_equal(gr, greedy, err_msg=f"greedy actions at step {t}")
         else:
             a = np.array([explore(self.seed, t, i, (1.0, 1.0, 1.0), A) for i in range(n)], np.int32)
         want_a = [explore(self.seed, t, i, self.eps, A) for i in range(n)]

@@ -105,6 +105,9 @@ def test_null_handle_is_an_error_not_a_crash():
     for name in ("dqn_sync_target", "dqn_stream_sync", "dqn_envs_reset", "dqn_reset_state", "dqn_episode_commit"):
         f = getattr(lib, name); f.argtypes = [C.c_void_p]; f.restype = C.c_int
         assert f(None) == -1 and b"null engine handle" in lib.dqn_last_error()
+    lib.dqn_envs_peek_q.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]; lib.dqn_envs_peek_q.restype = C.c_int
+    assert lib.dqn_envs_peek_q(None, None, None) == -1 and b"null engine handle" in lib.dqn_last_error()
+    assert pkg._abi.PROTOS["envs_peek_q"] == [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int32)]      # (e, q[n_envs][n_actions], greedy[n_envs])
     lib.dqn_engine_destroy.argtypes = [C.c_void_p]; lib.dqn_engine_destroy.restype = C.c_int
     assert lib.dqn_engine_destroy(None) == 0
 

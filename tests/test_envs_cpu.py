@@ -166,10 +166,44 @@ def test_evaluate_matches_host_rollout():
         np.testing.assert_array_equal(x, y)
 
 
+def test_peek_q_is_the_forward_of_the_rows_the_step_acted_on():
+    """ref_envs_peek_q: the Q columns (after the dueling join) and first-max greedy actions of the last vector step = ref_forward / ref_greedy_action on the observations
+    peeked before it; the executed action is the greedy one unless the copy explored; refused before the first vector step, after a zero-step call and after an evaluation"""
+    net = EC.gridworld_mlp_dueling()
+    tw, hp = make_twin(net)
+    EC.same_params([tw], net)
+    n = 16
+    tw.envs_create(envs.SimpleGridWorld(n=n), max_episode_length=5, seed=21)
+    with pytest.raises(pkg._abi.DQNError, match="has not taken a vector step"):
+        tw.envs_peek_q()
+    tw.rollout(0, t0=1)
+    with pytest.raises(pkg._abi.DQNError, match="has not taken a vector step"):
+        tw.envs_peek_q()
+    explored = 0
+    for t in range(1, 9):
+        obs0 = tw.envs_peek()[0]
+        tw.rollout(1, t0=t, train_freq=0, target_update_freq=0, eps=(0.5, 0.5, 1.0))
+        q, greedy = tw.envs_peek_q()
+        assert q.shape == (n, 4) and q.dtype == np.float32 and greedy.dtype == np.int32
+        np.testing.assert_array_equal(q, tw.forward(obs0))
+        np.testing.assert_array_equal(greedy, tw.greedy_action(obs0))
+        np.testing.assert_array_equal(greedy, np.argmax(q, axis=1))
+        a = tw.envs_peek()[1]
+        explored += int((a != greedy).sum())
+    assert 0 < explored < 8 * n
+    tw.rollout(3, t0=9, train_freq=0, target_update_freq=0, eps=(0.0, 0.0, 1.0))
+    np.testing.assert_array_equal(tw.envs_peek()[1], tw.envs_peek_q()[1])      # eps = 0: the executed actions are the greedy ones
+    tw.evaluate(3, 4)
+    with pytest.raises(pkg._abi.DQNError, match="vector step"):
+        tw.envs_peek_q()
+
+
 def test_errors():
     net = EC.gridworld_mlp_dueling()
     tw, hp = make_twin(net)
     with pytest.raises(pkg._abi.DQNError):
         tw.rollout(1)
+    with pytest.raises(pkg._abi.DQNError, match="no environments"):
+        tw.envs_peek_q()
     with pytest.raises(pkg._abi.DQNError):
         tw.envs_create(envs.TestMDP((14, 12), 4, 6, n=2))               # image MDP against a 2-input network

@@ -35,8 +35,21 @@ def make_pair(pkg, net, B, cap, plan_edit=None, **kw):
     return pkg.Engine(layers, hp, plan=plan), ref.Twin(layers, hp, plan=plan, threads=8), hp
 
 
+def peek_q(h):
+    """(q, greedy) of the last vector step's acting forward; None where the accessor is refused: before the set's first vector step and after an evaluation"""
+    try:
+        return h.envs_peek_q()
+    except ref.abi.DQNError as e:
+        assert "vector step" in str(e), e
+        return None
+
+
 def compare_state(g, t):
     for x, y in zip(g.envs_peek(), t.envs_peek()):
+        np.testing.assert_array_equal(x, y)
+    gq, tq = peek_q(g), peek_q(t)
+    assert (gq is None) == (tq is None), "the engine and the twin disagree on whether dqn_envs_peek_q is refused"
+    for x, y in zip(gq or (), tq or ()):      # the Q columns and greedy actions the last vector step computed, bit for bit
         np.testing.assert_array_equal(x, y)
     assert g.replay_size() == t.replay_size()
     np.testing.assert_array_equal(g.replay_priorities(), t.replay_priorities())

@@ -110,7 +110,8 @@ def test_every_ccall_names_a_declared_entry_point_with_the_right_arity():
     # and the data-path entry points are all bound
     bound = {n for n, _ in calls}
     for must in ("dqn_engine_create", "dqn_train_step", "dqn_replay_add", "dqn_replay_get_batch", "dqn_update_priorities", "dqn_forward", "dqn_sync_target",
-                 "dqn_get_params", "dqn_set_params", "dqn_train_step_drqn", "dqn_episode_add", "dqn_reset_state", "dqn_envs_create", "dqn_rollout", "dqn_evaluate"):
+                 "dqn_get_params", "dqn_set_params", "dqn_train_step_drqn", "dqn_episode_add", "dqn_reset_state", "dqn_envs_create", "dqn_rollout", "dqn_evaluate",
+                 "dqn_envs_peek_q"):
         assert must in bound, must
 
 
