@@ -34,7 +34,7 @@ struct LayerDev {
     int xu8;                           // this layer reads the observation arena and the arena holds BYTES (u8 replay): value = byte / 255f0, converted in the tile load
     int ph, pw;                        // Conv: symmetric zero padding per axis (dqn_layer_desc n_in / n_out slots); ih, iw stay the UNPADDED map, oh = (ih + 2 ph - kh) / sh + 1
     int src2;                          // DQN_LAYER_SKIPADD / _MAP: the block's entry P, the producer the block's first inner layer reads (src = the last inner layer K); -1 on every other layer
-    int dh, dw, groups;                // DQN_LAYER_CONV_DG: dilation per axis and the group count (conv_dg.hip); cin, cout stay the FULL channel counts, K = (cin / groups) * kh * kw.  0 on every other layer
+    int dh, dw, groups;                // DQN_LAYER_CONV_DG: dilation per axis and the group count (conv_own.hip); cin, cout stay the FULL channel counts, K = (cin / groups) * kh * kw.  0 on every other layer
 };
 
 // a layer with a hidden state carried over the T time steps of a sequence (Flux.Recur): Gx = Wi*x over all T*B columns, then the cell's recurrence
@@ -53,7 +53,7 @@ static inline bool is_global_pool(const LayerDev& L) { return is_adaptive_pool(L
 // EXTERNAL offsets are eb_off, then ew_off = eb_off + c (engine.hip).  Launched alone on its level, as pools and LayerNorm are
 static inline __host__ __device__ bool is_gn(int kind) { return kind == DQN_LAYER_GROUPNORM; }
 static inline float gn_eps(const LayerDev& L) { if (L.kw == 0) return 1e-5f; float f; memcpy(&f, &L.kw, sizeof f); return f; }
-// Flux Conv(...; dilation, groups) / DepthwiseConv (conv_dg.hip): a kind of its own, launched alone on its level as the padded Conv is; the pad-0 GEMM bodies never see it.
+// Flux Conv(...; dilation, groups) / DepthwiseConv (conv_own.hip): a kind of its own, launched alone on its level as the padded Conv is; the pad-0 GEMM bodies never see it.
 // is_conv_kind: what the plan rules say of "a conv" (dx_kc counts RAW taps, dw_kc counts positions * samples) holds for both kinds
 static inline __host__ __device__ bool is_cdg(int kind) { return kind == DQN_LAYER_CONV_DG; }
 static inline __host__ __device__ bool is_conv_kind(int kind) { return kind == DQN_LAYER_CONV || kind == DQN_LAYER_CONV_DG; }
@@ -82,10 +82,10 @@ static inline double do_p(const LayerDev& L) { const uint64_t b = (uint64_t)(uin
 // input-gradient launch, which therefore runs with the IDENTITY epilogue (src_act, engine_program.hip)
 // DQN_LAYER_SKIPADD_MAP: the same join on a (c, h, w) map, n = c * h * w features in the same layout -- the block's inner layers are padded Convs, its entry a Conv, a pool or
 // another map join; cout, ih, iw, oh, ow carry the map for the layer behind it.  Where K has no activation the forward add runs in the epilogue of K's launch and the
-// entry's + dY in the epilogue of F's input-gradient launch (conv_pad.hip; skip_fused, engine.h); every rule stated for "a join" holds for both kinds
+// entry's + dY in the epilogue of F's input-gradient launch (conv_own.hip; skip_fused, engine.h); every rule stated for "a join" holds for both kinds
 static inline __host__ __device__ bool is_skip(int kind) { return kind == DQN_LAYER_SKIPADD || kind == DQN_LAYER_SKIPADD_MAP; }
 static inline __host__ __device__ bool is_skip_map(int kind) { return kind == DQN_LAYER_SKIPADD_MAP; }
-// a Conv with pad != 0 (conv_pad.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
+// a Conv with pad != 0 (conv_own.hip): launched alone, as pools are -- the pad-0 kernels address their input separably as koff(k) + xb(pos) and never see one
 static inline __host__ __device__ bool is_padded(const LayerDev& L) { return L.kind == DQN_LAYER_CONV && (L.ph != 0 || L.pw != 0); }
 // ---- what the engine's host code knows about a layer kind, ONE row per kind ("own-level kinds"), keyed on the layer: a padded Conv is a row of its own.
 // The own-level rows come first, in the order in which the single-GPU refusals name them (refuse_replicas, engine.hip)
@@ -1186,17 +1186,14 @@ void launch_actl_fwd(hipStream_t st, int n, int act, const float* X, int ldx, in
 void launch_actl_bwd(hipStream_t st, int n, int act, const float* dY, const float* X, const float* Y, int ld, int B, float* dX, int act_src);
 void launch_gpool_fwd(hipStream_t st, const LayerDev& L, const float* X, int ldx, int col0, int ncols, float* Y /*[c][ncols]*/);
 void launch_gpool_bwd(hipStream_t st, const LayerDev& L, const float* dY /*[c][B]*/, const float* X /* the pool's input */, int ld /* of X */, int B, float* dX /*[in_feat][B]*/, int act_src);
-// conv_pad.hip: a padded Conv's forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act');
+// conv_own.hip: the forward (all plan chunks in the one launch), dW / db (into the gradient block or its S plan slabs) and dX (+ the producing layer's act') of a padded Conv
+// and of DQN_LAYER_CONV_DG (dilation, groups, depthwise), which L.kind tells apart;
 // mf = hp.use_mfma (MFMA tiles where the shape allows, the same bits either way); xu8: X is the byte arena of a u8 replay
-// R (or null): the residual operand of a map block's fused join, [out_feat][ldr] read on the columns rcol0 .. rcol0 + ncols: Y = act(tot + bias) + R
-void launch_cpad_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8, const float* R = nullptr, int ldr = 0, int rcol0 = 0);
-void launch_cpad_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
-// dY (or null): the addend of a map block's fused entry, [in_feat][B]: out = dact(acc + dY, ysrc, act_src).  May be the buffer dpre points at (single inner layer): both are read only
-void launch_cpad_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf, const float* dY = nullptr);
-// conv_dg.hip: DQN_LAYER_CONV_DG (dilation, groups, depthwise); the arguments of the padded conv's launchers, without the residual operands
-void launch_cdg_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8);
-void launch_cdg_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
-void launch_cdg_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf);
+// R (or null; padded Conv only): the residual operand of a map block's fused join, [out_feat][ldr] read on the columns rcol0 .. rcol0 + ncols: Y = act(tot + bias) + R
+void launch_conv_own_fwd(hipStream_t st, const LayerDev& L, const float* P, const void* X, int ldx, int col0, int ncols, float* Y /*[out_feat][ncols]*/, int mf, int xu8, const float* R = nullptr, int ldr = 0, int rcol0 = 0);
+void launch_conv_own_dw(hipStream_t st, const LayerDev& L, const void* X, int ldx, const float* dpre, int B, float* dst, int mf, int xu8);
+// dY (or null; padded Conv only): the addend of a map block's fused entry, [in_feat][B]: out = dact(acc + dY, ysrc, act_src).  May be the buffer dpre points at (single inner layer): both are read only
+void launch_conv_own_dx(hipStream_t st, const LayerDev& L, const float* P, const float* dpre, int B, float* out /*[in_feat][B]*/, const float* ysrc, int ldy, int act_src, int mf, const float* dY = nullptr);
 bool mfma_fwd_ok(const LayerDev& L, int ncols);
 bool mfma_dw_ok(const LayerDev& L, int B);
 bool mfma_dx_ok(const LayerDev& L, int B, int ldy);

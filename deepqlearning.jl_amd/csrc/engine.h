@@ -34,7 +34,7 @@ struct EngineOpts {
     int no_red_head = 0;          // DQN_NO_RED_HEAD: keep k_reduce_multi + k_head_td where the fused reduce + head launch (red_head.hip) would apply (A/B, both schedules under test)
     int no_pregather = 0;         // DQN_NO_PREGATHER: dqn_train_steps keeps the gather launch in every step (A/B)
     int gru_stepwise = 0;         // DQN_GRU_STEPWISE: GRU layers take the per-step recurrence / BPTT launches where the whole-sequence kernels would apply (both schedules under test)
-    int no_skip_fuse = 0;         // DQN_NO_SKIP_FUSE: a convolutional skip block keeps the join's launches of its own (skip.hip) where the residual epilogues of conv_pad.hip would apply (both schedules under test: the same bits)
+    int no_skip_fuse = 0;         // DQN_NO_SKIP_FUSE: a convolutional skip block keeps the join's launches of its own (skip.hip) where the residual epilogues of conv_own.hip would apply (both schedules under test: the same bits)
     int rnn_stepwise = 0;         // DQN_RNN_STEPWISE: RNN layers take the per-step recurrence / BPTT launches where the whole-sequence kernels would apply (both schedules under test)
     int force_allreduce = 0, dp_allreduce = 0, dp_overlap = -1 /* -1: decided from world size and bytes (engine_program.hip) */, dp_no_one_graph = 0;      // DQN_FORCE_ALLREDUCE / DQN_DP_ALLREDUCE / DQN_DP_OVERLAP / DQN_DP_NO_ONE_GRAPH
     // timing probes (wrong numbers, right schedule) and stamps
@@ -169,7 +169,7 @@ void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const f
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name, const float* X2 = nullptr, int ldx2 = 0);      // ... inside a profiling bracket
 // a skip block's join whose last inner layer has no activation: the join's backward is the identity, so dact[join] IS dact[src] (one buffer; engine.hip allocates, skip.hip)
 static inline bool skip_dact_alias(const dqn_engine* e, int i) { return is_skip(e->L[i].kind) && e->L[e->L[i].src].act == DQN_ACT_IDENTITY; }
-// a map block (DQN_LAYER_SKIPADD_MAP) whose entry add runs in the epilogue of its first inner layer's input-gradient launch (conv_pad.hip): every block, unless DQN_NO_SKIP_FUSE ...
+// a map block (DQN_LAYER_SKIPADD_MAP) whose entry add runs in the epilogue of its first inner layer's input-gradient launch (conv_own.hip): every block, unless DQN_NO_SKIP_FUSE ...
 static inline bool skip_fused_dx(const dqn_engine* e, int j) { return is_skip_map(e->L[j].kind) && !e->opt.no_skip_fuse; }
 // ... and whose forward add runs in the epilogue of its last inner layer's launch, which then writes the JOIN's activation: where that layer has no activation (its own
 // output is needed for nothing then: the join is its only consumer and the join's backward is the alias above).  The train step and the acting programs of emit_forward

@@ -90,7 +90,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
             if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);      // every kernel decodes the code on trust: an unknown one would train with some other law
             if (l.cin != c) return fail("layer %d: conv cin %d != incoming channels %d", i, l.cin, c);
-            // pad = (ph, pw) rides in the n_in / n_out slots (zero in every pad-0 descriptor): symmetric zero padding, at most kernel - 1 per axis (conv_pad.hip)
+            // pad = (ph, pw) rides in the n_in / n_out slots (zero in every pad-0 descriptor): symmetric zero padding, at most kernel - 1 per axis (conv_own.hip)
             l.ph = d[i].n_in; l.pw = d[i].n_out;
             if (l.ph < 0 || l.pw < 0) return fail("layer %d: Conv pad (%d, %d) must not be negative", i, l.ph, l.pw);
             if ((l.ph || l.pw) && (l.kh < 1 || l.kw < 1 || l.ph > l.kh - 1 || l.pw > l.kw - 1)) return fail("layer %d: Conv pad (%d, %d) is larger than kernel - 1 = (%d, %d): a window would lie in the padding alone", i, l.ph, l.pw, l.kh - 1, l.kw - 1);
@@ -99,7 +99,7 @@ static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, L
             if (l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
             l.ih = h; l.iw = w; l.oh = (h + 2 * l.ph - l.kh) / l.sh + 1; l.ow = (w + 2 * l.pw - l.kw) / l.sw + 1;      // trailing rows / columns of the extended map no window covers are dropped
             l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
-        } else if (is_cdg(l.kind)) {      // Flux Conv(...; dilation, groups) / DepthwiseConv (conv_dg.hip): a block of its own, so that no message of the Conv block above changes
+        } else if (is_cdg(l.kind)) {      // Flux Conv(...; dilation, groups) / DepthwiseConv (conv_own.hip): a block of its own, so that no message of the Conv block above changes
             l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
             if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: dilated / grouped Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
             // pad_h | pad_w << 16 rides in n_in, dh | dw << 8 | g << 16 in n_out (include/dqn_mi355x.h)
@@ -771,8 +771,7 @@ void launch_layer_fwd(hipStream_t st, const LayerDev& l, const float* P, const f
     else if (is_pool(l.kind)) launch_pool_fwd(st, l, X, ldx, col0, ncols, Y);
     else if (is_ln(l.kind)) launch_ln_fwd(st, l, P, X, ldx, col0, ncols, Y, ln_stat);
     else if (is_gn(l.kind)) { launch_gn_stat(st, l, X, ldx, col0, ncols, partials); launch_gn_norm(st, l, P, X, ldx, col0, ncols, Y, partials, ln_stat); }      // partials: >= gn_part_floats(l, ncols) floats
-    else if (is_padded(l)) launch_cpad_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);
-    else if (is_cdg(l.kind)) launch_cdg_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);      // a dilated / grouped conv (conv_dg.hip)
+    else if (is_padded(l) || is_cdg(l.kind)) launch_conv_own_fwd(st, l, P, X, ldx, col0, ncols, Y, use_mfma ? 1 : 0, xu8);      // a padded or a dilated / grouped conv (conv_own.hip)
     else if (!(use_mfma && launch_mfma_fwd(st, l, P, X, ldx, col0, ncols, Y, partials))) launch_valu_fwd(st, l, P, X, ldx, col0, ncols, Y, partials);
 }
 void fwd_layer(dqn_engine* e, const LayerDev& l, const float* P, const float* X, int ldx, int col0, int ncols, float* Y, const char* name, const float* X2, int ldx2) {

@@ -75,7 +75,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
         if (E.skip_last && last) continue;
         if (kind_traits(e->L[lv[0]]).own_level) {
             // a layer launched alone on its level (base chain only): one launch per pass it is active in, never grouped with a GEMM layer.  Per kind:
-            //   a pool (pool.hip; an adaptive / global pool whose resolved window is the whole map: pool_global.hip -- launch_layer_fwd decides), a padded conv (conv_pad.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
+            //   a pool (pool.hip; an adaptive / global pool whose resolved window is the whole map: pool_global.hip -- launch_layer_fwd decides), a padded or a dilated / grouped conv (conv_own.hip walks the plan chunks itself), a LayerNorm layer (layernorm.hip; the first pass keeps (mu, sigma) per column for the backward): every pass
             //   a GroupNorm layer (groupnorm.hip): every pass, TWO launches, "<pass>_gn<l>_stat" and "<pass>_gn<l>"; the first pass keeps (mu, r) per (group, column) for the backward
             //   the join of a skip block (skip.hip): every pass, y = (the last inner layer's stored output) + (the stored output of the block's entry, LayerDev::src2) on that pass's
             //     own activations -- where the entry or the last inner layer is a Dropout, its masked buffer in the train step's online pass and its producer's (the alias) elsewhere
@@ -83,7 +83,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
             //     must survive for the producer's backward -- and copies the s' columns behind them.  Every other pass emits NOTHING: the layer's activation pointer there is its producer's (engine.hip)
             //   a standalone activation layer (act_layer.hip): every pass, one element-wise launch on the producer's stored output of that pass
             //   a convolutional skip block whose last inner layer K has no activation (skip_fused_fwd): K's launch takes the entry's stored output of the pass as its residual
-            //     operand and writes act(tot + bias) + y_P straight into the JOIN's activation (conv_pad.hip), named "<pass>_conv<K>+skip<join>"; the join's level emits nothing.
+            //     operand and writes act(tot + bias) + y_P straight into the JOIN's activation (conv_own.hip), named "<pass>_conv<K>+skip<join>"; the join's level emits nothing.
             //     K's own activation buffer is then never written, and never read: its one consumer is the join, and the join's backward is the alias (skip_dact_alias)
             const int l = lv[0]; const LayerDev L = view(l); const bool dropout = is_do(L.kind), join = is_skip(L.kind);
             const int jn = is_padded(L) ? skip_join_of_last(e, l) : -1; const bool fuse_res = jn >= 0 && skip_fused_fwd(e, jn);
@@ -102,7 +102,7 @@ void emit_forward(dqn_engine* e, const Levels& levels, size_t li0, size_t li1, c
                 if (fuse_res) {
                     char nm[64]; snprintf(nm, sizeof nm, "%s_%s%d+skip%d", passes[pi].tag, kind_traits(L).tag, l, jn); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
                     const float* R = passes[pi].in[e->L[jn].src2]; float* Yj = passes[pi].out[jn];
-                    prog.push_back({name, [=](dqn_engine* en) { launch_cpad_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, Yj, mf ? 1 : 0, 0, R, q.ncols, 0); }});
+                    prog.push_back({name, [=](dqn_engine* en) { launch_conv_own_fwd(en->stream, L, q.P, q.X, q.ldx, q.col0, q.ncols, Yj, mf ? 1 : 0, 0, R, q.ncols, 0); }});
                     continue;
                 }
                 float* stat = pi == 0 ? stat0 : nullptr; const float* X2 = join ? passes[pi].in[L.src2] : nullptr;
@@ -329,7 +329,7 @@ int build_program(dqn_engine* e) {
         const int l0 = levels[0][0];
         int ldx2[2] = {ld0, ld0}, c02[2] = {0, B}, nc2[2] = {ncon, B};
         if (n_src == 1 && levels[0].size() == 1 && e->L[l0].src < 0 && !is_pool(e->L[l0].kind) /* pool.hip reads floats: a pool as the first layer keeps the fp32 arena */ && (e->L[l0].kind == DQN_LAYER_CONV || (!e->comm && !e->sim_world)) &&
-            (is_padded(e->L[l0]) /* conv_pad.hip converts bytes in its operand loads */ || is_cdg(e->L[l0].kind) /* and so does conv_dg.hip */ || (gemm_fwd_eligible(e->L[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; }
+            (is_padded(e->L[l0]) || is_cdg(e->L[l0].kind) /* conv_own.hip converts bytes in its operand loads */ || (gemm_fwd_eligible(e->L[l0], 2, ldx2, c02, nc2) && gemm_dw_eligible(e->L[l0], B, ld0)))) { e->arena_u8 = true; e->L[l0].xu8 = 1; }
     }
     // ---------------- small batches: the head level (forwards of both nets), the TD kernel and the head layers' dX run as ONE launch with a
     // workgroup per batch column (k_head_td); the heads' dW/db and the loss fold ride as tail tasks of the next backward launch
@@ -607,25 +607,20 @@ int build_program(dqn_engine* e) {
             // column sums dscale / dbias straight into the flat gradient, which the Adam launch reads like any bias range.  Always a dX: the layer has parameters and never reads the observation
             const float* P = e->p_on; const float* stat = ln_stat[l]; float *gs = e->grad + L.w_off, *gb = e->grad + L.b_off;
             e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_ln_bwd(en->stream, L, P, dpre, X, ncon, stat, ncon, B, out, act_src, gs, gb); }});
-        } else if (is_cdg(L.kind)) {
-            // a dilated / grouped conv (conv_dg.hip): the padded conv's two launches with its own kernels; never inside a skip block, so no fused entry
-            float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8; const float* P = e->p_on;
-            e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_cdg_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
-            if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cdg_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
         } else {
-            // a padded conv (conv_pad.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam), then -- unless the layer
-            // reads the observation -- dX with the producing layer's activation derivative
+            // a padded or a dilated / grouped conv (conv_own.hip): dW / db into the gradient block or its plan slabs (summed with the other layers' slabs before / inside Adam),
+            // then -- unless the layer reads the observation -- dX with the producing layer's activation derivative.  A dilated / grouped conv is never inside a skip block: no fused entry
             float* dst = dw_dst(L, dqn_nchunks(L.npos * B, L.dw_kc)); const int xu8 = L.xu8; const float* P = e->p_on;
-            e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_cpad_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
+            e->prog.push_back({pname(e, "dw", L, l), [=](dqn_engine* en) { launch_conv_own_dw(en->stream, L, X, ldx, dpre, B, dst, mf ? 1 : 0, xu8); }});
             // the FIRST inner layer of a convolutional skip block (fuse_entry): the launch adds the join's dY = dact[join] to its own sum and takes the entry's REAL activation
             // derivative after it -- dact[P] = (dF + dY) .* act_P'(y_P), what the bwd_entry launch (skip.hip) computes behind a raw dF; named "bwd_conv<F>+skip<join>".  With
             // one inner layer dpre IS dY (skip_dact_alias): read twice, written by nobody here
             if (wants_dx(l) && fuse_entry) {
                 char nm[64]; snprintf(nm, sizeof nm, "bwd_%s%d+skip%d", kind_traits(L).tag, l, jf); e->prog_names.push_back(nm); const char* name = e->prog_names.back().c_str();
                 const float* dYj = e->dact[jf]; const int act_p = e->L[L.src].act;
-                e->prog.push_back({name, [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_p, mf ? 1 : 0, dYj); }});
+                e->prog.push_back({name, [=](dqn_engine* en) { launch_conv_own_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_p, mf ? 1 : 0, dYj); }});
             }
-            else if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_cpad_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
+            else if (wants_dx(l)) e->prog.push_back({pname(e, "bwd", L, l), [=](dqn_engine* en) { launch_conv_own_dx(en->stream, L, P, dpre, B, out, Ysrc, ncon, act_src, mf ? 1 : 0); }});
         }
         return true;
     };

@@ -121,7 +121,7 @@ class Conv:
     or SamePad()), 0 <= pad <= (kernel - 1) * dilation.  Output map (H + 2 ph - (kh - 1) dh - 1) ÷ sh + 1 by (W + 2 pw - (kw - 1) dw - 1) ÷ sw + 1.  dilation: an int or
     (dh, dw) in this mirror's (H, W) order (Flux writes (W, H), as for stride).  groups = g divides cin and cout: output channels [j cout/g, (j+1) cout/g) read input channels
     [j cin/g, (j+1) cin/g); the weight is (kw, kh, cin ÷ g, cout) and the glorot fans are nfan of that size.  dilation = 1 and groups = 1 is the Conv it always was (layer
-    kind 1); anything else is layer kind 15 (csrc/conv_dg.hip): base chain only, not inside a SkipConnection."""
+    kind 1); anything else is layer kind 15 (csrc/conv_own.hip): base chain only, not inside a SkipConnection."""
     kind = "conv"
 
     def __init__(self, k, cin, cout, act=identity, stride=1, pad=0, dilation=1, groups=1):

@@ -156,7 +156,7 @@ typedef struct {
                                           block) and map (c, h, w) -> (c, h, w); P is a Conv (padded or not, any activation), a MaxPool / MeanPool or the join of a preceding
                                           SKIPADD_MAP block: never the observation, never a feature vector, never a SKIPADD join.  The join's output is a (c, h, w) map for whatever
                                           follows (a Conv, a pool, another block, or a Dense / recurrent layer on c * h * w features).  Where K has no activation the add runs in the
-                                          epilogue of K's forward launch, and the + dY of the entry in the epilogue of F's input-gradient launch (conv_pad.hip): the same bits as the
+                                          epilogue of K's forward launch, and the + dY of the entry in the epilogue of F's input-gradient launch (conv_own.hip): the same bits as the
                                           separate launches.  Base chain only, never the output layer, single GPU only */
 } dqn_layer_desc;
 

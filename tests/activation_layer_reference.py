@@ -207,7 +207,7 @@ def _table():
     t.append(_c("map_gmean_hardswish", lambda: nn.Chain(nn.Conv(3, 1, 4), nn.GlobalMeanPool(), A(HARDSWISH), nn.flattenbatch, nn.Dense(4, 4)), 16, obs=IMG, pscale=4.0, codes=(HARDSWISH,)))
     t.append(_c("vec_tanh_then_relu", lambda: nn.Chain(nn.Dense(6, 16), A(AR.TANH), A(AR.RELU), nn.Dense(16, 4)), 16,
                 plain=lambda: nn.Chain(nn.Dense(6, 16, nn.tanh), A(AR.RELU), nn.Dense(16, 4)), codes=(AR.TANH, AR.RELU)))
-    # 4. the post-add relu of ResNet-v1, the reason for the layer: on vectors (skip.hip) and on maps (conv_pad.hip epilogues)
+    # 4. the post-add relu of ResNet-v1, the reason for the layer: on vectors (skip.hip) and on maps (conv_own.hip epilogues)
     t.append(_c("postadd_vec", lambda: nn.Chain(nn.Dense(6, 16), _vblock(), A(AR.RELU), _vblock(), nn.Dense(16, 4)), 16, pscale=1.0, codes=(AR.RELU,)))
     t.append(_c("postadd_map", lambda: nn.Chain(nn.Conv(3, 1, 4), _mblock(), A(AR.RELU), _mblock(), nn.flattenbatch, nn.Dense(64, 4)), 16, obs=IMG, pscale=1.0, codes=(AR.RELU,)))
     # 5. dueling: the base chain ENDS in Activation(swish); the join's summed dX is the layer's dY

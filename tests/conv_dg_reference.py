@@ -1,5 +1,5 @@
 """fp64 reference of ONE batch_train! for networks with a dilated, grouped or depthwise convolution -- nn.Conv(...; dilation, groups), nn.DepthwiseConv (TEST INFRASTRUCTURE: layer
-kind 15, csrc/conv_dg.hip) --, feed-forward (src/solver.jl:191-236) and recurrent (src/solver.jl:239-287), over the package's nn descriptors.
+kind 15, csrc/conv_own.hip) --, feed-forward (src/solver.jl:191-236) and recurrent (src/solver.jl:239-287), over the package's nn descriptors.
 
 The law of the layer (Flux 0.14 over NNlib, recalled): output channel n of group j = n ÷ (cout/g) reads input channels [j cin/g, (j + 1) cin/g); tap (ky, kx) of the FLIPPED
 kernel reads iy = oy sh + ky dh - ph, ix = ox sw + kx dw - pw of the zero-extended map.
@@ -192,7 +192,7 @@ def contract_grads(net, g1):
     return g
 
 
-# ------------------------------------------------------------------ the case table: 6x6 .. 9x9 maps, the smallest shapes at which the index arithmetic of conv_dg.hip can go wrong
+# ------------------------------------------------------------------ the case table: 6x6 .. 9x9 maps, the smallest shapes at which the index arithmetic of conv_own.hip can go wrong
 def case(name, mk, B, obs, nA=4, dueling=False, u8=0, T=0, seed=1, pscale=2.0, wrong=()):
     """wrong: the wrong engines that apply to the case (each must land >= 100 tolerances off)"""
     return types.SimpleNamespace(name=name, mk=mk, B=B, obs=tuple(obs), nA=nA, dueling=dueling, dq=1, prio=0 if T else 1, u8=u8, mfma=1, T=T, seed=seed, gamma=0.95, pscale=pscale,

@@ -22,7 +22,7 @@ def extended(c, net, D):
     return layer_descs(net, pad=False), view, ext(D["s"]), ext(D["sp"])
 
 
-# ------------------------------------------------------------------ the table: the smallest shapes at which the index math of conv_pad.hip / the program can go wrong
+# ------------------------------------------------------------------ the table: the smallest shapes at which the index math of conv_own.hip / the program can go wrong
 # seeds: found with find_seed on the CPU, with the reference alone; fixed here
 SEEDS = {'same3': 1, 'all_border': 1, 'rect': 1, 'one_axis': 2, 'stride2': 1, 'aniso': 1, 'interior': 683, 'interior_tanh': 1, 'stack_same': 1, 'pool_after': 1, 'pool_before': 1, 'dueling_u8': 13}
 

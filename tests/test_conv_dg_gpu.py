@@ -1,5 +1,5 @@
 """GPU: train steps, policy forward, device loop, checkpoint, solver round trip and refusals of networks with a dilated, grouped or depthwise convolution (layer kind 15,
-csrc/conv_dg.hip), all through the C ABI, against the two-legged fp64 reference of conv_dg_reference.py.  Every case of its table runs STEPS train steps on given indices
+csrc/conv_own.hip), all through the C ABI, against the two-legged fp64 reference of conv_dg_reference.py.  Every case of its table runs STEPS train steps on given indices
 under the per-step checks of the feed-forward edge tests (Q on s and s', target Q, greedy indices exactly, y, td, loss, per-block gradients, grad_norm, parameters after fp64
 Adam, priorities; tolerances are the project's existing constants, unchanged; the margins are asserted on every step), then use_graph 0 against 1, use_mfma 0 against 1 and a
 second identical run, bit for bit, and the launch names.

@@ -1,4 +1,4 @@
-"""GPU: train steps, policy forward, device loop and refusals of networks with a PADDED convolution (csrc/conv_pad.hip) against the two-legged fp64 reference of
+"""GPU: train steps, policy forward, device loop and refusals of networks with a PADDED convolution (csrc/conv_own.hip) against the two-legged fp64 reference of
 feedforward_reference.py.  Every case of conv_pad_reference.CASES runs three train steps on given indices under the shared per-step checks of the feed-forward edge
 tests (Q, greedy indices exactly, y, td, loss, per-block gradients, grad_norm, parameters after fp64 Adam, priorities; tolerances unchanged); use_graph 0 and 1 and
 use_mfma 0 and 1 must give identical bits.

@@ -1,5 +1,5 @@
 """GPU: train steps, every forward pass, device loops, resume, solver round trip and refusals of networks with CONVOLUTIONAL Flux SkipConnection(layers, +) blocks --
-x + Conv(Conv(x)) on a (c, h, w) map, descriptor kind 10, the residual epilogues of csrc/conv_pad.hip --, all through the C ABI.  The join is read out EXACTLY through
+x + Conv(Conv(x)) on a (c, h, w) map, descriptor kind 10, the residual epilogues of csrc/conv_own.hip --, all through the C ABI.  The join is read out EXACTLY through
 centre-tap identity kernels (Q = 2^blocks * x in every pass) and through a zero branch (the network without the block, bit for bit); every case of
 conv_skip_reference.py's tables then runs three train steps, each against the two-legged fp64 reference at the engine's own previous parameters and batch (Q on s and
 s', target Q, greedy indices exactly under GAP, y, td, loss, per-block gradients -- live on the first step --, grad_norm, parameters after fp64 Adam, priorities;

@@ -1,6 +1,6 @@
 """usage (GPU box, repo root): python tools/conv_dg_profile.py [--reps 7] [--against deepqlearning.jl_amd/build/<other>.so]
-The launches of a dilated / grouped / depthwise Conv (csrc/conv_dg.hip, layer kind 15) in a MIDDLE train step (dqn_profile_steady_step), beside the padded Conv's
-(csrc/conv_pad.hip) on the same map: Conv(1, 4 => 32, relu) -> LAYER -> GlobalMeanPool -> Dense(32, 4) on (4, 20, 20) observations, LAYER one of
+The launches of a dilated / grouped / depthwise Conv (csrc/conv_own.hip, layer kind 15) in a MIDDLE train step (dqn_profile_steady_step), beside the padded Conv's
+(the same file's other geometry) on the same map: Conv(1, 4 => 32, relu) -> LAYER -> GlobalMeanPool -> Dense(32, 4) on (4, 20, 20) observations, LAYER one of
     padded     Conv(3, 32 => 32, relu; pad = 1)                 the yardstick: 32 x 9 x 32 x 400 MACs per column
     depthwise  DepthwiseConv(3, 32 => 32, relu; pad = 1)        1 / 32 of the yardstick's MACs
     grouped    Conv(3, 32 => 32, relu; groups = 2, pad = 1)     half of them

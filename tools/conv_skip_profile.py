@@ -1,5 +1,5 @@
 """usage (GPU box, repo root): python tools/conv_skip_profile.py [--pairs 5] [--mode trunk|padded]
-Convolutional skip blocks (DQN_LAYER_SKIPADD_MAP, the residual epilogues of csrc/conv_pad.hip), measured in ONE process, alternating:
+Convolutional skip blocks (DQN_LAYER_SKIPADD_MAP, the residual epilogues of csrc/conv_own.hip), measured in ONE process, alternating:
 
   --mode trunk   the residual trunk at the workload's shape -- Conv(8, 4 => 32, relu; stride = 4) on 84 x 84 x 4, two blocks of two Conv(3, 32 => 32; pad = 1) (relu
                  between them), Dense(12800, 512, relu), Dense(512, 4); f32 observations -- at B = 32 and B = 512: an engine created with DQN_NO_SKIP_FUSE unset (the
@@ -7,7 +7,7 @@ Convolutional skip blocks (DQN_LAYER_SKIPADD_MAP, the residual epilogues of csrc
                  launch count and the per-launch averages of dqn_profile_steady_step.
   --mode padded  the step time of a padded network WITHOUT a block -- Conv(3, 4 => 4, tanh; pad = 1) -> Conv(3, 4 => 8, sigmoid; pad = 1) -> Conv(3, 8 => 8, tanh;
                  pad = 1) -> Dense(288, 4) on 4 x 6 x 6 observations at B = 128, the stack_same network of tests/conv_pad_reference.py -- `pairs` times.  Run it under
-                 DQN_MI355X_LIB=<another build> and under the in-tree build in turn (one call of a shell loop) to compare two builds of conv_pad.hip.
+                 DQN_MI355X_LIB=<another build> and under the in-tree build in turn (one call of a shell loop) to compare two builds of conv_own.hip.
 One box, one call: quote it that way (docs/history/conv_skip.md)."""
 import argparse
 import importlib
