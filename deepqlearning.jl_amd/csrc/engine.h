@@ -180,7 +180,7 @@ static inline int skip_join_of_first(const dqn_engine* e, int l) { for (int j = 
 // the activation whose derivative layer l's input-gradient launch applies in its epilogue: its producer's -- unless that producer is the entry P of a skip block (then l is
 // the block's first inner layer and P has a second consumer, the join): the launch writes the RAW gradient and the block's entry launch (skip.hip) takes P's derivative
 // once, after the sum.  THE statement of the rule: every dX site of engine_program.hip goes through it (a map block's fused entry hands its launch P's real activation
-// instead: the sum is made in that launch's own epilogue, emit_own_level_bwd)
+// instead: the sum is made in that launch's own epilogue, bwd_own_level)
 static inline int src_act(const dqn_engine* e, int l) {
     const int s = e->L[l].src;
     for (int j = 0; j < e->nl; j++) if (is_skip(e->L[j].kind) && e->L[j].src2 == s) return DQN_ACT_IDENTITY;
@@ -203,9 +203,9 @@ template <class T> static T* upload(dqn_engine* e, const std::vector<T>& v) {
 }
 float* palloc(dqn_engine* e, size_t n);
 bool same_geo(const LayerDev& a, const LayerDev& b);
-void add_valu(dqn_engine* e, std::vector<VTask>& pend, const VTask& t);
 void flush_valu(dqn_engine* e, std::vector<VTask>& pend, const char* name, const PrioArgs* prio = nullptr);
 void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name);
+const char* lname(dqn_engine* e, const char* fmt, ...) __attribute__((format(printf, 2, 3)));      // THE interned launch name (kept in prog_names)
 const char* pname(dqn_engine* e, const char* op, const LayerDev& L, int i);      // "<op>_<the kind's tag><i>" (KindTraits::tag)
 typedef std::vector<std::vector<int>> Levels;
 Levels net_levels(const dqn_engine* e);      // the launch levels of the network: the base chain one layer per level, then the (value, advantage) layers pairwise

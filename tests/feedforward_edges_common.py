@@ -564,7 +564,7 @@ BOUNDARY = [
     case("dw_nt4", 64, mlp(64, 64, 32, 4), 32, prio=0, want={"dw0": "lds", "dwNT0": 4}),
     case("dw_nt2", 64, mlp(64, 96, 32, 4), 32, prio=0, dup=True, want={"dw0": "lds", "dwNT0": 2}),
     case("dw_nt1", 64, mlp(64, 48, 32, 4), 32, prio=0, want={"dw0": "lds", "dwNT0": 1}),
-    # (small_dw -- (K+1)*N <= 16384 at B <= 256 -- is a rule of the recurrent layers' dW only (engine_program.hip emit_dw1): no feed-forward network reaches it;
+    # (small_dw -- (K+1)*N <= 16384 at B <= 256 -- is a rule of the recurrent layers' dW only (engine_program.hip bwd_recurrent): no feed-forward network reaches it;
     #  tests/test_recurrent_edges_gpu.py runs recurrent layers on both sides of it)
     _cv("conv_dw_b32", (4, 12, 14), (3, 4, 16, 1), (3, 16, 32, 1), 32, 4, 32, want={"dw0": "lds", "dw1": "lds"}),          # chunks of whole 32-sample tiles
     _cv("conv_dw_b48", (4, 12, 14), (3, 4, 16, 1), (3, 16, 32, 1), 32, 4, 48, want={"dw0": "mfma", "dw1": "mfma"}),                           # sample-granular: multiples of B
