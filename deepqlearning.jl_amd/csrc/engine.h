@@ -1,5 +1,5 @@
 // engine.h -- internal header of libdqn_mi355x.so's host side: the engine record, error/alloc helpers and the functions the
-// translation units engine.hip (ABI core, graphs, policy), engine_program.hip (static launch program of the train step),
+// translation units engine.hip (ABI core, graphs, policy), engine_layers.hip (build_layers), engine_program.hip (static launch program of the train step),
 // engine_drqn.hip (EpisodeReplayBuffer + recurrent step) and engine_envs.hip (device-resident environments) share.
 #pragma once
 #include <dlfcn.h>
@@ -159,6 +159,8 @@ template <class T> static int dmalloc(T** p, size_t n) {
 #define DM(p, n) do { if (dmalloc(&(p), (n))) return -1; } while (0)
 #define NEED_REC(e) do { if (!(e)->hp.recurrence) return fail("this engine was created with recurrence = false"); } while (0)
 
+// engine_layers.hip (host only): the geometry of every layer, or -1 with the refusal; the last layer of each stream (-1: none), the external / internal parameter counts
+int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, LayerDev* L, int* lb, int* lv, int* la, size_t* P, size_t* Pint);
 // engine.hip
 void drop_graphs(dqn_engine* e);
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a);

@@ -71,217 +71,6 @@ static int refuse_replicas(const char* who, const LayerDev* L, int nl) {
     }
     return 0;
 }
-// geometry of every layer; shared by dqn_plan_default (host only) and dqn_engine_create
-static int build_layers(const dqn_layer_desc* d, int n, const dqn_hparams* hp, LayerDev* L, int* lb, int* lv, int* la, size_t* P, size_t* Pint) {
-    if (n <= 0 || n > DQN_MAX_LAYERS) return fail("bad layer count %d", n);
-    *lb = *lv = *la = -1; size_t off = 0, eoff = 0;
-    for (int i = 0; i < n; i++) {
-        LayerDev& l = L[i]; memset(&l, 0, sizeof l);
-        l.kind = d[i].kind; l.act = d[i].act; l.stream = d[i].stream; l.src2 = -1;
-        int prev;
-        if (l.stream == DQN_STREAM_BASE) prev = *lb; else if (l.stream == DQN_STREAM_VAL) prev = *lv >= 0 ? *lv : *lb; else prev = *la >= 0 ? *la : *lb;
-        l.src = prev;
-        int c, h, w;
-        if (prev < 0) { c = hp->obs_c; h = hp->obs_h; w = hp->obs_w; }
-        else if (out_is_map(L, prev)) { c = L[prev].cout; h = L[prev].oh; w = L[prev].ow; }
-        else { c = L[prev].out_feat; h = 1; w = 1; }
-        l.in_feat = c * h * w;
-        if (l.kind == DQN_LAYER_CONV) {
-            l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);      // every kernel decodes the code on trust: an unknown one would train with some other law
-            if (l.cin != c) return fail("layer %d: conv cin %d != incoming channels %d", i, l.cin, c);
-            // pad = (ph, pw) rides in the n_in / n_out slots (zero in every pad-0 descriptor): symmetric zero padding, at most kernel - 1 per axis (conv_own.hip)
-            l.ph = d[i].n_in; l.pw = d[i].n_out;
-            if (l.ph < 0 || l.pw < 0) return fail("layer %d: Conv pad (%d, %d) must not be negative", i, l.ph, l.pw);
-            if ((l.ph || l.pw) && (l.kh < 1 || l.kw < 1 || l.ph > l.kh - 1 || l.pw > l.kw - 1)) return fail("layer %d: Conv pad (%d, %d) is larger than kernel - 1 = (%d, %d): a window would lie in the padding alone", i, l.ph, l.pw, l.kh - 1, l.kw - 1);
-            if ((l.ph || l.pw) && l.stream != DQN_STREAM_BASE) return fail("layer %d: Conv with pad (%d, %d) is supported in the base chain only (not in a value / advantage stream)", i, l.ph, l.pw);
-            if ((l.ph || l.pw) && (l.sh < 1 || l.sw < 1 || l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw)) return fail("layer %d: Conv kernel (%d, %d) / stride (%d, %d) does not fit the %dx%d input map extended by pad (%d, %d)", i, l.kh, l.kw, l.sh, l.sw, h, w, l.ph, l.pw);
-            if (l.kh > h + 2 * l.ph || l.kw > w + 2 * l.pw || l.sh < 1 || l.sw < 1) return fail("layer %d: conv kernel/stride does not fit the %dx%d input", i, h, w);
-            l.ih = h; l.iw = w; l.oh = (h + 2 * l.ph - l.kh) / l.sh + 1; l.ow = (w + 2 * l.pw - l.kw) / l.sw + 1;      // trailing rows / columns of the extended map no window covers are dropped
-            l.K = l.cin * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
-        } else if (is_cdg(l.kind)) {      // Flux Conv(...; dilation, groups) / DepthwiseConv (conv_own.hip): a block of its own, so that no message of the Conv block above changes
-            l.cin = d[i].cin; l.cout = d[i].cout; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: dilated / grouped Conv activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
-            // pad_h | pad_w << 16 rides in n_in, dh | dw << 8 | g << 16 in n_out (include/dqn_mi355x.h)
-            if (d[i].n_in < 0 || d[i].n_out < 0) return fail("layer %d: dilated / grouped Conv: the packed slots n_in = %d (pad_h | pad_w << 16) and n_out = %d (dh | dw << 8 | groups << 16) must not be negative", i, d[i].n_in, d[i].n_out);
-            l.ph = d[i].n_in & 0xffff; l.pw = d[i].n_in >> 16; l.dh = d[i].n_out & 0xff; l.dw = (d[i].n_out >> 8) & 0xff; l.groups = d[i].n_out >> 16;
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a Conv with dilation (%d, %d) / groups %d is supported in the base chain only (not in a value / advantage stream)", i, l.dh, l.dw, l.groups);
-            if (l.dh < 1 || l.dw < 1) return fail("layer %d: Conv dilation (%d, %d) must be at least 1 per axis", i, l.dh, l.dw);
-            if (l.kh < 1 || l.kw < 1 || l.sh < 1 || l.sw < 1) return fail("layer %d: dilated / grouped Conv kernel (%d, %d) / stride (%d, %d) must be positive", i, l.kh, l.kw, l.sh, l.sw);
-            if (l.cin < 1 || l.cout < 1 || l.groups < 1 || l.cin % l.groups || l.cout % l.groups) return fail("layer %d: Conv groups = %d must be >= 1 and divide cin = %d and cout = %d", i, l.groups, l.cin, l.cout);
-            if (l.cin != c) return fail("layer %d: dilated / grouped Conv cin %d != incoming channels %d", i, l.cin, c);
-            { const long long eh = (long long)(l.kh - 1) * l.dh, ew = (long long)(l.kw - 1) * l.dw;      // the dilated extent minus one, per axis
-              if (l.ph > eh || l.pw > ew) return fail("layer %d: Conv pad (%d, %d) is larger than the dilated kernel extent - 1 = (%lld, %lld): a window would lie in the padding alone", i, l.ph, l.pw, eh, ew);
-              if (eh + 1 > h + 2 * l.ph || ew + 1 > w + 2 * l.pw) return fail("layer %d: Conv kernel (%d, %d) with dilation (%d, %d) spans (%lld, %lld) and does not fit the %dx%d input map extended by pad (%d, %d)", i, l.kh, l.kw, l.dh, l.dw, eh + 1, ew + 1, h, w, l.ph, l.pw);
-              l.ih = h; l.iw = w; l.oh = (int)((h + 2 * l.ph - eh - 1) / l.sh) + 1; l.ow = (int)((w + 2 * l.pw - ew - 1) / l.sw) + 1; }
-            l.K = (l.cin / l.groups) * l.kh * l.kw; l.N = l.cout; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
-        } else if (is_adaptive_pool(l.kind)) {      // Flux AdaptiveMaxPool / AdaptiveMeanPool((ow, oh)), GlobalMaxPool / GlobalMeanPool (output (1, 1)): kh, kw carry the OUTPUT size; resolved here into a pool's geometry
-            const char* nm = l.kind == DQN_LAYER_ADAPTIVEMAXPOOL ? "AdaptiveMaxPool" : "AdaptiveMeanPool";
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, nm, l.stream);
-            if (prev >= 0 && !out_is_map(L, prev)) return fail("layer %d: %s must be the first layer or follow a layer whose output is a (c, h, w) map (layer %d is %s, whose output is a feature vector of %d)", i, nm, prev,
-                                                                 is_actl(L[prev].kind) ? "an Activation layer on a feature vector" : L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer", L[prev].out_feat);
-            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
-            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
-            if (d[i].sh || d[i].sw || d[i].n_in || d[i].n_out) return fail("layer %d: %s uses cin, cout, kh and kw (the OUTPUT size (oh, ow)) only; sh / sw / n_in / n_out = %d / %d / %d / %d must be 0", i, nm, d[i].sh, d[i].sw, d[i].n_in, d[i].n_out);
-            if (d[i].kh < 1 || d[i].kw < 1) return fail("layer %d: %s output size (%d, %d) must be at least (1, 1)", i, nm, d[i].kh, d[i].kw);
-            if (d[i].kh > h || d[i].kw > w) return fail("layer %d: %s output size (%d, %d) is larger than the %dx%d input map (the adaptive rule needs 1 <= out <= in per axis)", i, nm, d[i].kh, d[i].kw, h, w);
-            // Flux's rule per axis (NOT torch's adaptive windows): stride = in / out, k = in - (out - 1) * stride, pad 0; then (in - k) / stride + 1 == out
-            l.cin = l.cout = c; l.oh = d[i].kh; l.ow = d[i].kw; l.sh = h / l.oh; l.sw = w / l.ow; l.kh = h - (l.oh - 1) * l.sh; l.kw = w - (l.ow - 1) * l.sw;
-            l.ih = h; l.iw = w; l.K = 0; l.N = 0; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
-        } else if (is_pool(l.kind)) {      // Flux MaxPool / MeanPool, pad 0 (pool.hip): per channel on the incoming (c, h, w) map; no parameters (K = N = 0), no activation
-            const char* nm = l.kind == DQN_LAYER_MAXPOOL ? "MaxPool" : "MeanPool";
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: %s layers are supported in the base chain only (not in a value / advantage stream)", i, nm);
-            if (prev >= 0 && !out_is_map(L, prev)) return fail("layer %d: %s must be the first layer or follow a Conv / MaxPool / MeanPool layer (it follows a Dense or recurrent layer, whose output is no (c, h, w) map)", i, nm);
-            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: %s has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, nm, d[i].act);
-            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: %s cin %d / cout %d != incoming channels %d", i, nm, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
-            if (d[i].sh < 1 || d[i].sw < 1) return fail("layer %d: %s stride (%d, %d) must be positive", i, nm, d[i].sh, d[i].sw);
-            if (d[i].kh < 1 || d[i].kw < 1 || d[i].kh > h || d[i].kw > w) return fail("layer %d: %s window (%d, %d) does not fit the %dx%d input map", i, nm, d[i].kh, d[i].kw, h, w);
-            l.cin = l.cout = c; l.kh = d[i].kh; l.kw = d[i].kw; l.sh = d[i].sh; l.sw = d[i].sw;
-            l.ih = h; l.iw = w; l.oh = (h - l.kh) / l.sh + 1; l.ow = (w - l.kw) / l.sw + 1;      // trailing rows / columns no window covers are dropped
-            l.K = 0; l.N = 0; l.npos = l.oh * l.ow; l.out_feat = l.cout * l.npos;
-        } else if (is_ln(l.kind)) {      // Flux LayerNorm(n, act; affine = true, eps) (layernorm.hip): per column over the n incoming features; K = N = n, parameters scale (n), bias (n)
-            if (prev < 0) return fail("layer %d: LayerNorm cannot be the first layer (it must directly follow a Dense or recurrent layer)", i);
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: LayerNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (is_actl(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is an Activation layer; a LayerNorm directly behind a standalone activation is not supported)", i, prev);
-            if (is_gn(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
-            if (has_map(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
-            if (is_ln(L[prev].kind)) return fail("layer %d: LayerNorm must directly follow a Dense or recurrent layer (layer %d is a LayerNorm layer)", i, prev);
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: LayerNorm n_in %d != n_out %d (both carry the size n)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_out < 2) return fail("layer %d: LayerNorm size n = %d must be >= 2 (over one feature sigma is identically 0 and the gradient is NaN)", i, d[i].n_out);
-            if (d[i].n_in != l.in_feat) return fail("layer %d: LayerNorm size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: LayerNorm activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
-            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: LayerNorm uses n_in, n_out, act and cin (the bit pattern of eps) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
-            l.cin = d[i].cin;      // the fp32 bit pattern of eps, 0 = the default 1f-5 (ln_eps)
-            { const float eps = ln_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: LayerNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].cin); }
-            l.K = l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (is_gn(l.kind)) {      // Flux GroupNorm(chs, G, act; eps) (groupnorm.hip): per column and group of c / G contiguous channels of the incoming (c, h, w) map, which it keeps; K = N = c, parameters beta (c), gamma (c)
-            if (prev < 0) return fail("layer %d: GroupNorm cannot be the first layer (normalising the observation is not supported; it must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block)", i);
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: GroupNorm layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (!out_is_map(L, prev)) return fail("layer %d: GroupNorm must directly follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional skip block (layer %d is %s, whose output is no (c, h, w) map)", i, prev,
-                                                    is_actl(L[prev].kind) ? "an Activation layer on a feature vector" : L[prev].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[prev].kind) ? "a recurrent layer" : is_ln(L[prev].kind) ? "a LayerNorm layer" : is_do(L[prev].kind) ? "a Dropout layer" : "a Dense layer");
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: GroupNorm activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
-            if ((d[i].cin || d[i].cout) && (d[i].cin != c || d[i].cout != c)) return fail("layer %d: GroupNorm chs (cin %d / cout %d) != incoming channels %d", i, d[i].cin, d[i].cout, c);      // both 0: taken from the incoming map
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: GroupNorm n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: GroupNorm size n = %d != incoming features %d * %d * %d = %d", i, d[i].n_in, c, h, w, l.in_feat);
-            if (d[i].sh || d[i].sw) return fail("layer %d: GroupNorm uses cin, cout, kh (the group count G), kw (the bit pattern of eps), n_in, n_out and act only; sh / sw = %d / %d must be 0", i, d[i].sh, d[i].sw);
-            if (d[i].kh < 1 || c % d[i].kh) return fail("layer %d: GroupNorm G = %d must be >= 1 and divide the channel count %d", i, d[i].kh, c);
-            if ((long long)(c / d[i].kh) * h * w < 2) return fail("layer %d: GroupNorm(%d, %d) on a (%d, %d, %d) map normalises over n_g = %d element (n_g must be >= 2: over one element the variance is identically 0 and the output is constant)", i, c, d[i].kh, c, h, w, (c / d[i].kh) * h * w);
-            l.cin = l.cout = c; l.kh = d[i].kh; l.kw = d[i].kw;      // G, and the fp32 bit pattern of eps, 0 = the default 1f-5 (gn_eps)
-            { const float eps = gn_eps(l); if (!(eps > 0.0f) || !(eps <= 3.402823466e38f)) return fail("layer %d: GroupNorm eps = %g (bit pattern 0x%08x) must be finite and > 0", i, (double)eps, (unsigned)d[i].kw); }
-            l.ih = l.oh = h; l.iw = l.ow = w; l.K = l.N = c; l.npos = h * w; l.out_feat = l.in_feat;
-        } else if (is_do(l.kind)) {      // Flux Dropout(p), dims = : (dropout.hip): per element of the n incoming features; no parameters (K = N = 0 as a pool's), p's Float64 bits in (cin, cout)
-            if (prev < 0) return fail("layer %d: Dropout cannot be the first layer (it must directly follow a Dense, recurrent or LayerNorm layer; dropout on the observation is not supported)", i);
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Dropout layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (is_actl(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is an Activation layer; a Dropout directly behind a standalone activation is not supported)", i, prev);
-            if (is_gn(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a GroupNorm layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
-            if (has_map(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Conv / MaxPool / MeanPool layer, whose output is a (%d, %d, %d) map)", i, prev, c, h, w);
-            if (is_do(L[prev].kind)) return fail("layer %d: Dropout must directly follow a Dense, recurrent or LayerNorm layer (layer %d is a Dropout layer)", i, prev);
-            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: Dropout has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: Dropout n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: Dropout size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            if (d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: Dropout uses n_in, n_out, cin and cout (the Float64 bit pattern of p) only; kh / kw / sh / sw = %d / %d / %d / %d must be 0", i, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
-            l.cin = d[i].cin; l.cout = d[i].cout;      // the Float64 bit pattern of p, low word then high word (do_p)
-            { const double p = do_p(l);
-              if (!(p >= 0.0) || !(p < 1.0)) return fail("layer %d: Dropout p = %g (bit pattern 0x%08x%08x) must be finite with 0 <= p < 1%s", i, p, (unsigned)d[i].cout, (unsigned)d[i].cin,
-                                                         p == 1.0 ? " (p = 1 drops every feature: Q would be constant)" : ""); }
-            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (is_skip_map(l.kind)) {      // the join of a CONVOLUTIONAL SkipConnection(layers, +) block: the same law on a (c, h, w) map; inner layers = padded Convs, entry = a Conv / pool / map join
-            const int m = d[i].cin;
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a convolutional skip block is supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: a convolutional skip block's join has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
-            if (m < 1) return fail("layer %d: a convolutional skip block holds at least one inner layer (cin = m = %d must be >= 1)", i, m);
-            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: a convolutional skip block's join uses n_in, n_out and cin (the number of inner layers) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
-            if (m > i) return fail("layer %d: the convolutional skip block's %d inner layers would start before the first layer (the block cannot be the first layer: its input is never the observation)", i, m);
-            for (int j = i - m; j < i; j++) {
-                if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the convolutional skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
-                if (is_skip(L[j].kind)) return fail("layer %d: the convolutional skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
-                if (is_actl(L[j].kind)) return fail("layer %d: the convolutional skip block holds an Activation layer (layer %d); its inner layers are Conv layers with pad != 0 only (a standalone activation inside a skip block is not supported)", i, j);
-                if (is_pool(L[j].kind)) return fail("layer %d: the convolutional skip block holds a MaxPool / MeanPool layer (layer %d); its inner layers are Conv layers with pad != 0 only", i, j);
-                if (is_cdg(L[j].kind)) return fail("layer %d: the convolutional skip block holds a Conv with dilation (%d, %d) / groups %d (layer %d); its inner layers are Conv layers with pad != 0, dilation 1 and groups 1 only (dilated and grouped residual blocks are not supported)", i, L[j].dh, L[j].dw, L[j].groups, j);
-                if (L[j].kind == DQN_LAYER_CONV && !is_padded(L[j])) return fail("layer %d: the convolutional skip block holds a Conv with pad 0 (layer %d, kernel (%d, %d)); its inner layers are Conv layers with pad != 0 only", i, j, L[j].kh, L[j].kw);
-                if (L[j].kind != DQN_LAYER_CONV) return fail("layer %d: the convolutional skip block holds %s (layer %d); its inner layers are Conv layers with pad != 0 only", i,
-                                                             is_recurrent(L[j].kind) ? "a recurrent layer" : is_ln(L[j].kind) ? "a LayerNorm layer" : is_do(L[j].kind) ? "a Dropout layer" : is_gn(L[j].kind) ? "a GroupNorm layer" : "a Dense layer", j);
-            }
-            const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
-            if (pp < 0) return fail("layer %d: the convolutional skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block)", i, i - m);
-            if (!out_is_map(L, pp)) return fail("layer %d: the convolutional skip block's input is the feature vector of layer %d (%s); a convolutional skip block stands on the (c, h, w) map of a Conv, MaxPool or MeanPool layer or of another convolutional skip block", i, pp,
-                                                  is_actl(L[pp].kind) ? "an Activation layer on a feature vector" : L[pp].kind == DQN_LAYER_SKIPADD ? "the join of a skip block on a feature vector" : is_recurrent(L[pp].kind) ? "a recurrent layer" : is_ln(L[pp].kind) ? "a LayerNorm layer" : is_do(L[pp].kind) ? "a Dropout layer" : "a Dense layer");
-            if (L[prev].cout != L[pp].cout || L[prev].oh != L[pp].oh || L[prev].ow != L[pp].ow) return fail("layer %d: the convolutional skip block maps a (%d, %d, %d) map to a (%d, %d, %d) map; SkipConnection(layers, +) needs layers: (c, h, w) -> (c, h, w)", i, L[pp].cout, L[pp].oh, L[pp].ow, L[prev].cout, L[prev].oh, L[prev].ow);
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: convolutional skip block n_in %d != n_out %d (both carry the feature count c * h * w, or both 0)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: convolutional skip block size n = %d != the block's features %d * %d * %d = %d", i, d[i].n_in, c, h, w, l.in_feat);
-            l.cin = m; l.src2 = pp; l.cout = c; l.ih = l.oh = h; l.iw = l.ow = w;      // (cin is m, NOT the channel count: the layer behind the join reads cout, oh, ow)
-            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat;
-        } else if (is_skip(l.kind)) {      // the join of a Flux SkipConnection(layers, +) block (skip.hip): y = y_K + y_P; cin = m, the number of inner layers (the m descriptors in front)
-            const int m = d[i].cin;
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: a skip block is supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (d[i].act != DQN_ACT_IDENTITY) return fail("layer %d: a skip block's join has no activation (act must be DQN_ACT_IDENTITY, got %d)", i, d[i].act);
-            if (m < 1) return fail("layer %d: a skip block holds at least one inner layer (cin = m = %d must be >= 1)", i, m);
-            if (d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: a skip block's join uses n_in, n_out and cin (the number of inner layers) only; cout / kh / kw / sh / sw = %d / %d / %d / %d / %d must be 0", i, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
-            if (m > i) return fail("layer %d: the skip block's %d inner layers would start before the first layer (the block cannot be the first layer: its input is never the observation)", i, m);
-            for (int j = i - m; j < i; j++) {
-                if (L[j].stream != DQN_STREAM_BASE) return fail("layer %d: the skip block's inner layer %d is not in the base chain (stream = %d)", i, j, L[j].stream);
-                if (is_skip(L[j].kind)) return fail("layer %d: the skip block's %d inner layers reach across the join of another skip block (layer %d); nested skip blocks are not supported", i, m, j);
-                if (is_recurrent(L[j].kind)) return fail("layer %d: the skip block holds a recurrent layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only", i, j);
-                if (is_actl(L[j].kind)) return fail("layer %d: the skip block holds an Activation layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (a standalone activation inside a skip block is not supported)", i, j);
-                if (is_gn(L[j].kind)) return fail("layer %d: the skip block holds a GroupNorm layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (GroupNorm inside a skip block is not supported)", i, j);
-                if (is_cdg(L[j].kind)) return fail("layer %d: the skip block holds a Conv with dilation (%d, %d) / groups %d (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (dilated and grouped residual blocks are not supported)", i, L[j].dh, L[j].dw, L[j].groups, j);
-                if (has_map(L[j].kind)) return fail("layer %d: the skip block holds a Conv / MaxPool / MeanPool layer (layer %d); its inner layers are Dense, LayerNorm and Dropout layers only (convolutional residual blocks are not supported)", i, j);
-            }
-            const int pp = L[i - m].src;      // the block's entry P: what the first inner layer reads
-            if (pp < 0) return fail("layer %d: the skip block's first inner layer (layer %d) reads the observation; a skip block cannot be the first layer (its input must be the output of a Dense, recurrent, LayerNorm or Dropout layer or of another skip block)", i, i - m);
-            if (is_gn(L[pp].kind)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a GroupNorm layer); a skip block stands on a feature vector", i, pp);
-            if (out_is_map(L, pp)) return fail("layer %d: the skip block's input is the (c, h, w) map of layer %d (a Conv / MaxPool / MeanPool layer); a skip block stands on a feature vector (convolutional residual blocks are not supported)", i, pp);
-            if (L[prev].out_feat != L[pp].out_feat) return fail("layer %d: the skip block maps %d features to %d; SkipConnection(layers, +) needs layers: n -> n", i, L[pp].out_feat, L[prev].out_feat);
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: skip block n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: skip block size n = %d != the block's features %d", i, d[i].n_in, l.in_feat);
-            l.cin = m; l.src2 = pp;
-            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (is_actl(l.kind)) {      // the standalone activation layer (act_layer.hip): y = σ(x) per element on whatever the layer in front yields -- a feature vector or a (c, h, w) map, kept; no parameters (K = N = 0 as a pool's)
-            if (prev < 0) return fail("layer %d: an Activation layer cannot be the first layer (its input is the stored output of the layer in front; an activation on the observation is not supported)", i);
-            if (l.stream != DQN_STREAM_BASE) return fail("layer %d: Activation layers are supported in the base chain only (not in a value / advantage stream; stream = %d)", i, l.stream);
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAYER_LAST) return fail("layer %d: Activation code %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAYER_LAST);
-            if (d[i].n_in != d[i].n_out) return fail("layer %d: Activation n_in %d != n_out %d (both carry the feature count n, or both 0)", i, d[i].n_in, d[i].n_out);
-            if (d[i].n_in != 0 && d[i].n_in != l.in_feat) return fail("layer %d: Activation size n = %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            if (d[i].cin || d[i].cout || d[i].kh || d[i].kw || d[i].sh || d[i].sw) return fail("layer %d: Activation uses act, n_in and n_out only; cin / cout / kh / kw / sh / sw = %d / %d / %d / %d / %d / %d must be 0", i, d[i].cin, d[i].cout, d[i].kh, d[i].kw, d[i].sh, d[i].sw);
-            l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY;      // σ, and what the generic epilogues read (common.h)
-            l.cin = l.cout = c; l.ih = l.oh = h; l.iw = l.ow = w;      // behind a map: the map, for the layer behind it (out_is_map); behind a feature vector: (n, 1, 1)
-            l.K = 0; l.N = 0; l.npos = 1; l.out_feat = l.in_feat;
-        } else if (l.kind == DQN_LAYER_DENSE) {
-            if (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_LAST) return fail("layer %d: Dense activation %d is not one of DQN_ACT_* (0..%d)", i, d[i].act, DQN_ACT_LAST);
-            if (d[i].n_in != l.in_feat) return fail("layer %d: dense n_in %d != incoming features %d", i, d[i].n_in, l.in_feat);
-            l.K = d[i].n_in; l.N = d[i].n_out; l.npos = 1; l.out_feat = l.N; l.ih = l.iw = l.oh = l.ow = 1;
-        } else if (is_recurrent(l.kind)) {      // the cell's activation (CellOps::has_act) goes to cell_act, never to act (the cell's kernels apply it); an RNN cell's σ is one of the
-                                                // first four codes: cell.h states the cell's arithmetic on its own, and the codes above DQN_ACT_SIGMOID are Dense / Conv / LayerNorm epilogues only
-            const CellOps* C = cell_ops(l.kind);
-            if (!hp->recurrence) return fail("DeepQLearningError: you passed in a recurrent model but recurrence is set to false");   // src/solver.jl:45-47
-            if (l.stream != DQN_STREAM_BASE) return fail("%s layers are supported in the base chain only", C->display);
-            if (d[i].n_in != l.in_feat) return fail("layer %d: %s n_in %d != incoming features %d", i, C->display, d[i].n_in, l.in_feat);
-            if (C->has_act && (d[i].act < DQN_ACT_IDENTITY || d[i].act > DQN_ACT_SIGMOID)) return fail("layer %d: %s activation %d is not one of DQN_ACT_*", i, C->display, d[i].act);
-            l.H = d[i].n_out; l.K = d[i].n_in; l.N = C->ngates * l.H; l.npos = 1; l.out_feat = l.H; if (C->has_act) l.cell_act = d[i].act; l.act = DQN_ACT_IDENTITY; l.ih = l.iw = l.oh = l.ow = 1;
-        } else return fail("layer %d: unknown kind %d", i, l.kind);
-        if (is_recurrent(l.kind)) {      // Flux.params Wi, Wh, b, h0(, c0) -> internal [Wi][b][Wh][junk][h0]([c0])[zeros]
-            const bool has_c = cell_ops(l.kind)->has_c;
-            const size_t kn = (size_t)l.K * l.N, hn = (size_t)l.H * l.N;
-            l.ew_off = eoff; eoff += kn; l.ewh_off = eoff; eoff += hn; l.eb_off = eoff; eoff += l.N; l.eh0_off = eoff; eoff += l.H; if (has_c) { l.ec0_off = eoff; eoff += l.H; }
-            off = (off + 3) / 4 * 4; l.w_off = off; off += kn; l.b_off = off; off += l.N; l.wh_off = off; off += hn; off += l.N /* junk bias row of the Wh dW pass */;
-            l.h0_off = off; off += l.H; if (has_c) { l.c0_off = off; off += l.H; } off = (off + 3) / 4 * 4; l.z_off = off; off += l.N;
-        } else {
-            const size_t wn = layer_wn(l);      // K * N weights; a LayerNorm's scale vector (N)
-            if (is_gn(l.kind)) { l.eb_off = eoff; eoff += l.N; l.ew_off = eoff; eoff += wn; }      // Flux.params of a GroupNorm: beta, THEN gamma
-            else { l.ew_off = eoff; eoff += wn; l.eb_off = eoff; eoff += l.N; }
-            off = (off + 3) / 4 * 4; l.w_off = off; off += wn; l.b_off = off; off += l.N;
-        }
-        if (l.stream == DQN_STREAM_BASE) *lb = i; else if (l.stream == DQN_STREAM_VAL) *lv = i; else *la = i;
-    }
-    *P = eoff; *Pint = (off + 3) / 4 * 4;
-    if (hp->dueling) {
-        if (*lv < 0 || *la < 0 || L[*lv].out_feat != 1 || L[*la].out_feat != hp->n_actions)
-            return fail("DeepQLearningError: the qnetwork provided is incompatible with dueling");   // src/dueling.jl:47
-    } else if (*lb < 0 || L[*lb].out_feat != hp->n_actions) return fail("network output size != n_actions");
-    if (!hp->dueling && !kind_traits(L[*lb]).output_ok) return fail("layer %d: %s cannot be the network's output layer", *lb, kind_traits(L[*lb]).a_noun);
-    if (hp->n_actions > DQN_MAX_ACTIONS) return fail("n_actions > %d unsupported", DQN_MAX_ACTIONS);
-    return 0;
-}
 // The default summation-order plan.  Chosen for gfx950 occupancy: long forward contractions
 // are cut into ~512-element chunks, dense dX into 256-element chunks, conv dW into ~256-sample chunks.
 // the ONE place the library reads its environment (besides trace builds): at dqn_engine_create, and -- the communicator switches only -- at dqn_comm_init

@@ -575,22 +575,30 @@ def lower(net):
             j -= 1
         return getattr(layers[j], "kind", None) if j >= 0 else None
 
+    NEVER_FIRST = {"activation": "its input is the stored output of the layer in front (an activation on the observation is not supported)",
+                   "groupnorm": "normalising the observation is not supported (it must follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional SkipConnection)"}
+
+    def placed(l, stream, is_last):
+        # the placement of an own-level kind, by name: never the first layer (the kinds of NEVER_FIRST), base chain only, never the output layer (every kind but a Conv)
+        if l.kind in NEVER_FIRST and not out:
+            raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the first layer: {NEVER_FIRST[l.kind]}")
+        if stream != _abi.STREAM_BASE:
+            raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+        if is_last and l.kind != "conv":
+            raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+
     def add(chain, stream):
         layers = list(chain)
         for i, l in enumerate(layers):
             d = _abi.LayerDesc()
+            is_last = i + 1 == len(layers) and chain is top
             if getattr(l, "kind", None) == "parallel":
                 raise _abi.DQNError("DeepQLearningError: Parallel is not supported; of Flux's branching layers the MI355X engine runs SkipConnection(layers, +) only")
             if getattr(l, "kind", None) == "skip":
-                add_skip(l, stream, not out, shape_kind(layers, i), i + 1 == len(layers) and chain is top, layers[i - 1] if i > 0 else None)
+                add_skip(l, stream, not out, shape_kind(layers, i), is_last, layers[i - 1] if i > 0 else None)
                 continue
             if getattr(l, "kind", None) == "activation":      # act = σ (0..14); n_in == n_out == 0: the engine fills in the incoming feature count and keeps the incoming shape
-                if not out:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the first layer: its input is the stored output of the layer in front (an activation on the observation is not supported)")
-                if stream != _abi.STREAM_BASE:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
-                if i + 1 == len(layers) and chain is top:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                placed(l, stream, is_last)
                 d.kind, d.act, d.stream = _abi.LAYER_ACTIVATION, l.code, stream
                 out.append(d)
                 continue
@@ -618,12 +626,7 @@ def lower(net):
                 d.kind, d.n_in, d.n_out = _abi.LAYER_LAYERNORM, l.n, l.n
                 d.cin = int(np.float32(l.eps).view(np.int32))
             elif l.kind == "groupnorm":      # cin == cout == chs, kh = G, the fp32 bit pattern of eps in kw; n_in == n_out == 0: the engine fills in c * h * w
-                if not out:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the first layer: normalising the observation is not supported (it must follow a Conv, MaxPool / MeanPool or GroupNorm layer or a convolutional SkipConnection)")
-                if stream != _abi.STREAM_BASE:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
-                if i + 1 == len(layers) and chain is top:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                placed(l, stream, is_last)
                 d.kind, d.cin, d.cout, d.kh = _abi.LAYER_GROUPNORM, l.chs, l.chs, l.G
                 d.kw = int(np.float32(l.eps).view(np.int32))
             elif l.kind == "dropout":      # n_in == n_out == 0: the engine fills in the incoming feature count; p crosses as its Float64 bit pattern, low word in cin, high in cout
@@ -631,10 +634,7 @@ def lower(net):
                 d.kind = _abi.LAYER_DROPOUT
                 d.cin, d.cout = int(np.uint32(bits & 0xFFFFFFFF).view(np.int32)), int(np.uint32(bits >> 32).view(np.int32))
             elif l.kind in ("adaptivemaxpool", "adaptivemeanpool"):      # kh, kw = the OUTPUT size (oh, ow); sh = sw = n_in = n_out = 0: the engine resolves the window from the map
-                if stream != _abi.STREAM_BASE:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
-                if i + 1 == len(layers) and chain is top:
-                    raise _abi.DQNError(f"DeepQLearningError: {l!r} cannot be the network's output layer")
+                placed(l, stream, is_last)
                 d.kind = _abi.LAYER_ADAPTIVEMAXPOOL if l.kind == "adaptivemaxpool" else _abi.LAYER_ADAPTIVEMEANPOOL
                 d.cin = d.cout = chan[0]
                 d.kh, d.kw = l.oh, l.ow
@@ -645,8 +645,7 @@ def lower(net):
             else:
                 d.cin, d.cout, d.kh, d.kw, d.sh, d.sw = l.cin, l.cout, l.kh, l.kw, l.sh, l.sw
                 if l.general:      # dilation != 1 or groups != 1: kind 15; the five small integers ride packed, pad_h | pad_w << 16 in n_in, dh | dw << 8 | g << 16 in n_out
-                    if stream != _abi.STREAM_BASE:
-                        raise _abi.DQNError(f"DeepQLearningError: {l!r} is supported in the base chain only (not in a value / advantage stream)")
+                    placed(l, stream, is_last)
                     d.kind = _abi.LAYER_CONV_DG
                     d.n_in, d.n_out = l.ph | (l.pw << 16), l.dh | (l.dw << 8) | (l.groups << 16)
                 else:

@@ -30,7 +30,7 @@ LR = 1e-3
 WORST = {}                                   # largest error / tolerance seen per quantity (1.0 = at the bound); printed by the test files
 
 
-# ------------------------------------------------------------------ geometry (engine.hip build_layers, restated)
+# ------------------------------------------------------------------ geometry (engine_layers.hip build_layers, restated)
 def _c4(x):
     return (x + 3) // 4 * 4
 
