@@ -205,6 +205,8 @@ PROTOS = {
     "group_destroy": [_vp],
     "rollout_many": [_vp, C.c_int, _P(RolloutCfg), _P(_P(Exploration)), _P(RolloutStats)],
     "rollout_many_info": [_vp, _P(C.c_int), _P(C.c_uint)],
+    "evaluate_many": [_vp, C.c_int, C.c_int, _P(C.c_uint64), _f64p, _f64p],
+    "evaluate_many_info": [_vp, C.c_int, C.c_int, _P(C.c_int), _P(C.c_int), _P(C.c_uint)],
 }
 
 class DQNError(RuntimeError):
@@ -761,6 +763,27 @@ class EngineGroup:
         n, lds = C.c_int(), C.c_uint()
         self._check(self.f["rollout_many_info"](self._g, C.byref(n), C.byref(lds)))
         return n.value, lds.value
+
+    def evaluate(self, n_eval, max_episode_length, seeds):
+        """dqn_evaluate_many: basic_evaluation of every member, n_eval greedy episodes each with the whole episode loop inside the kernel -> [(avg_reward, avg_steps)] * K,
+        member k's pair bit for bit what Handle.evaluate(n_eval, max_episode_length, seeds[k]) returns.  seeds: one per member."""
+        if "evaluate_many" not in self.f:
+            raise DQNError("this library does not export evaluate_many")
+        K = len(self.members)
+        seeds = list(seeds)
+        if len(seeds) != K:
+            raise DQNError(f"EngineGroup.evaluate: {len(seeds)} seeds were given for {K} members (one per member)")
+        sd = (C.c_uint64 * K)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds])
+        r, st = np.empty(K, np.float64), np.empty(K, np.float64)
+        self._check(self.f["evaluate_many"](self._g, int(n_eval), int(max_episode_length), sd, _ptr(r, _f64p), _ptr(st, _f64p)))
+        return [(float(r[k]), float(st[k])) for k in range(K)]
+
+    def evaluate_info(self, n_eval, max_episode_length):
+        """(launches per call, vector steps per launch at most, dynamic LDS bytes of the evaluation launch); raises with the member and the reason where a member
+        does not take the single-workgroup evaluation"""
+        n, b, lds = C.c_int(), C.c_int(), C.c_uint()
+        self._check(self.f["evaluate_many_info"](self._g, int(n_eval), int(max_episode_length), C.byref(n), C.byref(b), C.byref(lds)))
+        return n.value, b.value, lds.value
 
     def info(self):
         gi = GroupInfo()

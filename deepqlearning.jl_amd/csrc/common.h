@@ -1095,6 +1095,22 @@ struct TinyActArgs {
 // the step before left); last: the resets the step leaves pending are applied (a call's last step).  -1: the LDS attribute was refused
 int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int first, int last);
 int tiny_act_raise_lds(unsigned lds_bytes);      // what launch_tiny_act asks of the device, callable before anything is enqueued; -1: refused
+// ---- basic_evaluation of a network that fits in LDS (tiny_eval.hip): one workgroup runs the WHOLE greedy episode loop of a member's V.n evaluation copies, up to
+// TINY_EVAL_STEPS vector steps per launch.  The forward runs tile by tile (tw columns at a time: a.y_off / a.x_off are laid out for tw columns), the heads of all the
+// copies meet in `heads` [nA (+ 1)][V.n], and env_step_body is the step's tail on all V.n copies at once.  a.V is the member's EVALUATION set (eval_mode = 1), a.rs = &roll
+#define TINY_EVAL_STEPS 8       /* vector steps per launch, at most.  Measured (docs/history/group_evaluate.md): the longest launch -- 1024 copies of an 11 028-parameter member, the widest a group takes -- runs 407 us per vector step, 3.3 ms for 8 (6.5 ms for 16); a config-1 member pays 13 launches instead of 7 per 101 steps */
+struct EvalSums { double reward_sum; long long steps; };      // over the copies in ascending order: Float64 sum of the per-copy Float64 reward sums; the episode lengths
+struct TinyEvalArgs {
+    TinyActArgs a;
+    RolloutDev roll;      // the evaluation's step record (t = 0 at the call's start; travels through global memory between the launches of a call)
+    int tw, r_off;        // tile width (a multiple of 4); LDS float offset of the staging area of the sums (3 * V.n floats)
+    float* heads;         // [nA (+ 1 when dueling)][V.n]: the head outputs of every copy, as the tiles leave them
+    EvalSums* out;
+};
+// one launch of K workgroups, workgroup k = record a_dev[k], n_steps <= TINY_EVAL_STEPS vector steps.  first: reset!(env) of every copy (t = 0) before the first step;
+// last: the sums go to a.out.  -1: the LDS attribute was refused
+int launch_tiny_eval(hipStream_t st, TinyEvalArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int n_steps, int first, int last);
+int tiny_eval_raise_lds(unsigned lds_bytes);
 // ---- recurrent engines: the copies' open episodes (staging [n][T]) and the committed episode ring (envs.hip, engine_envs.hip)
 struct EpStage {
     int T; long long ep_cap;

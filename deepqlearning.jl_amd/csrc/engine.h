@@ -240,6 +240,8 @@ int build_program(dqn_engine* e);
 std::string tiny_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup step (tiny_step.hip); empty: it does.  THE eligibility rule
 // engine_group.hip
 std::string tiny_act_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup acting step (tiny_act.hip); empty: it does.  THE eligibility rule
+std::string tiny_eval_decline(const dqn_engine* e);      // why the engine does not take the single-workgroup evaluation (tiny_eval.hip); empty: it does.  THE eligibility rule
+int eval_envs_ensure(dqn_engine* e, int n_eval);      // the engine's evaluation copies (engine_envs.hip), allocated for n_eval
 // engine_envs.hip
 void free_envs(dqn_engine* e);
 int explore_check(const dqn_exploration* x, int n_steps);      // dqn_rollout_explore's table: 0, or -1 with the refusal (nothing is enqueued)

@@ -440,6 +440,27 @@ extern "C" int dqn_rollout_explore(dqn_engine_t* e, int n_steps, const dqn_rollo
     }
     return 0;
 }
+// the evaluation copies of an engine: n_eval copies of the training MDP with per-copy arrays of their own (the images, the spec and the tables are the training
+// set's), allocated on first use and again when n_eval changes.  dqn_evaluate and dqn_evaluate_many (engine_group.hip) step the same set
+int eval_envs_ensure(dqn_engine* e, int n_eval) {
+    EnvDev& W = e->eval_env;
+    if (e->eval_n == n_eval) return 0;
+    HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_env_arrays(W); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
+    W = e->env; W.n = n_eval; W.eval_mode = 1;
+    W.tm_s = W.tm_prev = nullptr; W.tm_t = nullptr; W.gw_pos = W.gw_prev = nullptr; W.tb_s = W.tb_o = W.tb_oprev = nullptr; W.actions = nullptr; W.rewards = nullptr; W.dones = W.pending = nullptr;
+    W.ep_reward = nullptr; W.ep_step = nullptr; W.fin_eps = nullptr; W.fin_reward = nullptr;
+    if (W.kind == DQN_ENV_TESTMDP) { DM(W.tm_s, (size_t)n_eval * 4); DM(W.tm_prev, (size_t)n_eval * 4); DM(W.tm_t, n_eval); }
+    else if (W.kind == DQN_ENV_TABULAR) { DM(W.tb_s, n_eval); DM(W.tb_o, n_eval); DM(W.tb_oprev, n_eval); }      // the tables are the training set's
+    else { DM(W.gw_pos, (size_t)n_eval * 2); DM(W.gw_prev, (size_t)n_eval * 2); }
+    DM(W.actions, n_eval); DM(W.rewards, n_eval); DM(W.dones, n_eval); DM(W.pending, n_eval); DM(W.ep_reward, n_eval); DM(W.ep_step, n_eval); DM(W.fin_eps, n_eval); DM(W.fin_reward, n_eval);
+    DM(e->eval_roll, DQN_ROLL_RECORDS);
+    free_eval_state(e);      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
+    for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
+        DM(e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(e->eval_gx[i], (size_t)e->L[i].N * n_eval);
+    }
+    e->eval_n = n_eval;
+    return 0;
+}
 // basic_evaluation (src/evaluation_policy.jl:17-42) on the device: n_eval copies of the training MDP run one greedy episode each
 // (while !done && step <= max_episode_length), rewards summed in Float64 like the reference's r_tot; returns the averages.
 extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length, uint64_t seed, double* avg_reward, double* avg_steps) { if (!e) return fail("null engine handle");
@@ -447,23 +468,8 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create (the evaluation copies share its MDP)");
     if (n_eval < 1 || n_eval > 1024) return fail("n_eval must be in 1..1024");
     if (max_episode_length < 1) return fail("max_episode_length must be >= 1");
+    if (eval_envs_ensure(e, n_eval)) return -1;
     EnvDev& W = e->eval_env;
-    if (e->eval_n != n_eval) {
-        HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_env_arrays(W); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
-        W = e->env; W.n = n_eval; W.eval_mode = 1;
-        W.tm_s = W.tm_prev = nullptr; W.tm_t = nullptr; W.gw_pos = W.gw_prev = nullptr; W.tb_s = W.tb_o = W.tb_oprev = nullptr; W.actions = nullptr; W.rewards = nullptr; W.dones = W.pending = nullptr;
-        W.ep_reward = nullptr; W.ep_step = nullptr; W.fin_eps = nullptr; W.fin_reward = nullptr;
-        if (W.kind == DQN_ENV_TESTMDP) { DM(W.tm_s, (size_t)n_eval * 4); DM(W.tm_prev, (size_t)n_eval * 4); DM(W.tm_t, n_eval); }
-        else if (W.kind == DQN_ENV_TABULAR) { DM(W.tb_s, n_eval); DM(W.tb_o, n_eval); DM(W.tb_oprev, n_eval); }      // the tables are the training set's
-        else { DM(W.gw_pos, (size_t)n_eval * 2); DM(W.gw_prev, (size_t)n_eval * 2); }
-        DM(W.actions, n_eval); DM(W.rewards, n_eval); DM(W.dones, n_eval); DM(W.pending, n_eval); DM(W.ep_reward, n_eval); DM(W.ep_step, n_eval); DM(W.fin_eps, n_eval); DM(W.fin_reward, n_eval);
-        DM(e->eval_roll, DQN_ROLL_RECORDS);
-        free_eval_state(e);      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
-        for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-            DM(e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(e->eval_gx[i], (size_t)e->L[i].N * n_eval);
-        }
-        e->eval_n = n_eval;
-    }
     for (int i = 0; i < e->nl; i++) if (e->eval_h[i]) {      // resetstate!(policy) of the evaluation: state0 of the online net on every stream
         launch_bcast_state(e->stream, e->p_on + e->L[i].h0_off, e->L[i].H, n_eval, e->eval_h[i]);
         if (e->eval_c[i]) launch_bcast_state(e->stream, e->p_on + e->L[i].c0_off, e->L[i].H, n_eval, e->eval_c[i]);

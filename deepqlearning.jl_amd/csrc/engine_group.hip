@@ -21,6 +21,11 @@ struct dqn_group {
     std::vector<RolloutDev> roll_host; RolloutDev* roll_dev = nullptr;
     std::vector<float> xtab_host; float* xtab_dev = nullptr; size_t xtab_cap = 0;
     struct RolloutScalars *ro_dev = nullptr, *ro_host = nullptr;      // ro_host: pinned
+    // dqn_evaluate_many: the members' evaluation records (rebuilt and uploaded per call: ONE H2D copy), the head outputs of every member's copies (ONE device array),
+    // the per-member sums of a call
+    std::vector<TinyEvalArgs> eval_host; TinyEvalArgs* eval_dev = nullptr;
+    float* heads_dev = nullptr; size_t heads_cap = 0;
+    EvalSums *es_dev = nullptr, *es_host = nullptr;      // es_host: pinned
 };
 
 // per member, what k_publish_scalars does for a standalone engine after the last step of a call: globalnorm = the fold of the step's per-block maxima (ONE slot, the
@@ -84,6 +89,8 @@ extern "C" int dqn_group_destroy(dqn_group_t* g) {
     if (g->stream) hipStreamDestroy(g->stream);
     if (g->out_host) hipHostFree(g->out_host);
     if (g->ro_host) hipHostFree(g->ro_host);
+    if (g->es_host) hipHostFree(g->es_host);
+    hipFree(g->es_dev); hipFree(g->heads_dev); hipFree(g->eval_dev);
     hipFree(g->ro_dev); hipFree(g->xtab_dev); hipFree(g->roll_dev); hipFree(g->act_dev);
     hipFree(g->out_dev); hipFree(g->args_dev);
     delete g;
@@ -337,6 +344,120 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
         const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
         if (o.err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o.step, more);
         return fail("member %d: device-side error %d at or before train step %llu%s", bad, o.err, o.step, more);
+    }
+    return 0;
+}
+
+// ---------------------------------------------------------------- grouped evaluation: dqn_evaluate_many (tiny_eval.hip)
+// the dynamic-LDS layout of the single-workgroup evaluation, in floats: the online parameters, the staging area of the sums (n_eval Float64 + n_eval Int32), then for ONE
+// TILE of tw copies the policy input x[E][tw] and per layer its activations [N][tw] (every part 16-byte aligned).  The tile width is the widest multiple of 4 the budget
+// of tiny_act_decline (144 KB with the kernel's static arrays, TINY_ACT_TAIL_LDS) leaves room for, at most n_eval rounded up to 4; 0: not even four copies fit.
+// t != null: the offsets are recorded
+static const size_t TINY_EVAL_LDS_FLOATS = (144 * 1024 - TINY_ACT_TAIL_LDS) / 4;
+static size_t tiny_eval_layout(const dqn_engine* e, int n_eval, TinyEvalArgs* t) {
+    size_t fl = 0; TinyEvalArgs tmp; TinyEvalArgs& T = t ? *t : tmp;
+    auto take = [&](size_t m) { const int o = (int)fl; fl += (m + 3) / 4 * 4; return o; };
+    T.a.p_off = take(e->Pint); T.r_off = take((size_t)3 * n_eval);
+    size_t per_copy = (size_t)e->E; for (int i = 0; i < e->nl; i++) per_copy += (size_t)e->L[i].N;
+    const size_t room = fl < TINY_EVAL_LDS_FLOATS ? (TINY_EVAL_LDS_FLOATS - fl) / per_copy / 4 * 4 : 0;
+    T.tw = (int)std::min<size_t>(room, ((size_t)n_eval + 3) / 4 * 4);
+    T.a.x_off = take((size_t)e->E * T.tw);
+    for (int i = 0; i < e->nl && i < TINY_MAX_LAYERS; i++) T.a.y_off[i] = take((size_t)e->L[i].N * T.tw);
+    return fl;
+}
+// THE eligibility rule of the single-workgroup evaluation: empty when the engine takes it, else the reason in words.  It does not depend on n_eval (judged at the
+// largest, 1024, whose staging area is the widest) nor on the training copies.  NOT every network that passes tiny_decline passes: that rule bounds 3 P + (2 E + 4 sum N)
+// batch_size floats, so at batch_size = 1 a Dense(7000, 1) passes it, and four of its columns (28 000 floats beside 7001 parameters) exceed the 25 856 floats of a
+// workgroup here.  A member with P at the limit of 16 384 fits while E + sum N <= 1600; every network of the README's tables is far inside
+std::string tiny_eval_decline(const dqn_engine* e) {
+    char buf[240];
+    if (!e->has_envs) return "it has no device environments (dqn_envs_create / dqn_envs_create_tabular)";
+    const std::string why = tiny_decline(e);
+    if (!why.empty()) return why;
+    TinyEvalArgs t;
+    if (tiny_eval_layout(e, 1024, &t), t.tw < 4) {
+        size_t per_copy = (size_t)e->E; for (int i = 0; i < e->nl; i++) per_copy += (size_t)e->L[i].N;
+        snprintf(buf, sizeof buf, "its %zu parameters and a tile of 4 evaluation copies (%zu floats of policy input and activations each) do not fit the %zu floats of LDS of one workgroup",
+                 e->Pint, per_copy, TINY_EVAL_LDS_FLOATS - 3072);
+        return buf;
+    }
+    return std::string();
+}
+// everything dqn_evaluate_many and dqn_evaluate_many_info refuse, before anything is enqueued or changed
+static int evaluate_many_check(const char* fn, dqn_group* g, int n_eval, int max_episode_length) {
+    if (!g) return fail("null group handle");
+    if (n_eval < 1 || n_eval > 1024) return fail("%s: n_eval = %d is outside 1..1024", fn, n_eval);
+    if (max_episode_length < 1) return fail("%s: max_episode_length = %d, at least 1 is needed", fn, max_episode_length);
+    for (int k = 0; k < g->K; k++) {
+        const std::string why = tiny_eval_decline(g->members[k]);
+        if (!why.empty()) return fail("%s: member %d does not take the single-workgroup evaluation: %s", fn, k, why.c_str());
+    }
+    return 0;
+}
+
+extern "C" int dqn_evaluate_many_info(dqn_group_t* g, int n_eval, int max_episode_length, int* launches, int* steps_per_launch, unsigned* max_lds_bytes) {
+    if (evaluate_many_check("dqn_evaluate_many_info", g, n_eval, max_episode_length)) return -1;
+    unsigned lds = 0;
+    for (int k = 0; k < g->K; k++) lds = std::max(lds, (unsigned)(tiny_eval_layout(g->members[k], n_eval, nullptr) * 4));
+    if (launches) *launches = (max_episode_length + 1 + TINY_EVAL_STEPS - 1) / TINY_EVAL_STEPS;
+    if (steps_per_launch) *steps_per_launch = TINY_EVAL_STEPS;
+    if (max_lds_bytes) *max_lds_bytes = lds;
+    return 0;
+}
+
+extern "C" int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_length, const uint64_t* seeds, double* avg_reward, double* avg_steps) {
+    if (evaluate_many_check("dqn_evaluate_many", g, n_eval, max_episode_length)) return -1;
+    if (!seeds) return fail("dqn_evaluate_many: seeds is NULL (one seed per member)");
+    if (!avg_reward && !avg_steps) return fail("dqn_evaluate_many: avg_reward and avg_steps are both NULL");
+    HIPCHK(hipSetDevice(g->device));
+    const int K = g->K; const size_t Ks = (size_t)K;
+    if (!g->eval_dev) { DM(g->eval_dev, Ks); DM(g->es_dev, Ks); HIPCHK(hipHostMalloc((void**)&g->es_host, sizeof(EvalSums) * Ks, hipHostMallocDefault)); g->eval_host.resize(Ks); }
+    // the members' evaluation copies (allocated as dqn_evaluate allocates them, on first use and when n_eval changes) and the head outputs of all of them
+    size_t nheads = 0;
+    for (dqn_engine* e : g->members) { if (eval_envs_ensure(e, n_eval)) return -1; nheads += (size_t)(e->nA + (e->hp.dueling ? 1 : 0)) * n_eval; }
+    if (nheads > g->heads_cap) {
+        HIPCHK(hipStreamSynchronize(g->stream)); hipFree(g->heads_dev); g->heads_dev = nullptr; g->heads_cap = 0;
+        DM(g->heads_dev, nheads); g->heads_cap = nheads;
+    }
+    // the call's records: the member's acting record with the evaluation set (this call's seed and episode bound) in the place of the training set, laid out by tile
+    unsigned lds = 0; size_t hoff = 0;
+    for (int k = 0; k < K; k++) {
+        dqn_engine* e = g->members[k]; TinyEvalArgs& T = g->eval_host[(size_t)k];
+        memset(&T, 0, sizeof T);
+        if (tiny_act_record(e, &g->eval_dev[k].roll, &T.a)) return -1;
+        T.a.lds_bytes = (unsigned)(tiny_eval_layout(e, n_eval, &T) * 4); lds = std::max(lds, T.a.lds_bytes);
+        T.a.V = e->eval_env; T.a.V.seed = seeds[k]; T.a.V.max_episode_length = max_episode_length;      // (the engine's own copy keeps what its evaluation program was built with)
+        T.roll.eps_steps = 1.0f;      // t = 0; the eps schedule (0, 0, 1): always greedy
+        T.heads = g->heads_dev + hoff; hoff += (size_t)(e->nA + (e->hp.dueling ? 1 : 0)) * n_eval;
+        T.out = g->es_dev + k;
+    }
+    if (tiny_eval_raise_lds(lds)) return fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
+    // in: the group's stream behind everything the members have enqueued
+    for (int k = 0; k < K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
+    (void)hipGetLastError();
+    for (dqn_engine* e : g->members) e->env_q_valid = false;      // the evaluation copies' forward writes pol_q / pol_a, as dqn_evaluate's does
+    int rc = 0;
+    hipError_t he = hipMemcpyAsync(g->eval_dev, g->eval_host.data(), sizeof(TinyEvalArgs) * Ks, hipMemcpyHostToDevice, g->stream);      // (the host array is the group's: it outlives the copy)
+    if (he != hipSuccess) rc = fail("dqn_evaluate_many: HIP error %s uploading the call's records", hipGetErrorString(he));
+    const int total = max_episode_length + 1;      // while !done && step <= max_episode_length
+    for (int s0 = 0; s0 < total && !rc; s0 += TINY_EVAL_STEPS) {
+        const int ns = std::min(TINY_EVAL_STEPS, total - s0);
+        if (launch_tiny_eval(g->stream, g->eval_dev, K, lds, ns, s0 == 0 ? 1 : 0, s0 + ns >= total ? 1 : 0)) rc = fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
+    }
+    if (!rc) {
+        he = hipGetLastError();
+        if (he == hipSuccess) he = hipMemcpyAsync(g->es_host, g->es_dev, sizeof(EvalSums) * Ks, hipMemcpyDeviceToHost, g->stream);
+        if (he != hipSuccess) rc = fail("dqn_evaluate_many: HIP error %s behind the group's evaluation", hipGetErrorString(he));
+    }
+    // out: every member's stream behind whatever the group enqueued -- on the error paths too
+    he = hipEventRecord(g->ev_done, g->stream);
+    for (int k = 0; k < K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
+    const hipError_t hs = hipStreamSynchronize(g->stream);
+    if (rc) return rc;
+    if (he != hipSuccess || hs != hipSuccess) return fail("dqn_evaluate_many: HIP error %s ordering the members' streams behind the group", hipGetErrorString(he != hipSuccess ? he : hs));
+    for (int k = 0; k < K; k++) {      // avg_r /= n_eval; avg_steps /= n_eval (dqn_evaluate's last lines)
+        if (avg_reward) avg_reward[k] = g->es_host[k].reward_sum / n_eval;
+        if (avg_steps) avg_steps[k] = (double)g->es_host[k].steps / n_eval;
     }
     return 0;
 }

@@ -714,5 +714,19 @@ function rollout_info(g::EngineGroup)      # (launches per vector step, dynamic 
     check(ccall((:dqn_rollout_many_info, LIB), Cint, (Ptr{Cvoid}, Ref{Cint}, Ref{Cuint}), g.h, n, lds))
     Int(n[]), Int(lds[])
 end
+# ---- grouped evaluation (dqn_evaluate_many): basic_evaluation of EVERY member, n_eval greedy episodes each, the whole episode loop inside the kernel.  seeds: one per
+# member.  Returns K (avg_reward, avg_steps) pairs; member k's is bit for bit what evaluate(g.members[k], n_eval, max_episode_length; seed = seeds[k]) returns
+function evaluate(g::EngineGroup, n_eval, max_episode_length; seeds)
+    K = length(g.members)
+    length(seeds) == K || error("evaluate: $(length(seeds)) seeds were given for $K members (one per member)")
+    sd = UInt64[UInt64(s) for s in seeds]; r = Vector{Float64}(undef, K); st = Vector{Float64}(undef, K)
+    check(ccall((:dqn_evaluate_many, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ptr{UInt64}, Ptr{Float64}, Ptr{Float64}), g.h, n_eval, max_episode_length, sd, r, st))
+    [(r[k], st[k]) for k in 1:K]
+end
+function evaluate_info(g::EngineGroup, n_eval, max_episode_length)      # (launches per call, vector steps per launch at most, dynamic LDS bytes); throws with the member and the reason where one is declined
+    n = Ref{Cint}(0); b = Ref{Cint}(0); lds = Ref{Cuint}(0)
+    check(ccall((:dqn_evaluate_many_info, LIB), Cint, (Ptr{Cvoid}, Cint, Cint, Ref{Cint}, Ref{Cint}, Ref{Cuint}), g.h, n_eval, max_episode_length, n, b, lds))
+    Int(n[]), Int(b[]), Int(lds[])
+end
 
 end # module

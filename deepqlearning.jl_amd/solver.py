@@ -476,14 +476,15 @@ class _Marks:
     save_next: bool = False                            # set at t % save_freq == 0, consumed at the next evaluation (src/solver.jl:109-113,150-152)
 
 
-def _device_marks(solver, env, policy, nxt, mk, d_eps, d_rew, loss, grad_norm):
-    """the eval / save / log marks of the device loop at vector step nxt (dqn_train_device and solve_many)"""
+def _device_marks(solver, env, policy, nxt, mk, d_eps, d_rew, loss, grad_norm, evaluated=None):
+    """the eval / save / log marks of the device loop at vector step nxt (dqn_train_device and solve_many).  evaluated: the (avg_reward, avg_steps) of this member's
+    basic_evaluation at this mark where the caller already has it (solve_many: one EngineGroup.evaluate for all members), else the member's own dqn_evaluate runs"""
     e = policy.engine
     if nxt % solver.save_freq == 0:
         mk.save_next = True
     if nxt % solver.eval_freq == 0:
         if solver.evaluation_policy is basic_evaluation:        # the default rollout evaluation also runs on the device
-            mk.scores_eval, steps_eval = e.evaluate(min(solver.num_ep_eval, 1024), solver.max_episode_length, seed=solver.seed + nxt)
+            mk.scores_eval, steps_eval = evaluated if evaluated is not None else e.evaluate(min(solver.num_ep_eval, 1024), solver.max_episode_length, seed=solver.seed + nxt)
             if solver.verbose:
                 print(f"Evaluation ... Avg Reward {mk.scores_eval:2.2f} | Avg Step {steps_eval:2.2f}")
         else:
@@ -500,6 +501,7 @@ def _device_marks(solver, env, policy, nxt, mk, d_eps, d_rew, loss, grad_norm):
 
 
 _MANY_EQUAL = ("train_freq", "target_update_freq", "max_steps", "train_start", "buffer_size", "batch_size", "eval_freq", "log_freq", "save_freq", "device")
+_MANY_EVAL_EQUAL = ("num_ep_eval", "max_episode_length")      # ... and these across the members that keep basic_evaluation: ONE EngineGroup.evaluate serves them all
 
 
 def check_many(solvers, member_envs):
@@ -520,10 +522,28 @@ def check_many(solvers, member_envs):
                 raise DQNError(f"solve_many: {f} differs between solvers 0 and {k} ({getattr(solvers[0], f)} vs {getattr(solvers[k], f)}): the members run in lock step")
         if member_envs[k].n != member_envs[0].n:
             raise DQNError(f"solve_many: env.n differs between solvers 0 and {k} ({member_envs[0].n} vs {member_envs[k].n}): the members run in lock step")
+    basic = [k for k, s in enumerate(solvers) if s.evaluation_policy is basic_evaluation]
+    for k in basic[1:]:
+        for f in _MANY_EVAL_EQUAL:
+            if getattr(solvers[k], f) != getattr(solvers[basic[0]], f):
+                raise DQNError(f"solve_many: {f} differs between solvers {basic[0]} and {k} ({getattr(solvers[basic[0]], f)} vs {getattr(solvers[k], f)}): "
+                               "one grouped evaluation serves every member that keeps basic_evaluation (a member with its own evaluation_policy is free)")
     for j in range(len(solvers)):
         for k in range(j + 1, len(solvers)):
             if solvers[j].logdir is not None and solvers[k].logdir is not None and os.path.abspath(solvers[j].logdir) == os.path.abspath(solvers[k].logdir):
                 raise DQNError(f"solve_many: logdir is the same for solvers {j} and {k} ({solvers[j].logdir!r}): each member saves its own qnetwork.bson (or pass logdir=None)")
+
+
+def _group_evaluate(group, solvers, nxt):
+    """the basic_evaluation of every member at the eval mark nxt, as ONE EngineGroup.evaluate (dqn_evaluate_many): [(avg_reward, avg_steps) or None] * K -- None for a
+    member with its own evaluation_policy, which keeps calling it (the group call evaluates its network too; that result is dropped).  Member k's pair is bit for
+    bit what its own Engine.evaluate(min(num_ep_eval, 1024), max_episode_length, seed + nxt) returns.  check_many made num_ep_eval and max_episode_length agree"""
+    basic = [k for k, s in enumerate(solvers) if s.evaluation_policy is basic_evaluation]
+    if nxt % solvers[0].eval_freq != 0 or not basic:
+        return [None] * len(solvers)
+    s0 = solvers[basic[0]]
+    got = group.evaluate(min(s0.num_ep_eval, 1024), s0.max_episode_length, [s.seed + nxt for s in solvers])
+    return [got[k] if k in basic else None for k in range(len(solvers))]
 
 
 def solve_many(solvers, env, engine_cls=None, init_seed=1):
@@ -533,7 +553,9 @@ def solve_many(solvers, env, engine_cls=None, init_seed=1):
     dqn_train_device.  The order inside a vector step is the standalone loop's (act, add, train, sync) and every device draw is keyed by (seed, t, copy, purpose),
     so member k ends bit for bit where solve(solvers[k], env) ends.  Where a member does not take the single-workgroup acting step (too many copies for its
     network: EngineGroup.rollout_info says why) the whole run keeps the per-member loop: every member's own rollout per block up to the next train / target-sync
-    boundary, then one group train step.  `env` is one environment -- every member then works on its own deep copy of it, as given -- or a list of K."""
+    boundary, then one group train step.  In both loops the evaluation at an eval_freq mark is ONE EngineGroup.evaluate (dqn_evaluate_many) for every member that
+    keeps basic_evaluation -- those members must agree on num_ep_eval and max_episode_length (check_many) -- and a member with its own evaluation_policy keeps
+    calling it; the policies carry what the marks left (policy.scores_eval, the last evaluation's average return).  `env` is one environment -- every member then works on its own deep copy of it, as given -- or a list of K."""
     import copy
     solvers = list(solvers)
     member_envs = list(env) if isinstance(env, (list, tuple)) else [copy.deepcopy(env) for _ in solvers]
@@ -564,10 +586,11 @@ def solve_many(solvers, env, engine_cls=None, init_seed=1):
             sts = group.rollout(nxt - t + 1, t0=t, train_freq=s0.train_freq, target_update_freq=s0.target_update_freq,
                                 eps=[tb.get("eps", (1.0, 1.0, 1.0)) for tb in tabs], explore=[tb.get("explore") for tb in tabs])
             t = nxt + 1
+            evals = _group_evaluate(group, solvers, nxt)
             for k, (s, ev, p) in enumerate(zip(solvers, member_envs, policies)):
                 d_eps, d_rew = sts[k]["episodes"] - episodes[k], sts[k]["reward_sum"] - reward_sum[k]
                 episodes[k], reward_sum[k] = sts[k]["episodes"], sts[k]["reward_sum"]
-                mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, sts[k]["loss"], sts[k]["grad_norm"])
+                mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, sts[k]["loss"], sts[k]["grad_norm"], evaluated=evals[k])
         while t <= s0.max_steps:
             nxt = min(min((t + m - 1) // m * m for m in bounds), s0.max_steps)
             want_stats = nxt % s0.log_freq == 0 and any(s.verbose for s in solvers)
@@ -581,16 +604,18 @@ def solve_many(solvers, env, engine_cls=None, init_seed=1):
                 for e in engines:
                     e.sync_target()
             t = nxt + 1
+            evals = _group_evaluate(group, solvers, nxt)
             for k, (s, ev, p) in enumerate(zip(solvers, member_envs, policies)):
                 d_eps = d_rew = 0
                 if want_stats:
                     d_eps, d_rew = sts[k]["episodes"] - episodes[k], sts[k]["reward_sum"] - reward_sum[k]
                     episodes[k], reward_sum[k] = sts[k]["episodes"], sts[k]["reward_sum"]
                 if any(nxt % m == 0 for m in marks):
-                    mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, float(loss[k]), float(gn[k]))
+                    mks[k] = _device_marks(s, ev, p, nxt, mks[k], d_eps, d_rew, float(loss[k]), float(gn[k]), evaluated=evals[k])
     finally:
         group.close()
     for s, p, mk in zip(solvers, policies, mks):
+        p.scores_eval = mk.scores_eval
         if mk.model_saved and s.verbose:
             restore_best_model(s, p)
     return policies

@@ -554,6 +554,29 @@ int dqn_rollout_many(dqn_group_t* g, int n_vector_steps, const dqn_rollout_cfg* 
                      dqn_rollout_stats* out /* NULL or [K] */);
 int dqn_rollout_many_info(dqn_group_t* g, int* launches_per_vector_step /* 1 */, unsigned* max_lds_bytes /* the acting launch's dynamic LDS: the largest member's */);
 
+/* ---- grouped evaluation: basic_evaluation of all K members, the whole greedy episode loop inside the kernel (tiny_eval.hip).
+ * In evaluation mode there is no replay, no tree and no exploration, and every copy is independent of every other, so nothing forces one launch per vector step: a
+ * workgroup holds its member's parameters in LDS, resets the member's n_eval evaluation copies and repeats observe -> forward -> act! until every copy's one episode
+ * is over.  The forward runs on one TILE of copies at a time (as many columns as fit in LDS beside the parameters); a column's values depend on that column alone, so
+ * the tiling cannot change a bit.  One launch runs at most `steps_per_launch` vector steps (a compile-time bound: a caller's max_episode_length does not set a
+ * kernel's duration); a call is ceil((max_episode_length + 1) / steps_per_launch) back-to-back launches of K workgroups, whatever K is.
+ *
+ * THE LAW.  After dqn_evaluate_many(g, n_eval, L, seeds, r, s), r[k] and s[k] are bit for bit the doubles dqn_evaluate(member_k, n_eval, L, seeds[k], ...) returns:
+ * per copy the Float64 sum of its Float32 rewards, summed over the copies in ascending order in Float64, divided by n_eval; likewise the episode lengths.  Member k
+ * is left as that call leaves it: training copies, open episodes, replay, tree, counters, parameters, Adam state and the bytes of a checkpoint are unchanged, and
+ * dqn_envs_peek_q is refused until the training set steps again (the evaluation copies' forward used the policy workspace).
+ *
+ * STREAM ORDER and ERRORS are the group's (above): events in from every member's stream, events out on every path, one synchronise at the end.
+ *
+ * REFUSED before anything is enqueued or changed, naming the value (and the member): a null handle, n_eval outside 1..1024, max_episode_length < 1, NULL seeds, both
+ * outputs NULL, and a member that does not take the single-workgroup evaluation: no device environments (of any of the three kinds), or a network whose parameters
+ * and a tile of four copies do not fit the LDS of one workgroup (with P at its limit of 16 384 that is E + sum of layer widths > 1600).  The rule does not depend on
+ * the number of training copies nor on n_eval.  The per-call work does not grow with K in launches or copies: one H2D copy of the K records, the launches, one D2H
+ * copy of the K sums -- and the 2 K event operations.  Out of scope: softmax or eps in evaluation, recurrent members, caller-defined evaluation policies. */
+int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_length, const uint64_t* seeds /* [K] */, double* avg_reward /* NULL or [K] */, double* avg_steps /* NULL or [K] */);
+int dqn_evaluate_many_info(dqn_group_t* g, int n_eval, int max_episode_length, int* launches /* per call -- independent of K */, int* steps_per_launch,
+                           unsigned* max_lds_bytes /* the evaluation launch's dynamic LDS: the largest member's */);
+
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
