@@ -171,6 +171,7 @@ PROTOS = {
     "comm_exchange_bytes": [_vp, _P(C.c_int64)],
     "sim_ranks_step": [_vp, _i64p, _f32p, _f32p, _f32p],
     "debug_ktrace": [_vp, _P(C.c_uint64), _sz],
+    "debug_devmem": [_P(_sz), _P(_sz)],
     "stream_sync": [_vp],
     "stream_handle": [_vp, _P(_vp)],
     "profile_step": [_vp, C.c_int, _P(C.c_char_p), _f32p, _P(C.c_int)],
@@ -228,6 +229,14 @@ def bind(lib: C.CDLL, prefix: str, aliases=None, argtypes=None):
     le.restype = C.c_char_p
     fns["last_error"] = le
     return fns
+
+
+def debug_devmem(fns):
+    """(live blocks, live bytes) of the device and pinned memory the library holds, process-wide (dqn_debug_devmem: no handle)."""
+    blocks, nbytes = C.c_size_t(), C.c_size_t()
+    if fns["debug_devmem"](C.byref(blocks), C.byref(nbytes)) != 0:
+        raise DQNError(fns["last_error"]().decode())
+    return blocks.value, nbytes.value
 
 
 def _ptr(a, ty):

@@ -3,6 +3,7 @@
 // engine_drqn.hip (EpisodeReplayBuffer + recurrent step) and engine_envs.hip (device-resident environments) share.
 #pragma once
 #include <dlfcn.h>
+#include <limits.h>
 #include <stdarg.h>
 #include <stdlib.h>
 #include <stdio.h>
@@ -13,8 +14,8 @@
 #include <string>
 #include <vector>
 #include "common.h"
+#include "devmem.h"
 
-int fail(const char* fmt, ...);      // records the message for dqn_last_error(), returns -1
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail("HIP error %s at %s:%d (%s)", hipGetErrorString(_e), __FILE__, __LINE__, #x); } while (0)
 
 // ---------------------------------------------------------------- engine
@@ -112,14 +113,14 @@ struct dqn_engine {
     // acting programs (forward on n columns + env kernels), one for the training envs and one for the evaluation envs
     // cycle: ONE graph of `cycle_F` acting steps (+ a plain sampled train step when cycle_train) -- the device loop's unit of work between two
     // train steps; a graph launch costs ~5 us of stream time, a GridWorld vector step 28
-    struct ActProg { std::vector<Step> steps; int n = 0; bool fused_tail = false; hipGraphExec_t graph = nullptr; std::vector<void*> allocs; int state_gen = -1, state_flip = -1;
+    struct ActProg { std::vector<Step> steps; int n = 0; bool fused_tail = false; hipGraphExec_t graph = nullptr; DevScope mem; int state_gen = -1, state_flip = -1;
                      hipGraphExec_t cycle = nullptr; int cycle_F = 0; bool cycle_train = false;
                      hipGraphExec_t envc = nullptr; int envc_due = 0; };      // envc: one vector step of the reference's cadence (the acting step + its `envc_due` pipelined train steps) as ONE graph
     // act_gen: the training set's acting program with the general four-launch tail, built only where `act` has the fused one and a rollout explores by table
     // (dqn_rollout_explore): both are kept, neither is rebuilt when calls alternate.  xtab: that entry point's table in HBM (engine-owned, grown on demand; the
     // pointer travels in the RolloutDev record, not in a kernel argument, so growing it leaves the captured graphs valid)
     ActProg act_gen; float* xtab = nullptr; size_t xtab_cap = 0;
-    ActProg act, evalp; std::vector<Step>* sink = nullptr; std::vector<void*>* alloc_sink = nullptr; RolloutDev *roll = nullptr, *eval_roll = nullptr;
+    ActProg act, evalp; std::vector<Step>* sink = nullptr; DevScope* alloc_sink = nullptr; RolloutDev *roll = nullptr, *eval_roll = nullptr;
     EnvDev eval_env{}; int eval_n = 0;
     std::vector<Step> prog; size_t prog_post_begin = 0, prog_pre1_end = 0; bool prog_built = false, prio_forked = false, prio_in_bwd = false;
     int gmax_used = 0;                    // live slots of gmax_part (per-block max |g| of the step's Adam jobs): what the on-demand fold reads
@@ -143,7 +144,9 @@ struct dqn_engine {
     bool mid_big_warm = false;      // the graph of MID_BIG middle steps (dqn_train_steps) has been launched at least once (its first launch is the expensive one)
     int dp_one_state = 0;           // replicas: the WHOLE step incl. its collective(s) as ONE graph (PH_DP_ONE); state 0 untried, 1 works, -1 RCCL refused the capture
     AdamSegs adam_segs; long final_reduce_step = -1;   // deferred dW slabs: reduced inside k_adam unless a communicator needs the materialised gradient
-    std::vector<void*> prog_allocs; std::vector<std::string> prog_names;
+    std::vector<std::string> prog_names;
+    // device memory by lifetime (devmem.h; the table of scopes is DESIGN.md section 2).  prof_gate: the mapped flag dqn_profile_step's gate kernel spins on (in mem)
+    DevScope mem, prog_mem, pol_mem, pol_state_mem, env_mem, eval_mem, dp_mem; int* prof_gate = nullptr;
     // profiling
     bool profiling = false; std::vector<ProfEntry> prof;
 };
@@ -151,12 +154,16 @@ struct dqn_engine {
 void prof_begin(dqn_engine* e, const char* name);
 void prof_end(dqn_engine* e);
 #define RUN(e, name, call) do { prof_begin(e, name); call; prof_end(e); } while (0)
-template <class T> static int dmalloc(T** p, size_t n) {
-    hipError_t e = hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T));
-    if (e != hipSuccess) return fail("hipMalloc of %zu bytes failed: %s", n * sizeof(T), hipGetErrorString(e));
-    return 0;
+// THE size rule of the split-K workspace `partials`: the slabs of the widest forward (ncon columns), dW and dense dX (Bc columns) the plan cuts, and a GroupNorm layer's chunk statistics (launch_layer_fwd)
+static inline size_t partials_need(const LayerDev* L, int nl, size_t Bc, size_t ncon) {
+    size_t need = 1;
+    for (int i = 0; i < nl; i++) { const LayerDev& l = L[i];
+        const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc, INT_MAX), l.dw_kc), sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1;
+        if (sf > 1) need = std::max(need, sf * (size_t)l.out_feat * ncon); if (sw > 1) need = std::max(need, sw * ((size_t)l.K + 1) * l.N); if (sx > 1) need = std::max(need, sx * (size_t)l.in_feat * Bc);
+        if (is_gn(l.kind)) need = std::max(need, gn_part_floats(l, (int)ncon));
+    }
+    return need;
 }
-#define DM(p, n) do { if (dmalloc(&(p), (n))) return -1; } while (0)
 #define NEED_REC(e) do { if (!(e)->hp.recurrence) return fail("this engine was created with recurrence = false"); } while (0)
 
 // engine_layers.hip (host only): the geometry of every layer, or -1 with the refusal; the last layer of each stream (-1: none), the external / internal parameter counts
@@ -199,11 +206,13 @@ int policy_state(dqn_engine* e, int n, bool force_reset);
 // engine_drqn.hip
 int drqn_train_steps(dqn_engine* e, int n, float* loss, float* grad_norm);
 // engine_program.hip
+// a block of the program being built, in its scope: null after a refused allocation, which the scope latches -- the builders test the latch once at their end, whatever touches a fresh block from the host tests the pointer first
+static inline DevScope& prog_scope(dqn_engine* e) { return e->alloc_sink ? *e->alloc_sink : e->prog_mem; }
 template <class T> static T* upload(dqn_engine* e, const std::vector<T>& v) {
-    T* d = nullptr; hipMalloc((void**)&d, sizeof(T) * v.size()); hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice);
-    (e->alloc_sink ? *e->alloc_sink : e->prog_allocs).push_back(d); return d;
+    T* d = nullptr; if (prog_scope(e).get(&d, v.size())) return nullptr;
+    hipMemcpy(d, v.data(), sizeof(T) * v.size(), hipMemcpyHostToDevice); return d;
 }
-float* palloc(dqn_engine* e, size_t n);
+static inline float* palloc(dqn_engine* e, size_t n) { float* d = nullptr; prog_scope(e).get(&d, n); return d; }
 bool same_geo(const LayerDev& a, const LayerDev& b);
 void flush_valu(dqn_engine* e, std::vector<VTask>& pend, const char* name, const PrioArgs* prio = nullptr);
 void emit_reduce(dqn_engine* e, std::vector<RSeg>& segs, const char* name);

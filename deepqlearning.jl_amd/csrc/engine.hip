@@ -203,8 +203,8 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
             // instead of running into a failed allocation there
             const LayerDev& l = e->L[i]; const size_t cap = (size_t)1 << 28;
             const size_t Bc_ = (size_t)e->B * (hp->recurrence ? std::max(1, hp->trace_length) : 1), ncon_ = hp->double_q ? 2 * Bc_ : Bc_;
-            const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = l.dw_kc > 0 ? dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc_, INT_MAX), l.dw_kc) : 1, sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1;
-            if ((sf > 1 && sf * l.out_feat * ncon_ > cap) || (sw > 1 && sw * ((size_t)l.K + 1) * l.N > cap) || (sx > 1 && sx * l.in_feat * Bc_ > cap))
+            const size_t sf = dqn_nchunks(l.K, l.fwd_kc), sw = dqn_nchunks((int)std::min<size_t>((size_t)l.npos * Bc_, INT_MAX), l.dw_kc), sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1;      // (for the message)
+            if (partials_need(&l, 1, Bc_, ncon_) > cap)
                 return fail("plan: layer %d: (fwd_kc, dx_kc, dw_kc) = (%d, %d, %d) cuts its sums into %zu / %zu / %zu chunks: the slabs of one layer may hold at most 2^28 floats", i, l.fwd_kc, l.dx_kc, l.dw_kc, sf, sx, sw);
         }
         if (is_conv_kind(e->L[i].kind) && e->L[i].dw_kc > 0 && e->L[i].dw_kc % e->B && (e->B % 32 || e->L[i].dw_kc % 32)) return fail("plan: conv dw_kc must be a multiple of batch_size (or, for batch sizes divisible by 32, of 32)");
@@ -232,13 +232,14 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     if (hp->recurrence && hp->obs_dtype == DQN_OBS_U8) return fail("DeepQLearningError: obs_dtype = u8 is not supported with recurrence = true (the episode replay stores Float32 rows, src/episode_replay.jl:3-20)");
     const int Bc = e->Bc = e->T * B;            // columns per sequence set: B, or T*B time-major columns for DRQN
     e->ncon = hp->double_q ? 2 * Bc : Bc;
-    DM(e->L_dev, e->nl); HIPCHK(hipMemcpy(e->L_dev, e->L, sizeof(LayerDev) * e->nl, hipMemcpyHostToDevice));
-    DM(e->p_on, e->Pint); DM(e->p_tg, e->Pint); DM(e->grad, e->Pint); DM(e->m, e->Pint); DM(e->v, e->Pint); DM(e->io_tmp, e->P);
+    DM(e->mem, e->L_dev, e->nl); HIPCHK(hipMemcpy(e->L_dev, e->L, sizeof(LayerDev) * e->nl, hipMemcpyHostToDevice));
+    DM(e->mem, e->p_on, e->Pint); DM(e->mem, e->p_tg, e->Pint); DM(e->mem, e->grad, e->Pint); DM(e->mem, e->m, e->Pint); DM(e->mem, e->v, e->Pint); DM(e->mem, e->io_tmp, e->P);
     HIPCHK(hipMemset(e->p_on, 0, e->Pint * 4)); HIPCHK(hipMemset(e->p_tg, 0, e->Pint * 4)); HIPCHK(hipMemset(e->grad, 0, e->Pint * 4));
     HIPCHK(hipMemset(e->m, 0, e->Pint * 4)); HIPCHK(hipMemset(e->v, 0, e->Pint * 4));
-    DM(e->state, 1);
-    // scalar mailbox: a coherent, mapped pinned ring the publish launch writes and the host polls (a failure here only disables the fast path)
-    DM(e->pub_ctr, 1); HIPCHK(hipMemset(e->pub_ctr, 0, sizeof(unsigned long long)));
+    DM(e->mem, e->state, 1);
+    // scalar mailbox: a coherent, mapped pinned ring the publish launch writes and the host polls (a failure here only disables the fast path).  THE one block no DevScope
+    // owns: a mapped allocation or, where the device refuses one, plain calloc memory -- released by hand in dqn_engine_destroy, by mail_plain
+    DM(e->mem, e->pub_ctr, 1); HIPCHK(hipMemset(e->pub_ctr, 0, sizeof(unsigned long long)));
     if (hipHostMalloc((void**)&e->mail_host, sizeof(StepMail) * DQN_MAIL_SLOTS, hipHostMallocMapped | hipHostMallocCoherent) == hipSuccess) {
         memset(e->mail_host, 0, sizeof(StepMail) * DQN_MAIL_SLOTS);
         if (hipHostGetDevicePointer((void**)&e->mail_dev, e->mail_host, 0) != hipSuccess) { hipHostFree(e->mail_host); e->mail_host = nullptr; e->mail_dev = nullptr; }
@@ -249,49 +250,45 @@ static int engine_init(dqn_engine* e, const dqn_layer_desc* layers, int n_layers
     HIPCHK(hipMemcpy(e->state, &s0, sizeof s0, hipMemcpyHostToDevice));
     e->cap = hp->recurrence ? B : hp->buffer_size; while (e->cap2 < e->cap) e->cap2 <<= 1;   // DRQN keeps episodes instead (below)
     const size_t osz = hp->obs_dtype == DQN_OBS_U8 ? 1 : 4;
-    { unsigned char *a = nullptr, *b = nullptr; DM(a, (size_t)e->cap * e->E * osz); DM(b, (size_t)e->cap * e->E * osz); e->s_rows = a; e->sp_rows = b; }
-    DM(e->ra, e->cap); DM(e->rr, e->cap); DM(e->rdone, e->cap); DM(e->tree, 2 * (size_t)e->cap2);
+    { unsigned char *a = nullptr, *b = nullptr; DM(e->mem, a, (size_t)e->cap * e->E * osz); DM(e->mem, b, (size_t)e->cap * e->E * osz); e->s_rows = a; e->sp_rows = b; }
+    DM(e->mem, e->ra, e->cap); DM(e->mem, e->rr, e->cap); DM(e->mem, e->rdone, e->cap); DM(e->mem, e->tree, 2 * (size_t)e->cap2);
     HIPCHK(hipMemset(e->tree, 0, 2 * (size_t)e->cap2 * 4));
-    DM(e->st_a, dqn_engine::ADD_CHUNK); DM(e->st_r, dqn_engine::ADD_CHUNK); DM(e->st_done, dqn_engine::ADD_CHUNK); DM(e->st_td, dqn_engine::ADD_CHUNK);
-    DM(e->idx, B); HIPCHK(hipMemset(e->idx, 0, B * 8)); DM(e->idx_pre, B); HIPCHK(hipMemset(e->idx_pre, 0, B * 8)); DM(e->x0, (size_t)e->E * 2 * Bc);
-    size_t pmax = 1, jmax = 1;
+    DM(e->mem, e->st_a, dqn_engine::ADD_CHUNK); DM(e->mem, e->st_r, dqn_engine::ADD_CHUNK); DM(e->mem, e->st_done, dqn_engine::ADD_CHUNK); DM(e->mem, e->st_td, dqn_engine::ADD_CHUNK);
+    DM(e->mem, e->idx, B); HIPCHK(hipMemset(e->idx, 0, B * 8)); DM(e->mem, e->idx_pre, B); HIPCHK(hipMemset(e->idx_pre, 0, B * 8)); DM(e->mem, e->x0, (size_t)e->E * 2 * Bc);
+    size_t jmax = 1;
     for (int i = 0; i < e->nl; i++) {
         const LayerDev& l = e->L[i];
-        DM(e->act_on[i], (size_t)l.out_feat * e->ncon);
-        if (skip_dact_alias(e, i)) e->dact[i] = e->dact[l.src];      // a skip join behind an inner chain that ends without an activation: dK IS dY (an alias, never freed; skip.hip)
-        else DM(e->dact[i], (size_t)l.out_feat * Bc);
-        if (is_do(l.kind)) e->act_tg[i] = e->act_tg[l.src];      // inactive in the target pass: the consumer reads the producer's output (an alias, never freed)
-        else DM(e->act_tg[i], (size_t)l.out_feat * Bc);
-        const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
-        const size_t sw = dqn_nchunks(l.npos * Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
-        const size_t sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * Bc);
+        DM(e->mem, e->act_on[i], (size_t)l.out_feat * e->ncon);
+        if (skip_dact_alias(e, i)) e->dact[i] = e->dact[l.src];      // a skip join behind an inner chain that ends without an activation: dK IS dY (an alias, not registered; skip.hip)
+        else DM(e->mem, e->dact[i], (size_t)l.out_feat * Bc);
+        if (is_do(l.kind)) e->act_tg[i] = e->act_tg[l.src];      // inactive in the target pass: the consumer reads the producer's output (an alias, not registered)
+        else DM(e->mem, e->act_tg[i], (size_t)l.out_feat * Bc);
         jmax = std::max(jmax, (size_t)l.in_feat * Bc);
-        if (is_gn(l.kind)) pmax = std::max(pmax, gn_part_floats(l, e->ncon));      // the chunk statistics of the launches outside the train program (launch_layer_fwd)
         if (is_recurrent(l.kind)) {
             // gates, tcb (CellSeq::aux) and dcn (CellBwdArgs::dh2) belong to the cells with a gate stash: the RNN's BPTT reads h_t back from act_on and has one gate gradient
             const CellOps* C = cell_ops(l.kind);
-            DM(e->gx_on[i], (size_t)l.N * e->ncon); DM(e->gx_tg[i], (size_t)l.N * Bc); DM(e->hprev_buf[i], (size_t)l.H * Bc);
-            if (C->has_c) { DM(e->cst_on[i], (size_t)l.H * e->ncon); DM(e->cst_tg[i], (size_t)l.H * Bc); DM(e->cprev_buf[i], (size_t)l.H * Bc); }
-            if (C->ngates > 1) { DM(e->gates[i], (size_t)l.N * Bc); DM(e->tcb[i], (size_t)l.H * Bc); DM(e->dcn[i], (size_t)l.H * B); }
-            DM(e->dG[i], (C->two_dG ? 2 : 1) * (size_t)l.N * Bc); DM(e->dhn[i], (size_t)l.H * B);
+            DM(e->mem, e->gx_on[i], (size_t)l.N * e->ncon); DM(e->mem, e->gx_tg[i], (size_t)l.N * Bc); DM(e->mem, e->hprev_buf[i], (size_t)l.H * Bc);
+            if (C->has_c) { DM(e->mem, e->cst_on[i], (size_t)l.H * e->ncon); DM(e->mem, e->cst_tg[i], (size_t)l.H * Bc); DM(e->mem, e->cprev_buf[i], (size_t)l.H * Bc); }
+            if (C->ngates > 1) { DM(e->mem, e->gates[i], (size_t)l.N * Bc); DM(e->mem, e->tcb[i], (size_t)l.H * Bc); DM(e->mem, e->dcn[i], (size_t)l.H * B); }
+            DM(e->mem, e->dG[i], (C->two_dG ? 2 : 1) * (size_t)l.N * Bc); DM(e->mem, e->dhn[i], (size_t)l.H * B);
         }
     }
     if (hp->recurrence) {   // EpisodeReplayBuffer (src/episode_replay.jl:3-40): buffer_size EPISODES, first trace_length transitions of each
         e->ep_cap = hp->buffer_size; e->ep_len_host.assign((size_t)e->ep_cap, 0);
         if (hp->obs_dtype != DQN_OBS_F32) return fail("DRQN episode storage is float32 only");
-        DM(e->ep_s, (size_t)e->ep_cap * e->T * e->E); DM(e->ep_sp, (size_t)e->ep_cap * e->T * e->E); DM(e->ep_a, (size_t)e->ep_cap * e->T); DM(e->ep_r, (size_t)e->ep_cap * e->T);
-        DM(e->ep_done, (size_t)e->ep_cap * e->T); DM(e->ep_len, e->ep_cap + 2); HIPCHK(hipMemset(e->ep_len, 0, (size_t)(e->ep_cap + 2) * 4));      // + the device-side (cursor, count) of a recurrent env set
+        DM(e->mem, e->ep_s, (size_t)e->ep_cap * e->T * e->E); DM(e->mem, e->ep_sp, (size_t)e->ep_cap * e->T * e->E); DM(e->mem, e->ep_a, (size_t)e->ep_cap * e->T); DM(e->mem, e->ep_r, (size_t)e->ep_cap * e->T);
+        DM(e->mem, e->ep_done, (size_t)e->ep_cap * e->T); DM(e->mem, e->ep_len, e->ep_cap + 2); HIPCHK(hipMemset(e->ep_len, 0, (size_t)(e->ep_cap + 2) * 4));      // + the device-side (cursor, count) of a recurrent env set
         // positions past an episode's stored prefix are never read by a gather; zeroed so that an export is a function of what was added
         HIPCHK(hipMemset(e->ep_s, 0, (size_t)e->ep_cap * e->T * e->E * 4)); HIPCHK(hipMemset(e->ep_sp, 0, (size_t)e->ep_cap * e->T * e->E * 4));
         HIPCHK(hipMemset(e->ep_a, 0, (size_t)e->ep_cap * e->T * 4)); HIPCHK(hipMemset(e->ep_r, 0, (size_t)e->ep_cap * e->T * 4)); HIPCHK(hipMemset(e->ep_done, 0, (size_t)e->ep_cap * e->T));
-        DM(e->ep_idx, B); DM(e->ep_start, B); DM(e->r_a, Bc); DM(e->r_r, Bc); DM(e->r_done, Bc); DM(e->r_mask, Bc);
+        DM(e->mem, e->ep_idx, B); DM(e->mem, e->ep_start, B); DM(e->mem, e->r_a, Bc); DM(e->mem, e->r_r, Bc); DM(e->mem, e->r_done, Bc); DM(e->mem, e->r_mask, Bc);
     }
-    e->partials_elems = pmax; DM(e->partials, 2 * pmax);   // second half: the target net's split-K partials (fused on+tg launches)
-    DM(e->join_tmp, jmax); DM(e->gmax_part, gmax_slots(e->Pint)); HIPCHK(hipMemset(e->gmax_part, 0, (size_t)gmax_slots(e->Pint) * 4));
-    DM(e->w_is, B); DM(e->td, Bc); DM(e->q_on_s, (size_t)B * e->nA); DM(e->q_on_sp, (size_t)B * e->nA); DM(e->q_tg_sp, (size_t)B * e->nA);
-    DM(e->ytarget, B); DM(e->best, B);
-    DM(e->gb_rows, (size_t)B * e->E); DM(e->gb_r, B); DM(e->gb_done, B); DM(e->gb_w, B); DM(e->gb_a, B); DM(e->gb_idx, B);
-    DM(e->gb_r2, B); DM(e->gb_done2, B); DM(e->gb_w2, B); DM(e->gb_a2, B);
+    if (grow(e->mem, &e->partials, &e->partials_elems, partials_need(e->L, e->nl, Bc, e->ncon), 0)) return -1;
+    DM(e->mem, e->join_tmp, jmax); DM(e->mem, e->gmax_part, gmax_slots(e->Pint)); HIPCHK(hipMemset(e->gmax_part, 0, (size_t)gmax_slots(e->Pint) * 4));
+    DM(e->mem, e->w_is, B); DM(e->mem, e->td, Bc); DM(e->mem, e->q_on_s, (size_t)B * e->nA); DM(e->mem, e->q_on_sp, (size_t)B * e->nA); DM(e->mem, e->q_tg_sp, (size_t)B * e->nA);
+    DM(e->mem, e->ytarget, B); DM(e->mem, e->best, B);
+    DM(e->mem, e->gb_rows, (size_t)B * e->E); DM(e->mem, e->gb_r, B); DM(e->mem, e->gb_done, B); DM(e->mem, e->gb_w, B); DM(e->mem, e->gb_a, B); DM(e->mem, e->gb_idx, B);
+    DM(e->mem, e->gb_r2, B); DM(e->mem, e->gb_done2, B); DM(e->mem, e->gb_w2, B); DM(e->mem, e->gb_a2, B);
     HIPCHK(hipStreamSynchronize(e->stream));
     return 0;
 }
@@ -306,14 +303,11 @@ void drop_graphs(dqn_engine* e) {
 }
 void drop_act(dqn_engine* e, dqn_engine::ActProg& a) {
     drop_act_graphs(a);
-    if (!a.allocs.empty()) hipStreamSynchronize(e->stream);
-    for (void* p : a.allocs) hipFree(p);
-    a.allocs.clear(); a.steps.clear(); a.n = 0;
+    if (!a.mem.blocks.empty()) hipStreamSynchronize(e->stream);
+    a.mem.release(); a.steps.clear(); a.n = 0;
 }
 static void free_policy_ws(dqn_engine* e) {
-    hipFree(e->pol_obs); hipFree(e->pol_x); hipFree(e->pol_q); hipFree(e->pol_a);
-    for (int i = 0; i < e->nl; i++) { if (!is_do(e->L[i].kind)) hipFree(e->pol_act[i]); e->pol_act[i] = nullptr; }      // (a Dropout layer's is its producer's)
-    e->pol_obs = e->pol_x = e->pol_q = nullptr; e->pol_a = nullptr; e->pol_n = 0; e->env_q_valid = false;
+    e->pol_mem.release(); e->pol_obs = e->pol_x = e->pol_q = nullptr; e->pol_a = nullptr; e->pol_n = 0; e->env_q_valid = false; for (int i = 0; i < e->nl; i++) e->pol_act[i] = nullptr;
 }
 extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     if (!e) return 0;
@@ -322,34 +316,15 @@ extern "C" int dqn_engine_destroy(dqn_engine_t* e) {
     if (e->stream) hipStreamSynchronize(e->stream);
     drop_graphs(e);
     if (e->comm && g_rccl.CommDestroy) g_rccl.CommDestroy(e->comm);
-    if (e->ktrace_buf) { gemm_set_ktrace(nullptr); hipFree(e->ktrace_buf); }
-    hipFree(e->L_dev); hipFree(e->p_on); hipFree(e->p_tg); hipFree(e->grad); hipFree(e->m); hipFree(e->v); hipFree(e->io_tmp); hipFree(e->state);
-    hipFree(e->s_rows); hipFree(e->sp_rows); hipFree(e->ra); hipFree(e->rr); hipFree(e->rdone); hipFree(e->tree);
-    if (e->state_host) hipHostFree(e->state_host);
-    if (e->mail_host) { if (e->mail_plain) free(e->mail_host); else hipHostFree(e->mail_host); }
-    if (e->draw_idx_h) hipHostFree(e->draw_idx_h);
-    if (e->draw_start_h) hipHostFree(e->draw_start_h);
+    if (e->ktrace_buf) gemm_set_ktrace(nullptr); if (e->mail_host) { if (e->mail_plain) free(e->mail_host); else hipHostFree(e->mail_host); }      // (the one block outside the scopes: engine_init)
+    free_policy_ws(e); free_envs(e) /* drops the three acting programs */; e->pol_state_mem.release(); e->dp_mem.release(); e->prog_mem.release(); e->mem.release();
     for (int k = 0; k < 4; k++) if (e->draw_ev[k]) hipEventDestroy(e->draw_ev[k]);
-    hipFree(e->pub_ctr);
-    hipFree(e->st_a); hipFree(e->st_r); hipFree(e->st_done); hipFree(e->st_td); hipFree(e->idx); hipFree(e->idx_pre); hipFree(e->x0);
-    for (int i = 0; i < e->nl; i++) { hipFree(e->act_on[i]); if (!is_do(e->L[i].kind)) hipFree(e->act_tg[i]); if (!skip_dact_alias(e, i)) hipFree(e->dact[i]); }
-    hipFree(e->join_tmp); hipFree(e->partials); hipFree(e->gmax_part); hipFree(e->w_is); hipFree(e->td); hipFree(e->q_on_s); hipFree(e->q_on_sp); hipFree(e->q_tg_sp);
-    hipFree(e->ytarget); hipFree(e->best); hipFree(e->gb_rows); hipFree(e->gb_r); hipFree(e->gb_done); hipFree(e->gb_w); hipFree(e->gb_a); hipFree(e->gb_idx);
-    hipFree(e->gb_r2); hipFree(e->gb_done2); hipFree(e->gb_w2); hipFree(e->gb_a2);
-    free_policy_ws(e); free_envs(e); hipFree(e->dp_send); hipFree(e->dp_recv);
-    for (void* p : e->prog_allocs) hipFree(p);
-    hipFree(e->ep_s); hipFree(e->ep_sp); hipFree(e->ep_a); hipFree(e->ep_r); hipFree(e->ep_done); hipFree(e->ep_len); hipFree(e->ep_idx); hipFree(e->ep_start);
-    hipFree(e->r_a); hipFree(e->r_r); hipFree(e->r_done); hipFree(e->r_mask);
-    for (int i = 0; i < e->nl; i++) { hipFree(e->gx_on[i]); hipFree(e->gx_tg[i]); hipFree(e->cst_on[i]); hipFree(e->cst_tg[i]); hipFree(e->gates[i]); hipFree(e->tcb[i]); hipFree(e->hprev_buf[i]);
-        hipFree(e->cprev_buf[i]); hipFree(e->dG[i]); hipFree(e->dhn[i]); hipFree(e->dcn[i]); for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); } hipFree(e->pol_gx[i]); }
     if (e->stream) hipStreamDestroy(e->stream);
     if (e->stream2) hipStreamDestroy(e->stream2);
     if (e->stream3) hipStreamDestroy(e->stream3);
     if (e->ev_xa) hipEventDestroy(e->ev_xa); if (e->ev_xb) hipEventDestroy(e->ev_xb); if (e->ev_xc) hipEventDestroy(e->ev_xc);
-    hipFree(e->dp_recv_b); hipFree(e->sim_idx); hipFree(e->sim_td);
     if (e->ev_fork) hipEventDestroy(e->ev_fork);
     if (e->ev_join) hipEventDestroy(e->ev_join);
-
     delete e; return 0;
 }
 extern "C" int dqn_engine_get_plan(dqn_engine_t* e, dqn_layer_plan* p) { if (!e) return fail("null engine handle");
@@ -829,7 +804,7 @@ int fetch_scalars(dqn_engine* e, float* loss, float* gn) {
     // globalnorm (helpers.jl:38-46): fold the Adam kernel's per-block maxima only when the host asks for the scalar
     if (gn) launch_update_priorities(e->stream, 0, e->cap2, e->idx, e->td, e->hp.prio_eps, e->hp.prio_alpha, e->tree, e->state, 1, 1.0, 1.0, e->gmax_part, (e->gmax_used > 0 && e->gmax_used <= gmax_slots(e->Pint)) ? e->gmax_used : gmax_slots(e->Pint));
     // pinned landing buffer: a device -> pageable copy is staged and costs ~100 us per call (seen as a fixed cost of every dqn_train_steps)
-    if (!e->state_host) HIPCHK(hipHostMalloc((void**)&e->state_host, sizeof(StepState), hipHostMallocDefault));
+    if (!e->state_host && e->mem.get_pinned(&e->state_host, 1, hipHostMallocDefault)) return -1;
     HIPCHK(hipMemcpyAsync(e->state_host, e->state, sizeof(StepState), hipMemcpyDeviceToHost, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));
     const StepState s = *e->state_host;
     if (s.err) { HIPCHK(hipMemsetD32Async((hipDeviceptr_t)&e->state->err, 0, 1, e->stream)); HIPCHK(hipStreamSynchronize(e->stream)); }      // reported once, not on every later call
@@ -905,7 +880,7 @@ extern "C" int dqn_sim_ranks_step(dqn_engine_t* e, const int64_t* idx, float* lo
     if (check_idx(e, idx, k * B)) return -1;
     if (build_program(e)) return -1;
     if (!e->dp_gather) return fail("DQN_SIM_WORLD needs the gather exchange (no wide dense layer in this network, or DQN_DP_ALLREDUCE is set)");
-    if (!e->sim_idx) { DM(e->sim_idx, (size_t)k * B); DM(e->sim_td, (size_t)k * B); }      // per-rank index / TD copies: owned by the engine, allocated once (sim_world and B are fixed at create)
+    if (!e->sim_idx) { DM(e->dp_mem, e->sim_idx, (size_t)k * B); DM(e->dp_mem, e->sim_td, (size_t)k * B); }      // per-rank index / TD copies: owned by the engine, allocated once (sim_world and B are fixed at create)
     long long* s_idx = e->sim_idx; float* s_td = e->sim_td;
     StepKey pre, post; pre.phase = PH_PRE; post.phase = PH_POST; pre.sampled = post.sampled = false;      // the given-indices PRE graph and the POST graph of run_step
     int rc = 0;
@@ -1001,19 +976,19 @@ int policy_ws(dqn_engine* e, int n) {
     HIPCHK(hipStreamSynchronize(e->stream)); free_policy_ws(e); drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
     size_t need = 1;   // split-K partials of the widest forward at n columns
     for (int i = 0; i < e->nl; i++) { const size_t sf = dqn_nchunks(e->L[i].K, e->L[i].fwd_kc); if (sf > 1) need = std::max(need, sf * (size_t)e->L[i].out_feat * n); if (is_gn(e->L[i].kind)) need = std::max(need, gn_part_floats(e->L[i], n)); }
-    if (need > e->partials_elems) { drop_graphs(e); hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * need); e->partials_elems = need; }
-    DM(e->pol_obs, (size_t)n * e->E); DM(e->pol_x, (size_t)n * e->E); DM(e->pol_q, (size_t)n * e->nA); DM(e->pol_a, n);
-    for (int i = 0; i < e->nl; i++) { if (is_do(e->L[i].kind)) e->pol_act[i] = e->pol_act[e->L[i].src]; else DM(e->pol_act[i], (size_t)e->L[i].out_feat * n); }      // Dropout: inactive when acting, the producer's output
+    if (need > e->partials_elems) { drop_graphs(e); if (grow(e->mem, &e->partials, &e->partials_elems, need, 0)) return -1; }
+    DevScope& M = e->pol_mem; DM(M, e->pol_obs, (size_t)n * e->E); DM(M, e->pol_x, (size_t)n * e->E); DM(M, e->pol_q, (size_t)n * e->nA); DM(M, e->pol_a, n);
+    for (int i = 0; i < e->nl; i++) { if (is_do(e->L[i].kind)) e->pol_act[i] = e->pol_act[e->L[i].src]; else DM(M, e->pol_act[i], (size_t)e->L[i].out_feat * n); }      // Dropout: inactive when acting, the producer's output (an alias, not registered)
     e->pol_n = n; return 0;
 }
 int policy_state(dqn_engine* e, int n, bool force_reset) {
     // Recur state of the policy network: one (h, c) column per observation stream; reset = state0 of the ONLINE net (policy.jl:32-34)
     if (!e->hp.recurrence) return 0;
     if (n != e->pol_state_n) {
+        DevScope& M = e->pol_state_mem; M.release(); e->pol_state_n = 0;      // (none until every layer has its own)
         for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
             const bool has_c = cell_ops(e->L[i].kind)->has_c;      // else the cell carries h only
-            for (int k = 0; k < 2; k++) { hipFree(e->pol_h[i][k]); hipFree(e->pol_c[i][k]); e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(e->pol_h[i][k], (size_t)e->L[i].H * n); if (has_c) DM(e->pol_c[i][k], (size_t)e->L[i].H * n); }
-            hipFree(e->pol_gx[i]); e->pol_gx[i] = nullptr; DM(e->pol_gx[i], (size_t)e->L[i].N * n);
+            for (int k = 0; k < 2; k++) { e->pol_h[i][k] = e->pol_c[i][k] = nullptr; DM(M, e->pol_h[i][k], (size_t)e->L[i].H * n); if (has_c) DM(M, e->pol_c[i][k], (size_t)e->L[i].H * n); } e->pol_gx[i] = nullptr; DM(M, e->pol_gx[i], (size_t)e->L[i].N * n);
         }
         e->pol_state_n = n; e->pol_state_gen++; force_reset = true;
     }
@@ -1091,21 +1066,14 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     e->rank = rank; e->world = world; e->sim_world = 0; e->force_comm = e->opt.force_allreduce != 0; e->dp_one_state = 0;
     // the launch program depends on the exchange mode and the world size: rebuild it on the next step
     drop_graphs(e); HIPCHK(hipStreamSynchronize(e->stream));
-    for (void* p : e->prog_allocs) hipFree(p);
-    e->prog_allocs.clear(); e->prog.clear(); e->prog_built = false; e->prog_post_begin = 0; e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs);
-    hipFree(e->dp_send); hipFree(e->dp_recv); e->dp_send = e->dp_recv = nullptr; e->dp_gather = e->dp_pack_folds = e->dp_adam_folds = false; e->dp_count = 0;
+    e->prog_mem.release(); e->prog.clear(); e->prog_built = false; e->prog_post_begin = 0; e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs);
+    e->dp_mem.release(); e->dp_send = e->dp_recv = e->dp_recv_b = e->sim_td = nullptr; e->sim_idx = nullptr; e->dp_gather = e->dp_pack_folds = e->dp_adam_folds = false; e->dp_count = 0;
     if (cgp) {
         HIPCHK(hipStreamSynchronize(e->stream));
         dqn_layer_plan defp[DQN_MAX_LAYERS]; default_plan(e->L, e->nl, e->B, defp, &e->hp, /*allow_cg*/ false);
-        size_t pmax = e->partials_elems;
-        for (int i = 0; i < e->nl; i++) {
-            LayerDev& l = e->L[i]; l.fwd_kc = defp[i].fwd_kc; l.dx_kc = defp[i].dx_kc; l.dw_kc = defp[i].dw_kc;
-            const size_t sf = dqn_nchunks(l.K, l.fwd_kc); if (sf > 1) pmax = std::max(pmax, sf * (size_t)l.out_feat * e->ncon);
-            const size_t sw = dqn_nchunks(l.npos * e->Bc, l.dw_kc); if (sw > 1) pmax = std::max(pmax, sw * (size_t)(l.K + 1) * l.N);
-            const size_t sx = !is_conv_kind(l.kind) ? dqn_nchunks(l.N, l.dx_kc) : 1; if (sx > 1) pmax = std::max(pmax, sx * (size_t)l.in_feat * e->Bc);
-        }
+        for (int i = 0; i < e->nl; i++) { LayerDev& l = e->L[i]; l.fwd_kc = defp[i].fwd_kc; l.dx_kc = defp[i].dx_kc; l.dw_kc = defp[i].dw_kc; }
         HIPCHK(hipMemcpy(e->L_dev, e->L, sizeof(LayerDev) * e->nl, hipMemcpyHostToDevice));
-        if (pmax > e->partials_elems) { hipFree(e->partials); e->partials = nullptr; DM(e->partials, 2 * pmax); e->partials_elems = pmax; }
+        if (grow(e->mem, &e->partials, &e->partials_elems, partials_need(e->L, e->nl, e->Bc, e->ncon), 0)) return -1;
     }
     return 0;
 }
@@ -1134,6 +1102,8 @@ extern "C" int dqn_comm_exchange_bytes(dqn_engine_t* e, int64_t* bytes) { if (!e
 // ---------------------------------------------------------------- misc
 extern "C" int dqn_stream_sync(dqn_engine_t* e) { if (!e) return fail("null engine handle"); HIPCHK(hipSetDevice(e->device)); HIPCHK(hipStreamSynchronize(e->stream)); return 0; }
 extern "C" int dqn_stream_handle(dqn_engine_t* e, void** s) { if (!e) return fail("null engine handle"); *s = (void*)e->stream; return 0; }
+// debug aid: live blocks and bytes of every DevScope of the process (devmem.h): what the memory tests read before an engine's life and compare after it
+extern "C" int dqn_debug_devmem(size_t* blocks, size_t* bytes) { if (blocks) *blocks = g_devmem_blocks.load(); if (bytes) *bytes = g_devmem_bytes.load(); return 0; }
 // debug aid: per-workgroup s_memtime records of the forward GEMM kernels (nn_gemm.hip, KTRACE).  out == NULL: start recording (room for 65536
 // records); out != NULL: stop and copy counter + records (n 64-bit words) to the host.  Process-wide (one engine at a time).
 // (not declared in the public header: a development hook of trace builds, bound by tools/ktrace*.py only)
@@ -1141,7 +1111,7 @@ extern "C" __attribute__((visibility("default"))) int dqn_debug_ktrace(dqn_engin
     const size_t words = 1 + 8 * 65536ull;
     HIPCHK(hipSetDevice(e->device)); HIPCHK(hipStreamSynchronize(e->stream));
     if (!out) {
-        if (!e->ktrace_buf) HIPCHK(hipMalloc((void**)&e->ktrace_buf, words * 8));
+        if (!e->ktrace_buf) DM(e->mem, e->ktrace_buf, words);
         HIPCHK(hipMemset(e->ktrace_buf, 0, words * 8));
         if (gemm_set_ktrace(e->ktrace_buf)) return fail("this library was built without -DDQN_KTRACE (DQN_EXTRA_DEF=DQN_KTRACE python __graft_entry__.py --force)");
         return 0;
@@ -1165,9 +1135,8 @@ static int profile_step(dqn_engine_t* e, int max_entries, const char** names, fl
     if (!e->hp.recurrence && e->size < e->B) return fail("AssertionError: r._curr_size >= r.batch_size");
     if (e->hp.recurrence && e->ep_size < e->B) return fail("AssertionError: r._curr_size >= r.batch_size");
     HIPCHK(hipStreamSynchronize(e->stream));
-    static int* gate = nullptr;
-    if (!gate) HIPCHK(hipHostMalloc((void**)&gate, sizeof(int), hipHostMallocMapped));
-    *gate = 0;
+    if (!e->prof_gate && e->mem.get_pinned(&e->prof_gate, 1, hipHostMallocMapped)) return -1;
+    int* const gate = e->prof_gate; *gate = 0;
     hipLaunchKernelGGL(k_gate, dim3(1), dim3(1), 0, e->stream, (volatile int*)gate);
     e->profiling = true; e->prof.clear();
     int rc = 0;

@@ -4,26 +4,14 @@
 #include "engine.h"
 
 // ---------------------------------------------------------------- vectorised environments on the device
-static void free_env_arrays(EnvDev& V) {      // the per-copy arrays of an evaluation env set (images and spec are shared with the training set)
-    hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(V.tb_s); hipFree(V.tb_o); hipFree(V.tb_oprev);
-    hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
-    memset(&V, 0, sizeof V);
-}
-static void free_eval_state(dqn_engine* e) {      // the evaluation copies' private Recur state
-    for (int i = 0; i < DQN_MAX_LAYERS; i++) { hipFree(e->eval_h[i]); hipFree(e->eval_c[i]); hipFree(e->eval_gx[i]); e->eval_h[i] = e->eval_c[i] = e->eval_gx[i] = nullptr; }
+// the evaluation copies: eval_mem holds their per-copy arrays, eval_roll and their private Recur state (images, spec and tables are the training set's)
+static void free_eval_envs(dqn_engine* e) {
+    e->eval_mem.release(); memset(&e->eval_env, 0, sizeof e->eval_env); e->eval_roll = nullptr; e->eval_n = 0; for (int i = 0; i < DQN_MAX_LAYERS; i++) e->eval_h[i] = e->eval_c[i] = e->eval_gx[i] = nullptr;
 }
 void free_envs(dqn_engine* e) {
-    EnvDev& V = e->env;
-    hipFree(e->env_images); hipFree(V.tm_s); hipFree(V.tm_prev); hipFree(V.tm_t); hipFree(V.gw_pos); hipFree(V.gw_prev); hipFree(e->roll);
-    hipFree(e->env_tab); hipFree(e->env_term); hipFree(V.tb_s); hipFree(V.tb_o); hipFree(V.tb_oprev); e->env_tab = nullptr; e->env_term = nullptr;
-    hipFree(V.actions); hipFree(V.rewards); hipFree(V.dones); hipFree(V.pending); hipFree(V.ep_reward); hipFree(V.ep_step); hipFree(V.fin_eps); hipFree(V.fin_reward);
-    e->env_images = nullptr; e->roll = nullptr; memset(&V, 0, sizeof V); e->has_envs = false; e->env_q_valid = false;
-    free_env_arrays(e->eval_env); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
-    drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp);
-    hipFree(e->xtab); e->xtab = nullptr; e->xtab_cap = 0;
-    free_eval_state(e);
-    EpStage& S = e->ep_stage;      // the open episodes go with the env set; the committed ring is the engine's
-    hipFree(S.st_s); hipFree(S.st_sp); hipFree(S.st_a); hipFree(S.st_r); hipFree(S.st_done); hipFree(S.open_len); memset(&S, 0, sizeof S);
+    drop_act(e, e->act); drop_act(e, e->act_gen); drop_act(e, e->evalp); free_eval_envs(e);
+    e->env_mem.release();      // the per-copy arrays, images, tables, roll, xtab and -- the open episodes go with the env set; the committed ring is the engine's -- ep_stage
+    memset(&e->env, 0, sizeof e->env); memset(&e->ep_stage, 0, sizeof e->ep_stage); e->has_envs = false; e->env_q_valid = false; e->env_images = nullptr; e->env_tab = nullptr; e->env_term = nullptr; e->roll = nullptr; e->xtab = nullptr; e->xtab_cap = 0;
 }
 // what every kind of env set checks before it replaces the engine's current one
 static int envs_admit(dqn_engine* e, int n_envs, int max_episode_length) {
@@ -54,29 +42,29 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
         if (e->nA != 4) return fail("TestMDP has 4 actions, the network has %d outputs", e->nA);
         V.H = e->hp.obs_h; V.W = e->hp.obs_w; V.max_time = sp->max_time;
         const size_t ib = (size_t)3 * V.H * V.W;
-        DM(e->env_images, ib); HIPCHK(hipMemcpy(e->env_images, sp->images, ib, hipMemcpyHostToDevice)); V.images = e->env_images;
-        DM(V.tm_s, (size_t)n * 4); DM(V.tm_prev, (size_t)n * 4); DM(V.tm_t, n);
+        DM(e->env_mem, e->env_images, ib); HIPCHK(hipMemcpy(e->env_images, sp->images, ib, hipMemcpyHostToDevice)); V.images = e->env_images;
+        DM(e->env_mem, V.tm_s, (size_t)n * 4); DM(e->env_mem, V.tm_prev, (size_t)n * 4); DM(e->env_mem, V.tm_t, n);
     } else if (sp->kind == DQN_ENV_GRIDWORLD) {
         if (u8) return fail("SimpleGridWorld observations are Float32[x, y]: use obs_dtype f32");
         if (e->E != 2 || e->nA != 4) return fail("SimpleGridWorld: observation has 2 elements and there are 4 actions (network: %d in, %d out)", e->E, e->nA);
         if (sp->n_reward_cells < 0 || sp->n_reward_cells > 8) return fail("at most 8 reward cells");
         V.size_x = sp->size_x; V.size_y = sp->size_y; V.tprob = sp->tprob; V.n_reward = sp->n_reward_cells;
         for (int k = 0; k < V.n_reward; k++) { V.reward_xy[k][0] = sp->reward_xy[k][0]; V.reward_xy[k][1] = sp->reward_xy[k][1]; V.reward_val[k] = sp->reward_val[k]; }
-        DM(V.gw_pos, (size_t)n * 2); DM(V.gw_prev, (size_t)n * 2);
+        DM(e->env_mem, V.gw_pos, (size_t)n * 2); DM(e->env_mem, V.gw_prev, (size_t)n * 2);
     } else return fail("unknown environment kind %d", sp->kind);
     return envs_finish(e);
 }
 // the per-copy loop state every kind shares, the open episodes of a recurrent engine, and the first reset
 static int envs_finish(dqn_engine* e) {
     EnvDev& V = e->env; const int n = V.n; const bool rec = e->hp.recurrence != 0;
-    DM(V.actions, n); DM(V.rewards, n); DM(V.dones, n); DM(V.pending, n); DM(V.ep_reward, n); DM(V.ep_step, n); DM(V.fin_eps, n); DM(V.fin_reward, n); DM(e->roll, DQN_ROLL_RECORDS);
+    DM(e->env_mem, V.actions, n); DM(e->env_mem, V.rewards, n); DM(e->env_mem, V.dones, n); DM(e->env_mem, V.pending, n); DM(e->env_mem, V.ep_reward, n); DM(e->env_mem, V.ep_step, n); DM(e->env_mem, V.fin_eps, n); DM(e->env_mem, V.fin_reward, n); DM(e->env_mem, e->roll, DQN_ROLL_RECORDS);
     HIPCHK(hipMemsetAsync(V.fin_eps, 0, (size_t)n * 8, e->stream)); HIPCHK(hipMemsetAsync(V.fin_reward, 0, (size_t)n * 8, e->stream));
     HIPCHK(hipMemsetAsync(V.actions, 0, (size_t)n * 4, e->stream)); HIPCHK(hipMemsetAsync(V.rewards, 0, (size_t)n * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->roll, 0, sizeof(RolloutDev) * DQN_ROLL_RECORDS, e->stream));
     if (rec) {      // the copies' open episodes: staging [n][T] (rows of s, rows of sp, a, r, done) and the open length
         EpStage& S = e->ep_stage; const size_t nt = (size_t)n * e->T;
         S.T = e->T; S.ep_cap = e->ep_cap;
-        DM(S.st_s, nt * e->E); DM(S.st_sp, nt * e->E); DM(S.st_a, nt); DM(S.st_r, nt); DM(S.st_done, nt); DM(S.open_len, n);
+        DM(e->env_mem, S.st_s, nt * e->E); DM(e->env_mem, S.st_sp, nt * e->E); DM(e->env_mem, S.st_a, nt); DM(e->env_mem, S.st_r, nt); DM(e->env_mem, S.st_done, nt); DM(e->env_mem, S.open_len, n);
         S.ep_s = e->ep_s; S.ep_sp = e->ep_sp; S.ep_a = e->ep_a; S.ep_r = e->ep_r; S.ep_done = e->ep_done; S.ep_len = e->ep_len; S.cur = e->ep_len + e->ep_cap;
     }
     e->has_envs = true;
@@ -134,11 +122,11 @@ extern "C" int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* s
     EnvDev& V = e->env; const int n = sp->n_envs;
     V.kind = DQN_ENV_TABULAR; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
     V.tb_S = (int)S; V.tb_O = (int)O;
-    DM(e->env_tab, tot); HIPCHK(hipMemcpy(e->env_tab, h.data(), tot * sizeof(float), hipMemcpyHostToDevice));
-    DM(e->env_term, (size_t)S); HIPCHK(hipMemcpy(e->env_term, sp->terminal, (size_t)S, hipMemcpyHostToDevice));
+    DM(e->env_mem, e->env_tab, tot); HIPCHK(hipMemcpy(e->env_tab, h.data(), tot * sizeof(float), hipMemcpyHostToDevice));
+    DM(e->env_mem, e->env_term, (size_t)S); HIPCHK(hipMemcpy(e->env_term, sp->terminal, (size_t)S, hipMemcpyHostToDevice));
     V.tb_T = e->env_tab + oT; V.tb_R = e->env_tab + oR; V.tb_Z = O ? e->env_tab + oZ : nullptr; V.tb_Z0 = O ? e->env_tab + oZ0 : nullptr; V.tb_b0 = e->env_tab + oB; V.tb_feat = e->env_tab + oF;
     V.tb_term = e->env_term;
-    DM(V.tb_s, n); DM(V.tb_o, n); DM(V.tb_oprev, n);
+    DM(e->env_mem, V.tb_s, n); DM(e->env_mem, V.tb_o, n); DM(e->env_mem, V.tb_oprev, n);
     HIPCHK(hipMemsetAsync(V.tb_oprev, 0, (size_t)n * 4, e->stream));
     return envs_finish(e);
 }
@@ -178,13 +166,8 @@ static RecurState recur_state(dqn_engine* e, bool eval) {
 // dqn_forward on a stream reset at the same points), with the state in ONE buffer set so that the step replays as a graph -- the cell writes h_t into the layer's
 // activation and c_t over c_{t-1} (element-wise: each thread reads and writes its own element), then h_t is copied over h_{t-1}.
 //   k_recur_reset (copies whose episode ended) | layers | k_env_step_rec (Q, argmax, eps-greedy, act!, staging of a / r / done) | k_env_observe_rec | k_ep_commit, k_ep_advance
-static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs) {
+static int emit_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs) {
     const int n = V.n; const bool eval = V.eval_mode != 0;
-    const int gen = eval ? -2 : e->pol_state_gen, flip = eval ? 0 : e->pol_flip;
-    if (ap.n == n && ap.state_gen == gen && ap.state_flip == flip) return 0;
-    if (policy_ws(e, std::max(n, std::max(e->env.n, e->eval_n)))) return -1;
-    drop_act(e, ap);
-    e->prog_names.reserve(512);
     const bool mf = e->hp.use_mfma != 0; const float* P = e->p_on;
     const RecurState RS = recur_state(e, eval); const EnvDev Vc = V; const EpStage ES = e->ep_stage;
     if (!eval) ap.steps.push_back({"recur_reset", [=](dqn_engine* en) { launch_recur_reset(en->stream, Vc.pending, n, RS); }});
@@ -210,20 +193,14 @@ static int build_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const E
     ap.steps.push_back({"env_step_stage", [=](dqn_engine* en) { launch_env_step_rec(en->stream, Vc, rs, Hd, ES); }});
     ap.steps.push_back({"env_observe_stage", [=](dqn_engine* en) { launch_env_observe_rec(en->stream, Vc, rs, ES, px); }});
     if (!eval) ap.steps.push_back({"episode_commit", [=](dqn_engine* en) { launch_ep_commit(en->stream, Vc, ES); }});
-    ap.n = n; ap.fused_tail = false; ap.state_gen = gen; ap.state_flip = flip; return 0;
+    ap.fused_tail = false; return 0;
 }
 // the acting program: online net forward on the n columns of pol_x (batch-innermost), then Q columns + first-max argmax
 // (action(policy, obs), src/policy.jl:38-64) -- the train step's forward emitter (emit_forward, engine_program.hip) with one pass: the same tiled kernels, plan and
 // selection rules, compiled once per n
 // general: keep the four-launch tail where the fused one would apply (a rollout that explores by table)
-static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs, bool general = false) {
+static int emit_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs, bool general) {
     const int n = V.n;
-    if (e->hp.recurrence) return build_act_program_rec(e, ap, V, rs);      // act_head.hip and the GEMM grouping below stay feed-forward only
-    if (ap.n == n) return 0;
-    if (policy_ws(e, std::max(n, std::max(e->env.n, e->eval_n)))) return -1;      // one workspace serves both env sets (no realloc when they alternate)
-    drop_act(e, ap);
-    e->prog_names.reserve(512);
-    e->sink = &ap.steps; e->alloc_sink = &ap.allocs;
     const Levels levels = net_levels(e);
     const float* P = e->p_on;
     HeadSrc head[DQN_MAX_LAYERS][2];      // [layer][0]: the acting forward is one pass
@@ -251,19 +228,30 @@ static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDe
         }
         const int Gc = n / 4, NC = La.K / 32;
         h.partials = palloc(e, (size_t)Gc * 4 * h.NO * NC); h.tickets = (unsigned*)palloc(e, (size_t)Gc);
-        hipMemsetAsync(h.tickets, 0, (size_t)Gc * 4, e->stream);
+        if (!h.tickets) return -1;      // (refused: the message is the scope's)
+        HIPCHK(hipMemsetAsync(h.tickets, 0, (size_t)Gc * 4, e->stream));
         h.q_out = e->pol_q; h.amax = e->pol_a; h.rs = rs; h.V = V; h.R = R;
-        e->sink = nullptr; e->alloc_sink = nullptr;
         ap.steps.push_back({"act_head_step", [=](dqn_engine* en) { launch_act_head(en->stream, h); }});
         ap.steps.push_back({"env_observe_tree", [=](dqn_engine* en) { launch_env_observe2(en->stream, Vc, rs, u8, srows, sprows, cap, px, 1, &R); }});
-        ap.n = n; ap.fused_tail = true; return 0;
+        ap.fused_tail = true; return 0;
     }
-    e->sink = nullptr; e->alloc_sink = nullptr; ap.fused_tail = false;
+    ap.fused_tail = false;
     ActHeads Hd; memset(&Hd, 0, sizeof Hd); Hd.adv = head[lq][0]; if (e->hp.dueling) Hd.val = head[e->last_val][0]; Hd.dueling = e->hp.dueling; Hd.q_out = e->pol_q; Hd.amax = e->pol_a;
     // act!, add_exp!, observe, episode bookkeeping
     ap.steps.push_back({"env_step_commit", [=](dqn_engine* en) { launch_env_step(en->stream, Vc, rs, Hd, R); }});
-    ap.steps.push_back({"env_observe", [=](dqn_engine* en) { launch_env_observe2(en->stream, Vc, rs, u8, srows, sprows, cap, px); }});
-    ap.n = n; return 0;
+    ap.steps.push_back({"env_observe", [=](dqn_engine* en) { launch_env_observe2(en->stream, Vc, rs, u8, srows, sprows, cap, px); }}); return 0;
+}
+// the acting program of V in ap, rebuilt when n or (recurrent engines) the Recur state it reads moved.  A refusal -- an emitter's, or an allocation of its scope refused below -- leaves ap empty, the sinks the step program's again
+static int build_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev& V, RolloutDev* rs, bool general = false) {
+    const int n = V.n; const bool rec = e->hp.recurrence != 0, eval = V.eval_mode != 0; const int gen = !rec ? -1 : eval ? -2 : e->pol_state_gen, flip = !rec ? -1 : eval ? 0 : e->pol_flip;      // (-1: ActProg's own initial values)
+    if (ap.n == n && ap.state_gen == gen && ap.state_flip == flip) return 0;
+    if (policy_ws(e, std::max(n, std::max(e->env.n, e->eval_n)))) return -1;      // one workspace serves both env sets (no realloc when they alternate)
+    drop_act(e, ap); e->prog_names.reserve(512); e->sink = &ap.steps; e->alloc_sink = &ap.mem;
+    int rc = rec ? emit_act_program_rec(e, ap, V, rs) : emit_act_program(e, ap, V, rs, general);      // act_head.hip and the GEMM grouping stay feed-forward only
+    e->sink = nullptr; e->alloc_sink = nullptr;
+    if (!rc && ap.mem.failed) { const std::string why = dqn_last_error(); rc = fail("build_act_program: a device allocation failed (%s)", why.c_str()); }
+    if (rc) { drop_act(e, ap); return -1; }
+    ap.n = n; ap.state_gen = gen; ap.state_flip = flip; return 0;
 }
 static int act_graph(dqn_engine* e, dqn_engine::ActProg& ap) {
     if (ap.graph) return 0;
@@ -306,10 +294,7 @@ int explore_check(const dqn_exploration* x, int n_steps) {
 static int explore_upload(dqn_engine* e, const dqn_exploration* x, long long t0, RolloutDev& h) {
     if (!x) return 0;
     const size_t m = (size_t)x->n_values;
-    if (m > e->xtab_cap) {
-        HIPCHK(hipStreamSynchronize(e->stream)); hipFree(e->xtab); e->xtab = nullptr; e->xtab_cap = 0;
-        const size_t cap = std::max<size_t>(256, 2 * m); DM(e->xtab, cap); e->xtab_cap = cap;
-    }
+    if (m > e->xtab_cap) { HIPCHK(hipStreamSynchronize(e->stream)); if (grow(e->env_mem, &e->xtab, &e->xtab_cap, m, 256)) return -1; }
     HIPCHK(hipMemcpyAsync(e->xtab, x->values, m * sizeof(float), hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));      // the caller's array is not kept
     h.xkind = x->kind; h.xtab = e->xtab; h.xtab_t0 = t0; h.xtab_n = x->n_values;
     return 0;
@@ -445,18 +430,14 @@ extern "C" int dqn_rollout_explore(dqn_engine_t* e, int n_steps, const dqn_rollo
 int eval_envs_ensure(dqn_engine* e, int n_eval) {
     EnvDev& W = e->eval_env;
     if (e->eval_n == n_eval) return 0;
-    HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_env_arrays(W); hipFree(e->eval_roll); e->eval_roll = nullptr; e->eval_n = 0;
-    W = e->env; W.n = n_eval; W.eval_mode = 1;
-    W.tm_s = W.tm_prev = nullptr; W.tm_t = nullptr; W.gw_pos = W.gw_prev = nullptr; W.tb_s = W.tb_o = W.tb_oprev = nullptr; W.actions = nullptr; W.rewards = nullptr; W.dones = W.pending = nullptr;
-    W.ep_reward = nullptr; W.ep_step = nullptr; W.fin_eps = nullptr; W.fin_reward = nullptr;
-    if (W.kind == DQN_ENV_TESTMDP) { DM(W.tm_s, (size_t)n_eval * 4); DM(W.tm_prev, (size_t)n_eval * 4); DM(W.tm_t, n_eval); }
-    else if (W.kind == DQN_ENV_TABULAR) { DM(W.tb_s, n_eval); DM(W.tb_o, n_eval); DM(W.tb_oprev, n_eval); }      // the tables are the training set's
-    else { DM(W.gw_pos, (size_t)n_eval * 2); DM(W.gw_prev, (size_t)n_eval * 2); }
-    DM(W.actions, n_eval); DM(W.rewards, n_eval); DM(W.dones, n_eval); DM(W.pending, n_eval); DM(W.ep_reward, n_eval); DM(W.ep_step, n_eval); DM(W.fin_eps, n_eval); DM(W.fin_reward, n_eval);
-    DM(e->eval_roll, DQN_ROLL_RECORDS);
-    free_eval_state(e);      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
-    for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {
-        DM(e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(e->eval_gx[i], (size_t)e->L[i].N * n_eval);
+    HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_eval_envs(e);
+    W = e->env; W.n = n_eval; W.eval_mode = 1; DevScope& M = e->eval_mem;
+    if (W.kind == DQN_ENV_TESTMDP) { DM(M, W.tm_s, (size_t)n_eval * 4); DM(M, W.tm_prev, (size_t)n_eval * 4); DM(M, W.tm_t, n_eval); }
+    else if (W.kind == DQN_ENV_TABULAR) { DM(M, W.tb_s, n_eval); DM(M, W.tb_o, n_eval); DM(M, W.tb_oprev, n_eval); }      // the tables are the training set's
+    else { DM(M, W.gw_pos, (size_t)n_eval * 2); DM(M, W.gw_prev, (size_t)n_eval * 2); }
+    DM(M, W.actions, n_eval); DM(M, W.rewards, n_eval); DM(M, W.dones, n_eval); DM(M, W.pending, n_eval); DM(M, W.ep_reward, n_eval); DM(M, W.ep_step, n_eval); DM(M, W.fin_eps, n_eval); DM(M, W.fin_reward, n_eval); DM(M, e->eval_roll, DQN_ROLL_RECORDS);
+    for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
+        DM(M, e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(M, e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(M, e->eval_gx[i], (size_t)e->L[i].N * n_eval);
     }
     e->eval_n = n_eval;
     return 0;

@@ -26,6 +26,7 @@ struct dqn_group {
     std::vector<TinyEvalArgs> eval_host; TinyEvalArgs* eval_dev = nullptr;
     float* heads_dev = nullptr; size_t heads_cap = 0;
     EvalSums *es_dev = nullptr, *es_host = nullptr;      // es_host: pinned
+    DevScope mem;      // owns every device and pinned block above (devmem.h)
 };
 
 // per member, what k_publish_scalars does for a standalone engine after the last step of a call: globalnorm = the fold of the step's per-block maxima (ONE slot, the
@@ -64,11 +65,8 @@ extern "C" int dqn_group_create(dqn_engine_t* const* members, int n_members, dqn
     std::vector<TinyArgs> recs((size_t)n_members);
     for (int k = 0; k < n_members; k++) { recs[k] = members[k]->tiny_args[0]; g->max_lds = std::max(g->max_lds, recs[k].lds_bytes); }
     auto bail = [&](const char* what, hipError_t err) { const int rc = fail("dqn_group_create: %s failed: %s", what, hipGetErrorString(err)); dqn_group_destroy(g); return rc; };
-    hipError_t err;
-    if ((err = hipMalloc((void**)&g->args_dev, sizeof(TinyArgs) * (size_t)n_members)) != hipSuccess) return bail("hipMalloc of the members' records", err);
+    hipError_t err; if (g->mem.get(&g->args_dev, (size_t)n_members) || g->mem.get(&g->out_dev, (size_t)n_members) || g->mem.get_pinned(&g->out_host, (size_t)n_members, hipHostMallocDefault)) { dqn_group_destroy(g); return -1; }      // (the message survives: destroy never calls fail)
     if ((err = hipMemcpy(g->args_dev, recs.data(), sizeof(TinyArgs) * (size_t)n_members, hipMemcpyHostToDevice)) != hipSuccess) return bail("the upload of the members' records", err);
-    if ((err = hipMalloc((void**)&g->out_dev, sizeof(GroupScalars) * (size_t)n_members)) != hipSuccess) return bail("hipMalloc of the scalars", err);
-    if ((err = hipHostMalloc((void**)&g->out_host, sizeof(GroupScalars) * (size_t)n_members, hipHostMallocDefault)) != hipSuccess) return bail("hipHostMalloc of the scalars", err);
     if ((err = hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking)) != hipSuccess) return bail("hipStreamCreate", err);
     if ((err = hipEventCreateWithFlags(&g->ev_done, hipEventDisableTiming)) != hipSuccess) return bail("hipEventCreate", err);
     g->ev_in.assign((size_t)n_members, nullptr);
@@ -87,12 +85,7 @@ extern "C" int dqn_group_destroy(dqn_group_t* g) {
     for (hipEvent_t ev : g->ev_in) if (ev) hipEventDestroy(ev);
     if (g->ev_done) hipEventDestroy(g->ev_done);
     if (g->stream) hipStreamDestroy(g->stream);
-    if (g->out_host) hipHostFree(g->out_host);
-    if (g->ro_host) hipHostFree(g->ro_host);
-    if (g->es_host) hipHostFree(g->es_host);
-    hipFree(g->es_dev); hipFree(g->heads_dev); hipFree(g->eval_dev);
-    hipFree(g->ro_dev); hipFree(g->xtab_dev); hipFree(g->roll_dev); hipFree(g->act_dev);
-    hipFree(g->out_dev); hipFree(g->args_dev);
+    g->mem.release();
     delete g;
     return 0;
 }
@@ -252,7 +245,7 @@ static int rollout_many_check(dqn_group* g, int n_steps, const dqn_rollout_cfg* 
 // when they differ from what the device array holds
 static int rollout_many_records(dqn_group* g) {
     const size_t K = (size_t)g->K;
-    if (!g->roll_dev) { DM(g->roll_dev, K); DM(g->act_dev, K); DM(g->ro_dev, K); HIPCHK(hipHostMalloc((void**)&g->ro_host, sizeof(RolloutScalars) * K, hipHostMallocDefault)); g->roll_host.resize(K); }
+    if (!g->ro_host) { DM(g->mem, g->roll_dev, K); DM(g->mem, g->act_dev, K); DM(g->mem, g->ro_dev, K); if (g->mem.get_pinned(&g->ro_host, K, hipHostMallocDefault)) return -1; g->roll_host.resize(K); }      // (tested by the LAST of the four)
     std::vector<TinyActArgs> recs(K); unsigned lds = 0;
     for (size_t k = 0; k < K; k++) { if (tiny_act_record(g->members[k], g->roll_dev + k, &recs[k])) return -1; lds = std::max(lds, recs[k].lds_bytes); }
     if (g->act_host.size() != K || memcmp(g->act_host.data(), recs.data(), sizeof(TinyActArgs) * K) != 0) {
@@ -288,10 +281,7 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     // the call's records and tables: ONE contiguous array each, ONE H2D copy each
     size_t nx = 0;
     for (int k = 0; k < K; k++) if (explore && explore[k]) nx += (size_t)explore[k]->n_values;
-    if (nx > g->xtab_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream)); hipFree(g->xtab_dev); g->xtab_dev = nullptr; g->xtab_cap = 0;
-        const size_t cap = std::max<size_t>(1024, 2 * nx); DM(g->xtab_dev, cap); g->xtab_cap = cap;
-    }
+    if (nx > g->xtab_cap) { HIPCHK(hipStreamSynchronize(g->stream)); if (grow(g->mem, &g->xtab_dev, &g->xtab_cap, nx, 1024)) return -1; }
     g->xtab_host.clear();
     for (int k = 0; k < K; k++) {
         dqn_engine* e = g->members[k]; const dqn_rollout_cfg& c = cfgs[k]; const int n = e->env.n;
@@ -411,14 +401,11 @@ extern "C" int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_len
     if (!avg_reward && !avg_steps) return fail("dqn_evaluate_many: avg_reward and avg_steps are both NULL");
     HIPCHK(hipSetDevice(g->device));
     const int K = g->K; const size_t Ks = (size_t)K;
-    if (!g->eval_dev) { DM(g->eval_dev, Ks); DM(g->es_dev, Ks); HIPCHK(hipHostMalloc((void**)&g->es_host, sizeof(EvalSums) * Ks, hipHostMallocDefault)); g->eval_host.resize(Ks); }
+    if (!g->es_host) { DM(g->mem, g->eval_dev, Ks); DM(g->mem, g->es_dev, Ks); if (g->mem.get_pinned(&g->es_host, Ks, hipHostMallocDefault)) return -1; g->eval_host.resize(Ks); }      // (tested by the LAST of the three)
     // the members' evaluation copies (allocated as dqn_evaluate allocates them, on first use and when n_eval changes) and the head outputs of all of them
     size_t nheads = 0;
     for (dqn_engine* e : g->members) { if (eval_envs_ensure(e, n_eval)) return -1; nheads += (size_t)(e->nA + (e->hp.dueling ? 1 : 0)) * n_eval; }
-    if (nheads > g->heads_cap) {
-        HIPCHK(hipStreamSynchronize(g->stream)); hipFree(g->heads_dev); g->heads_dev = nullptr; g->heads_cap = 0;
-        DM(g->heads_dev, nheads); g->heads_cap = nheads;
-    }
+    if (nheads > g->heads_cap) { HIPCHK(hipStreamSynchronize(g->stream)); if (grow(g->mem, &g->heads_dev, &g->heads_cap, nheads, 0)) return -1; }
     // the call's records: the member's acting record with the evaluation set (this call's seed and episode bound) in the place of the training set, laid out by tile
     unsigned lds = 0; size_t hoff = 0;
     for (int k = 0; k < K; k++) {

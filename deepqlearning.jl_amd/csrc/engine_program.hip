@@ -2,7 +2,6 @@
 // shape and plan is fixed at engine creation, so the step is compiled ONCE into a list of launches (closures) and merely replayed (and captured into a hipGraph).
 // Small independent kernels are batched: one k_valu_multi launch per network level, one k_reduce_multi per level, head reductions folded into k_td.
 #include "engine.h"
-float* palloc(dqn_engine* e, size_t n) { float* d = nullptr; hipMalloc((void**)&d, n * 4); (e->alloc_sink ? *e->alloc_sink : e->prog_allocs).push_back(d); return d; }
 bool same_geo(const LayerDev& a, const LayerDev& b) {
     return a.kind == b.kind && a.act == b.act && a.K == b.K && a.N == b.N && a.npos == b.npos && a.cin == b.cin && a.kh == b.kh && a.kw == b.kw &&
            a.sh == b.sh && a.sw == b.sw && a.ph == b.ph && a.pw == b.pw && a.dh == b.dh && a.dw == b.dw && a.groups == b.groups && a.ih == b.ih && a.iw == b.iw && a.fwd_kc == b.fwd_kc && a.src == b.src;
@@ -307,8 +306,8 @@ static int column_group_program(StepBuild& b) {
         a.hw_off[hd] = (unsigned)L.w_off; a.hb_off[hd] = (unsigned)L.b_off; a.hN[hd] = L.N; a.hact[hd] = L.act; a.h_S[hd] = dqn_nchunks(L.K, L.fwd_kc); a.h_kc[hd] = dqn_chunk_len(L.K, L.fwd_kc); }
     a.p_on = e->p_on; a.p_tg = e->p_tg; a.ep_s = e->ep_s; a.ep_sp = e->ep_sp; a.ep_a = e->ep_a; a.ep_r = e->ep_r; a.ep_done = e->ep_done; a.ep_len = e->ep_len;
     if (!e->draw_idx_h) {      // the draw ring: mapped, coherent pinned host memory (survives program rebuilds; freed with the engine)
-        HIPCHK(hipHostMalloc((void**)&e->draw_idx_h, sizeof(long long) * DQN_DRAW_SLOTS * Bb, hipHostMallocMapped | hipHostMallocCoherent));
-        HIPCHK(hipHostMalloc((void**)&e->draw_start_h, sizeof(int) * DQN_DRAW_SLOTS * Bb, hipHostMallocMapped | hipHostMallocCoherent));
+        if (e->mem.get_pinned(&e->draw_idx_h, (size_t)DQN_DRAW_SLOTS * Bb, hipHostMallocMapped | hipHostMallocCoherent)) return -1;
+        if (e->mem.get_pinned(&e->draw_start_h, (size_t)DQN_DRAW_SLOTS * Bb, hipHostMallocMapped | hipHostMallocCoherent)) return -1;
         memset(e->draw_idx_h, 0, sizeof(long long) * DQN_DRAW_SLOTS * Bb); memset(e->draw_start_h, 0, sizeof(int) * DQN_DRAW_SLOTS * Bb);
         HIPCHK(hipHostGetDevicePointer((void**)&e->draw_idx_d, e->draw_idx_h, 0)); HIPCHK(hipHostGetDevicePointer((void**)&e->draw_start_d, e->draw_start_h, 0));
         for (int k = 0; k < 4; k++) { HIPCHK(hipEventCreateWithFlags(&e->draw_ev[k], hipEventDisableTiming)); e->draw_ev_used[k] = false; }
@@ -316,7 +315,7 @@ static int column_group_program(StepBuild& b) {
     a.ring_idx = e->draw_idx_d; a.ring_np = e->draw_start_d;
     if (e->opt.drqn_probe & 4) {      // TIMING PROBE: the draws come from DEVICE memory (episode 0, one row, for every column -- wrong numbers, right schedule): what the PCIe read of the host ring costs
         long long* di = (long long*)palloc(e, (size_t)DQN_DRAW_SLOTS * Bb * 2); int* dn = (int*)palloc(e, (size_t)DQN_DRAW_SLOTS * Bb);
-        std::vector<long long> zi((size_t)DQN_DRAW_SLOTS * Bb, 0); std::vector<int> zn((size_t)DQN_DRAW_SLOTS * Bb, 1);
+        std::vector<long long> zi((size_t)DQN_DRAW_SLOTS * Bb, 0); std::vector<int> zn((size_t)DQN_DRAW_SLOTS * Bb, 1); if (!di || !dn) return -1;
         HIPCHK(hipMemcpy(di, zi.data(), zi.size() * 8, hipMemcpyHostToDevice)); HIPCHK(hipMemcpy(dn, zn.data(), zn.size() * 4, hipMemcpyHostToDevice));
         a.ring_idx = di; a.ring_np = dn;
     }
@@ -455,8 +454,9 @@ static int emit_red_head(StepBuild& b) {
     h.idx = e->idx; h.idx_pre = e->idx_pre; const int Gc = B / 4, NC = h.K / 32;
     h.partials = palloc(e, (size_t)Gc * 12 * h.NO * NC); h.tickets = (unsigned*)palloc(e, (size_t)Gc);
     h.ypm = (h.S > 1 && !e->opt.no_rh_pm) ? palloc(e, (size_t)Gc * h.nstream * h.K * 4) : nullptr;
+    if (!h.tickets) return -1;      // (refused: the message is the scope's, as below)
     HIPCHK(hipMemset(h.tickets, 0, (size_t)Gc * 4));      // armed once; every launch's last arrivers re-arm their groups
-    if (e->opt.drqn_stamps) { h.stamps = (unsigned long long*)palloc(e, 64); HIPCHK(hipMemset(h.stamps, 0, 256)); e->drqn_stamps = h.stamps; }
+    if (e->opt.drqn_stamps) { h.stamps = (unsigned long long*)palloc(e, 64); if (!h.stamps) return -1; HIPCHK(hipMemset(h.stamps, 0, 256)); e->drqn_stamps = h.stamps; }
     const RedHeadArgs* h_dev = upload(e, std::vector<RedHeadArgs>(1, h));
     e->prog.push_back({h.S == 1 ? "head_cols4" : "red_head", [=](dqn_engine* en) { launch_red_head(en->stream, h, h_dev, en->cur.sampled ? 1 : 0, en->cur.take_pre ? 1 : 0); }});
     return 0;
@@ -832,12 +832,12 @@ static int emit_dp_pack(StepBuild& b, DpSumArgs& dsum, std::vector<DpDw>& dpdw) 
     };
     for (auto& h : holes) { small(cur, h.first); cur = h.second; }
     small(cur, e->Pint); off = (off + 3) / 4 * 4;
-    if (e->dp_count != off) { hipFree(e->dp_send); hipFree(e->dp_recv); e->dp_send = e->dp_recv = nullptr; HIPCHK(hipMalloc((void**)&e->dp_send, off * 4)); HIPCHK(hipMalloc((void**)&e->dp_recv, off * 4 * W)); e->dp_count = off; }
+    DevScope& M = e->dp_mem; if (e->dp_count != off) { M.drop(e->dp_send); M.drop(e->dp_recv); e->dp_send = e->dp_recv = nullptr; e->dp_count = 0; DM(M, e->dp_send, off); DM(M, e->dp_recv, off * W); e->dp_count = off; }
     pk.send = e->dp_send; dsum.recv = e->dp_recv; dsum.stride = off; dsum.world = W; dsum.grad = e->grad;
     unsigned long long off_a = 0;      // end of the wide layers' operands inside the block
     for (auto& q : dpdw) off_a = std::max(off_a, q.d_off + (unsigned long long)q.L.N * B);
     if (b.overlap_cand && off_a % 4 == 0 && off_a < off) {
-        e->dp_overlap = true; e->dp_count_a = off_a; hipFree(e->dp_recv_b); e->dp_recv_b = nullptr; HIPCHK(hipMalloc((void**)&e->dp_recv_b, (off - off_a) * 4 * W));
+        e->dp_overlap = true; e->dp_count_a = off_a; M.drop(e->dp_recv_b); e->dp_recv_b = nullptr; DM(M, e->dp_recv_b, (off - off_a) * W);
         DpPackArgs pa; memset(&pa, 0, sizeof pa); DpPackArgs pb; memset(&pb, 0, sizeof pb); pa.send = pb.send = e->dp_send;
         for (int i = 0; i < pk.n; i++) { if (pk.r[i].dst < off_a) pa.r[pa.n++] = pk.r[i]; else pb.r[pb.n++] = pk.r[i]; }
         e->dp_pk_a = pa; pk = pb; dsum.recv = e->dp_recv_b; dsum.stride = off - off_a; for (int i = 0; i < dsum.n; i++) dsum.r[i].src -= off_a;
@@ -892,18 +892,12 @@ static void emit_adam(StepBuild& b) {
     e->gmax_used = (int)(J.segs.blocks + J.sblocks);
 }
 // The train step's program, in program order.  The first two stages build a whole step and return; the rest is the general program
-int build_program(dqn_engine* e) {
-    if (e->prog_built) return 0;
-    HIPCHK(hipSetDevice(e->device));
-    // the engine-side record of the program at rest: every exit below overwrites what its program sets differently, before anything reads it
-    e->pg_ok = false; e->adam_step = -1; e->gmax_used = 0; e->tiny = false; e->drqn_fused = false; e->arena_u8 = false; e->prio_forked = false; e->prio_in_bwd = false;
-    e->dp_gather = false; e->dp_overlap = false; e->prog_pre1_end = 0; e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs); for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0;
-    HIPCHK(hipMemsetAsync(e->gmax_part, 0, (size_t)gmax_slots(e->Pint) * 4, e->stream));      // per-block maxima of an earlier program shape must not survive
+static int build_stages(dqn_engine* e) {
     e->prog_names.reserve(512); StepBuild b(e);
     int whole = column_group_program(b);             //  1  recurrent, column-group dW chunks: drqn_cols + adam
     if (whole < 0) return whole;
     if (!whole) whole = single_workgroup_program(b); //  2  the network fits in LDS: tiny_step
-    if (whole) { e->prog_built = true; return 0; }
+    if (whole) return 0;
     choose_byte_arena(b);                            //  3  u8 replay: the observation arena in bytes
     choose_head_fusion(b);                           //  4  head level + TD + head dX as one launch, with or without the split-K reduce
     emit_forward_levels(b);                          //  5  forward levels, the recurrence behind a recurrent level
@@ -914,6 +908,20 @@ int build_program(dqn_engine* e) {
     emit_final_reduce(b);                            // 10  the dW slab reduce and adam_segs
     if (emit_replica_exchange(b)) return -1;         // 11  the replica pack layout, the post-exchange dW
     emit_adam(b);                                    // 12  the Adam launch and the pre-gather record
-    e->prog_built = true;
     return 0;
+}
+// the engine-side record of the program at rest: every exit of build_stages overwrites what its program sets differently, before anything reads it
+static void program_at_rest(dqn_engine* e) {
+    e->pg_ok = false; e->adam_step = -1; e->gmax_used = 0; e->tiny = false; e->drqn_fused = false; e->arena_u8 = false; e->prio_forked = false; e->prio_in_bwd = false;
+    e->dp_gather = false; e->dp_overlap = false; e->prog_post_begin = e->prog_pre1_end = 0; e->final_reduce_step = -1; memset(&e->adam_segs, 0, sizeof e->adam_segs); for (int i = 0; i < e->nl; i++) e->L[i].xu8 = 0; e->drqn_stamps = nullptr;
+}
+// EVERY refusal -- a stage's own, or a refused allocation of the program's scope (the closures capture those pointers by value) -- leaves an empty program: no steps, no blocks, the record at rest.  The next call starts over
+int build_program(dqn_engine* e) {
+    if (e->prog_built) return 0;
+    HIPCHK(hipSetDevice(e->device));
+    program_at_rest(e);
+    HIPCHK(hipMemsetAsync(e->gmax_part, 0, (size_t)gmax_slots(e->Pint) * 4, e->stream));      // per-block maxima of an earlier program shape must not survive
+    int rc = build_stages(e); if (!rc && e->prog_mem.failed) { const std::string why = dqn_last_error(); rc = fail("build_program: a device allocation failed (%s)", why.c_str()); }
+    if (rc) { hipStreamSynchronize(e->stream); e->prog.clear(); e->prog_mem.release(); program_at_rest(e); return -1; }
+    e->prog_built = true; return 0;
 }

@@ -577,6 +577,11 @@ int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_length, const 
 int dqn_evaluate_many_info(dqn_group_t* g, int n_eval, int max_episode_length, int* launches /* per call -- independent of K */, int* steps_per_launch,
                            unsigned* max_lds_bytes /* the evaluation launch's dynamic LDS: the largest member's */);
 
+/* ---- debug entries.
+ * dqn_debug_devmem: the device and pinned host memory the library holds at this moment, process-wide (no handle): live blocks and their bytes, over every engine and
+ * group.  Exact counters of the library's own allocations -- not what the device reports, which includes other processes.  After every handle is destroyed, and
+ * after a refused dqn_engine_create, both are what they were before.  Either pointer may be NULL. */
+int dqn_debug_devmem(size_t* blocks, size_t* bytes);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
