@@ -96,6 +96,11 @@ class TabularEnv(C.Structure):
                 ("T", C.c_void_p), ("Z", C.c_void_p), ("Z0", C.c_void_p), ("R", C.c_void_p), ("terminal", C.c_void_p), ("b0", C.c_void_p), ("features", C.c_void_p)]
 
 
+class ControlEnv(C.Structure):
+    """dqn_control_env (include/dqn_mi355x.h): MountainCar / InvertedPendulum, every constant of the laws a named double"""
+    _fields_ = [("kind", C.c_int32), ("n_envs", C.c_int32), ("max_episode_length", C.c_int32), ("seed", C.c_uint64)] + [(k, C.c_double) for k in envs._ControlEnv.FIELDS]
+
+
 class RolloutCfg(C.Structure):
     _fields_ = [("train_freq", C.c_int32), ("target_update_freq", C.c_int32),
                 ("eps_start", C.c_float), ("eps_stop", C.c_float), ("eps_steps", C.c_float), ("cadence_env_steps", C.c_int32), ("t0", C.c_int64)]
@@ -120,7 +125,7 @@ class Counters(C.Structure):
     _fields_ = [("size", C.c_int64), ("widx", C.c_int64), ("sample_ctr", C.c_uint64), ("train_steps", C.c_uint64)]
 
 
-ENV_TESTMDP, ENV_GRIDWORLD, ENV_TABULAR = 0, 1, 2
+ENV_TESTMDP, ENV_GRIDWORLD, ENV_TABULAR, ENV_MOUNTAINCAR, ENV_PENDULUM = 0, 1, 2, 3, 4
 
 _P = C.POINTER
 _f32p, _i32p, _i64p, _u8p, _f64p = _P(C.c_float), _P(C.c_int32), _P(C.c_int64), _P(C.c_uint8), _P(C.c_double)
@@ -187,6 +192,8 @@ PROTOS = {
     "set_hidden": [_vp, _f32p, _sz],
     "envs_create": [_vp, _P(EnvSpec)],
     "envs_create_tabular": [_vp, _P(TabularEnv)],
+    "envs_create_control": [_vp, _P(ControlEnv)],
+    "envs_peek_state": [_vp, _f64p, _f64p],
     "envs_reset": [_vp],
     "rollout": [_vp, C.c_int, _P(RolloutCfg), _P(RolloutStats)],
     "rollout_explore": [_vp, C.c_int, _P(RolloutCfg), _P(Exploration), _P(RolloutStats)],
@@ -518,7 +525,10 @@ class Handle:
 
     # ---- vectorised environments on the device
     def envs_create(self, env, n_envs=None, max_episode_length=100, seed=0):
-        """`env` is an envs.TestMDP / envs.SimpleGridWorld / envs.TabularPOMDP instance used as the SPEC (images, sizes, rewards, tables); its own state is not used."""
+        """`env` is an envs.TestMDP / envs.SimpleGridWorld / envs.TabularPOMDP instance used as the SPEC (images, sizes, rewards, tables); its own state is not used.
+        An envs.MountainCar / envs.InvertedPendulum goes through dqn_envs_create_control with its constants."""
+        if envs.is_control(env):
+            return self.envs_create_control(env.KIND, n_envs=n_envs if n_envs is not None else env.n, max_episode_length=max_episode_length, seed=seed, **env.constants())
         if envs.is_tabular(env):
             return self.envs_create_tabular(env.T, env.R, env.terminal, env.b0, env.features, Z=env.Z, Z0=env.Z0,
                                             n_envs=n_envs if n_envs is not None else env.n, max_episode_length=max_episode_length, seed=seed)
@@ -551,6 +561,31 @@ class Handle:
             setattr(sp, k, None if a is None else a.ctypes.data)
         self._check(self.f["envs_create_tabular"](self._h, C.byref(sp)))
         self.n_envs = sp.n_envs
+
+    def envs_create_control(self, kind, n_envs=1, max_episode_length=100, seed=0, **constants):
+        """dqn_envs_create_control: kind 3 (MountainCar) or 4 (InvertedPendulum); constants not given take the POMDPModels defaults (alpha: 1 / (m + M))."""
+        if "envs_create_control" not in self.f:
+            raise DQNError("this library does not export envs_create_control")
+        c = {**envs._ControlEnv.ALL_DEFAULTS, **constants}
+        if c["alpha"] is None:
+            c["alpha"] = 1.0 / (float(c["m"]) + float(c["M"]))
+        sp = ControlEnv()
+        sp.kind, sp.n_envs, sp.max_episode_length, sp.seed = int(kind), int(n_envs), int(max_episode_length), int(seed)
+        for k in envs._ControlEnv.FIELDS:
+            setattr(sp, k, float(c.pop(k)))
+        if c:
+            raise DQNError(f"envs_create_control: unknown constant {sorted(c)[0]!r}")
+        self._check(self.f["envs_create_control"](self._h, C.byref(sp)))
+        self.n_envs = sp.n_envs
+
+    def envs_peek_state(self):
+        """(state[n_envs][2], prev[n_envs][2]) in Float64: the control copies' states as they stand and the states they held before their last step"""
+        if "envs_peek_state" not in self.f:
+            raise DQNError("this library does not export envs_peek_state")
+        n = getattr(self, "n_envs", 0)      # (no env set yet: the library refuses)
+        s, p = np.empty((n, 2), np.float64), np.empty((n, 2), np.float64)
+        self._check(self.f["envs_peek_state"](self._h, _ptr(s, _f64p), _ptr(p, _f64p)))
+        return s, p
 
     def envs_reset(self):
         self._check(self.f["envs_reset"](self._h))

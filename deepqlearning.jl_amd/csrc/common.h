@@ -1050,7 +1050,15 @@ struct EnvDev {
     // tabular (PO)MDP (DQN_ENV_TABULAR): tb_T / tb_Z / tb_Z0 / tb_b0 hold CUMULATIVE rows (built on the host at creation); tb_O == 0: an MDP, the observation
     // index is the state index.  Per copy: state, observation index, observation index before the step
     int tb_S, tb_O; const float *tb_T, *tb_Z, *tb_Z0, *tb_R, *tb_b0, *tb_feat; const unsigned char* tb_term; int *tb_s, *tb_o, *tb_oprev;
+    // control (DQN_ENV_MOUNTAINCAR / DQN_ENV_PENDULUM): ct_c = the spec's constants, device-resident behind ONE pointer (the record is passed by value to several kernels
+    // and staged word by word by the single-workgroup steps: CT_N doubles in it would be paid by every kind), indexed by CT_*.  Per copy: the Float64 state [n][2] and the
+    // state before the step
+    const double* ct_c; double *ct_s, *ct_prev;
 };
+// dqn_control_env's constants in the struct's own order (force is the first; engine_envs.hip copies CT_N doubles from there)
+enum { CT_FORCE, CT_FREQ, CT_GRAVITY, CT_VMAX, CT_XMIN, CT_GOAL, CT_COST, CT_JACKPOT, CT_X0, CT_V0, CT_G, CT_M, CT_L, CT_MCART, CT_ALPHA, CT_DT, CT_UMAX, CT_NOISE, CT_THETAMAX, CT_INITHALF, CT_N };
+static inline __host__ __device__ bool env_is_control(int kind) { return kind == DQN_ENV_MOUNTAINCAR || kind == DQN_ENV_PENDULUM; }
+static inline __host__ __device__ bool env_is_builtin(int kind) { return kind == DQN_ENV_TESTMDP || kind == DQN_ENV_GRIDWORLD; }      // what dqn_envs_create makes and k_act_head steps
 // t, widx: values of the LAST completed vector step.  Exploration: xtab == nullptr is the linear eps law of (eps_start, eps_stop, eps_steps); else
 // vector step t reads xtab[clamp(t - xtab_t0, 0, xtab_n - 1)] -- eps (xkind = DQN_EXPLORE_EPS_GREEDY) or the softmax temperature (DQN_EXPLORE_SOFTMAX).  Only the
 // general tail (k_env_step) reads the three x* fields; the fused tail (act_head.hip) serves the linear law and is never launched with a table
@@ -1093,8 +1101,8 @@ struct TinyActArgs {
 };
 // one launch of K workgroups, workgroup k = record a_dev[k].  first: the policy input is observe(env) of the states as they stand (a call's first step; else pol_x, which
 // the step before left); last: the resets the step leaves pending are applied (a call's last step).  -1: the LDS attribute was refused
-int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int first, int last);
-int tiny_act_raise_lds(unsigned lds_bytes);      // what launch_tiny_act asks of the device, callable before anything is enqueued; -1: refused
+int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int first, int last, int control /* a member is of a control kind */);
+int tiny_act_raise_lds(unsigned lds_bytes, int control);      // what launch_tiny_act asks of the device, callable before anything is enqueued; -1: refused
 // ---- basic_evaluation of a network that fits in LDS (tiny_eval.hip): one workgroup runs the WHOLE greedy episode loop of a member's V.n evaluation copies, up to
 // TINY_EVAL_STEPS vector steps per launch.  The forward runs tile by tile (tw columns at a time: a.y_off / a.x_off are laid out for tw columns), the heads of all the
 // copies meet in `heads` [nA (+ 1)][V.n], and env_step_body is the step's tail on all V.n copies at once.  a.V is the member's EVALUATION set (eval_mode = 1), a.rs = &roll
@@ -1109,8 +1117,8 @@ struct TinyEvalArgs {
 };
 // one launch of K workgroups, workgroup k = record a_dev[k], n_steps <= TINY_EVAL_STEPS vector steps.  first: reset!(env) of every copy (t = 0) before the first step;
 // last: the sums go to a.out.  -1: the LDS attribute was refused
-int launch_tiny_eval(hipStream_t st, TinyEvalArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int n_steps, int first, int last);
-int tiny_eval_raise_lds(unsigned lds_bytes);
+int launch_tiny_eval(hipStream_t st, TinyEvalArgs* a_dev /* [K] */, int K, unsigned max_lds_bytes, int n_steps, int first, int last, int control);
+int tiny_eval_raise_lds(unsigned lds_bytes, int control);
 // ---- recurrent engines: the copies' open episodes (staging [n][T]) and the committed episode ring (envs.hip, engine_envs.hip)
 struct EpStage {
     int T; long long ep_cap;

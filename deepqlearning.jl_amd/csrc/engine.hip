@@ -1048,6 +1048,7 @@ extern "C" int dqn_comm_init(dqn_engine_t* e, const void* id128, int rank, int w
     if (refuse_replicas("dqn_comm_init", e->L, e->nl)) return -1;
     if (e->in_groups > 0) return fail("dqn_comm_init: this engine is a member of %d live group%s: replicas take the multi-launch step program, and a group steps the program its members had when it was created -- destroy the group first (dqn_group_destroy)", e->in_groups, e->in_groups > 1 ? "s" : "");
     if (e->has_envs && e->env.kind == DQN_ENV_TABULAR) return fail("dqn_comm_init: this engine has tabular device environments (dqn_envs_create_tabular); no exchange path has run with them (single GPU only)");
+    if (e->has_envs && env_is_control(e->env.kind)) return fail("dqn_comm_init: this engine has control device environments (dqn_envs_create_control); no exchange path has run with them (single GPU only)");
     if (e->hp.recurrence && e->has_envs) return fail("dqn_comm_init: this recurrent engine has device environments; their episode commits and the host sampler's mirror are single-device -- create the communicator first (and collect on the host), or use an engine without env sets");
     if (rccl_load()) return -1;
     HIPCHK(hipSetDevice(e->device));

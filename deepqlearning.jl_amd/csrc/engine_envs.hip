@@ -1,5 +1,5 @@
-// engine_envs.hip -- C ABI of the device-resident environments: dqn_envs_create / dqn_rollout / dqn_evaluate /
-// dqn_envs_peek / dqn_envs_peek_q; kernels in envs.hip.
+// engine_envs.hip -- C ABI of the device-resident environments: dqn_envs_create / dqn_envs_create_tabular /
+// dqn_envs_create_control / dqn_rollout / dqn_evaluate / dqn_envs_peek / dqn_envs_peek_q / dqn_envs_peek_state; kernels in envs.hip.
 #include <cmath>
 #include "engine.h"
 
@@ -130,6 +130,47 @@ extern "C" int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* s
     HIPCHK(hipMemsetAsync(V.tb_oprev, 0, (size_t)n * 4, e->stream));
     return envs_finish(e);
 }
+// MountainCar / InvertedPendulum (the laws: include/dqn_mi355x.h).  Everything is validated before the engine's current env set is touched.
+extern "C" int dqn_envs_create_control(dqn_engine_t* e, const dqn_control_env* sp) { if (!e) return fail("null engine handle");
+    if (!sp) return fail("null control spec");
+    HIPCHK(hipSetDevice(e->device));
+    if (!env_is_control(sp->kind)) return fail("control env: unknown kind %d (3: MountainCar, 4: InvertedPendulum)", sp->kind);
+    const char* const who = sp->kind == DQN_ENV_MOUNTAINCAR ? "MountainCar" : "InvertedPendulum";
+    if (e->hp.obs_dtype == DQN_OBS_U8) return fail("control env: %s observations are Float32[state[1], state[2]], this engine stores observations as u8: use obs_dtype f32", who);
+    if (e->E != 2 || e->nA != 3) return fail("control env: %s has an observation of 2 floats and 3 actions (network: %d in, %d out)", who, e->E, e->nA);
+    if (e->comm) return fail("control env: these device environments are single-device: this engine has a communicator (dqn_comm_init)");
+    if (e->opt.sim_world >= 1) return fail("control env: these device environments are single-device: this engine was created under DQN_SIM_WORLD");
+    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
+    static const char* const names[CT_N] = {"force", "freq", "gravity", "v_max", "x_min", "goal", "cost", "jackpot", "x0", "v0", "g", "m", "l", "M", "alpha", "dt", "u_max", "noise", "theta_max", "init_half"};
+    static_assert(offsetof(dqn_control_env, init_half) - offsetof(dqn_control_env, force) == (CT_N - 1) * sizeof(double), "CT_* follows the struct's own order");
+    const double* const c = &sp->force;
+    for (int k = 0; k < CT_N; k++) if (!std::isfinite(c[k])) return fail("control env: %s = %g is not finite", names[k], c[k]);
+    if (sp->kind == DQN_ENV_MOUNTAINCAR) {
+        if (!(sp->v_max > 0.0)) return fail("control env: v_max = %g must be > 0", sp->v_max);
+        if (!(sp->x_min < sp->goal)) return fail("control env: x_min = %g must lie below goal = %g", sp->x_min, sp->goal);
+    } else {
+        if (!(sp->dt > 0.0)) return fail("control env: dt = %g must be > 0", sp->dt);
+        if (!(sp->l > 0.0)) return fail("control env: l = %g must be > 0", sp->l);
+        if (!(sp->alpha * sp->m < 4.0 / 3.0)) return fail("control env: alpha * m = %g must lie below 4/3 (alpha = %g, m = %g): the denominator (4/3) l - alpha m l cos^2(theta) can reach 0", sp->alpha * sp->m, sp->alpha, sp->m);
+    }
+    HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
+    EnvDev& V = e->env; const int n = sp->n_envs;
+    V.kind = sp->kind; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
+    double* cb = nullptr; DM(e->env_mem, cb, (size_t)CT_N); HIPCHK(hipMemcpy(cb, c, CT_N * sizeof(double), hipMemcpyHostToDevice)); V.ct_c = cb;
+    DM(e->env_mem, V.ct_s, (size_t)n * 2); DM(e->env_mem, V.ct_prev, (size_t)n * 2);
+    HIPCHK(hipMemsetAsync(V.ct_prev, 0, (size_t)n * 2 * sizeof(double), e->stream));
+    return envs_finish(e);
+}
+extern "C" int dqn_envs_peek_state(dqn_engine_t* e, double* state, double* prev) { if (!e) return fail("null engine handle");
+    HIPCHK(hipSetDevice(e->device));
+    if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
+    if (!env_is_control(e->env.kind)) return fail("dqn_envs_peek_state: the env set is of kind %d; only MountainCar (3) and InvertedPendulum (4) carry a Float64 state", e->env.kind);
+    const size_t bytes = (size_t)e->env.n * 2 * sizeof(double);
+    HIPCHK(hipStreamSynchronize(e->stream));
+    if (state) HIPCHK(hipMemcpy(state, e->env.ct_s, bytes, hipMemcpyDeviceToHost));
+    if (prev) HIPCHK(hipMemcpy(prev, e->env.ct_prev, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
 extern "C" int dqn_envs_reset(dqn_engine_t* e) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
@@ -207,7 +248,7 @@ static int emit_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev
     // the fused tail (act_head.hip): reduce of the heads' producers + heads + Q / argmax + eps-greedy + act! + add_exp!'s per-experience part in ONE launch, where the shapes allow
     // (the layout of the train step's fused reduce + head launch, fused_head_layout, + this kernel's own test); else k_reduce_multi + the heads' forward + k_env_step
     const int lq = e->hp.dueling ? e->last_adv : e->last_base, lvh = e->hp.dueling ? e->last_val : -1;
-    const bool builtin_env = V.kind != DQN_ENV_TABULAR;      // k_act_head steps the two built-in kinds only: a tabular set keeps the general four-launch tail
+    const bool builtin_env = env_is_builtin(V.kind);      // k_act_head steps the two built-in kinds only: a tabular or a control set keeps the general four-launch tail
     // ... and so does a network with a padded conv, a LayerNorm layer, a Dropout layer (nothing is emitted for the layer itself) or a skip block (common.h general_only): fused_tail = 0
     bool use_ah = !general && !e->opt.no_act_head && !general_only(e->L, e->nl, true) && builtin_env; int ah_pa = -1, ah_pv = -1, ah_S = 0;
     if (use_ah) { ah_S = fused_head_layout(e, levels, lq, lvh, &ah_pa, &ah_pv); use_ah = ah_S > 0 && act_head_ok(n, e->L[lq].K, ah_S, e->nA, lvh >= 0 ? 2 : 1, e->L[lq].N, lvh >= 0 ? e->L[lvh].N : 0); }
@@ -434,6 +475,7 @@ int eval_envs_ensure(dqn_engine* e, int n_eval) {
     W = e->env; W.n = n_eval; W.eval_mode = 1; DevScope& M = e->eval_mem;
     if (W.kind == DQN_ENV_TESTMDP) { DM(M, W.tm_s, (size_t)n_eval * 4); DM(M, W.tm_prev, (size_t)n_eval * 4); DM(M, W.tm_t, n_eval); }
     else if (W.kind == DQN_ENV_TABULAR) { DM(M, W.tb_s, n_eval); DM(M, W.tb_o, n_eval); DM(M, W.tb_oprev, n_eval); }      // the tables are the training set's
+    else if (env_is_control(W.kind)) { DM(M, W.ct_s, (size_t)n_eval * 2); DM(M, W.ct_prev, (size_t)n_eval * 2); }      // the constants are the training set's
     else { DM(M, W.gw_pos, (size_t)n_eval * 2); DM(M, W.gw_prev, (size_t)n_eval * 2); }
     DM(M, W.actions, n_eval); DM(M, W.rewards, n_eval); DM(M, W.dones, n_eval); DM(M, W.pending, n_eval); DM(M, W.ep_reward, n_eval); DM(M, W.ep_step, n_eval); DM(M, W.fin_eps, n_eval); DM(M, W.fin_reward, n_eval); DM(M, e->eval_roll, DQN_ROLL_RECORDS);
     for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {      // recurrent engines: the evaluation copies' private Recur state, n_eval streams

@@ -276,7 +276,8 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     if (rollout_many_check(g, n_steps, cfgs, explore, &train_at)) return -1;
     HIPCHK(hipSetDevice(g->device));
     if (rollout_many_records(g)) return -1;
-    if (tiny_act_raise_lds(g->act_lds)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds);
+    int control = 0; for (dqn_engine* e : g->members) control |= env_is_control(e->env.kind) ? 1 : 0;      // picks the acting kernel's instantiation (env_body.h)
+    if (tiny_act_raise_lds(g->act_lds, control)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds);
     const int K = g->K; const dqn_rollout_cfg& c0 = cfgs[0];
     // the call's records and tables: ONE contiguous array each, ONE H2D copy each
     size_t nx = 0;
@@ -303,7 +304,7 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     if (he != hipSuccess) rc = fail("dqn_rollout_many: HIP error %s uploading the call's records", hipGetErrorString(he));
     for (int j = 0; j < n_steps && !rc; j++) {
         const long long t = c0.t0 + j;
-        if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds); break; }
+        if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0, control)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds); break; }
         for (dqn_engine* e : g->members) { const int n = e->env.n; e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); e->env_q_valid = true; }      // what dqn_rollout_explore keeps on the host
         if (train_at[(size_t)j]) {      // :134-139, for all members in one launch
             if (launch_tiny_group(g->stream, g->args_dev, K, g->max_lds, 1)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the group train launch (hipFuncSetAttribute)", g->max_lds); break; }
@@ -418,7 +419,8 @@ extern "C" int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_len
         T.heads = g->heads_dev + hoff; hoff += (size_t)(e->nA + (e->hp.dueling ? 1 : 0)) * n_eval;
         T.out = g->es_dev + k;
     }
-    if (tiny_eval_raise_lds(lds)) return fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
+    int control = 0; for (dqn_engine* e : g->members) control |= env_is_control(e->env.kind) ? 1 : 0;
+    if (tiny_eval_raise_lds(lds, control)) return fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
     // in: the group's stream behind everything the members have enqueued
     for (int k = 0; k < K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
     (void)hipGetLastError();
@@ -429,7 +431,7 @@ extern "C" int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_len
     const int total = max_episode_length + 1;      // while !done && step <= max_episode_length
     for (int s0 = 0; s0 < total && !rc; s0 += TINY_EVAL_STEPS) {
         const int ns = std::min(TINY_EVAL_STEPS, total - s0);
-        if (launch_tiny_eval(g->stream, g->eval_dev, K, lds, ns, s0 == 0 ? 1 : 0, s0 + ns >= total ? 1 : 0)) rc = fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
+        if (launch_tiny_eval(g->stream, g->eval_dev, K, lds, ns, s0 == 0 ? 1 : 0, s0 + ns >= total ? 1 : 0, control)) rc = fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
     }
     if (!rc) {
         he = hipGetLastError();

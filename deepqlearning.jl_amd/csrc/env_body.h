@@ -1,5 +1,5 @@
 // env_body.h -- the device side of one vector step of the environment loop, shared by the kernels of envs.hip (the acting program of a standalone engine) and
-// tiny_act.hip (the single-workgroup acting step of an engine group): the Philox draws, the observation and reset laws of the three environment kinds, the sum-tree
+// tiny_act.hip (the single-workgroup acting step of an engine group): the Philox draws, the observation and reset laws of the environment kinds, the sum-tree
 // rebuild of add_exp! and env_step_body, the whole tail of a vector step as ONE workgroup.  The environment laws are stated here and nowhere else.
 #pragma once
 #include "common.h"
@@ -51,8 +51,45 @@ __device__ __forceinline__ int softmax_pick(QF q, int nA, float tau, float u) {
 }
 enum { TAB_NEXT = DQN_ENV_RAND_TAB_NEXT, TAB_OBS = DQN_ENV_RAND_TAB_OBS, TAB_INIT = DQN_ENV_RAND_TAB_INIT, TAB_INIT_OBS = DQN_ENV_RAND_TAB_INIT_OBS };
 
-// element f of the observation of an env in state (sw = the 4 TestMDP state bytes packed little-endian | px, py; tabular: px = the observation index).  No local
-// arrays: a dynamically indexed one would live in scratch.
+// control kinds (the laws: include/dqn_mi355x.h; POMDPModels' MountainCar and InvertedPendulum, third-party, recalled).  Plain double arithmetic in the written order:
+// no contraction (the pragma; the build's -ffp-contract=off says the same), the device library's double cos / sin.  c = the spec's constants (CT_*, common.h)
+__device__ __forceinline__ void control_reset(const EnvDev& V, int i, unsigned long long t, double* s0, double* s1) {
+#pragma clang fp contract(off)
+    const double* __restrict__ c = V.ct_c;
+    if (V.kind == DQN_ENV_MOUNTAINCAR) { *s0 = c[CT_X0]; *s1 = c[CT_V0]; return; }
+    const double u13 = (double)u01(env_rand(V.seed, t, i, DQN_ENV_RAND_PEND_THETA0)), u14 = (double)u01(env_rand(V.seed, t, i, DQN_ENV_RAND_PEND_OMEGA0));
+    *s0 = (u13 - 0.5) * 2.0 * c[CT_INITHALF]; *s1 = (u14 - 0.5) * 2.0 * c[CT_INITHALF];
+}
+// one step of copy i under action index a at vector step t: the state in place, the reward (still Float64) and the terminal flag
+__device__ __forceinline__ void control_step(const EnvDev& V, int i, unsigned long long t, int a, double* s0, double* s1, double* r, unsigned char* done) {
+#pragma clang fp contract(off)
+    const double* __restrict__ c = V.ct_c;
+    const double push = (double)(a - 1);
+    if (V.kind == DQN_ENV_MOUNTAINCAR) {
+        const double x = *s0, v = *s1, vmax = c[CT_VMAX];
+        double vp = v + push * c[CT_FORCE] + cos(c[CT_FREQ] * x) * (-c[CT_GRAVITY]);
+        vp = fmax(fmin(vmax, vp), -vmax);
+        double xp = x + vp;
+        if (xp < c[CT_XMIN]) { xp = c[CT_XMIN]; vp = 0.0; }
+        const bool goal = xp >= c[CT_GOAL];
+        *s0 = xp; *s1 = vp; *r = c[CT_COST] + (goal ? c[CT_JACKPOT] : 0.0); *done = goal ? 1 : 0;
+        return;
+    }
+    const double th = *s0, om = *s1, g = c[CT_G], m = c[CT_M], l = c[CT_L], al = c[CT_ALPHA], dt = c[CT_DT];
+    const double u = push * c[CT_UMAX] + c[CT_NOISE] * ((double)u01(env_rand(V.seed, t, i, DQN_ENV_RAND_PEND_NOISE)) - 0.5);
+    const double sn = sin(th), cs = cos(th), s2 = sin(2.0 * th);
+    const double acc = (g * sn - al * m * l * om * om * s2 * 0.5 - al * cs * u) / ((4.0 / 3.0) * l - al * m * l * cs * cs);
+    const double thp = th + om * dt, omp = om + acc * dt;
+    const bool fell = fabs(thp) > c[CT_THETAMAX];
+    *s0 = thp; *s1 = omp; *r = fell ? c[CT_COST] : 0.0; *done = fell ? 1 : 0;
+}
+
+// element f of the observation of an env in state (sw = the 4 TestMDP state bytes packed little-endian | px, py; tabular: px = the observation index; control: px, py =
+// the bits of Float32(state[1]), Float32(state[2]) -- convert_s is all an observation needs of the Float64 state).  No local arrays: a dynamically indexed one would
+// live in scratch.
+// CTL (here and in the three helpers below): false compiles the control kinds' branch out -- for a caller that a control set can never reach (k_env_observe2's 16-byte
+// instantiations: E = 2), so that its code stays what it was
+template <bool CTL = true>
 __device__ __forceinline__ float obs_elem(const EnvDev& V, uint32_t sw, int px_, int py_, int f, unsigned char* raw) {
     if (V.kind == DQN_ENV_TESTMDP) {
         const int hw = V.H * V.W, c = f / hw, px = f - c * hw;            // obs[.., c] = observations[s[end - c]]  (test/test_env.jl:56-58)
@@ -61,30 +98,38 @@ __device__ __forceinline__ float obs_elem(const EnvDev& V, uint32_t sw, int px_,
         *raw = b; return (float)b / 255.0f;
     }
     if (V.kind == DQN_ENV_TABULAR) { *raw = 0; return V.tb_feat[(size_t)px_ * V.E + f]; }      // convert_o / convert_s row of the index
+    if (CTL && env_is_control(V.kind)) { *raw = 0; return __int_as_float(f == 0 ? px_ : py_); }       // Float32[state[1], state[2]]
     *raw = 0; return (float)(f == 0 ? px_ : py_);                          // Float32[x, y]
 }
+template <bool CTL = true>
 __device__ __forceinline__ void reset_state(const EnvDev& V, int i, unsigned long long t, uint32_t* sw, int* tm_t, int* px, int* py) {
     if (V.kind == DQN_ENV_TESTMDP) { *sw = 0x01010101u; *tm_t = 1; }                                                  // initialstate, :46-52
     else if (V.kind == DQN_ENV_TABULAR) {      // s ~ b0, o ~ Z0[s] (an MDP: o = s); py = state, px = observation index
         const int s = cdf_pick(V.tb_b0, V.tb_S, u01(env_rand(V.seed, t, i, TAB_INIT)));
         *py = s; *px = V.tb_O ? cdf_pick(V.tb_Z0 + (size_t)s * V.tb_O, V.tb_O, u01(env_rand(V.seed, t, i, TAB_INIT_OBS))) : s;
     }
+    else if (CTL && env_is_control(V.kind)) { double s0, s1; control_reset(V, i, t, &s0, &s1); *px = __float_as_int((float)s0); *py = __float_as_int((float)s1); }
     else { *px = 1 + (int)(env_rand(V.seed, t, i, 5u) % (uint32_t)V.size_x); *py = 1 + (int)(env_rand(V.seed, t, i, 6u) % (uint32_t)V.size_y); }
 }
+template <bool CTL = true>
 __device__ __forceinline__ void load_state(const EnvDev& V, int i, uint32_t* sw, int* px, int* py) {
     *sw = 0x01010101u; *px = *py = 0;
     if (V.kind == DQN_ENV_TESTMDP) *sw = *(const uint32_t*)(V.tm_s + i * 4);
     else if (V.kind == DQN_ENV_TABULAR) { *px = V.tb_o[i]; *py = V.tb_s[i]; }
+    else if (CTL && env_is_control(V.kind)) { *px = __float_as_int((float)V.ct_s[i * 2]); *py = __float_as_int((float)V.ct_s[i * 2 + 1]); }
     else { *px = V.gw_pos[i * 2]; *py = V.gw_pos[i * 2 + 1]; }
 }
 // the state the last k_env_step saved before it stepped: what the transition's s is the observation of
+template <bool CTL = true>
 __device__ __forceinline__ void load_prev(const EnvDev& V, int i, uint32_t* sw, int* px, int* py) {
     *sw = 0x01010101u; *px = *py = 0;
     if (V.kind == DQN_ENV_TESTMDP) *sw = *(const uint32_t*)(V.tm_prev + i * 4);
     else if (V.kind == DQN_ENV_TABULAR) *px = V.tb_oprev[i];
+    else if (CTL && env_is_control(V.kind)) { *px = __float_as_int((float)V.ct_prev[i * 2]); *py = __float_as_int((float)V.ct_prev[i * 2 + 1]); }
     else { *px = V.gw_prev[i * 2]; *py = V.gw_prev[i * 2 + 1]; }
 }
 __device__ __forceinline__ void store_reset(const EnvDev& V, int i, unsigned long long t) {
+    if (env_is_control(V.kind)) { double s0, s1; control_reset(V, i, t, &s0, &s1); V.ct_s[i * 2] = s0; V.ct_s[i * 2 + 1] = s1; return; }      // the Float64 state itself
     uint32_t sw; int tm = 1, px, py; reset_state(V, i, t, &sw, &tm, &px, &py);
     if (V.kind == DQN_ENV_TESTMDP) { *(uint32_t*)(V.tm_s + i * 4) = sw; V.tm_t[i] = tm; }
     else if (V.kind == DQN_ENV_TABULAR) { V.tb_s[i] = py; V.tb_o[i] = px; }
@@ -160,7 +205,9 @@ __device__ __forceinline__ void env_tree_rebuild(const ReplayMeta& R, const int 
 //   eps-greedy (POMDPTools EpsGreedyPolicy: rand(rng) < eps ? rand(rng, actions) : greedy), act! (:89): transition, reward, terminal;
 //   add_exp!(replay, exp, abs(exp.r)) (:91-94): metadata + leaf priority, then the sum-tree ancestors of the written leaves.
 // REC (recurrent engines, envs_drqn below): add_exp! goes to the copy's open-episode staging area instead of the prioritized ring -- no ring row, no leaf, no tree
-template <bool REC>
+// CTL: the instantiation that steps the control kinds.  Their law (double cos / sin: registers, and scratch for the argument reduction) is compiled into it alone, so the
+// kernels that step the other kinds keep the code they had; a launcher picks CTL = true where a set (any member of a group launch) is of a control kind
+template <bool REC, bool CTL>
 __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const ReplayMeta& R, const EpStage* ES) {
     const int n = V.n;
     const unsigned long long t_prev = (unsigned long long)rs->t, t = t_prev + 1;
@@ -231,6 +278,7 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
         }
         if (V.kind == DQN_ENV_TESTMDP) *(uint32_t*)(V.tm_prev + i * 4) = *(const uint32_t*)(V.tm_s + i * 4);       // s of this transition = observation of the pre-step state
         else if (V.kind == DQN_ENV_TABULAR) V.tb_oprev[i] = V.tb_o[i];
+        else if (env_is_control(V.kind)) { V.ct_prev[i * 2] = V.ct_s[i * 2]; V.ct_prev[i * 2 + 1] = V.ct_s[i * 2 + 1]; }
         else { V.gw_prev[i * 2] = V.gw_pos[i * 2]; V.gw_prev[i * 2 + 1] = V.gw_pos[i * 2 + 1]; }
         int a = 0;
         float v = 0.0f, mean = 0.0f;
@@ -272,6 +320,13 @@ __device__ __forceinline__ void env_step_body(const EnvDev& V, RolloutDev* rs, c
             const int o = V.tb_O ? cdf_pick(V.tb_Z + ((size_t)a * V.tb_S + sp) * V.tb_O, V.tb_O, u01(env_rand(V.seed, t, i, TAB_OBS))) : sp;
             r = V.tb_R[row + sp]; done = V.tb_term[sp];
             V.tb_s[i] = sp; V.tb_o[i] = o;
+        } else if (env_is_control(V.kind)) {
+            if constexpr (!CTL) { r = 0.0f; done = 0; if (!REC && !V.eval_mode) R.state->err = 1; }      // (never launched on these kinds; if a launcher ever forgets the flag the copy stands still and, where the step has an assertion flag, the call fails)
+            else {
+            double s0 = V.ct_s[i * 2], s1 = V.ct_s[i * 2 + 1], rd;
+            control_step(V, i, t, a, &s0, &s1, &rd, &done);
+            V.ct_s[i * 2] = s0; V.ct_s[i * 2 + 1] = s1; r = (float)rd;                              // the replay holds Float32(r)
+            }
         } else {
             int* p = V.gw_pos + i * 2; float rv = 0.0f;
             for (int k = 0; k < V.n_reward; k++) if (p[0] == V.reward_xy[k][0] && p[1] == V.reward_xy[k][1]) rv = V.reward_val[k];

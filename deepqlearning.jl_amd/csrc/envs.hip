@@ -1,6 +1,6 @@
 // envs.hip -- vectorised environments on the device: the env loop of dqn_train! (src/solver.jl:82-132) for n
 // lock-stepped copies without any host round trip.  TestMDP restates test/test_env.jl:10-87, SimpleGridWorld restates the
-// POMDPModels defaults (third-party; recalled), a tabular (PO)MDP is stepped from its matrices (POMDPTools' MDPCommonRLEnv / POMDPCommonRLEnv; recalled).  All randomness is Philox4x32-10 with counter (vector step, env, purpose) so
+// POMDPModels defaults (third-party; recalled), a tabular (PO)MDP is stepped from its matrices (POMDPTools' MDPCommonRLEnv / POMDPCommonRLEnv; recalled), MountainCar and InvertedPendulum restate POMDPModels' laws on a Float64 state (recalled; env_body.h).  All randomness is Philox4x32-10 with counter (vector step, env, purpose) so
 // that the CPU twin (oracle/dqn_ref.c) reproduces trajectories bit for bit.
 //
 // One vector step is: [policy forward on pol_x -> greedy]  k_env_step  k_env_observe2   -- every argument is a fixed device
@@ -25,13 +25,16 @@ void launch_env_observe(hipStream_t st, const EnvDev& V, void* rows, int rows_u8
     hipLaunchKernelGGL(k_env_observe, dim3(blocks), dim3(256), 0, st, V, rows, rows_u8, x);
 }
 
-__global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, ActHeads Hd, ReplayMeta R) { env_step_body<false>(V, rs, Hd, R, nullptr); }
-__global__ __launch_bounds__(1024) void k_env_step_rec(EnvDev V, RolloutDev* rs, ActHeads Hd, EpStage ES) { ReplayMeta R; R.cap = 1; R.cap2 = 1; R.a = nullptr; R.r = nullptr; R.done = nullptr; R.tree = nullptr; R.state = nullptr; R.eps = 0.0f; R.alpha = 0.0f; env_step_body<true>(V, rs, Hd, R, &ES); }
+// CTL: the instantiation for the control kinds (env_body.h); every other kind runs CTL = false
+template <bool CTL> __global__ __launch_bounds__(1024) void k_env_step(EnvDev V, RolloutDev* rs, ActHeads Hd, ReplayMeta R) { env_step_body<false, CTL>(V, rs, Hd, R, nullptr); }
+template <bool CTL> __global__ __launch_bounds__(1024) void k_env_step_rec(EnvDev V, RolloutDev* rs, ActHeads Hd, EpStage ES) { ReplayMeta R; R.cap = 1; R.cap2 = 1; R.a = nullptr; R.r = nullptr; R.done = nullptr; R.tree = nullptr; R.state = nullptr; R.eps = 0.0f; R.alpha = 0.0f; env_step_body<true, CTL>(V, rs, Hd, R, &ES); }
 void launch_env_step(hipStream_t st, const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const ReplayMeta& R) {
-    hipLaunchKernelGGL(k_env_step, dim3(1), dim3(1024), 0, st, V, rs, Hd, R);
+    if (env_is_control(V.kind)) hipLaunchKernelGGL(k_env_step<true>, dim3(1), dim3(1024), 0, st, V, rs, Hd, R);
+    else hipLaunchKernelGGL(k_env_step<false>, dim3(1), dim3(1024), 0, st, V, rs, Hd, R);
 }
 void launch_env_step_rec(hipStream_t st, const EnvDev& V, RolloutDev* rs, const ActHeads& Hd, const EpStage& ES) {
-    hipLaunchKernelGGL(k_env_step_rec, dim3(1), dim3(1024), 0, st, V, rs, Hd, ES);
+    if (env_is_control(V.kind)) hipLaunchKernelGGL(k_env_step_rec<true>, dim3(1), dim3(1024), 0, st, V, rs, Hd, ES);
+    else hipLaunchKernelGGL(k_env_step_rec<false>, dim3(1), dim3(1024), 0, st, V, rs, Hd, ES);
 }
 
 // after k_env_step: the transition's rows go straight into the ring -- s = observation of the saved pre-step state, sp = observe(env)
@@ -54,6 +57,8 @@ __device__ __forceinline__ void obs_vec(const EnvDev& V, uint32_t sw, int px_, i
         const FeatV v = *(const FeatV*)(V.tb_feat + (size_t)px_ * V.E + f);
 #pragma unroll
         for (int u = 0; u < VEC; u++) { ob[u] = 0; of[u] = v[u]; }
+    } else if (VEC == 1 && env_is_control(V.kind)) {      // E = 2: never the 16-byte path (VEC is a template argument: the VEC = 4 kernels carry no such branch)
+        ob[0] = 0; of[0] = __int_as_float(f == 0 ? px_ : py_);
     } else {
 #pragma unroll
         for (int u = 0; u < VEC; u++) { ob[u] = 0; of[u] = (float)((f + u) == 0 ? px_ : py_); }
@@ -81,8 +86,8 @@ __global__ __launch_bounds__(256) void k_env_observe2(EnvDev V, const RolloutDev
         const RolloutDev* rs = rs0 + (grouped ? (i >> 2) : 0u);
         long long slot = rs->widx + i; if (slot >= cap) slot -= cap;
         uint32_t sw0, sw1; int p0x, p0y, p1x, p1y;
-        load_state(V, (int)i, &sw1, &p1x, &p1y);
-        load_prev(V, (int)i, &sw0, &p0x, &p0y);
+        load_state<VEC == 1>(V, (int)i, &sw1, &p1x, &p1y);
+        load_prev<VEC == 1>(V, (int)i, &sw0, &p0x, &p0y);
         float of[VEC]; unsigned char ob[VEC]; RowT r[VEC];
         const size_t dst = (size_t)slot * E + f;
         obs_vec<VEC>(V, sw0, p0x, p0y, (int)f, of, ob);
@@ -102,9 +107,9 @@ __global__ __launch_bounds__(256) void k_env_observe2(EnvDev V, const RolloutDev
         float nx[VEC];
 #pragma unroll
         for (int u = 0; u < VEC; u++) {
-            uint32_t sw; int px, py, tm = 0; load_state(V, (int)(i0 + u), &sw, &px, &py);
-            if (V.pending[i0 + u] && !V.eval_mode) reset_state(V, (int)(i0 + u), t, &sw, &tm, &px, &py);
-            unsigned char b; nx[u] = obs_elem(V, sw, px, py, (int)f, &b);
+            uint32_t sw; int px, py, tm = 0; load_state<VEC == 1>(V, (int)(i0 + u), &sw, &px, &py);
+            if (V.pending[i0 + u] && !V.eval_mode) reset_state<VEC == 1>(V, (int)(i0 + u), t, &sw, &tm, &px, &py);
+            unsigned char b; nx[u] = obs_elem<VEC == 1>(V, sw, px, py, (int)f, &b);
         }
         { typedef float obs_f4 __attribute__((ext_vector_type(4)));      // the policy input is read by the very next launch, mostly from other XCDs: written through (sc1) as it is produced
           if constexpr (VEC == 4) { const obs_f4 v = {nx[0], nx[1], nx[2], nx[3]}; asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" ::"v"(x + (size_t)f * n + i0), "v"(v) : "memory"); }

@@ -13,7 +13,8 @@
 #include "env_body.h"
 #include "tiny_fwd.h"
 
-template <int NTH>
+// CTL: the instantiation a group launches when any member's env set is of a control kind (env_body.h); every other group runs CTL = false
+template <int NTH, bool CTL>
 __global__ __launch_bounds__(NTH) void k_tiny_act(const TinyActArgs* __restrict__ Ap, int first, int last) {
     extern __shared__ __align__(16) float sm[];
     // layer descriptors, the env set and the replay record in LDS: a per-item `A.L[l].field` / `A.V.field` is a dependent GLOBAL load (the record lives in device
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(NTH) void k_tiny_act(const TinyActArgs* __restrict_
         const int lq = A.dueling ? A.last_adv : A.last_base;
         auto head_of = [&](int l) { HeadSrc h; h.p = sm + LD[l][F_Y]; h.ld = n; h.S = 1; h.per_s = 0; h.bias = nullptr; h.act = DQN_ACT_IDENTITY; return h; };
         ActHeads Hd; Hd.adv = head_of(lq); Hd.val = head_of(A.dueling ? A.last_val : lq); Hd.dueling = A.dueling; Hd.q_out = A.pol_q; Hd.amax = A.pol_a;
-        env_step_body<false>(V, A.rs, Hd, Rs, nullptr);
+        env_step_body<false, CTL>(V, A.rs, Hd, Rs, nullptr);
     }
     __syncthreads();      // (full: the env states, the pending flags and the record's t / widx travel through global memory from the thread of a copy to the threads of its elements)
     // ---- phase 3: the transition's rows into the ring, the next policy input (k_env_observe2's elements)
@@ -88,12 +89,13 @@ __global__ __launch_bounds__(NTH) void k_tiny_act(const TinyActArgs* __restrict_
     }
 }
 // the function's dynamic-LDS request (tiny_fwd.h tiny_fn_raise_lds)
-int tiny_act_raise_lds(unsigned lds_bytes) {
-    static TinyLdsAsk ask;
-    return tiny_fn_raise_lds(reinterpret_cast<const void*>(&k_tiny_act<1024>), ask, lds_bytes);
+int tiny_act_raise_lds(unsigned lds_bytes, int control) {
+    static TinyLdsAsk ask[2];
+    return tiny_fn_raise_lds(control ? reinterpret_cast<const void*>(&k_tiny_act<1024, true>) : reinterpret_cast<const void*>(&k_tiny_act<1024, false>), ask[control ? 1 : 0], lds_bytes);
 }
-int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev, int K, unsigned max_lds_bytes, int first, int last) {
-    if (tiny_act_raise_lds(max_lds_bytes)) return -1;
-    hipLaunchKernelGGL((k_tiny_act<1024>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, first, last);
+int launch_tiny_act(hipStream_t st, const TinyActArgs* a_dev, int K, unsigned max_lds_bytes, int first, int last, int control) {
+    if (tiny_act_raise_lds(max_lds_bytes, control)) return -1;
+    if (control) hipLaunchKernelGGL((k_tiny_act<1024, true>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, first, last);
+    else hipLaunchKernelGGL((k_tiny_act<1024, false>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, first, last);
     return 0;
 }

@@ -21,7 +21,8 @@ __host__ __device__ __forceinline__ int tiny_eval_tile(int n, int tw, int c0) {
     return w;
 }
 
-template <int NTH>
+// CTL: as k_tiny_act's -- the instantiation for a group with a member of a control kind
+template <int NTH, bool CTL>
 __global__ __launch_bounds__(NTH) void k_tiny_eval(TinyEvalArgs* Ap, int n_steps, int first, int last) {
     extern __shared__ __align__(16) float sm[];
     __shared__ int LD[TINY_MAX_LAYERS][F_NF];
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(NTH) void k_tiny_eval(TinyEvalArgs* Ap, int n_steps
             c0 += w;
         }
         __syncthreads();      // (full: the heads travel through global memory)
-        env_step_body<false>(V, &T.roll, Hd, Rs, nullptr);
+        env_step_body<false, CTL>(V, &T.roll, Hd, Rs, nullptr);
         __syncthreads();      // (full: the states, the pending flags and the record's t travel through global memory)
     }
     if (!last) return;
@@ -88,12 +89,13 @@ __global__ __launch_bounds__(NTH) void k_tiny_eval(TinyEvalArgs* Ap, int n_steps
         EvalSums o; o.reward_sum = r; o.steps = s; *T.out = o;
     }
 }
-int tiny_eval_raise_lds(unsigned lds_bytes) {
-    static TinyLdsAsk ask;
-    return tiny_fn_raise_lds(reinterpret_cast<const void*>(&k_tiny_eval<1024>), ask, lds_bytes);
+int tiny_eval_raise_lds(unsigned lds_bytes, int control) {
+    static TinyLdsAsk ask[2];
+    return tiny_fn_raise_lds(control ? reinterpret_cast<const void*>(&k_tiny_eval<1024, true>) : reinterpret_cast<const void*>(&k_tiny_eval<1024, false>), ask[control ? 1 : 0], lds_bytes);
 }
-int launch_tiny_eval(hipStream_t st, TinyEvalArgs* a_dev, int K, unsigned max_lds_bytes, int n_steps, int first, int last) {
-    if (tiny_eval_raise_lds(max_lds_bytes)) return -1;
-    hipLaunchKernelGGL((k_tiny_eval<1024>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, n_steps, first, last);
+int launch_tiny_eval(hipStream_t st, TinyEvalArgs* a_dev, int K, unsigned max_lds_bytes, int n_steps, int first, int last, int control) {
+    if (tiny_eval_raise_lds(max_lds_bytes, control)) return -1;
+    if (control) hipLaunchKernelGGL((k_tiny_eval<1024, true>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, n_steps, first, last);
+    else hipLaunchKernelGGL((k_tiny_eval<1024, false>), dim3(K), dim3(1024), max_lds_bytes, st, a_dev, n_steps, first, last);
     return 0;
 }

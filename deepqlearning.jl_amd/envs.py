@@ -18,6 +18,10 @@ TabularPOMDP  any discrete MDP / POMDP given as its matrices T[s, a, sp], Z[a, s
 TigerPOMDP     POMDPModels.TigerPOMDP as tables (third-party; recalled, not executed): 2 states (index = Bool: 0 tiger right,
                1 tiger left), actions listen / open-left / open-right, 2 observations, listening reports the side correctly with
                p_listen_correctly, opening re-draws the state, no terminal state, observation Float32[o].
+MountainCar, InvertedPendulum  POMDPModels' two continuous-state control problems (third-party; recalled, not executed): two Float64 state
+               values per copy, three actions, observation Float32[state[1], state[2]], discount 0.99.  These are the CPU twins of the device's
+               control kinds (dqn_envs_create_control): the header's laws expression by expression in NumPy float64, and the device's own
+               Philox draws keyed by (seed, vector step, copy, purpose) -- unlike the classes above, which draw from a NumPy generator.
 
 Actions are 0-based here.  `n` environments step in lock-step as NumPy arrays (BASELINE config 3 shards 256 of
 them over 8 ranks).
@@ -200,6 +204,154 @@ class TabularPOMDP:
 def is_tabular(env):
     """the env spec carries tables: the device loop steps it through dqn_envs_create_tabular"""
     return isinstance(env, TabularPOMDP)
+
+
+def philox_u32(seed, t, env, purpose):
+    """the device's keyed draw: word 0 of Philox4x32-10 under key = seed and counter (t low, t high, env, purpose).  `env` may be an array of copy indices"""
+    env = np.asarray(env, np.uint64)
+    m32 = np.uint64(0xFFFFFFFF)
+    k0, k1 = np.uint64(int(seed) & 0xFFFFFFFF), np.uint64((int(seed) >> 32) & 0xFFFFFFFF)
+    c = [np.full(env.shape, int(t) & 0xFFFFFFFF, np.uint64), np.full(env.shape, (int(t) >> 32) & 0xFFFFFFFF, np.uint64), env & m32, np.full(env.shape, int(purpose), np.uint64)]
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]      # 32 x 32 bits: no overflow in 64
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & m32, p1 & m32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & m32, p0 & m32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & m32, (k1 + np.uint64(0xBB67AE85)) & m32
+    return c[0]
+
+
+def u01(r):
+    """the device's 24-bit uniform in [0, 1): Float32(r >> 8) * 2^-24"""
+    return (np.asarray(r, np.uint64) >> np.uint64(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+class _ControlEnv:
+    """Two Float64 state values per copy, three actions, observation Float32[state[1], state[2]]: the CPU twin of the device's control kinds (dqn_envs_create_control).
+    The laws are the header's, expression by expression, in NumPy float64; the draws are the device's: u = Float64(u01(philox(seed, t, copy, purpose))), t = the vector
+    step (the number of act() calls so far; a reset draws at the step it follows, 0 at construction)."""
+    KIND = None      # DQN_ENV_MOUNTAINCAR / DQN_ENV_PENDULUM
+    FIELDS = ("force", "freq", "gravity", "v_max", "x_min", "goal", "cost", "jackpot", "x0", "v0", "g", "m", "l", "M", "alpha", "dt", "u_max", "noise", "theta_max", "init_half")
+    ALL_DEFAULTS = dict(force=0.001, freq=3.0, gravity=0.0025, v_max=0.07, x_min=-1.2, goal=0.5, cost=-1.0, jackpot=100.0, x0=-0.5, v0=0.0,
+                        g=9.81, m=2.0, l=8.0, M=8.0, alpha=None, dt=0.1, u_max=50.0, noise=20.0, theta_max=np.pi / 2, init_half=0.1)
+    P_NOISE, P_THETA0, P_OMEGA0 = 12, 13, 14      # DQN_ENV_RAND_PEND_*
+
+    def __init__(self, n=1, seed=0, discount=0.99, **constants):
+        name = type(self).__name__
+        for k in constants:
+            if k not in self.FIELDS:
+                raise ValueError(f"{name}: unknown constant {k!r} (the fields of dqn_control_env: {', '.join(self.FIELDS)})")
+        c = {**self.ALL_DEFAULTS, **constants}
+        if c["alpha"] is None:
+            c["alpha"] = 1.0 / (float(c["m"]) + float(c["M"]))
+        self.c = {k: np.float64(c[k]) for k in self.FIELDS}
+        for k, v in self.c.items():
+            if not np.isfinite(v):
+                raise ValueError(f"{name}: {k} = {float(v):g} is not finite")
+        self.check()
+        self.n, self.seed, self.discount = int(n), int(seed), discount
+        self.n_actions, self.obs_shape = 3, (2,)
+        self.kwargs = dict(constants)
+        self.t = 0
+        self.s = np.zeros((self.n, 2), np.float64)
+        self.reset()
+
+    def constants(self):
+        """the spec's constants as Python floats, in the struct's order"""
+        return {k: float(self.c[k]) for k in self.FIELDS}
+
+    def host_copy(self, n, seed=0):
+        """another host instance of the same model with n copies"""
+        return type(self)(n=n, seed=seed, discount=self.discount, **self.kwargs)
+
+    def u(self, t, purpose, idx=None):
+        return u01(philox_u32(self.seed, t, np.arange(self.n) if idx is None else idx, purpose)).astype(np.float64)
+
+    def reset(self, mask=None):
+        new = self.reset_law(self.u(self.t, self.P_THETA0), self.u(self.t, self.P_OMEGA0))
+        if mask is None:
+            self.s = new
+            self.done = np.zeros(self.n, bool)
+        else:
+            mask = np.asarray(mask, bool)
+            self.s[mask] = new[mask]
+            self.done[mask] = False
+
+    def observe(self):
+        return self.s.astype(np.float32)
+
+    def terminated(self):
+        return self.done
+
+    def act(self, a):
+        self.t += 1
+        self.s, r, self.done, self.margin = self.step_law(self.s, np.asarray(a), self.u(self.t, self.P_NOISE))
+        return r.astype(np.float32)
+
+
+class MountainCar(_ControlEnv):
+    """POMDPModels.MountainCar (third-party; recalled, not executed).  State (x, v); actions 0, 1, 2 push -1, 0, +1; reset to (x0, v0)."""
+    KIND = 3
+
+    def check(self):
+        c = self.c
+        if not c["v_max"] > 0:
+            raise ValueError(f"MountainCar: v_max = {float(c['v_max']):g} must be > 0")
+        if not c["x_min"] < c["goal"]:
+            raise ValueError(f"MountainCar: x_min = {float(c['x_min']):g} must lie below goal = {float(c['goal']):g}")
+
+    def reset_law(self, u13, u14):
+        return np.stack([np.full(len(u13), self.c["x0"]), np.full(len(u13), self.c["v0"])], 1)
+
+    def step_law(self, s, a, u12=None):
+        """(state', Float64 reward, done, margin): margin = per copy the smallest distance of a branch quantity from its switch point (x' - goal, x' - x_min before the
+        wall rule, |v'| - v_max before the clamp)"""
+        c = self.c
+        x, v, push = s[:, 0], s[:, 1], np.asarray(a).astype(np.float64) - 1.0
+        vp = v + push * c["force"] + np.cos(c["freq"] * x) * (-c["gravity"])
+        m_v = np.abs(np.abs(vp) - c["v_max"])
+        vp = np.maximum(np.minimum(c["v_max"], vp), -c["v_max"])
+        xp = x + vp
+        m_w = np.abs(xp - c["x_min"])
+        wall = xp < c["x_min"]
+        xp, vp = np.where(wall, c["x_min"], xp), np.where(wall, 0.0, vp)
+        done = xp >= c["goal"]
+        r = c["cost"] + np.where(done, c["jackpot"], 0.0)
+        return np.stack([xp, vp], 1), r, done, np.minimum(np.minimum(m_v, m_w), np.abs(xp - c["goal"]))
+
+
+class InvertedPendulum(_ControlEnv):
+    """POMDPModels.InvertedPendulum, Lagoudakis & Parr's pendulum (third-party; recalled, not executed).  State (theta, omega); actions 0, 1, 2 apply -u_max, 0, +u_max
+    plus uniform noise; explicit Euler from the pre-step state; falls at |theta| > theta_max; reset uniform in [-init_half, init_half)^2."""
+    KIND = 4
+
+    def check(self):
+        c = self.c
+        if not c["dt"] > 0:
+            raise ValueError(f"InvertedPendulum: dt = {float(c['dt']):g} must be > 0")
+        if not c["l"] > 0:
+            raise ValueError(f"InvertedPendulum: l = {float(c['l']):g} must be > 0")
+        if not c["alpha"] * c["m"] < 4.0 / 3.0:
+            raise ValueError(f"InvertedPendulum: alpha * m = {float(c['alpha'] * c['m']):g} must lie below 4/3: the denominator (4/3) l - alpha m l cos^2(theta) can reach 0")
+
+    def reset_law(self, u13, u14):
+        c = self.c
+        return np.stack([(u13 - 0.5) * 2.0 * c["init_half"], (u14 - 0.5) * 2.0 * c["init_half"]], 1)
+
+    def step_law(self, s, a, u12):
+        """(state', Float64 reward, done, margin): margin = | |theta'| - theta_max | per copy"""
+        c = self.c
+        th, om, push = s[:, 0], s[:, 1], np.asarray(a).astype(np.float64) - 1.0
+        g, m, l, al, dt = c["g"], c["m"], c["l"], c["alpha"], c["dt"]
+        u = push * c["u_max"] + c["noise"] * (u12 - 0.5)
+        sn, cs, s2 = np.sin(th), np.cos(th), np.sin(2.0 * th)
+        acc = (g * sn - al * m * l * om * om * s2 * 0.5 - al * cs * u) / ((4.0 / 3.0) * l - al * m * l * cs * cs)
+        thp, omp = th + om * dt, om + acc * dt
+        done = np.abs(thp) > c["theta_max"]
+        return np.stack([thp, omp], 1), np.where(done, c["cost"], 0.0), done, np.abs(np.abs(thp) - c["theta_max"])
+
+
+def is_control(env):
+    """the env spec is one of the continuous-state control problems: the device loop steps it through dqn_envs_create_control"""
+    return isinstance(env, _ControlEnv)
 
 
 class TigerPOMDP(TabularPOMDP):

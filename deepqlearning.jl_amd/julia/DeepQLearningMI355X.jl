@@ -21,6 +21,7 @@ import DeepQLearning: batch_train!, add_exp!, update_priorities!, get_batch, pop
 import CommonRLInterface: AbstractEnv, observe, actions, act!, reset!, terminated
 import TensorBoardLogger: TBLogger, log_value
 import StatsBase
+import POMDPModels      # the problem types of envs_create_control! (MountainCar, InvertedPendulum)
 export MI355XSolver, HIPReplayBuffer, HIPEpisodeReplayBuffer, HIPNNPolicy, train_steps!, EngineGroup, close!, group_info, rollout_info
 
 const LIB = get(ENV, "DQN_MI355X_LIB", "libdqn_mi355x.so")
@@ -632,6 +633,30 @@ function envs_create_tabular!(e::Engine, problem::Union{MDP,POMDP}; n_envs, max_
         spec = TabularEnv(n_envs, max_episode_length, seed, t.n_states, t.n_obs, pointer(t.T), pz, pz0, pointer(t.R), pointer(t.terminal), pointer(t.b0), pointer(t.features))
         check(ccall((:dqn_envs_create_tabular, LIB), Cint, (Ptr{Cvoid}, Ref{TabularEnv}), e.h, spec))
     end
+end
+# ---- continuous-state control problems (dqn_control_env): POMDPModels' MountainCar and InvertedPendulum on the device loop.  Fields the problem carries itself
+# (MountainCar: cost, jackpot; InvertedPendulum: g, m, l, M, alpha, dt, cost) come from it, the rest are the header's defaults (recalled from POMDPModels 0.4)
+struct ControlEnv
+    kind::Int32; n_envs::Int32; max_episode_length::Int32; seed::UInt64
+    force::Float64; freq::Float64; gravity::Float64; v_max::Float64; x_min::Float64; goal::Float64; cost::Float64; jackpot::Float64; x0::Float64; v0::Float64
+    g::Float64; m::Float64; l::Float64; M::Float64; alpha::Float64; dt::Float64; u_max::Float64; noise::Float64; theta_max::Float64; init_half::Float64
+end
+const ENV_MOUNTAINCAR = Int32(3)
+const ENV_PENDULUM = Int32(4)
+control_spec(mdp::POMDPModels.MountainCar, n_envs, max_episode_length, seed) =
+    ControlEnv(ENV_MOUNTAINCAR, n_envs, max_episode_length, seed, 0.001, 3.0, 0.0025, 0.07, -1.2, 0.5, mdp.cost, mdp.jackpot, -0.5, 0.0,
+               9.81, 2.0, 8.0, 8.0, 1 / (2.0 + 8.0), 0.1, 50.0, 20.0, pi / 2, 0.1)
+control_spec(mdp::POMDPModels.InvertedPendulum, n_envs, max_episode_length, seed) =
+    ControlEnv(ENV_PENDULUM, n_envs, max_episode_length, seed, 0.001, 3.0, 0.0025, 0.07, -1.2, 0.5, mdp.cost, 100.0, -0.5, 0.0,
+               mdp.g, mdp.m, mdp.l, mdp.M, mdp.alpha, mdp.dt, 50.0, 20.0, pi / 2, 0.1)
+function envs_create_control!(e::Engine, mdp::Union{POMDPModels.MountainCar,POMDPModels.InvertedPendulum}; n_envs, max_episode_length = 100, seed = 0)
+    check(ccall((:dqn_envs_create_control, LIB), Cint, (Ptr{Cvoid}, Ref{ControlEnv}), e.h, control_spec(mdp, n_envs, max_episode_length, seed)))
+end
+# inspection: the Float64 states (2 x n_envs) of the control copies as they stand, and the states they held before their last step
+function envs_peek_state(e::Engine, n_envs)
+    s = zeros(Float64, 2, n_envs); p = zeros(Float64, 2, n_envs)
+    check(ccall((:dqn_envs_peek_state, LIB), Cint, (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), e.h, s, p))
+    s, p
 end
 function evaluate(e::Engine, n_eval, max_episode_length; seed = 0)                   # basic_evaluation (src/evaluation_policy.jl:17-42) on the device
     r = Ref{Float64}(0); st = Ref{Float64}(0)

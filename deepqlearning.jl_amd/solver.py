@@ -347,8 +347,8 @@ def initialize_replay_buffer(solver, env, engine):
         replay = HIPEpisodeReplayBuffer(engine)                      # EpisodeReplayBuffer(env, buffer_size, batch_size, trace_length), :183
         if not (solver.device_envs and getattr(engine, "recurrent_device_envs", False)):      # the device loop prefills itself (populate_episode_replay_device)
             populate_episode_replay(replay, env, max_pop=solver.train_start, rng=solver.rng)
-        elif envs.is_tabular(env):
-            # a tabular env on the device loop: the reference's own populate_replay_buffer! on a one-copy host instance of the same model, before the env set exists.
+        elif envs.is_tabular(env) or envs.is_control(env):
+            # a tabular or a control env on the device loop: the reference's own populate_replay_buffer! on a one-copy host instance of the same model, before the env set exists.
             # Its random episodes are committed whether or not they terminated (src/episode_replay.jl:97-130) -- for a model without terminal states (TigerPOMDP) the
             # training loop never commits one (add_exp!, :46-52), so this prefill is all the replay ever holds, as in the reference
             populate_episode_replay(replay, env.host_copy(1, seed=solver.seed), max_pop=solver.train_start, rng=solver.rng)
@@ -449,7 +449,7 @@ def dqn_train_device(solver, env, policy, replay):
     episode end); the default basic_evaluation runs on the device too (dqn_evaluate), a user-supplied one on the host copy."""
     e = policy.engine
     e.sync_target()
-    if solver.recurrence and not envs.is_tabular(env):           # (a tabular env was prefilled on the host, initialize_replay_buffer)
+    if solver.recurrence and not (envs.is_tabular(env) or envs.is_control(env)):           # (a tabular or a control env was prefilled on the host, initialize_replay_buffer)
         populate_episode_replay_device(solver, env, e)      # then the env set is created again under the solver's seed; committed episodes stay
     e.envs_create(env, n_envs=env.n, max_episode_length=solver.max_episode_length, seed=solver.seed)
     mk = _Marks()

@@ -405,6 +405,52 @@ typedef struct {
     const float*   features;      /* [O ? O : S][E]  convert_o / convert_s row per index, E = obs_c*obs_h*obs_w */
 } dqn_tabular_env;
 int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* spec);
+/* ---- continuous-state control problems: POMDPModels' MountainCar and InvertedPendulum on the device loop.  The state of a copy is two Float64 values, carried from
+ * step to step as the reference's MDPCommonRLEnv carries it; the observation is Float32[state[1], state[2]] (convert_s); there are three actions.  After creation the
+ * set behaves exactly as one made by dqn_envs_create: dqn_rollout, dqn_rollout_explore (both kinds), dqn_evaluate, dqn_envs_reset, dqn_envs_peek, dqn_envs_peek_q,
+ * dqn_envs_info and the lifecycle rules above apply unchanged, on feed-forward and recurrent engines, and as a member of an engine group.  The acting step takes the
+ * general four-launch tail (dqn_envs_info: fused_tail = 0).  dqn_envs_create answers "unknown environment kind" for these kinds, as it does for DQN_ENV_TABULAR.
+ *
+ * THE LAWS are those of POMDPModels 0.4 (third-party): RECALLED, NOT EXECUTED here.  Every constant is a field of the spec, so a different recollection is a
+ * different spec, not a different build.  Both laws are plain IEEE double arithmetic in the written order, left to right, without fused multiply-add; cos / sin are
+ * the device library's double versions (no fast intrinsic).  a = the action index 0, 1, 2.
+ *
+ * MOUNTAINCAR, state (x, v), push = a - 1:
+ *     v' = v + push * force + cos(freq * x) * (-gravity);   v' = max(min(v_max, v'), -v_max);   x' = x + v';   if x' < x_min: x' = x_min, v' = 0
+ *     done = x' >= goal;   r = cost + (done ? jackpot : 0).   Reset: (x0, v0), no draw.
+ * INVERTEDPENDULUM (Lagoudakis & Parr), state (theta, omega), explicit Euler from the pre-step state:
+ *     u = (a - 1) * u_max + noise * (U12 - 0.5)
+ *     acc = (g * sin(theta) - alpha * m * l * omega * omega * sin(2 * theta) * 0.5 - alpha * cos(theta) * u) / ((4 / 3) * l - alpha * m * l * cos(theta) * cos(theta))
+ *     theta' = theta + omega * dt;   omega' = omega + acc * dt;   done = |theta'| > theta_max;   r = done ? cost : 0
+ *     Reset: theta = (U13 - 0.5) * 2 * init_half,  omega = (U14 - 0.5) * 2 * init_half.
+ * A draw is U = (double)u01(philox(seed, t, i, purpose)) with the counter layout and the 24-bit u01 of the other kinds; U12 is drawn at the vector step of the
+ * transition, U13 / U14 at the step whose reset they serve (0 for dqn_envs_reset), as the other kinds' reset draws are.  The transition's s is the Float32
+ * observation of the pre-step state, sp that of the post-step state; the reward goes to the replay as (float)r.  Episode bookkeeping, truncation, pending resets,
+ * priorities and the open-episode rules of a recurrent engine are the loop's: nothing in them depends on the kind.
+ *
+ * Refused before the engine's current env set is touched, each with a message naming the field and the value: an unknown kind; n_envs outside what the engine
+ * kind allows (above); a constant that is not finite; dt <= 0; v_max <= 0; l <= 0; x_min >= goal; a pendulum whose denominator can reach 0 (4/3 <= alpha * m); an
+ * engine whose observation is not 2 floats or whose network has not 3 outputs; an engine with a u8 replay; an engine with a communicator or created under
+ * DQN_SIM_WORLD -- and dqn_comm_init once such a set exists (single GPU only). */
+enum { DQN_ENV_MOUNTAINCAR = 3, DQN_ENV_PENDULUM = 4 };
+enum { DQN_ENV_RAND_PEND_NOISE = 12, DQN_ENV_RAND_PEND_THETA0 = 13, DQN_ENV_RAND_PEND_OMEGA0 = 14 };      /* the pendulum's action noise, its reset of theta and of omega; 1-11 are taken */
+typedef struct {
+    int32_t kind;               /* DQN_ENV_MOUNTAINCAR or DQN_ENV_PENDULUM; the other member's constants are checked for finiteness only */
+    int32_t n_envs;
+    int32_t max_episode_length;
+    uint64_t seed;
+    /* MountainCar.  POMDPModels defaults: force 0.001, freq 3, gravity 0.0025, v_max 0.07, x_min -1.2, goal 0.5, cost -1, jackpot 100, x0 -0.5, v0 0 (discount 0.99) */
+    double force, freq, gravity, v_max, x_min, goal;
+    double cost;                /* both members: MountainCar's reward per step, the pendulum's reward on falling.  Default -1 for either */
+    double jackpot, x0, v0;
+    /* InvertedPendulum.  POMDPModels defaults: g 9.81, m 2, l 8, M 8, alpha 1 / (m + M), dt 0.1, u_max 50, noise 20, theta_max pi / 2, init_half 0.1 (discount 0.99).
+     * M enters the law through alpha only */
+    double g, m, l, M, alpha, dt, u_max, noise, theta_max, init_half;
+} dqn_control_env;
+int dqn_envs_create_control(dqn_engine_t* e, const dqn_control_env* spec);
+/* inspection (parity tests): the Float64 state of the training copies as it stands, and the state each copy held before its last step (what the last transition's s
+ * is the observation of; zero before the set's first step).  Either pointer may be NULL.  Refused on an env set of another kind. */
+int dqn_envs_peek_state(dqn_engine_t* e, double* state /* [n_envs][2] */, double* prev /* [n_envs][2] or NULL */);
 int dqn_envs_reset(dqn_engine_t* e);
 int dqn_rollout(dqn_engine_t* e, int n_vector_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* stats_or_null);
 /* ---- exploration by table: POMDPTools' two exploration policies, EpsGreedyPolicy and SoftmaxPolicy, each with any schedule (a number, a LinearDecaySchedule, any
