@@ -1,6 +1,7 @@
 // engine.h -- internal header of libdqn_mi355x.so's host side: the engine record, error/alloc helpers and the functions the
 // translation units engine.hip (ABI core, graphs, policy), engine_layers.hip (build_layers), engine_program.hip (static launch program of the train step),
-// engine_drqn.hip (EpisodeReplayBuffer + recurrent step) and engine_envs.hip (device-resident environments) share.
+// engine_drqn.hip (EpisodeReplayBuffer + recurrent step), engine_envs.hip (device-resident environments: env sets, acting programs, the rollout driver, evaluation)
+// and engine_group.hip (dqn_group_*: the group frame, grouped train steps, rollouts and evaluation) share.  rollout_sched.h: the rollout cadence (no HIP).
 #pragma once
 #include <dlfcn.h>
 #include <limits.h>
@@ -15,6 +16,7 @@
 #include <vector>
 #include "common.h"
 #include "devmem.h"
+#include "rollout_sched.h"
 
 #define HIPCHK(x) do { hipError_t _e = (x); if (_e != hipSuccess) return fail("HIP error %s at %s:%d (%s)", hipGetErrorString(_e), __FILE__, __LINE__, #x); } while (0)
 
@@ -254,5 +256,9 @@ int eval_envs_ensure(dqn_engine* e, int n_eval);      // the engine's evaluation
 // engine_envs.hip
 void free_envs(dqn_engine* e);
 int explore_check(const dqn_exploration* x, int n_steps);      // dqn_rollout_explore's table: 0, or -1 with the refusal (nothing is enqueued)
-int ep_mirror_push(dqn_engine* e);      // recurrent env sets: host (ep_widx, ep_size) -> the device cursor, before a rollout
+ReplayMeta replay_meta(const dqn_engine* e);      // the engine's transition ring as the acting tails are handed it
+RolloutDev rollout_record(const dqn_rollout_cfg* cfg, const dqn_engine* e);      // the RolloutDev a call starts from; cfg == NULL: the greedy record of an evaluation
+// THE host's ring cursor behind n added transitions (the device writes them; the host keeps count)
+static inline void ring_advance(dqn_engine* e, long long n) { e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); }
+int ep_mirror_push(dqn_engine* e);     // recurrent env sets: host (ep_widx, ep_size) -> the device cursor, before a rollout
 int ep_mirror_pull(dqn_engine* e);      // ... and the device cursor and lengths -> the host mirror (ep_widx, ep_size, ep_len_host): one D2H + one synchronize

@@ -28,13 +28,44 @@ static int envs_admit(dqn_engine* e, int n_envs, int max_episode_length) {
     if (max_episode_length < 1) return fail("max_episode_length must be >= 1");
     return 0;
 }
+// THE start of every creator: the family's refusals that need nothing but the engine -- u8 rows, the network's shape, single device (each in the family's own
+// wording) -- then envs_admit, then the header every kind shares, in H.  Nothing of the engine is touched: the creator validates the rest of its spec, then envs_install
+enum { ENV_FAM_BUILTIN = 0, ENV_FAM_TABULAR = 1, ENV_FAM_CONTROL = 2 };
+static int envs_begin(dqn_engine* e, int family, int kind, int n_envs, int max_episode_length, uint64_t seed, EnvDev& H) {
+    const char* const who = kind == DQN_ENV_MOUNTAINCAR ? "MountainCar" : "InvertedPendulum";
+    const char* const tag = family == ENV_FAM_TABULAR ? "tabular env" : "control env";
+    if (family != ENV_FAM_BUILTIN) {      // (the built-in kinds take replicas; SimpleGridWorld refuses u8 rows with its own shape rules)
+        if (e->hp.obs_dtype == DQN_OBS_U8) return family == ENV_FAM_TABULAR ? fail("%s: the feature rows are floats, this engine stores observations as u8: use obs_dtype f32", tag)
+                                                                             : fail("%s: %s observations are Float32[state[1], state[2]], this engine stores observations as u8: use obs_dtype f32", tag, who);
+        if (family == ENV_FAM_CONTROL && (e->E != 2 || e->nA != 3)) return fail("%s: %s has an observation of 2 floats and 3 actions (network: %d in, %d out)", tag, who, e->E, e->nA);
+        const char* const sets = family == ENV_FAM_TABULAR ? "device environments from tables" : "these device environments";
+        if (e->comm) return fail("%s: %s are single-device: this engine has a communicator (dqn_comm_init)", tag, sets);
+        if (e->opt.sim_world >= 1) return fail("%s: %s are single-device: this engine was created under DQN_SIM_WORLD", tag, sets);
+    }
+    if (envs_admit(e, n_envs, max_episode_length)) return -1;
+    memset(&H, 0, sizeof H);
+    H.kind = kind; H.n = n_envs; H.E = e->E; H.nA = e->nA; H.max_episode_length = max_episode_length; H.seed = seed; H.prioritized = e->hp.prioritized_replay ? 1 : 0;
+    return 0;
+}
+// the engine's current env set goes, H is the new one's header
+static int envs_install(dqn_engine* e, const EnvDev& H) { HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e); e->env = H; return 0; }
+// THE per-copy arrays of n copies of V's kind, in M: the kind's state, then the eight loop arrays every kind shares.  The training set (envs_finish) and the evaluation
+// copies (eval_envs_ensure) both come here, so a new kind is added once.  The two arrays a transition's s is read from before the set's first step are zeroed with
+// their kind -- for the evaluation copies too, where nothing reads them before a step writes them
+static int env_copy_state(DevScope& M, EnvDev& V, int n, hipStream_t st) {
+    if (V.kind == DQN_ENV_TESTMDP) { DM(M, V.tm_s, (size_t)n * 4); DM(M, V.tm_prev, (size_t)n * 4); DM(M, V.tm_t, n); }
+    else if (V.kind == DQN_ENV_TABULAR) { DM(M, V.tb_s, n); DM(M, V.tb_o, n); DM(M, V.tb_oprev, n); HIPCHK(hipMemsetAsync(V.tb_oprev, 0, (size_t)n * 4, st)); }
+    else if (env_is_control(V.kind)) { DM(M, V.ct_s, (size_t)n * 2); DM(M, V.ct_prev, (size_t)n * 2); HIPCHK(hipMemsetAsync(V.ct_prev, 0, (size_t)n * 2 * sizeof(double), st)); }
+    else { DM(M, V.gw_pos, (size_t)n * 2); DM(M, V.gw_prev, (size_t)n * 2); }
+    DM(M, V.actions, n); DM(M, V.rewards, n); DM(M, V.dones, n); DM(M, V.pending, n); DM(M, V.ep_reward, n); DM(M, V.ep_step, n); DM(M, V.fin_eps, n); DM(M, V.fin_reward, n);
+    return 0;
+}
 static int envs_finish(dqn_engine* e);
 extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
-    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
-    HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
-    EnvDev& V = e->env; const int n = sp->n_envs;
-    V.kind = sp->kind; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
+    EnvDev H;
+    if (envs_begin(e, ENV_FAM_BUILTIN, sp->kind, sp->n_envs, sp->max_episode_length, sp->seed, H) || envs_install(e, H)) return -1;
+    EnvDev& V = e->env;
     const bool u8 = e->hp.obs_dtype == DQN_OBS_U8;
     if (sp->kind == DQN_ENV_TESTMDP) {
         if (!sp->images) return fail("TestMDP needs its three images");
@@ -43,21 +74,20 @@ extern "C" int dqn_envs_create(dqn_engine_t* e, const dqn_env_spec* sp) { if (!e
         V.H = e->hp.obs_h; V.W = e->hp.obs_w; V.max_time = sp->max_time;
         const size_t ib = (size_t)3 * V.H * V.W;
         DM(e->env_mem, e->env_images, ib); HIPCHK(hipMemcpy(e->env_images, sp->images, ib, hipMemcpyHostToDevice)); V.images = e->env_images;
-        DM(e->env_mem, V.tm_s, (size_t)n * 4); DM(e->env_mem, V.tm_prev, (size_t)n * 4); DM(e->env_mem, V.tm_t, n);
     } else if (sp->kind == DQN_ENV_GRIDWORLD) {
         if (u8) return fail("SimpleGridWorld observations are Float32[x, y]: use obs_dtype f32");
         if (e->E != 2 || e->nA != 4) return fail("SimpleGridWorld: observation has 2 elements and there are 4 actions (network: %d in, %d out)", e->E, e->nA);
         if (sp->n_reward_cells < 0 || sp->n_reward_cells > 8) return fail("at most 8 reward cells");
         V.size_x = sp->size_x; V.size_y = sp->size_y; V.tprob = sp->tprob; V.n_reward = sp->n_reward_cells;
         for (int k = 0; k < V.n_reward; k++) { V.reward_xy[k][0] = sp->reward_xy[k][0]; V.reward_xy[k][1] = sp->reward_xy[k][1]; V.reward_val[k] = sp->reward_val[k]; }
-        DM(e->env_mem, V.gw_pos, (size_t)n * 2); DM(e->env_mem, V.gw_prev, (size_t)n * 2);
     } else return fail("unknown environment kind %d", sp->kind);
     return envs_finish(e);
 }
 // the per-copy loop state every kind shares, the open episodes of a recurrent engine, and the first reset
 static int envs_finish(dqn_engine* e) {
     EnvDev& V = e->env; const int n = V.n; const bool rec = e->hp.recurrence != 0;
-    DM(e->env_mem, V.actions, n); DM(e->env_mem, V.rewards, n); DM(e->env_mem, V.dones, n); DM(e->env_mem, V.pending, n); DM(e->env_mem, V.ep_reward, n); DM(e->env_mem, V.ep_step, n); DM(e->env_mem, V.fin_eps, n); DM(e->env_mem, V.fin_reward, n); DM(e->env_mem, e->roll, DQN_ROLL_RECORDS);
+    if (env_copy_state(e->env_mem, V, n, e->stream)) return -1;
+    DM(e->env_mem, e->roll, DQN_ROLL_RECORDS);
     HIPCHK(hipMemsetAsync(V.fin_eps, 0, (size_t)n * 8, e->stream)); HIPCHK(hipMemsetAsync(V.fin_reward, 0, (size_t)n * 8, e->stream));
     HIPCHK(hipMemsetAsync(V.actions, 0, (size_t)n * 4, e->stream)); HIPCHK(hipMemsetAsync(V.rewards, 0, (size_t)n * 4, e->stream));
     HIPCHK(hipMemsetAsync(e->roll, 0, sizeof(RolloutDev) * DQN_ROLL_RECORDS, e->stream));
@@ -77,10 +107,8 @@ extern "C" int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* s
     const long long S = sp->n_states, O = sp->n_obs, A = e->nA, E = e->E, NO = O ? O : S;
     if (S < 1 || S > 1024) return fail("tabular env: n_states = %d must be in 1..1024", sp->n_states);
     if (O < 0 || O > 1024) return fail("tabular env: n_obs = %d must be in 0..1024 (0: an MDP)", sp->n_obs);
-    if (e->hp.obs_dtype == DQN_OBS_U8) return fail("tabular env: the feature rows are floats, this engine stores observations as u8: use obs_dtype f32");
-    if (e->comm) return fail("tabular env: device environments from tables are single-device: this engine has a communicator (dqn_comm_init)");
-    if (e->opt.sim_world >= 1) return fail("tabular env: device environments from tables are single-device: this engine was created under DQN_SIM_WORLD");
-    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
+    EnvDev H;
+    if (envs_begin(e, ENV_FAM_TABULAR, DQN_ENV_TABULAR, sp->n_envs, sp->max_episode_length, sp->seed, H)) return -1;
     if (!sp->T) return fail("tabular env: T (transition table [S][A][S]) is NULL");
     if (!sp->R) return fail("tabular env: R (reward table [S][A][S]) is NULL");
     if (!sp->terminal) return fail("tabular env: terminal ([S]) is NULL");
@@ -118,16 +146,13 @@ extern "C" int dqn_envs_create_tabular(dqn_engine_t* e, const dqn_tabular_env* s
     if (rows("b0", sp->b0, 1, 1, 1, S, false, h.data() + oB)) return -1;
     for (size_t q = 0; q < nT; q++) { const float v = sp->R[q]; if (!std::isfinite(v)) return fail("tabular env: R[%zu][%zu][%zu] = %g is not finite", q / (size_t)(A * S), q / (size_t)S % (size_t)A, q % (size_t)S, (double)v); h[oR + q] = v; }
     for (size_t q = 0; q < nF; q++) { const float v = sp->features[q]; if (!std::isfinite(v)) return fail("tabular env: features[%zu][%zu] = %g is not finite", q / (size_t)E, q % (size_t)E, (double)v); h[oF + q] = v; }
-    HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
-    EnvDev& V = e->env; const int n = sp->n_envs;
-    V.kind = DQN_ENV_TABULAR; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
+    if (envs_install(e, H)) return -1;
+    EnvDev& V = e->env;
     V.tb_S = (int)S; V.tb_O = (int)O;
     DM(e->env_mem, e->env_tab, tot); HIPCHK(hipMemcpy(e->env_tab, h.data(), tot * sizeof(float), hipMemcpyHostToDevice));
     DM(e->env_mem, e->env_term, (size_t)S); HIPCHK(hipMemcpy(e->env_term, sp->terminal, (size_t)S, hipMemcpyHostToDevice));
     V.tb_T = e->env_tab + oT; V.tb_R = e->env_tab + oR; V.tb_Z = O ? e->env_tab + oZ : nullptr; V.tb_Z0 = O ? e->env_tab + oZ0 : nullptr; V.tb_b0 = e->env_tab + oB; V.tb_feat = e->env_tab + oF;
     V.tb_term = e->env_term;
-    DM(e->env_mem, V.tb_s, n); DM(e->env_mem, V.tb_o, n); DM(e->env_mem, V.tb_oprev, n);
-    HIPCHK(hipMemsetAsync(V.tb_oprev, 0, (size_t)n * 4, e->stream));
     return envs_finish(e);
 }
 // MountainCar / InvertedPendulum (the laws: include/dqn_mi355x.h).  Everything is validated before the engine's current env set is touched.
@@ -135,12 +160,8 @@ extern "C" int dqn_envs_create_control(dqn_engine_t* e, const dqn_control_env* s
     if (!sp) return fail("null control spec");
     HIPCHK(hipSetDevice(e->device));
     if (!env_is_control(sp->kind)) return fail("control env: unknown kind %d (3: MountainCar, 4: InvertedPendulum)", sp->kind);
-    const char* const who = sp->kind == DQN_ENV_MOUNTAINCAR ? "MountainCar" : "InvertedPendulum";
-    if (e->hp.obs_dtype == DQN_OBS_U8) return fail("control env: %s observations are Float32[state[1], state[2]], this engine stores observations as u8: use obs_dtype f32", who);
-    if (e->E != 2 || e->nA != 3) return fail("control env: %s has an observation of 2 floats and 3 actions (network: %d in, %d out)", who, e->E, e->nA);
-    if (e->comm) return fail("control env: these device environments are single-device: this engine has a communicator (dqn_comm_init)");
-    if (e->opt.sim_world >= 1) return fail("control env: these device environments are single-device: this engine was created under DQN_SIM_WORLD");
-    if (envs_admit(e, sp->n_envs, sp->max_episode_length)) return -1;
+    EnvDev H;
+    if (envs_begin(e, ENV_FAM_CONTROL, sp->kind, sp->n_envs, sp->max_episode_length, sp->seed, H)) return -1;
     static const char* const names[CT_N] = {"force", "freq", "gravity", "v_max", "x_min", "goal", "cost", "jackpot", "x0", "v0", "g", "m", "l", "M", "alpha", "dt", "u_max", "noise", "theta_max", "init_half"};
     static_assert(offsetof(dqn_control_env, init_half) - offsetof(dqn_control_env, force) == (CT_N - 1) * sizeof(double), "CT_* follows the struct's own order");
     const double* const c = &sp->force;
@@ -153,12 +174,8 @@ extern "C" int dqn_envs_create_control(dqn_engine_t* e, const dqn_control_env* s
         if (!(sp->l > 0.0)) return fail("control env: l = %g must be > 0", sp->l);
         if (!(sp->alpha * sp->m < 4.0 / 3.0)) return fail("control env: alpha * m = %g must lie below 4/3 (alpha = %g, m = %g): the denominator (4/3) l - alpha m l cos^2(theta) can reach 0", sp->alpha * sp->m, sp->alpha, sp->m);
     }
-    HIPCHK(hipStreamSynchronize(e->stream)); free_envs(e);
-    EnvDev& V = e->env; const int n = sp->n_envs;
-    V.kind = sp->kind; V.n = n; V.E = e->E; V.nA = e->nA; V.max_episode_length = sp->max_episode_length; V.seed = sp->seed; V.prioritized = e->hp.prioritized_replay ? 1 : 0;
-    double* cb = nullptr; DM(e->env_mem, cb, (size_t)CT_N); HIPCHK(hipMemcpy(cb, c, CT_N * sizeof(double), hipMemcpyHostToDevice)); V.ct_c = cb;
-    DM(e->env_mem, V.ct_s, (size_t)n * 2); DM(e->env_mem, V.ct_prev, (size_t)n * 2);
-    HIPCHK(hipMemsetAsync(V.ct_prev, 0, (size_t)n * 2 * sizeof(double), e->stream));
+    if (envs_install(e, H)) return -1;
+    double* cb = nullptr; DM(e->env_mem, cb, (size_t)CT_N); HIPCHK(hipMemcpy(cb, c, CT_N * sizeof(double), hipMemcpyHostToDevice)); e->env.ct_c = cb;
     return envs_finish(e);
 }
 extern "C" int dqn_envs_peek_state(dqn_engine_t* e, double* state, double* prev) { if (!e) return fail("null engine handle");
@@ -236,6 +253,8 @@ static int emit_act_program_rec(dqn_engine* e, dqn_engine::ActProg& ap, const En
     if (!eval) ap.steps.push_back({"episode_commit", [=](dqn_engine* en) { launch_ep_commit(en->stream, Vc, ES); }});
     ap.fused_tail = false; return 0;
 }
+// THE description of the engine's transition ring the acting tails write into (emit_act_program, tiny_act_record of engine_group.hip)
+ReplayMeta replay_meta(const dqn_engine* e) { return ReplayMeta{e->cap, e->cap2, e->ra, e->rr, e->rdone, e->tree, e->state, e->hp.prio_eps, e->hp.prio_alpha}; }
 // the acting program: online net forward on the n columns of pol_x (batch-innermost), then Q columns + first-max argmax
 // (action(policy, obs), src/policy.jl:38-64) -- the train step's forward emitter (emit_forward, engine_program.hip) with one pass: the same tiled kernels, plan and
 // selection rules, compiled once per n
@@ -256,7 +275,7 @@ static int emit_act_program(dqn_engine* e, dqn_engine::ActProg& ap, const EnvDev
     FwdEmit fe; fe.gemm = "act_fwd"; fe.valu = "act_fwd_valu"; fe.reduce = "act_reduce"; fe.skip_last = use_ah /* the head level runs inside k_act_head */; fe.last_on_the_fly = true; fe.head = head;
     if (use_ah) { fe.prod[0] = ah_pa; fe.prod[1] = ah_pv; fe.pm_ok = ah_S > 1 && !e->opt.no_rh_pm; }
     emit_forward(e, levels, 0, levels.size(), {{P, e->pol_x, n, 0, e->pol_act, e->pol_act, n, "act_fwd"}}, fe);
-    ReplayMeta R; R.cap = e->cap; R.cap2 = e->cap2; R.a = e->ra; R.r = e->rr; R.done = e->rdone; R.tree = e->tree; R.state = e->state; R.eps = e->hp.prio_eps; R.alpha = e->hp.prio_alpha;
+    const ReplayMeta R = replay_meta(e);
     const bool u8 = e->hp.obs_dtype == DQN_OBS_U8;
     void *srows = e->s_rows, *sprows = e->sp_rows; float* px = e->pol_x; const long long cap = e->cap; const EnvDev Vc = V;
     if (use_ah) {
@@ -340,131 +359,111 @@ static int explore_upload(dqn_engine* e, const dqn_exploration* x, long long t0,
     h.xkind = x->kind; h.xtab = e->xtab; h.xtab_t0 = t0; h.xtab_n = x->n_values;
     return 0;
 }
-// dqn_rollout on a recurrent engine: the acting step (graph or launches), then -- when train steps are due and the ring holds a batch of episodes -- the sampled
-// recurrent step(s) with the host SplitMix sampler, whose mirror of the ring (ep_size, ep_widx, ep_len_host) is refreshed from the device before the draw.  No cycle
-// or whole-step graphs: the draw is a host decision.  The train step works on its own sequence buffers and leaves the policy's Recur state alone (src/solver.jl:137-139).
-static int rollout_rec(dqn_engine* e, int n_steps, const dqn_rollout_cfg* cfg, const dqn_exploration* x, dqn_rollout_stats* out) {
-    EnvDev& V = e->env; const int n = V.n;
-    if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before dqn_rollout");
-    if (e->comm) return fail("device environments on a recurrent engine are single-device: this engine has a communicator");
-    if (policy_state(e, n, false)) return -1;      // (the host ran another stream count in between: n streams again, at state0)
-    if (build_act_program(e, e->act, V, e->roll)) return -1;
-    if (cfg->train_freq > 0 && build_program(e)) return -1;
-    RolloutDev h; memset(&h, 0, sizeof h); h.t = cfg->t0 - 1; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
-    if (explore_upload(e, x, cfg->t0, h)) return -1;
-    { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
-      HIPCHK(hipMemcpyAsync(e->roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); if (ep_mirror_push(e)) return -1; }
-    launch_env_observe(e->stream, V, nullptr, 0, e->pol_x);
-    const bool graph = e->hp.use_graph && !e->profiling;
-    if (graph && act_graph(e, e->act)) return -1;
-    const bool envc = cfg->cadence_env_steps != 0; const long long tf = cfg->train_freq, tu = cfg->target_update_freq;
-    long long trained = 0;
-    for (int k = 0; k < n_steps; k++) {
-        const long long t = cfg->t0 + k;
-        if (graph) HIPCHK(hipGraphLaunch(e->act.graph, e->stream));
-        else for (auto& s : e->act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
-        const long long due = tf > 0 ? (envc ? (t * n) / tf - ((t - 1) * n) / tf : (t % tf == 0 ? 1 : 0)) : 0;
-        if (due > 0) {
-            if (ep_mirror_pull(e)) return -1;
-            if (e->ep_size >= e->B) { if (envc ? drqn_train_steps(e, (int)due, nullptr, nullptr) : dqn_train_step_drqn(e, nullptr, nullptr, nullptr, nullptr)) return -1; trained += due; }
-        }
-        if (tu > 0 && (envc ? (t * n) / tu != ((t - 1) * n) / tu : t % tu == 0)) { if (dqn_sync_target(e)) return -1; }
-    }
-    if (n_steps > 0) e->env_q_valid = true;      // pol_q / pol_a: the last vector step's (dqn_envs_peek_q)
-    launch_recur_reset(e->stream, V.pending, n, recur_state(e, false));      // resetstate!(policy) of the copies whose episode ended in the last step, then their env reset
-    launch_env_reset_pending(e->stream, V, e->roll, 0);
-    std::vector<long long> fe(n); std::vector<double> fr(n);
-    HIPCHK(hipMemcpyAsync(fe.data(), V.fin_eps, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(fr.data(), V.fin_reward, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-    if (ep_mirror_pull(e)) return -1;      // dqn_episode_export / dqn_get_counters describe the committed ring
-    if (out) {
-        out->last_loss = out->last_grad_norm = 0.0f;
-        if (trained && fetch_scalars(e, &out->last_loss, &out->last_grad_norm)) return -1;
-        out->episodes = 0; out->reward_sum = 0.0; out->train_steps = trained;
-        for (int i = 0; i < n; i++) { out->episodes += fe[i]; out->reward_sum += fr[i]; }
-    }
+// THE RolloutDev record a call starts from: the step counter, the ring cursor behind which the first vector step writes (a recurrent engine keeps no host ring
+// cursor: its episode ring's is on the device, ep_mirror_push) and the linear eps law.  cfg == NULL: the greedy record of an evaluation (t = 0, the schedule (0, 0, 1))
+RolloutDev rollout_record(const dqn_rollout_cfg* cfg, const dqn_engine* e) {
+    RolloutDev h; memset(&h, 0, sizeof h);
+    if (!cfg) { h.eps_steps = 1.0f; return h; }
+    h.t = cfg->t0 - 1; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
+    if (!e->hp.recurrence) { const int n = e->env.n; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; }
+    return h;
+}
+// ... uploaded as the DQN_ROLL_RECORDS records of an env set: one per group of four copies (k_act_head ticks its group's), record 0 = the four-launch tail's.  The
+// synchronise that keeps the host copies alive is this function's -- or, mirror: ep_mirror_push's, which sends the host's episode cursor behind the records
+static int roll_upload(dqn_engine* e, RolloutDev* dev, const RolloutDev& h, bool mirror) {
+    const std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
+    HIPCHK(hipMemcpyAsync(dev, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream));
+    if (mirror) return ep_mirror_push(e);
+    HIPCHK(hipStreamSynchronize(e->stream)); return 0;
+}
+// THE way a vector step is enqueued (the rollouts, dqn_evaluate): the program's graph, else its launches inside profiling brackets
+static int act_step(dqn_engine* e, dqn_engine::ActProg& ap, bool graph) {
+    if (graph) HIPCHK(hipGraphLaunch(ap.graph, e->stream)); else for (auto& s : ap.steps) RUN(e, s.name, s.fn(e));
     return 0;
 }
+// the statistics of a rollout call: the episodes finished and their rewards, summed in copy order, beside the last train step's scalars.  Where the two engine kinds
+// synchronise differs and is kept: a recurrent engine pulls the episode mirror (dqn_episode_export / dqn_get_counters describe the committed ring) whether or not
+// the caller wants statistics, and that pull is its synchronise; a feed-forward engine synchronises only for a caller who does (fetch_scalars, or the stream)
+static int rollout_stats(dqn_engine* e, long long trained, dqn_rollout_stats* out) {
+    const EnvDev& V = e->env; const int n = V.n; const bool rec = e->hp.recurrence != 0;
+    std::vector<long long> fe(n); std::vector<double> fr(n);
+    if (out || rec) {
+        HIPCHK(hipMemcpyAsync(fe.data(), V.fin_eps, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+        HIPCHK(hipMemcpyAsync(fr.data(), V.fin_reward, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
+    }
+    if (rec && ep_mirror_pull(e)) return -1;
+    if (!out) return 0;
+    out->last_loss = out->last_grad_norm = 0.0f;
+    if (trained) { if (fetch_scalars(e, &out->last_loss, &out->last_grad_norm)) return -1; } else if (!rec) HIPCHK(hipStreamSynchronize(e->stream));
+    out->episodes = 0; out->reward_sum = 0.0; out->train_steps = trained;
+    for (int i = 0; i < n; i++) { out->episodes += fe[i]; out->reward_sum += fr[i]; }
+    return 0;
+}
+// the `due` train steps behind a PLAIN unit, where the replay holds a batch; *trained counts them.  A feed-forward engine: the sampled step, or dqn_train_steps back to
+// back under the env-step cadence (the pipelined gather applies).  A recurrent engine draws on the host (SplitMix), so its mirror of the episode ring is refreshed
+// from the device before the draw; the train step works on its own sequence buffers and leaves the policy's Recur state alone (src/solver.jl:137-139)
+static int rollout_train(dqn_engine* e, bool envc, long long due, long long* trained) {
+    if (due <= 0) return 0;
+    if (e->hp.recurrence) {
+        if (ep_mirror_pull(e)) return -1;
+        if (e->ep_size < e->B) return 0;
+        if (envc ? drqn_train_steps(e, (int)due, nullptr, nullptr) : dqn_train_step_drqn(e, nullptr, nullptr, nullptr, nullptr)) return -1;
+    } else {
+        if (e->size < e->B) return 0;
+        if (envc ? dqn_train_steps(e, (int)due, nullptr, nullptr) : run_step(e, true)) return -1;     // :134-139
+    }
+    *trained += due; return 0;
+}
 extern "C" int dqn_rollout(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, dqn_rollout_stats* out) { return dqn_rollout_explore(e, n_steps, cfg, nullptr, out); }
-// x == NULL: dqn_rollout.  Else the exploration table is validated (nothing is enqueued by a refused call), uploaded, and named by the RolloutDev records
+// THE rollout driver, feed-forward and recurrent engines: a prologue (refusals, programs, the call's record and table, the first observe, the acting graph), a loop
+// over the units rollout_sched.h chooses, an epilogue (pending resets, statistics).  x == NULL: dqn_rollout.  Else the exploration table is validated (nothing is
+// enqueued by a refused call), uploaded, and named by the RolloutDev records.  A recurrent engine differs in named places only: its refusals and policy_state here,
+// the mirror push in roll_upload, no ring cursor (rollout_record, the loop), PLAIN units only (rollout_unit), rollout_train, the recur_reset before the last env
+// reset, the mirror pull in rollout_stats
 extern "C" int dqn_rollout_explore(dqn_engine_t* e, int n_steps, const dqn_rollout_cfg* cfg, const dqn_exploration* x, dqn_rollout_stats* out) { if (!e) return fail("null engine handle");
     HIPCHK(hipSetDevice(e->device));
     if (!e->has_envs) return fail("no device environments: call dqn_envs_create");
     if (cfg->t0 < 1) return fail("t0 counts from 1 (src/solver.jl:82)");
     if (explore_check(x, n_steps)) return -1;
-    if (e->hp.recurrence) return rollout_rec(e, n_steps, cfg, x, out);
-    EnvDev& V = e->env; const int n = V.n;
+    EnvDev& V = e->env; const int n = V.n; const bool rec = e->hp.recurrence != 0;
+    if (rec) {
+        if (e->ep_cur_len > 0) return fail("an episode is open on the host side (dqn_episode_add without its terminal transition): finish it or call dqn_episode_commit before dqn_rollout");
+        if (e->comm) return fail("device environments on a recurrent engine are single-device: this engine has a communicator");
+        if (policy_state(e, n, false)) return -1;      // (the host ran another stream count in between: n streams again, at state0)
+    }
     if (build_act_program(e, e->act, V, e->roll)) return -1;
     // a table is read by the general tail only: where the set's program has the fused one, its general twin runs this call (both stay built)
     if (x && e->act.fused_tail && build_act_program(e, e->act_gen, V, e->roll, true)) return -1;
     dqn_engine::ActProg& act = (x && e->act.fused_tail) ? e->act_gen : e->act;
     if (cfg->train_freq > 0 && build_program(e)) return -1;       // may reallocate split-K workspaces: before any capture
-    RolloutDev h; memset(&h, 0, sizeof h); h.t = cfg->t0 - 1; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; h.eps_start = cfg->eps_start; h.eps_stop = cfg->eps_stop; h.eps_steps = cfg->eps_steps;
-    if (explore_upload(e, x, cfg->t0, h)) return -1;
-    { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);      // one record per group of four copies (k_act_head ticks its group's), record 0 = the four-launch tail's
-      HIPCHK(hipMemcpyAsync(e->roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream)); }   // hs lives in this scope
+    RolloutDev h = rollout_record(cfg, e);
+    if (explore_upload(e, x, cfg->t0, h) || roll_upload(e, e->roll, h, rec)) return -1;
     launch_env_observe(e->stream, V, nullptr, 0, e->pol_x);
     const bool graph = e->hp.use_graph && !e->profiling;
     if (graph && act_graph(e, act)) return -1;
+    // whole cycles -- train_freq acting steps ending on a train step (or 4 acting steps when nothing trains) -- and whole vector steps of the env-step cadence replay
+    // as ONE graph where the schedule allows it (rollout_unit); d: what is due behind the unit's last step
+    RollFacts f; f.graph = graph; f.single = e->world <= 1 && !(e->comm && e->force_comm); f.tiny = e->tiny; f.rec = rec; f.n = n; f.cap = e->cap; f.B = e->B;
+    const int F = rollout_cycle_len(*cfg); const bool envc = cfg->cadence_env_steps != 0;
     long long trained = 0;
-    // whole cycles -- train_freq acting steps ending on a train step (or 4 acting steps when nothing trains) -- replay as ONE graph where the
-    // schedule allows it: single device, the train step due exactly at the cycle's last step, the replay already holding a batch, no target sync
-    // before the cycle's last step
-    const bool single = e->world <= 1 && !(e->comm && e->force_comm);
-    const int F = cfg->train_freq > 0 ? cfg->train_freq : 4;
-    const bool envc = cfg->cadence_env_steps != 0;      // train_freq / target_update_freq count ENV steps (src/solver.jl:136-145): n / train_freq train steps per vector step
-    const bool cyc = graph && single && F >= 2 && F <= 16 && !envc;
-    for (int k = 0; k < n_steps; k++) {
+    for (int k = 0, len = 1; k < n_steps; k += len) {
         const long long t = cfg->t0 + k;
-        if (envc) {
-            // the whole vector step as one graph where every vector step owes the same number of train steps and the replay holds a batch once this step's experiences are in
-            if (graph && single && !e->tiny && cfg->train_freq > 0 && n % cfg->train_freq == 0 && n / cfg->train_freq <= 64 && std::min(e->cap, e->size + n) >= e->B) {
-                const int due_c = n / cfg->train_freq;
-                if (envc_graph(e, act, due_c)) return -1;
-                HIPCHK(hipGraphLaunch(act.envc, e->stream));
-                e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); trained += due_c;
-                if (cfg->target_update_freq > 0 && (t * n) / cfg->target_update_freq != ((t - 1) * n) / cfg->target_update_freq) { if (dqn_sync_target(e)) return -1; }
-                continue;
-            }
-            if (graph) HIPCHK(hipGraphLaunch(act.graph, e->stream));
-            else for (auto& s : act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
-            e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n);
-            const long long due = cfg->train_freq > 0 ? (t * n) / cfg->train_freq - ((t - 1) * n) / cfg->train_freq : 0;
-            if (due > 0 && e->size >= e->B) { if (dqn_train_steps(e, (int)due, nullptr, nullptr)) return -1; trained += due; }      // back to back: the pipelined gather applies
-            if (cfg->target_update_freq > 0 && (t * n) / cfg->target_update_freq != ((t - 1) * n) / cfg->target_update_freq) { if (dqn_sync_target(e)) return -1; }
-            continue;
-        }
-        if (cyc && k + F <= n_steps) {
-            const long long tl = t + F - 1;      // the cycle's last step
-            bool ok = cfg->train_freq > 0 ? (tl % cfg->train_freq == 0 && std::min(e->cap, e->size + (long long)F * n) >= e->B) : true;
-            if (cfg->target_update_freq > 0) for (long long u = t; u < tl; u++) ok = ok && (u % cfg->target_update_freq != 0);
-            if (ok) {
-                if (cycle_graph(e, act, F, cfg->train_freq > 0)) return -1;
-                HIPCHK(hipGraphLaunch(act.cycle, e->stream));
-                for (int f = 0; f < F; f++) { e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); }
-                if (cfg->train_freq > 0) trained++;
-                if (cfg->target_update_freq > 0 && tl % cfg->target_update_freq == 0) { if (dqn_sync_target(e)) return -1; }
-                k += F - 1; continue;
-            }
-        }
-        if (graph) HIPCHK(hipGraphLaunch(act.graph, e->stream));
-        else for (auto& s : act.steps) { prof_begin(e, s.name); s.fn(e); prof_end(e); }
-        e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n);
-        if (cfg->train_freq > 0 && t % cfg->train_freq == 0 && e->size >= e->B) { if (run_step(e, true)) return -1; trained++; }     // :134-139
-        if (cfg->target_update_freq > 0 && t % cfg->target_update_freq == 0) { if (dqn_sync_target(e)) return -1; }                // :142-145
+        f.left = n_steps - k; f.size = e->size;
+        const RollUnit u = rollout_unit(*cfg, t, f);
+        len = u == ROLL_CYCLE ? F : 1;
+        const RollDue d = rollout_due(*cfg, t + len - 1, n);
+        if (u == ROLL_ENVC) { if (envc_graph(e, act, (int)d.due)) return -1; HIPCHK(hipGraphLaunch(act.envc, e->stream)); }
+        else if (u == ROLL_CYCLE) { if (cycle_graph(e, act, F, d.due > 0)) return -1; HIPCHK(hipGraphLaunch(act.cycle, e->stream)); }
+        else if (act_step(e, act, graph)) return -1;
+        if (!rec) ring_advance(e, (long long)len * n);
+        if (u != ROLL_PLAIN) trained += d.due;      // (inside the unit's graph)
+        else if (rollout_train(e, envc, d.due, &trained)) return -1;
+        if (d.sync && dqn_sync_target(e)) return -1;      // :142-145
     }
     if (n_steps > 0) e->env_q_valid = true;      // pol_q / pol_a: the last vector step's (dqn_envs_peek_q)
+    if (rec) launch_recur_reset(e->stream, V.pending, n, recur_state(e, false));      // resetstate!(policy) of the copies whose episode ended in the last step, then their env reset
     launch_env_reset_pending(e->stream, V, e->roll, 0);      // episode bookkeeping of the last step (src/solver.jl:99-132)
-    if (out) {
-        std::vector<long long> fe(n); std::vector<double> fr(n);
-        HIPCHK(hipMemcpyAsync(fe.data(), V.fin_eps, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipMemcpyAsync(fr.data(), V.fin_reward, (size_t)n * 8, hipMemcpyDeviceToHost, e->stream));
-        out->last_loss = out->last_grad_norm = 0.0f;
-        if (trained) { if (fetch_scalars(e, &out->last_loss, &out->last_grad_norm)) return -1; } else HIPCHK(hipStreamSynchronize(e->stream));
-        out->episodes = 0; out->reward_sum = 0.0; out->train_steps = trained;
-        for (int i = 0; i < n; i++) { out->episodes += fe[i]; out->reward_sum += fr[i]; }
-    }
-    return 0;
+    return rollout_stats(e, trained, out);
 }
 // the evaluation copies of an engine: n_eval copies of the training MDP with per-copy arrays of their own (the images, the spec and the tables are the training
 // set's), allocated on first use and again when n_eval changes.  dqn_evaluate and dqn_evaluate_many (engine_group.hip) step the same set
@@ -473,11 +472,8 @@ int eval_envs_ensure(dqn_engine* e, int n_eval) {
     if (e->eval_n == n_eval) return 0;
     HIPCHK(hipStreamSynchronize(e->stream)); drop_act(e, e->evalp); free_eval_envs(e);
     W = e->env; W.n = n_eval; W.eval_mode = 1; DevScope& M = e->eval_mem;
-    if (W.kind == DQN_ENV_TESTMDP) { DM(M, W.tm_s, (size_t)n_eval * 4); DM(M, W.tm_prev, (size_t)n_eval * 4); DM(M, W.tm_t, n_eval); }
-    else if (W.kind == DQN_ENV_TABULAR) { DM(M, W.tb_s, n_eval); DM(M, W.tb_o, n_eval); DM(M, W.tb_oprev, n_eval); }      // the tables are the training set's
-    else if (env_is_control(W.kind)) { DM(M, W.ct_s, (size_t)n_eval * 2); DM(M, W.ct_prev, (size_t)n_eval * 2); }      // the constants are the training set's
-    else { DM(M, W.gw_pos, (size_t)n_eval * 2); DM(M, W.gw_prev, (size_t)n_eval * 2); }
-    DM(M, W.actions, n_eval); DM(M, W.rewards, n_eval); DM(M, W.dones, n_eval); DM(M, W.pending, n_eval); DM(M, W.ep_reward, n_eval); DM(M, W.ep_step, n_eval); DM(M, W.fin_eps, n_eval); DM(M, W.fin_reward, n_eval); DM(M, e->eval_roll, DQN_ROLL_RECORDS);
+    if (env_copy_state(M, W, n_eval, e->stream)) return -1;      // (the tables, constants and images stay the training set's)
+    DM(M, e->eval_roll, DQN_ROLL_RECORDS);
     for (int i = 0; i < e->nl; i++) if (is_recurrent(e->L[i].kind)) {      // recurrent engines: the evaluation copies' private Recur state, n_eval streams
         DM(M, e->eval_h[i], (size_t)e->L[i].H * n_eval); if (cell_ops(e->L[i].kind)->has_c) DM(M, e->eval_c[i], (size_t)e->L[i].H * n_eval); DM(M, e->eval_gx[i], (size_t)e->L[i].N * n_eval);
     }
@@ -500,10 +496,7 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
     if (W.seed != seed || W.max_episode_length != max_episode_length) { W.seed = seed; W.max_episode_length = max_episode_length; drop_act(e, e->evalp); }   // baked into the program
     if (build_act_program(e, e->evalp, W, e->eval_roll)) return -1;
     e->env_q_valid = false;      // the evaluation copies' forward writes pol_q / pol_a (dqn_envs_peek_q is refused until the training set steps again)
-    RolloutDev h; memset(&h, 0, sizeof h);                                   // t = 0; eps schedule (0, 0, 1): always greedy
-    h.eps_steps = 1.0f;
-    { std::vector<RolloutDev> hs(DQN_ROLL_RECORDS, h);
-      HIPCHK(hipMemcpyAsync(e->eval_roll, hs.data(), sizeof(RolloutDev) * DQN_ROLL_RECORDS, hipMemcpyHostToDevice, e->stream)); HIPCHK(hipStreamSynchronize(e->stream)); }
+    if (roll_upload(e, e->eval_roll, rollout_record(nullptr, e), false)) return -1;      // always greedy
     HIPCHK(hipMemsetAsync(W.fin_reward, 0, (size_t)n_eval * 8, e->stream));
     launch_env_reset_pending(e->stream, W, e->eval_roll, 1);                   // reset!(env), resetstate!(policy)
     launch_env_observe(e->stream, W, nullptr, 0, e->pol_x);
@@ -511,7 +504,7 @@ extern "C" int dqn_evaluate(dqn_engine_t* e, int n_eval, int max_episode_length,
     if (graph && act_graph(e, e->evalp)) return -1;
     std::vector<unsigned char> pend(n_eval);
     for (int k = 0; k <= max_episode_length; k++) {
-        if (graph) HIPCHK(hipGraphLaunch(e->evalp.graph, e->stream)); else for (auto& s : e->evalp.steps) s.fn(e);
+        if (act_step(e, e->evalp, graph)) return -1;
         if ((k & 7) == 7) {     // every 8 vector steps: stop early once every episode is over
             HIPCHK(hipMemcpyAsync(pend.data(), W.pending, n_eval, hipMemcpyDeviceToHost, e->stream)); HIPCHK(hipStreamSynchronize(e->stream));
             bool alive = false; for (int i = 0; i < n_eval; i++) alive = alive || !pend[i];

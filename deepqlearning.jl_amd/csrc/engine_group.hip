@@ -41,6 +41,39 @@ __global__ __launch_bounds__(256) void k_group_scalars(const TinyArgs* __restric
     out[k] = o;
 }
 
+// THE frame of a group call (dqn_group_train_steps, dqn_rollout_many, dqn_evaluate_many).  In: the group's stream behind everything the members have enqueued
+// (replay_add, their own steps, target syncs, rollouts).  body() enqueues on the group's stream and returns 0, or -1 with its refusal.  Out: every member's stream
+// behind whatever the group enqueued -- on the error paths too: a later member call must never run beside steps already enqueued, and whatever the member enqueues
+// next sees the group's work without a host synchronise.  Then ONE synchronise of the group's stream: the results and the assertion flags of this call
+template <class Body> static int group_call(dqn_group* g, const char* who, Body body) {
+    for (int k = 0; k < g->K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
+    (void)hipGetLastError();
+    const int rc = body();
+    hipError_t he = hipEventRecord(g->ev_done, g->stream);
+    for (int k = 0; k < g->K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
+    const hipError_t hs = hipStreamSynchronize(g->stream);
+    if (rc) return rc;
+    if (he != hipSuccess || hs != hipSuccess) return fail("%s: HIP error %s ordering the members' streams behind the group", who, hipGetErrorString(he != hipSuccess ? he : hs));
+    return 0;
+}
+// the last thing a body enqueues: the D2H copy of the call's per-member results, behind `what` -- whose launch errors surface here
+static int group_gather(dqn_group* g, const char* who, const char* what, void* host, const void* dev, size_t bytes) {
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, g->stream);
+    return he == hipSuccess ? 0 : fail("%s: HIP error %s behind the group's %s", who, hipGetErrorString(he), what);
+}
+// ... and what a call reports of its members' consumed assertion flags, over the (err, step) every per-member result carries: the first failing member, and whether others failed
+template <class Rec> static int group_members_failed(const Rec* o, int K) {
+    int bad = -1, nbad = 0;
+    for (int k = 0; k < K; k++) if (o[k].err) { if (bad < 0) bad = k; nbad++; }
+    if (bad < 0) return 0;
+    const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
+    if (o[bad].err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o[bad].step, more);
+    return fail("member %d: device-side error %d at or before train step %llu%s", bad, o[bad].err, o[bad].step, more);
+}
+// does any member step a control kind: picks the acting / evaluation kernel's instantiation (env_body.h)
+static int group_has_control(const dqn_group* g) { int c = 0; for (const dqn_engine* e : g->members) c |= env_is_control(e->env.kind) ? 1 : 0; return c; }
+
 extern "C" int dqn_group_create(dqn_engine_t* const* members, int n_members, dqn_group_t** out) {
     if (!out) return fail("dqn_group_create: out is NULL");
     *out = nullptr;
@@ -103,40 +136,14 @@ extern "C" int dqn_group_train_steps(dqn_group_t* g, int n, float* loss, float* 
     // (a member's step program cannot change under a live group: dqn_comm_init, the one call that rebuilds it, is refused on a grouped engine)
     for (int k = 0; k < g->K; k++) if (g->members[k]->size < g->members[k]->B) return fail("member %d: AssertionError: r._curr_size >= r.batch_size", k);   // ...replay.jl:83
     HIPCHK(hipSetDevice(g->device));
-    // in: the group's stream behind everything the members have enqueued (replay_add, their own steps, target syncs, rollouts)
-    for (int k = 0; k < g->K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
-    (void)hipGetLastError();
-    int rc = 0;
-    if (launch_tiny_group(g->stream, g->args_dev, g->K, g->max_lds, n))
-        rc = fail("dqn_group_train_steps: the device refused %u bytes of dynamic LDS for the group launch (hipFuncSetAttribute)", g->max_lds);
-    hipError_t he = hipSuccess;
-    if (!rc) {
-        hipLaunchKernelGGL(k_group_scalars, dim3((g->K + 255) / 256), dim3(256), 0, g->stream, g->args_dev, g->K, g->out_dev);
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpyAsync(g->out_host, g->out_dev, sizeof(GroupScalars) * (size_t)g->K, hipMemcpyDeviceToHost, g->stream);
-        if (he != hipSuccess) rc = fail("dqn_group_train_steps: HIP error %s behind the group's steps", hipGetErrorString(he));
-    }
-    // out: every member's stream behind whatever the group enqueued -- on the error paths too: a later member call must never run beside steps already enqueued.
-    // Whatever the member enqueues next sees the group's steps, without a host synchronise
-    he = hipEventRecord(g->ev_done, g->stream);
-    for (int k = 0; k < g->K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
-    const hipError_t hs = hipStreamSynchronize(g->stream);      // the scalars and the assertion flags of this call
-    if (rc) return rc;
-    if (he != hipSuccess || hs != hipSuccess) return fail("dqn_group_train_steps: HIP error %s ordering the members' streams behind the group", hipGetErrorString(he != hipSuccess ? he : hs));
-    int bad = -1, nbad = 0;
-    for (int k = 0; k < g->K; k++) {
-        const GroupScalars& o = g->out_host[k];
-        if (loss) loss[k] = o.loss;
-        if (grad_norm) grad_norm[k] = o.gnorm;
-        if (o.err) { if (bad < 0) bad = k; nbad++; }
-    }
-    if (bad >= 0) {
-        const GroupScalars& o = g->out_host[bad];
-        const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
-        if (o.err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o.step, more);
-        return fail("member %d: device-side error %d at or before train step %llu%s", bad, o.err, o.step, more);
-    }
-    return 0;
+    static const char who[] = "dqn_group_train_steps";
+    if (group_call(g, who, [&]() {
+            if (launch_tiny_group(g->stream, g->args_dev, g->K, g->max_lds, n))
+                return fail("dqn_group_train_steps: the device refused %u bytes of dynamic LDS for the group launch (hipFuncSetAttribute)", g->max_lds);
+            hipLaunchKernelGGL(k_group_scalars, dim3((g->K + 255) / 256), dim3(256), 0, g->stream, g->args_dev, g->K, g->out_dev);
+            return group_gather(g, who, "steps", g->out_host, g->out_dev, sizeof(GroupScalars) * (size_t)g->K); })) return -1;
+    for (int k = 0; k < g->K; k++) { if (loss) loss[k] = g->out_host[k].loss; if (grad_norm) grad_norm[k] = g->out_host[k].gnorm; }
+    return group_members_failed(g->out_host, g->K);
 }
 
 // ---------------------------------------------------------------- grouped acting: dqn_rollout_many (tiny_act.hip)
@@ -176,7 +183,7 @@ static int tiny_act_record(dqn_engine* e, RolloutDev* rs, TinyActArgs* out) {
     a.rows_u8 = e->hp.obs_dtype == DQN_OBS_U8 ? 1 : 0; a.P = e->Pint;
     for (size_t li = 0; li < levels.size(); li++) { a.lev_n[li] = (int)levels[li].size(); a.lev_l[li][0] = levels[li][0]; a.lev_l[li][1] = levels[li].size() > 1 ? levels[li][1] : levels[li][0]; }
     a.p_on = e->p_on; a.pol_x = e->pol_x; a.pol_q = e->pol_q; a.pol_a = e->pol_a; a.s_rows = e->s_rows; a.sp_rows = e->sp_rows; a.rs = rs; a.V = e->env;
-    ReplayMeta& R = a.R; R.cap = e->cap; R.cap2 = e->cap2; R.a = e->ra; R.r = e->rr; R.done = e->rdone; R.tree = e->tree; R.state = e->state; R.eps = e->hp.prio_eps; R.alpha = e->hp.prio_alpha;
+    a.R = replay_meta(e);
     *out = a; return 0;
 }
 // Flux.loadparams!(target_q, params(active_q)) of every member: workgroup k copies member k's online parameters over its target parameters (dqn_sync_target keeps no host state)
@@ -231,7 +238,7 @@ static int rollout_many_check(dqn_group* g, int n_steps, const dqn_rollout_cfg* 
         for (int j = 0; j < n_steps; j++) {
             const long long t = c0.t0 + j;
             for (int k = 0; k < g->K; k++) size[k] = std::min(g->members[k]->cap, size[k] + g->members[k]->env.n);
-            if (t % c0.train_freq != 0) continue;
+            if (!rollout_due(c0, t, g->members[0]->env.n).due) continue;      // (the vector-step cadence: n does not enter)
             const bool w0 = size[0] >= g->members[0]->B;
             for (int k = 1; k < g->K; k++) if ((size[k] >= g->members[k]->B) != w0)
                 return fail("dqn_rollout_many: members 0 and %d disagree at vector step %lld on whether the train step runs (member 0 holds %lld of its batch of %d, member %d holds %lld of %d): "
@@ -276,7 +283,7 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     if (rollout_many_check(g, n_steps, cfgs, explore, &train_at)) return -1;
     HIPCHK(hipSetDevice(g->device));
     if (rollout_many_records(g)) return -1;
-    int control = 0; for (dqn_engine* e : g->members) control |= env_is_control(e->env.kind) ? 1 : 0;      // picks the acting kernel's instantiation (env_body.h)
+    const int control = group_has_control(g);
     if (tiny_act_raise_lds(g->act_lds, control)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds);
     const int K = g->K; const dqn_rollout_cfg& c0 = cfgs[0];
     // the call's records and tables: ONE contiguous array each, ONE H2D copy each
@@ -285,58 +292,33 @@ extern "C" int dqn_rollout_many(dqn_group_t* g, int n_steps, const dqn_rollout_c
     if (nx > g->xtab_cap) { HIPCHK(hipStreamSynchronize(g->stream)); if (grow(g->mem, &g->xtab_dev, &g->xtab_cap, nx, 1024)) return -1; }
     g->xtab_host.clear();
     for (int k = 0; k < K; k++) {
-        dqn_engine* e = g->members[k]; const dqn_rollout_cfg& c = cfgs[k]; const int n = e->env.n;
-        RolloutDev h; memset(&h, 0, sizeof h);
-        h.t = c.t0 - 1; h.widx = ((e->widx - n) % e->cap + e->cap) % e->cap; h.eps_start = c.eps_start; h.eps_stop = c.eps_stop; h.eps_steps = c.eps_steps;
+        RolloutDev h = rollout_record(&cfgs[k], g->members[k]);
         if (explore && explore[k]) {
             const dqn_exploration* x = explore[k];
-            h.xkind = x->kind; h.xtab = g->xtab_dev + g->xtab_host.size(); h.xtab_t0 = c.t0; h.xtab_n = x->n_values;
+            h.xkind = x->kind; h.xtab = g->xtab_dev + g->xtab_host.size(); h.xtab_t0 = cfgs[k].t0; h.xtab_n = x->n_values;
             g->xtab_host.insert(g->xtab_host.end(), x->values, x->values + x->n_values);      // the caller's arrays are not kept
         }
         g->roll_host[(size_t)k] = h;
     }
-    // in: the group's stream behind everything the members have enqueued
-    for (int k = 0; k < K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
-    (void)hipGetLastError();
-    int rc = 0; hipError_t he = hipSuccess; long long trained = 0;
-    he = hipMemcpyAsync(g->roll_dev, g->roll_host.data(), sizeof(RolloutDev) * (size_t)K, hipMemcpyHostToDevice, g->stream);
-    if (he == hipSuccess && nx) he = hipMemcpyAsync(g->xtab_dev, g->xtab_host.data(), sizeof(float) * nx, hipMemcpyHostToDevice, g->stream);      // (both host arrays are the group's: they outlive the copies)
-    if (he != hipSuccess) rc = fail("dqn_rollout_many: HIP error %s uploading the call's records", hipGetErrorString(he));
-    for (int j = 0; j < n_steps && !rc; j++) {
-        const long long t = c0.t0 + j;
-        if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0, control)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds); break; }
-        for (dqn_engine* e : g->members) { const int n = e->env.n; e->widx = (e->widx + n) % e->cap; e->size = std::min(e->cap, e->size + n); e->env_q_valid = true; }      // what dqn_rollout_explore keeps on the host
-        if (train_at[(size_t)j]) {      // :134-139, for all members in one launch
-            if (launch_tiny_group(g->stream, g->args_dev, K, g->max_lds, 1)) { rc = fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the group train launch (hipFuncSetAttribute)", g->max_lds); break; }
-            trained++;
-        }
-        if (c0.target_update_freq > 0 && t % c0.target_update_freq == 0) hipLaunchKernelGGL(k_group_sync_target, dim3(K), dim3(256), 0, g->stream, g->args_dev);      // :142-145
-    }
-    if (!rc) {
-        hipLaunchKernelGGL(k_group_rollout_scalars, dim3((K + 255) / 256), dim3(256), 0, g->stream, g->args_dev, g->act_dev, K, trained > 0 ? 1 : 0, g->ro_dev);
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpyAsync(g->ro_host, g->ro_dev, sizeof(RolloutScalars) * (size_t)K, hipMemcpyDeviceToHost, g->stream);
-        if (he != hipSuccess) rc = fail("dqn_rollout_many: HIP error %s behind the group's steps", hipGetErrorString(he));
-    }
-    // out: every member's stream behind whatever the group enqueued -- on the error paths too
-    he = hipEventRecord(g->ev_done, g->stream);
-    for (int k = 0; k < K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
-    const hipError_t hs = hipStreamSynchronize(g->stream);
-    if (rc) return rc;
-    if (he != hipSuccess || hs != hipSuccess) return fail("dqn_rollout_many: HIP error %s ordering the members' streams behind the group", hipGetErrorString(he != hipSuccess ? he : hs));
-    int bad = -1, nbad = 0;
-    for (int k = 0; k < K; k++) {
-        const RolloutScalars& o = g->ro_host[k];
-        if (out) { out[k].episodes = o.episodes; out[k].reward_sum = o.reward_sum; out[k].train_steps = trained; out[k].last_loss = o.loss; out[k].last_grad_norm = o.gnorm; }
-        if (o.err) { if (bad < 0) bad = k; nbad++; }
-    }
-    if (bad >= 0) {
-        const RolloutScalars& o = g->ro_host[bad];
-        const char* more = nbad > 1 ? "; further members failed too, the other members' steps stand" : "; the other members' steps stand";
-        if (o.err == 2) return fail("member %d: AssertionError: all(new_priorities .> 0f0) (at or before train step %llu)%s", bad, o.step, more);
-        return fail("member %d: device-side error %d at or before train step %llu%s", bad, o.err, o.step, more);
-    }
-    return 0;
+    static const char who[] = "dqn_rollout_many";
+    long long trained = 0;
+    if (group_call(g, who, [&]() {
+            hipError_t he = hipMemcpyAsync(g->roll_dev, g->roll_host.data(), sizeof(RolloutDev) * (size_t)K, hipMemcpyHostToDevice, g->stream);
+            if (he == hipSuccess && nx) he = hipMemcpyAsync(g->xtab_dev, g->xtab_host.data(), sizeof(float) * nx, hipMemcpyHostToDevice, g->stream);      // (both host arrays are the group's: they outlive the copies)
+            if (he != hipSuccess) return fail("dqn_rollout_many: HIP error %s uploading the call's records", hipGetErrorString(he));
+            for (int j = 0; j < n_steps; j++) {
+                if (launch_tiny_act(g->stream, g->act_dev, K, g->act_lds, j == 0 ? 1 : 0, j == n_steps - 1 ? 1 : 0, control)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the acting launch (hipFuncSetAttribute)", g->act_lds);
+                for (dqn_engine* e : g->members) { ring_advance(e, e->env.n); e->env_q_valid = true; }      // what dqn_rollout_explore keeps on the host
+                if (train_at[(size_t)j]) {      // :134-139, for all members in one launch
+                    if (launch_tiny_group(g->stream, g->args_dev, K, g->max_lds, 1)) return fail("dqn_rollout_many: the device refused %u bytes of dynamic LDS for the group train launch (hipFuncSetAttribute)", g->max_lds);
+                    trained++;
+                }
+                if (rollout_due(c0, c0.t0 + j, g->members[0]->env.n).sync) hipLaunchKernelGGL(k_group_sync_target, dim3(K), dim3(256), 0, g->stream, g->args_dev);      // :142-145
+            }
+            hipLaunchKernelGGL(k_group_rollout_scalars, dim3((K + 255) / 256), dim3(256), 0, g->stream, g->args_dev, g->act_dev, K, trained > 0 ? 1 : 0, g->ro_dev);
+            return group_gather(g, who, "steps", g->ro_host, g->ro_dev, sizeof(RolloutScalars) * (size_t)K); })) return -1;
+    for (int k = 0; k < K && out; k++) { const RolloutScalars& o = g->ro_host[k]; out[k].episodes = o.episodes; out[k].reward_sum = o.reward_sum; out[k].train_steps = trained; out[k].last_loss = o.loss; out[k].last_grad_norm = o.gnorm; }
+    return group_members_failed(g->ro_host, K);
 }
 
 // ---------------------------------------------------------------- grouped evaluation: dqn_evaluate_many (tiny_eval.hip)
@@ -415,35 +397,23 @@ extern "C" int dqn_evaluate_many(dqn_group_t* g, int n_eval, int max_episode_len
         if (tiny_act_record(e, &g->eval_dev[k].roll, &T.a)) return -1;
         T.a.lds_bytes = (unsigned)(tiny_eval_layout(e, n_eval, &T) * 4); lds = std::max(lds, T.a.lds_bytes);
         T.a.V = e->eval_env; T.a.V.seed = seeds[k]; T.a.V.max_episode_length = max_episode_length;      // (the engine's own copy keeps what its evaluation program was built with)
-        T.roll.eps_steps = 1.0f;      // t = 0; the eps schedule (0, 0, 1): always greedy
+        T.roll = rollout_record(nullptr, e);      // always greedy
         T.heads = g->heads_dev + hoff; hoff += (size_t)(e->nA + (e->hp.dueling ? 1 : 0)) * n_eval;
         T.out = g->es_dev + k;
     }
-    int control = 0; for (dqn_engine* e : g->members) control |= env_is_control(e->env.kind) ? 1 : 0;
+    const int control = group_has_control(g);
     if (tiny_eval_raise_lds(lds, control)) return fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
-    // in: the group's stream behind everything the members have enqueued
-    for (int k = 0; k < K; k++) { HIPCHK(hipEventRecord(g->ev_in[k], g->members[k]->stream)); HIPCHK(hipStreamWaitEvent(g->stream, g->ev_in[k], 0)); }
-    (void)hipGetLastError();
-    for (dqn_engine* e : g->members) e->env_q_valid = false;      // the evaluation copies' forward writes pol_q / pol_a, as dqn_evaluate's does
-    int rc = 0;
-    hipError_t he = hipMemcpyAsync(g->eval_dev, g->eval_host.data(), sizeof(TinyEvalArgs) * Ks, hipMemcpyHostToDevice, g->stream);      // (the host array is the group's: it outlives the copy)
-    if (he != hipSuccess) rc = fail("dqn_evaluate_many: HIP error %s uploading the call's records", hipGetErrorString(he));
-    const int total = max_episode_length + 1;      // while !done && step <= max_episode_length
-    for (int s0 = 0; s0 < total && !rc; s0 += TINY_EVAL_STEPS) {
-        const int ns = std::min(TINY_EVAL_STEPS, total - s0);
-        if (launch_tiny_eval(g->stream, g->eval_dev, K, lds, ns, s0 == 0 ? 1 : 0, s0 + ns >= total ? 1 : 0, control)) rc = fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
-    }
-    if (!rc) {
-        he = hipGetLastError();
-        if (he == hipSuccess) he = hipMemcpyAsync(g->es_host, g->es_dev, sizeof(EvalSums) * Ks, hipMemcpyDeviceToHost, g->stream);
-        if (he != hipSuccess) rc = fail("dqn_evaluate_many: HIP error %s behind the group's evaluation", hipGetErrorString(he));
-    }
-    // out: every member's stream behind whatever the group enqueued -- on the error paths too
-    he = hipEventRecord(g->ev_done, g->stream);
-    for (int k = 0; k < K && he == hipSuccess; k++) he = hipStreamWaitEvent(g->members[k]->stream, g->ev_done, 0);
-    const hipError_t hs = hipStreamSynchronize(g->stream);
-    if (rc) return rc;
-    if (he != hipSuccess || hs != hipSuccess) return fail("dqn_evaluate_many: HIP error %s ordering the members' streams behind the group", hipGetErrorString(he != hipSuccess ? he : hs));
+    static const char who[] = "dqn_evaluate_many";
+    if (group_call(g, who, [&]() {
+            for (dqn_engine* e : g->members) e->env_q_valid = false;      // the evaluation copies' forward writes pol_q / pol_a, as dqn_evaluate's does
+            const hipError_t he = hipMemcpyAsync(g->eval_dev, g->eval_host.data(), sizeof(TinyEvalArgs) * Ks, hipMemcpyHostToDevice, g->stream);      // (the host array is the group's: it outlives the copy)
+            if (he != hipSuccess) return fail("dqn_evaluate_many: HIP error %s uploading the call's records", hipGetErrorString(he));
+            const int total = max_episode_length + 1;      // while !done && step <= max_episode_length
+            for (int s0 = 0; s0 < total; s0 += TINY_EVAL_STEPS) {
+                const int ns = std::min(TINY_EVAL_STEPS, total - s0);
+                if (launch_tiny_eval(g->stream, g->eval_dev, K, lds, ns, s0 == 0 ? 1 : 0, s0 + ns >= total ? 1 : 0, control)) return fail("dqn_evaluate_many: the device refused %u bytes of dynamic LDS for the evaluation launch (hipFuncSetAttribute)", lds);
+            }
+            return group_gather(g, who, "evaluation", g->es_host, g->es_dev, sizeof(EvalSums) * Ks); })) return -1;
     for (int k = 0; k < K; k++) {      // avg_r /= n_eval; avg_steps /= n_eval (dqn_evaluate's last lines)
         if (avg_reward) avg_reward[k] = g->es_host[k].reward_sum / n_eval;
         if (avg_steps) avg_steps[k] = (double)g->es_host[k].steps / n_eval;

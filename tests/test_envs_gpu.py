@@ -219,6 +219,71 @@ def test_rollout_env_step_cadence_bit_exact(pkg, envs):
     assert total >= 6 * 18 // 4 - 2          # ~1.5 train steps per vector step in the env-step chunks
 
 
+UNIT_CALLS = (dict(n_steps=40, t0=1, train_freq=4, target_update_freq=6, env_step_cadence=False),      # cycles refused for want of a batch, refused by a sync inside, accepted
+              dict(n_steps=10, t0=41, train_freq=2, target_update_freq=6, env_step_cadence=True))      # 4 copies: two train steps per vector step
+
+
+@pytest.mark.parametrize("tiny", [True, False])
+def test_every_rollout_unit_equals_plain_launches(pkg, envs, monkeypatch, tiny):
+    """every unit the rollout driver chooses (csrc/rollout_sched.h) in one engine's life, held to plain launches: two engines that differ in hp.use_graph only run
+    the same two calls and agree bit for bit after each -- parameters, Adam state, sum-tree, ring rows and metadata (checkpoint), counters, the last step's
+    observables, dqn_envs_peek / _peek_q and the returned stats -- and with the CPU twin where this file compares against it.  4 GridWorld copies, batch 64:
+    call 1 (t = 1..40, a train step every 4 vector steps, a sync every 6) refuses the cycles at t = 1, 5, 9 (the replay holds 16, 32, 48 of 64 at their last step),
+    accepts 13..16, refuses 17 and 29 (a sync at 18 / 30 inside), accepts 21, 25, 33, 37; call 2 runs the env-step cadence at train_freq = 2.  The network takes the
+    single-workgroup train step, whose engines keep call 2 on plain units: tiny = False creates both engines under DQN_NO_TINY, where call 2 is the env-cadence graph"""
+    from group_rollout_common import assert_same, observables
+    net = EC.gridworld_mlp_dueling()
+    if not tiny:
+        monkeypatch.setenv("DQN_NO_TINY", "1")
+    g1, t, hp = make_pair(pkg, net, B=64, cap=128, prioritized_replay=1, use_graph=1)
+    g0, t0_, _ = make_pair(pkg, net, B=64, cap=128, prioritized_replay=1, use_graph=0)
+    t0_.close()
+    monkeypatch.delenv("DQN_NO_TINY", raising=False)
+    EC.same_params([g1, g0, t], net)
+    for h in (g1, g0, t):
+        h.envs_create(envs.SimpleGridWorld(n=4), max_episode_length=20, seed=5)
+    total = 0
+    for call in UNIT_CALLS:
+        kw = dict(call, eps=(1.0, 0.05, 30.0)); n_steps = kw.pop("n_steps")
+        s1, s0, st = (h.rollout(n_steps, **kw) for h in (g1, g0, t))
+        assert s1 == s0 == st, (s1, s0, st)
+        assert_same(observables(g1, s1), observables(g0, s0), f"use_graph 1 vs 0 after {call}")
+        compare_state(g1, t)
+        for which in (0, 1):
+            np.testing.assert_array_equal(g1.get_params(which), t.get_params(which))
+        total += s1["train_steps"]
+    assert total == 7 + 20      # t = 16, 20, .., 40 (a batch is held from t = 16 on); 2 per vector step of call 2
+    assert g1.replay_size() == (128, 128)      # 200 transitions: the ring wrapped
+
+
+def test_every_rollout_unit_on_a_recurrent_engine(pkg, envs):
+    """the same two calls on a recurrent engine (the smallest LSTM case, 4 copies), use_graph 1 against 0: every unit is the plain one and each of the driver's
+    recurrent hooks is in place -- Recur state, episode ring and its cursor, counters, parameters, Adam state, dqn_envs_peek and the stats agree bit for bit"""
+    import recurrent_envs_common as RC
+    nn = importlib.import_module(pkg.__name__ + ".nn")
+    spec, net, _, T, cap, B, max_len = RC.cases(nn, envs)["lstm"]
+    case, hs = (spec, net, 4, T, cap, B, max_len), []
+    for graph in (1, 0):
+        g, _ = RC.make_engine(pkg, nn, case, graph=graph)
+        p = RC.noisy_params(nn, net)
+        g.set_params(p, 0); g.set_params((p * 0.9).astype(np.float32), 1)
+        g.envs_create(spec, n_envs=4, max_episode_length=max_len, seed=RC.ENV_SEED["lstm"])
+        hs.append(g)
+    total = 0
+    for call in UNIT_CALLS:
+        kw = dict(call, eps=(1.0, 0.1, 20.0)); n_steps = kw.pop("n_steps")
+        s1, s0 = (h.rollout(n_steps, **kw) for h in hs)
+        assert s1 == s0, (s1, s0)
+        a, b = (dict(peek=h.envs_peek(), ring=h.episode_export(), adam=h.get_adam_state(), p=(h.get_params(0), h.get_params(1))) for h in hs)
+        for k in a:
+            for x, y in zip(a[k], b[k]):
+                np.testing.assert_array_equal(x, y, err_msg=f"{k} after {call}")
+        RC.hidden_equal(hs[0].get_hidden(4), hs[1].get_hidden(4))
+        assert hs[0].episode_count() == hs[1].episode_count() and hs[0].get_counters() == hs[1].get_counters()
+        total += s1["train_steps"]
+    assert total > 20      # call 2 alone owes 20 once two episodes are committed (4 copies finish one every 5 steps)
+
+
 @pytest.mark.parametrize("kind", ["testmdp", "testmdp_u8", "gridworld"])
 def test_evaluate_bit_exact_and_isolated(pkg, envs, kind):
     """dqn_evaluate (device basic_evaluation) == the twin's: average return (Float64) and steps identical; the training envs, the
